@@ -6,8 +6,16 @@ reset, render kernel, fixed-point -> float finalize) into a device framebuffer, 
 single RCCL gather of the fp32 row tiles to rank 0. Inputs (scene, camera) are built once; the
 framebuffers stay resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...        (one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps, writes the last step's image (--dump-outputs) and
+prints the result line: its headline (value, ms_per_step) and what the timed launches' own
+statistics give (roofline from their kernel times, paths). --full adds everything that takes runs of
+its own after the timed region: the CPU baselines (--no-cpu-baseline skips them), the kernel time of
+launches run one at a time, the image-writer timings, the quality renders and the reference-leaks
+leg (--no-extras skips those two), and for N > 1 the gather timings and the check of the gathered
+image against a 1-GPU render.
 
 Workloads (BASELINE.json configs):
   c2  1024x768 @ 64 spp, cosine-weighted (:474-477)
@@ -267,6 +275,25 @@ def image_writer(spt, full, w, h, with_cpu: bool):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, img: np.ndarray) -> None:
+    """--dump-outputs: the image of the last timed step as out_dir/image.npy (float32, (h, w, 3)).
+    An image over DUMP_MAX_BYTES (the 4096^2 configs: 201 MB) is written as a fixed sample instead:
+    2^21 distinct pixels drawn with a seeded generator, the same for every run of a given size,
+    as image_sample.npy (n, 3) with their flat indices (y * w + x) in image_sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    npix = img.shape[0] * img.shape[1]
+    idx = np.sort(np.random.default_rng(20240607).choice(npix, size=min(npix, 1 << 21), replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), img.reshape(npix, 3)[idx])
+    np.save(os.path.join(out_dir, "image_sample_index.npy"), idx.astype(np.float64))
+
+
 def free_port() -> int:
     import socket
 
@@ -358,7 +385,17 @@ def main() -> None:
     ap.add_argument("--spp", type=int, default=0, help="override spp (per-GPU for weak scaling)")
     ap.add_argument("--chunk", type=int, default=int(os.environ.get("SPT_CHUNK", "0")),
                     help="samples per work unit (0 = auto; A/B scripts set SPT_CHUNK)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything that takes runs of its own: CPU "
+                         "baselines, isolated kernel launches, image-writer timings, quality renders, "
+                         "the reference-leaks leg, and for N > 1 the gather timings and the check "
+                         "against a 1-GPU render (off: those fields of the line are null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the image the last timed step produced (what rank 0 holds after its "
+                         "gather) as DIR/image.npy, float32 (h, w, 3); above 64 MB a fixed seeded "
+                         "pixel sample instead: DIR/image_sample.npy (n, 3) and its flat pixel "
+                         "indices DIR/image_sample_index.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_c3.json"),
                     help="PMC traffic summary (HBM bytes per render launch) to attach, if present")
@@ -387,7 +424,8 @@ def main() -> None:
                          "SPT_FLAG_REFERENCE_LEAKS) instead of ending at their first miss (contract v6)")
     ap.add_argument("--verify-gather", dest="verify_gather", action="store_true", default=None,
                     help="rank 0 re-renders the whole image alone and checks the gathered one bit for "
-                         "bit (default on for N > 1: the RCCL gather has not run on hardware before)")
+                         "bit (default on for N > 1 with --full: the RCCL gather has not run on "
+                         "hardware before)")
     ap.add_argument("--no-verify-gather", dest="verify_gather", action="store_false")
     ap.add_argument("--gather", choices=["spt", "torch"], default="spt",
                     help="N > 1 over nccl: the library's gather (spt_comm: grouped ncclSend/ncclRecv "
@@ -403,8 +441,8 @@ def main() -> None:
                     help="--gpus N > 1 without a launcher: seconds the spawned ranks may run in all "
                          "before they are ended (exit status 124)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="profiling sessions only: skip everything after the timed region that launches "
-                         "the render kernel again (the reference-leaks leg, the quality renders), so a "
+                    help="--full in profiling sessions: skip what launches the render kernel again "
+                         "after the timed region (the reference-leaks leg, the quality renders), so a "
                          "rocprofv3 summary of the run averages the warm-up and timed dispatches only")
     ap.add_argument("--probe-env", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -431,7 +469,7 @@ def main() -> None:
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.verify_gather is None:
-        args.verify_gather = world > 1
+        args.verify_gather = world > 1 and args.full
 
     # Bounded set-up: a rank that cannot join the process group or the RCCL communicator (a peer
     # missing, a wrong address) exits with a clear error instead of hanging the job.
@@ -645,12 +683,18 @@ def main() -> None:
     assert len(kstats) == args.steps, (len(kstats), args.steps)
     last = (args.steps - 1) % nfly
     shard, full = shards[last], fulls[last]
+    # the last timed step's image, before anything below renders into the frame buffers again
+    need_img = bool(args.full or args.dump_outputs or args.save_ppm or args.verify_gather)
+    img = full.cpu().numpy() if rank == 0 and need_img else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, img)
     # The roofline's kernel time: with two frames in flight a launch's HIP-event span also covers
-    # the neighbouring frame's overlap, so the per-launch time is measured on 3 launches run one at
-    # a time after the timed region (the same kernel and work; rocprofv3 sees them as well).
+    # the neighbouring frame's overlap, so --full measures the per-launch time on 3 launches run one
+    # at a time after the timed region (the same kernel and work; rocprofv3 sees them as well). A
+    # plain run reports the timed launches' own spans.
     kms_flight = float(np.mean([s["kernel_ms"] for s in kstats]))
     iso = []
-    for _ in range(3 if nfly > 1 else 0):
+    for _ in range(3 if nfly > 1 and args.full else 0):
         rens[0].render_async(prims, cam, params, shards[0].data_ptr(), streams[0].cuda_stream)
         iso.append(rens[0].stats())
     torch.cuda.synchronize()
@@ -660,9 +704,10 @@ def main() -> None:
     if world > 1:
         # Per-rank evidence for the N > 1 line: each rank's isolated kernel time, its timed-region
         # wall time and the gather alone (3 gathers after a barrier each, the fastest; the image
-        # they gather is the frame just rendered into buffer 0, so nothing checked changes).
+        # they gather is the frame just rendered into buffer 0, so nothing checked changes; --full
+        # only, gather_ms is null in a plain run).
         gms = []
-        for _ in range(3):
+        for _ in range(3 if args.full else 0):
             dist.barrier()
             torch.cuda.synchronize()
             t_ = time.perf_counter()
@@ -678,7 +723,8 @@ def main() -> None:
             torch.cuda.synchronize()
             gms.append((time.perf_counter() - t_) * 1e3)
         dev = "cuda" if backend == "nccl" else "cpu"
-        mine = torch.tensor([float(kms.mean()), kms_flight, elapsed * 1e3, min(gms)],
+        mine = torch.tensor([float(kms.mean()), kms_flight, elapsed * 1e3,
+                             min(gms) if gms else float("nan")],
                             dtype=torch.float64, device=dev)
         every = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
@@ -688,9 +734,10 @@ def main() -> None:
                     "kernel_ms_max": round(float(every[:, 0].max()), 3),
                     "kernel_ms_in_flight": [round(float(x), 3) for x in every[:, 1]],
                     "timed_region_ms": [round(float(x), 2) for x in every[:, 2]],
-                    "gather_ms": [round(float(x), 3) for x in every[:, 3]],
-                    "gather_ms_source": "3 gathers alone after the timed region, each after a "
-                                        "barrier, fastest (wall clock incl. the barrier release)",
+                    "gather_ms": [round(float(x), 3) for x in every[:, 3]] if args.full else None,
+                    "gather_ms_source": ("3 gathers alone after the timed region, each after a "
+                                         "barrier, fastest (wall clock incl. the barrier release)"
+                                         if args.full else "not measured (--full)"),
                     "launcher": ("bench.py (spawned ranks)" if os.environ.get("SPT_BENCH_SPAWNED")
                                  else "external (torch.distributed.run or equivalent)")}
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -773,7 +820,6 @@ def main() -> None:
 
     gather_exact = None
     if rank == 0:
-        img = full.cpu().numpy()
         if args.verify_gather:  # the whole image on this GPU alone (1 shard) must equal the gather
             p1 = spt.default_params(width=w, height=h, spp=spp, nee_prob=cfg["nee_prob"],
                                     max_depth=cfg["max_depth"], tile_rows=8, device=local,
@@ -783,7 +829,7 @@ def main() -> None:
             assert gather_exact, "gathered image differs from the 1-GPU render"
         cpu = None
         port = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # (the reference binaries hold the unedited table: no reference leg for an edited scene)
             cpu = None if edited else reference_baseline(cfg, args.cpu_budget)
             omp = None if edited else reference_baseline(cfg, args.cpu_budget, threads=host_threads())
@@ -796,9 +842,10 @@ def main() -> None:
                 cpu["port"] = port
         if args.save_ppm:
             spt.write_ppm(args.save_ppm, img)
-        writer = image_writer(spt, full, w, h, with_cpu=not args.no_cpu_baseline)
+        writer = image_writer(spt, full, w, h, with_cpu=not args.no_cpu_baseline) if args.full else None
+        extras = args.full and not args.no_extras
         qual = None
-        if (args.config in QUALITY_FIXTURES and world == 1 and not edited and not args.no_extras
+        if (args.config in QUALITY_FIXTURES and world == 1 and not edited and extras
                 and os.path.exists(QUALITY_FIXTURES[args.config][0])):
             # 15 more seeds of the same render (after the timed region): the matched-budget RMSE
             extra = [spt.render(prims, cam, spt.default_params(
@@ -814,7 +861,7 @@ def main() -> None:
         # bench image: K steps through the same pipeline (value_reference_leaks) and 3 isolated
         # launches (kernel_ms_reference_leaks), VERDICT r05 item 4
         leak = None
-        if world == 1 and cfg["scene"] == "cornell" and not args.no_extras:
+        if world == 1 and cfg["scene"] == "cornell" and extras:
             if args.reference_leaks:
                 leak = {"rule": "off: leaked paths go on from the miss vertex as the reference's "
                                 "(:371-377, SPT_FLAG_REFERENCE_LEAKS)"}
@@ -860,7 +907,7 @@ def main() -> None:
                                f"launches one at a time for the kernel time"}
         out = {
             "metric": METRIC, "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world,
-            "steps": args.steps, "warmup": n_warm,
+            "steps": args.steps, "warmup": n_warm, "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": scaling, "vs_baseline": None, "dtype": "f32",
             "data": ("synthetic: the reference's Cornell-box scene (smallpt.cpp:287-311)"

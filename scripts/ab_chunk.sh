@@ -7,7 +7,7 @@ mkdir -p gpurun_out/ab_chunk
 export TMPDIR=/tmp
 for r in 1 2; do
   for c in "$@"; do
-    out=$(timeout -k 10 120 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --chunk $c 2>/dev/null) || { echo "chunk $c FAILED"; exit 1; }
+    out=$(timeout -k 10 120 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --chunk $c 2>/dev/null) || { echo "chunk $c FAILED"; exit 1; }
     echo "chunk $c $(echo "$out" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["roofline"]["kernel_ms"])')"
   done
 done | tee gpurun_out/ab_chunk/times.txt

@@ -28,7 +28,7 @@ declare -A ARGS=(
 )
 ORDER="c3 c3_tilted c3_light c3_light_tilted c3_light_grow c3_movebox c3_room c3_room160 c3_refleaks c3_movebox_cornell c3_const c3_cornell c3_generic c2 c2_tilted c2_light"
 for name in ${LEVELS:-$ORDER}; do
-  timeout -k 10 240 python bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline ${ARGS[$name]} \
+  timeout -k 10 240 python bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline ${ARGS[$name]} \
     > gpurun_out/${TAG}_level_$name.json 2> gpurun_out/${TAG}_level_$name.err
   rc=$?; echo "level $name exit $rc"; [ $rc -eq 0 ] || exit $rc
 done

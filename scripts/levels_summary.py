@@ -37,7 +37,7 @@ for name, d in lines.items():
         e["value_reference_leaks"] = lk["value_reference_leaks"]
     out[name] = e
 spt = __import__("importlib").import_module("small-pathtracer_amd")
-out["_session"] = (f"scripts/levels.sh (TAG={tag}): bench.py --steps 5 --warmup 2 --no-cpu-baseline "
+out["_session"] = (f"scripts/levels.sh (TAG={tag}): bench.py --full --steps 5 --warmup 2 --no-cpu-baseline "
                    f"per level, one box; kernel_ms_isolated = 3 launches one at a time after the timed "
                    f"region")
 out["_kernel_sources_sha16"] = spt.kernel_sources_sha16()

@@ -76,7 +76,7 @@ fi
 if has bench; then
   for cfg in c3 c2 c4 c5; do
     st=5; [ $cfg = c4 ] && st=3; [ $cfg = c5 ] && st=2
-    timeout -k 10 420 python bench.py --config $cfg --steps $st --warmup 1 \
+    timeout -k 10 420 python bench.py --full --config $cfg --steps $st --warmup 1 \
       > gpurun_out/${TAG}_bench_$cfg.json 2> gpurun_out/${TAG}_bench_$cfg.err
     rc=$?; echo "bench $cfg exit $rc"; [ $rc -eq 0 ] || exit $rc
   done

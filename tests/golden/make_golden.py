@@ -119,6 +119,38 @@ def variant_pins():
         json.dump(out, f, indent=1)
 
 
+# The runs of tests/test_oracle.py's *_other_seeds tests: (binary, w, h, spp, seed)
+OTHER_SEED_RUNS = ([(est, w, h, spp, seed) for seed, w, h, spp in ((7, 40, 30, 3), (123, 33, 17, 5))
+                    for est in ("nee", "cos", "uni")]
+                   + [(est + xs, 33, 17, 5, seed) for est in ("q05", "sph", "sph16")
+                      for seed, xs in ((7, ""), (9, "_xs"))])
+
+
+def other_seed_key(binary, w, h, spp, seed):
+    return f"{w}x{h}_s{spp}_seed{seed}_{binary}"
+
+
+def other_seed_pins():
+    """md5s of the reference binaries' PPMs at odd sizes and other seeds (`--other-seed-pins`),
+    stored as golden.json["reference_md5_other_seeds"], so tests/test_oracle.py's *_other_seeds
+    tests also run where oracle/_ref is not built."""
+    subprocess.run([os.path.join(ROOT, "oracle", "build_ref.sh")], check=True)
+    ref = os.path.join(ROOT, "oracle", "_ref")
+    tmp = "/tmp/spt_golden"
+    os.makedirs(tmp, exist_ok=True)
+    path = os.path.join(HERE, "golden.json")
+    out = json.load(open(path))
+    pins = out["reference_md5_other_seeds"] = {}
+    for binary, w, h, spp, seed in OTHER_SEED_RUNS:
+        ppm = os.path.join(tmp, "other_seed.ppm")
+        subprocess.run([os.path.join(ref, f"smallpt_{binary}"), str(w), str(h), str(spp), str(seed), ppm],
+                       check=True, cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        pins[other_seed_key(binary, w, h, spp, seed)] = md5(ppm)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(pins, indent=1))
+
+
 def quality_c3(ref, tmp, w=1024, h=768, spp=512, seeds=range(201, 217), k=32, est="nee", cfg="c3"):
     """bench.py's `quality` fixture (`--quality-c3`): the reference's own C3 image (HEAD NEE,
     1024x768 @ 512 spp, the bench's config) as 32x32-block means of its linearised PPM, one set
@@ -186,6 +218,9 @@ def main():
         return
     if "--variant-pins" in sys.argv:
         variant_pins()
+        return
+    if "--other-seed-pins" in sys.argv:
+        other_seed_pins()
         return
     if "--fidelity-add" in sys.argv:  # one more estimator in the P2 fixture (e.g. uni)
         est = sys.argv[sys.argv.index("--fidelity-add") + 1]

@@ -43,18 +43,27 @@ def test_reference_ppm_fixture_matches(oracle, tmp_path, est):
     assert open(path, "rb").read() == open(os.path.join(HERE, "golden", f"ref_64x48_s4_{est}.ppm"), "rb").read()
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_DIR, "smallpt_nee")),
-                    reason="oracle/_ref not built (reference absent)")
+def _reference_md5_other_seed(tmp_path, binary, w, h, spp, seed):
+    """The reference binary's PPM md5 for this run, recorded in golden.json (make_golden.py
+    --other-seed-pins); where oracle/_ref is built, the live binary must give the same."""
+    pinned = GOLD["reference_md5_other_seeds"][f"{w}x{h}_s{spp}_seed{seed}_{binary}"]
+    exe = os.path.join(REF_DIR, f"smallpt_{binary}")
+    if os.path.exists(exe):
+        ref_path = str(tmp_path / f"ref_{binary}.ppm")
+        subprocess.run([exe, str(w), str(h), str(spp), str(seed), ref_path], check=True,
+                       cwd=str(tmp_path), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        assert hashlib.md5(open(ref_path, "rb").read()).hexdigest() == pinned
+    return pinned
+
+
 @pytest.mark.parametrize("seed,w,h,spp", [(7, 40, 30, 3), (123, 33, 17, 5)])
 def test_compat_restatement_matches_reference_binary_other_seeds(oracle, tmp_path, seed, w, h, spp):
-    """Beyond the committed md5s: odd sizes and other seeds against the live reference binary."""
+    """Beyond the seed-1 md5s: odd sizes and other seeds against the reference binary's output
+    (recorded, and the live binary too where it is built)."""
     for est in ("nee", "cos", "uni"):
-        ref_path = str(tmp_path / f"ref_{est}.ppm")
-        subprocess.run([os.path.join(REF_DIR, f"smallpt_{est}"), str(w), str(h), str(spp), str(seed),
-                        ref_path], check=True, cwd=str(tmp_path), stdout=subprocess.DEVNULL,
-                       stderr=subprocess.DEVNULL)
+        want = _reference_md5_other_seed(tmp_path, est, w, h, spp, seed)
         img = oracle.compat_render(w, h, spp, seed=seed, nee=(est != "cos"), uniform=(est == "uni"))
-        assert _md5_of_ppm(oracle, img, tmp_path, "c.ppm") == hashlib.md5(open(ref_path, "rb").read()).hexdigest()
+        assert _md5_of_ppm(oracle, img, tmp_path, "c.ppm") == want
 
 
 @pytest.mark.parametrize("w,h", [(64, 48), (256, 192)])
@@ -69,21 +78,17 @@ def test_compat_restatement_matches_reference_variants_md5(oracle, spt, tmp_path
     assert _md5_of_ppm(oracle, img, tmp_path, "c.ppm") == GOLD["reference_md5"][f"{w}x{h}_s4_seed1_{est}"]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_DIR, "smallpt_sph")),
-                    reason="oracle/_ref not built (reference absent)")
 @pytest.mark.parametrize("est", ["q05", "sph", "sph16"])
 def test_compat_variants_match_reference_binary_other_seeds(oracle, spt, tmp_path, est):
-    """The same variants against the live reference binaries at an odd size and other seeds, plus
-    their row-seeded (_xs) builds (the P2 fixture's runs)."""
+    """The same variants against the reference binaries' output at an odd size and other seeds
+    (recorded, and the live binaries too where they are built), plus their row-seeded (_xs) builds
+    (the P2 fixture's runs)."""
     prims = spt.spheres32_scene() if est.startswith("sph") else None
     kw = dict(prims=prims, qthr=0.5 if est == "q05" else 1.0, max_depth=16 if est == "sph16" else 0)
     for seed, xs in ((7, False), (9, True)):
-        ref_path = str(tmp_path / "ref.ppm")
-        subprocess.run([os.path.join(REF_DIR, f"smallpt_{est}" + ("_xs" if xs else "")), "33", "17",
-                        "5", str(seed), ref_path], check=True, cwd=str(tmp_path),
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        want = _reference_md5_other_seed(tmp_path, est + ("_xs" if xs else ""), 33, 17, 5, seed)
         img = oracle.compat_render(33, 17, 5, seed=seed, row_seed=xs, **kw)
-        assert _md5_of_ppm(oracle, img, tmp_path, "c.ppm") == hashlib.md5(open(ref_path, "rb").read()).hexdigest()
+        assert _md5_of_ppm(oracle, img, tmp_path, "c.ppm") == want
 
 
 def test_erand48_kat(oracle):
