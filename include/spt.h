@@ -25,9 +25,11 @@
 extern "C" {
 #endif
 
-#define SPT_ABI_VERSION 5 /* 2: spt_stats gained shadow_traced, sphere_vertices, flop_executed;
+#define SPT_ABI_VERSION 6 /* 2: spt_stats gained shadow_traced, sphere_vertices, flop_executed;
                              3: shadow_proven; 4: spt_gather_plan, spt_deinterleave_source,
-                             spt_gather_staging_floats, spt_shutdown; 5: SPT_FLAG_REFERENCE_LEAKS */
+                             spt_gather_staging_floats, spt_shutdown; 5: SPT_FLAG_REFERENCE_LEAKS;
+                             6: spt_kernel_count, spt_kernel_name, spt_select_kernel,
+                             spt_context_kernel */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -209,6 +211,33 @@ spt_status spt_render_async(spt_context* ctx, const spt_prim* prims, int32_t n_p
  * A render that hit the kernel's runaway-iteration guard returns SPT_ERR_HIP here and leaves its
  * rgb_dev all NaN (never a partial image). */
 spt_status spt_context_stats(spt_context* ctx, spt_stats* out);
+
+/* ---- which kernel runs ----
+ * A render launches one of spt_kernel_count() variants of the render kernel, all of which compute
+ * the same contract bit for bit; the host picks the most specialised one it can prove applicable
+ * to the scene, the camera and the params (capped by SPT_FLAG_KERNEL_LEVEL). These calls make that
+ * choice observable; none of them changes a render. */
+int32_t spt_kernel_count(void);
+/* "generic", "cornell", "const", "const_nee", ..., "uplight_cos_cam"; NULL for an id out of range. */
+const char* spt_kernel_name(int32_t id);
+typedef struct spt_kernel_choice {
+  int32_t kernel;        /* variant id in [0, spt_kernel_count()) */
+  int32_t leak_end;      /* 1 = leaked paths end at their first miss (contract v6's leak-end rule),
+                            0 = they go on as the reference's (SPT_FLAG_REFERENCE_LEAKS, or a scene
+                            the rule cannot be proven for) */
+  int32_t early_resolve; /* 1 = the variant resolves some NEE shadow rays without a trace
+                            (spt_stats.shadow_proven): the literal HEAD NEE kernels always, the sphere
+                            NEE kernels when the scene allows a threshold, the kernels with uploaded
+                            boxes when the room, the light and the boxes are within their clauses'
+                            margins; 0 = every shadow ray is traced */
+} spt_kernel_choice;
+/* The variant spt_render / spt_render_async would launch for these arguments. A pure host function:
+ * no device, no context; the same argument validation as a render. */
+spt_status spt_select_kernel(const spt_prim* prims, int32_t n_prims, const spt_camera* cam,
+                             const spt_params* p, spt_kernel_choice* out);
+/* Name of the variant of the context's last launch; NULL before any launch and after a render of a
+ * shard without rows. ctx == NULL: the calling thread's last spt_render() (which owns its context). */
+const char* spt_context_kernel(spt_context* ctx);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

@@ -1078,6 +1078,10 @@ static void c_find_early_clauses(c_ctx* C) {
       lo[ax] = R->k0 < R->k1 ? R->k0 : R->k1;
       hi[ax] = R->k0 < R->k1 ? R->k1 : R->k0;
       ok = ok && lo[ax] >= 0.0f && hi[ax] - lo[ax] <= 1000.0f;
+      /* a wall at -0.0 passes lo >= 0 with the bits 0x80000000: the span below would wrap and the
+         uint compare hold for every negative coordinate. +0.0 instead: a vertex at exactly -0.0
+         then fails the compare and is traced, which is exact */
+      if (lo[ax] == 0.0f) lo[ax] = 0.0f;
     }
     yl = L->k;
     ok = ok && L->ha >= 0.0f && L->hb >= 0.0f && L->ma - L->ha >= lo[0] + 1.0f &&
@@ -1113,6 +1117,8 @@ static int c_light_test_xz(const c_ctx* C, fv o, fv d, float* tt_out) {
   *tt_out = tt;
   return fabsf(a) <= L->ha && fabsf(b) <= L->hb && c_key(tt, C->light_pos) < C_KEY_NONE;
 }
+/* (The literal room below compares float bits against positive constants: a coordinate with the
+ * sign bit, -0.0 included, fails and is traced. Bounds taken from a scene: c_find_early_clauses.) */
 static int c_early_nee_proven(const c_ctx* C, fv o, fv d, float* tl) {
   const float tt = c_pt(81.5f, o.y, spt_oracle_rcp_nr(d.y));
   const float a = fmaf(d.x, tt, o.x - 50.0f), b = fmaf(d.z, tt, o.z - 79.5f);

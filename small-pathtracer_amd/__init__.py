@@ -87,6 +87,11 @@ class spt_stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class spt_kernel_choice(ctypes.Structure):
+    _fields_ = [("kernel", ctypes.c_int32), ("leak_end", ctypes.c_int32),
+                ("early_resolve", ctypes.c_int32)]
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -107,7 +112,8 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_comm_unique_id", "spt_comm_create", "spt_comm_destroy", "spt_comm_reserve",
            "spt_gather_framebuffer", "spt_deinterleave_rows", "spt_render_multi", "spt_shutdown",
            "spt_gather_plan", "spt_gather_staging_floats", "spt_deinterleave_source",
-           "spt_build_sources_sha16"]
+           "spt_build_sources_sha16", "spt_kernel_count", "spt_kernel_name", "spt_select_kernel",
+           "spt_context_kernel"]
 IMAGE_FORMATS = {"p3": 0, "p6": 1, "pfm": 2}
 FLAG_UNIFORM_SCATTER = 1  # spt_params.flags: random_scattering from the uniform code of :352-359
 # spt_params.flags: leaked paths go on from the miss vertex as the reference's (:371-377) instead of
@@ -192,6 +198,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_gather_staging_floats.restype = U64
     lib.spt_deinterleave_source.argtypes = [P(spt_params), I32, I32, P(I32), P(I32)]
     lib.spt_shutdown.argtypes = []
+    lib.spt_kernel_count.argtypes = []
+    lib.spt_kernel_count.restype = I32
+    lib.spt_kernel_name.argtypes = [I32]
+    lib.spt_kernel_name.restype = ctypes.c_char_p
+    lib.spt_select_kernel.argtypes = [P(spt_prim), I32, P(spt_camera), P(spt_params),
+                                      P(spt_kernel_choice)]
+    lib.spt_select_kernel.restype = I32
+    lib.spt_context_kernel.argtypes = [VP]
+    lib.spt_context_kernel.restype = ctypes.c_char_p
     for name in ("spt_comm_unique_id", "spt_comm_create", "spt_comm_destroy", "spt_comm_reserve",
                  "spt_gather_framebuffer", "spt_deinterleave_rows", "spt_render_multi",
                  "spt_deinterleave_source", "spt_shutdown"):
@@ -458,9 +473,33 @@ def _scene_array(prims: Sequence[spt_prim]):
     return arr
 
 
+def kernel_names() -> list:
+    """The render kernel's variants by id (spt_kernel_count / spt_kernel_name)."""
+    lib = load_library()
+    return [lib.spt_kernel_name(i).decode() for i in range(lib.spt_kernel_count())]
+
+
+def select_kernel(prims: Sequence[spt_prim], cam: Camera, params: spt_params) -> dict:
+    """spt_select_kernel(): the kernel variant a render of these arguments launches -- {"id", "name",
+    "leak_end", "early_resolve"}. A pure host function (no device)."""
+    lib = load_library()
+    ch = spt_kernel_choice()
+    _check(lib.spt_select_kernel(_scene_array(prims), len(prims), ctypes.byref(cam._c),
+                                 ctypes.byref(params), ctypes.byref(ch)))
+    return {"id": int(ch.kernel), "name": lib.spt_kernel_name(ch.kernel).decode(),
+            "leak_end": int(ch.leak_end), "early_resolve": bool(ch.early_resolve)}
+
+
+def _kernel_of(ctx) -> str | None:
+    name = load_library().spt_context_kernel(ctx)
+    return name.decode() if name is not None else None
+
+
 def render(prims: Sequence[spt_prim], cam: Camera, params: spt_params, return_stats=False):
     """Drop-in for :528-542: returns (rows, w, 3) float32 linear clamped RGB (rows = this shard's
-    rows, the whole image when shard_count == 1), y=0 top row. Runs on the GPU only."""
+    rows, the whole image when shard_count == 1), y=0 top row. Runs on the GPU only.
+    return_stats: also the spt_stats as a dict, plus "kernel": the name of the variant that ran
+    (None for a shard without rows)."""
     lib = load_library()
     rows = int(lib.spt_shard_rows(ctypes.byref(params), None, 0))
     out = np.empty((rows, params.width, 3), dtype=np.float32)
@@ -468,7 +507,11 @@ def render(prims: Sequence[spt_prim], cam: Camera, params: spt_params, return_st
     _check(lib.spt_render(_scene_array(prims), len(prims), ctypes.byref(cam._c),
                           ctypes.byref(params),
                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(st)))
-    return (out, st.as_dict()) if return_stats else out
+    if not return_stats:
+        return out
+    d = st.as_dict()
+    d["kernel"] = _kernel_of(None)
+    return out, d
 
 
 class Renderer:
@@ -506,6 +549,11 @@ class Renderer:
         st = spt_stats()
         _check(self.lib.spt_context_stats(self._ctx, ctypes.byref(st)))
         return st.as_dict()
+
+    def kernel(self) -> str | None:
+        """spt_context_kernel(): the variant of the last launch (None before any, and for a shard
+        without rows)."""
+        return _kernel_of(self._ctx)
 
 
 def render_multi(prims: Sequence[spt_prim], cam: Camera, params: spt_params, devices,

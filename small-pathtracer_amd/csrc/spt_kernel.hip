@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -794,6 +795,9 @@ __device__ __forceinline__ bool light_accepts(const SPT_CONST KParams* P, const 
 // Faces crossed beyond t_L fail their y bounds (y > 81.5 there) or lose to the light on t. The
 // oracle restates the predicate and checks it against its own intersect() (spt_oracle_proof_*,
 // tests/test_oracle.py); it covers ~77 % of the shadow rays that reach the light at C3.
+// (Compares on float bits: every bound here is a positive literal, so a coordinate with the sign
+// bit set -- negative, or -0.0 -- compares above it, fails and is traced; no signed zero reaches a
+// bound. The bounds that come from a scene are early_geo_setup's, which takes a zero as +0.0.)
 __device__ __forceinline__ int early_room_ok(f3 x) {
   return (int)(__float_as_uint(x.x) - __float_as_uint(1.0f) <=
                __float_as_uint(99.0f) - __float_as_uint(1.0f)) &
@@ -1772,6 +1776,14 @@ static const RenderFn kRenderKernels[KV_COUNT] = {
     render_kernel<TopoCornellUpBox, CfgHeadNeeCam>, render_kernel<TopoCornellUpBox, CfgHeadCosCam>,
     render_kernel<TopoCornellUpLight, CfgHeadNee>, render_kernel<TopoCornellUpLight, CfgHeadCos>,
     render_kernel<TopoCornellUpLight, CfgHeadNeeCam>, render_kernel<TopoCornellUpLight, CfgHeadCosCam>};
+// The variants' public names (spt_kernel_name, spt_context_kernel), in the enum's order.
+static const char* const kKernelNames[] = {
+    "generic", "cornell", "const", "const_nee", "const_cos", "sphdiff", "wide",
+    "sphdiff_nee", "rectdiff", "const_nee_ref", "const_cos_ref", "sphdiff_nee_ref",
+    "cornell_nee", "cornell_cos", "rectdiff_nee", "rectdiff_cos", "upbox_nee", "upbox_cos",
+    "const_nee_cam", "const_cos_cam", "upbox_nee_cam", "upbox_cos_cam", "uplight_nee",
+    "uplight_cos", "uplight_nee_cam", "uplight_cos_cam"};
+static_assert(sizeof kKernelNames / sizeof kKernelNames[0] == KV_COUNT, "one name per kernel variant");
 
 struct spt_context {
   int device = 0;
@@ -1802,6 +1814,7 @@ struct spt_context {
   KParams* h_kp = nullptr;   // pinned staging
   uint64_t samples = 0;      // pixel-samples of the last render (exact, not counted in-kernel)
   bool nee_by_identity = false;  // the last kernel derives nee_events from vertices - samples
+  int last_kv = -1;          // variant of the last launch (-1: none yet, or a shard without rows)
   double scene_flop = 0;     // FLOP-model cost of one ray against the scene
 };
 
@@ -1851,6 +1864,12 @@ static spt_status validate(const spt_prim* prims, int32_t n, const spt_camera* c
   return SPT_OK;
 }
 
+// max(c) of a primitive's fp32 colour: the Russian-roulette survival probability (:447)
+static float prim_pmax(const spt_prim& s) {
+  const float cx = (float)s.c[0], cy = (float)s.c[1], cz = (float)s.c[2];
+  return cx > cy && cx > cz ? cx : cy > cz ? cy : cz;
+}
+
 static void to_dev(const spt_prim* s, int n, DevPrim* out) {
   for (int i = 0; i < n; ++i) {
     DevPrim P;
@@ -1868,7 +1887,7 @@ static void to_dev(const spt_prim* s, int n, DevPrim* out) {
     }
     P.ex = (float)s[i].e[0]; P.ey = (float)s[i].e[1]; P.ez = (float)s[i].e[2];
     P.cx = (float)s[i].c[0]; P.cy = (float)s[i].c[1]; P.cz = (float)s[i].c[2];
-    P.pmax = P.cx > P.cy && P.cx > P.cz ? P.cx : P.cy > P.cz ? P.cy : P.cz;  // :447
+    P.pmax = prim_pmax(s[i]);
     P.ip = 1.0f / P.pmax;  // IEEE single division, as the device's 1.0f / p
     // u * 2^-16 < p (u < 2^16 an integer, p * 2^16 exact) <=> u < ceil(p * 2^16): the RR draw as
     // one integer compare instead of a conversion, a scale and a float compare (same decision)
@@ -2181,6 +2200,10 @@ static void early_geo_setup(const SceneGeo& g, int light_pos, bool on, KParams* 
     lo[ax] = std::min(R.k0, R.k1);
     hi[ax] = std::max(R.k0, R.k1);
     ok = ok && lo[ax] >= 0.0f && hi[ax] - lo[ax] <= 1000.0f;
+    // a wall at -0.0 passes lo >= 0 with the bits 0x80000000: the span below would wrap and the
+    // uint compare hold for every negative coordinate. +0.0 instead: a vertex at exactly -0.0 then
+    // fails the compare and is traced, which is exact
+    if (lo[ax] == 0.0f) lo[ax] = 0.0f;
   }
   const GeoRect& L = g.rect[light_pos];
   const float yl = L.k;
@@ -2212,6 +2235,189 @@ static void early_geo_setup(const SceneGeo& g, int light_pos, bool on, KParams* 
     K->er_lo[a] = blo;
     K->er_span[a] = btop - blo;
   }
+}
+
+// The kernel variant of a render, a pure host decision (no device, no context: spt_select_kernel
+// answers it for any validated scene, spt_render_async launches what it returns). g, light_pos: the
+// scene's grouped geometry (build_geo). Also sets what the variant runs under in *K: light_black,
+// leak_end, the sphere kernel's early_y0, the uploaded-geometry kernels' clauses (early_geo_setup)
+// and ul_ybits.
+static int select_variant(const spt_prim* prims, int n_prims, const spt_camera* cam_in,
+                          const spt_params* p, const SceneGeo& g, int light_pos, KParams* Kp) {
+  KParams& K = *Kp;
+  float cam[12];  // the kernel's fp32 camera (KParams::cam)
+  for (int i = 0; i < 3; ++i) {
+    cam[i] = (float)cam_in->origin[i];
+    cam[3 + i] = (float)cam_in->lower_left_corner[i];
+    cam[6 + i] = (float)cam_in->horizontal[i];
+    cam[9 + i] = (float)cam_in->vertical[i];
+  }
+  K.light_black = light_pos >= 0 && prim_pmax(prims[p->light_id]) == 0.0f ? 1 : 0;
+  // Topology specialisation: the HEAD Cornell box (6 XY, 5 XZ, 6 YZ rects, light at grouped
+  // position 8) runs a fully unrolled intersect; anything else the generic loops.
+  bool all_diff = true;
+  for (int i = 0; i < n_prims; ++i) all_diff = all_diff && prims[i].refl == SPT_DIFF;
+  // The HEAD-topology kernels are all-DIFF, cosine-scatter specialisations; anything else (SPEC/
+  // REFR, the uniform hemisphere) runs the generic kernel.
+  // spt_params.flags SPT_FLAG_KERNEL_LEVEL (A/B and tests; never changes results): cap the
+  // specialisation level. 0 = auto (the most specialised kernel the host can prove).
+  const uint32_t klevel = (p->flags & SPT_FLAG_KERNEL_LEVEL_MASK) >> 8;
+  const int kcap = klevel == SPT_KERNEL_LEVEL_GENERIC   ? 0
+                   : klevel == SPT_KERNEL_LEVEL_CORNELL ? 1
+                   : klevel == SPT_KERNEL_LEVEL_CONST   ? 2
+                                                        : 3;
+  const bool cornell = kcap >= 1 && all_diff && !(p->flags & SPT_FLAG_UNIFORM_SCATTER) &&
+                       g.n_xy == 6 && g.n_xz == 5 && g.n_yz == 6 && g.n_sph == 0 && light_pos == 8 &&
+                       g.n_txy == 0 && g.n_txz == 1 && g.n_tyz == 0 && g.has_room && g.n_box == 2;
+  const bool cconst = cornell && kcap >= 2 && cornell_const_match(g, light_pos);
+  // Estimator specialisations of the HEAD-geometry kernel (Cfg): the reference's own settings.
+  // axis-aligned camera (Cfg CAMAX): horizontal.y/z and vertical.x/z zero, origin nonzero
+  // (the contract-v5 terms L = llc - origin and Au_x, Av_y nonzero: the zero products then vanish
+  // exactly, see the kernel's camera ray)
+  bool cam_axis = cam[7] == 0.0f && cam[8] == 0.0f && cam[9] == 0.0f && cam[11] == 0.0f;
+  for (int c = 0; c < 3; ++c) cam_axis = cam_axis && (cam[3 + c] - cam[c]) != 0.0f;
+  cam_axis = cam_axis && cam[6] * (1.0f / (float)p->width) != 0.0f &&
+             cam[10] * (1.0f / (float)p->height) != 0.0f;
+  for (int i = 0; i < 12; ++i) cam_axis = cam_axis && std::isfinite(cam[i]);
+  const bool lref = p->rr_depth == kRefRrDepth && p->light_id == kRefLightId &&
+                    p->light_x0 == kRefLx0 && p->light_dx == 36.0f && p->light_z0 == kRefLz0 &&
+                    p->light_dz == 36.0f && p->light_y == kRefLy && p->light_area == kRefLarea;
+  K.leak_end = (p->flags & SPT_FLAG_REFERENCE_LEAKS) ? 0 : leak_end_of(prims, n_prims, g);
+  // (each estimator kernel in two forms: the leak-end rule, or leaked paths as the reference's)
+  const bool ref_est = K.light_black && p->max_depth == 0 && p->rr_depth >= 1 && cam_axis && lref;
+  const bool head_est = cconst && kcap >= 3 && ref_est;
+  // any other camera (finite): the literal kernels' CAMAX 2 forms (round 6; leak-end rule only)
+  bool cam_fin = true;
+  for (int i = 0; i < 12; ++i) cam_fin = cam_fin && std::isfinite(cam[i]);
+  const bool ref_est_cam = K.light_black && p->max_depth == 0 && p->rr_depth >= 1 && cam_fin && lref &&
+                           !cam_axis && K.leak_end;
+  const bool head_est_cam = cconst && kcap >= 3 && ref_est_cam;
+  const bool upbox_cam = cornell && !cconst && kcap >= 3 && ref_est_cam && cornell_room_match(g);
+  const bool wrap_nee = p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP;
+  // the HEAD topology with uploaded geometry (an edited rect[]: a box moved, a wall resized) and
+  // the reference's estimator: geometry from LDS, the estimator's branches compile-time
+  const bool cornell_est = cornell && !cconst && kcap >= 2 && ref_est && K.leak_end;
+  int kv = g.n_sph_wide > 0 ? KV_WIDE : KV_GENERIC;  // (only the wide kernel has the fp64 loop)
+  if (head_est && p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP)
+    kv = K.leak_end ? KV_CONST_NEE : KV_CONST_NEE_REF;
+  else if (head_est && p->nee_prob <= 0.0f) kv = K.leak_end ? KV_CONST_COS : KV_CONST_COS_REF;
+  else if (head_est_cam && wrap_nee) kv = KV_CONST_NEE_CAM;
+  else if (head_est_cam && p->nee_prob <= 0.0f) kv = KV_CONST_COS_CAM;
+  else if (cconst) kv = KV_CONST;
+  else if (upbox_cam && wrap_nee) kv = KV_UPBOX_NEE_CAM;
+  else if (upbox_cam && p->nee_prob <= 0.0f) kv = KV_UPBOX_COS_CAM;
+  else if (cornell_est && p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP) kv = KV_CORNELL_NEE;
+  else if (cornell_est && p->nee_prob <= 0.0f) kv = KV_CORNELL_COS;
+  else if (cornell) kv = KV_CORNELL;
+  else if (kv == KV_GENERIC && kcap >= 1 && all_diff && !(p->flags & SPT_FLAG_UNIFORM_SCATTER))
+    kv = g.n_sph == 0
+             // any other rect-only DIFF scene: run-time loops over the uploaded tests; with the
+             // reference's estimator its branches compile-time as well
+             ? (kcap >= 2 && ref_est && K.leak_end && p->nee_prob >= 1.0f &&
+                        p->light_mode == SPT_LIGHT_GLIBC_WRAP
+                    ? KV_RECTDIFF_NEE
+                    : kcap >= 2 && ref_est && K.leak_end && p->nee_prob <= 0.0f ? KV_RECTDIFF_COS
+                                                                                 : KV_RECTDIFF)
+         : kcap >= 3 && K.light_black && lref && p->nee_prob >= 1.0f &&
+                 p->light_mode == SPT_LIGHT_GLIBC_WRAP && light_pos >= 0 &&
+                 prims[p->light_id].kind == SPT_RECT_XZ
+             ? (K.leak_end ? KV_SPHDIFF_NEE : KV_SPHDIFF_NEE_REF)
+             : KV_SPHDIFF;
+  // the room HEAD's: the room literal, the boxes uploaded, the light literal when it is HEAD's too
+  const bool light_head = cornell_light_match(g, light_pos);
+  if (kv == KV_CORNELL_COS && kcap >= 3 && cornell_room_match(g)) kv = light_head ? KV_UPBOX_COS : KV_UPLIGHT_COS;
+  if (kv == KV_UPBOX_NEE_CAM && !light_head) kv = KV_UPLIGHT_NEE_CAM;
+  if (kv == KV_UPBOX_COS_CAM && !light_head) kv = KV_UPLIGHT_COS_CAM;
+  // The sphere NEE kernel's early resolve needs the HEAD room (rect[] :287-294, light at index 6)
+  // as prims 0..6, nothing else but narrow spheres, and a threshold above every sphere's top
+  // (early_room_proven); otherwise it stays off (+inf) and every shadow ray is traced.
+  K.early_y0 = INFINITY;
+  if ((kv == KV_SPHDIFF_NEE || kv == KV_SPHDIFF_NEE_REF) && n_prims > 7 && g.n_sph_wide == 0) {
+    spt_prim head[17];
+    int32_t nh = 0;
+    bool ok = spt_scene_cornell(head, 17, &nh) == SPT_OK;
+    for (int i = 0; ok && i < 7; ++i) ok = std::memcmp(&prims[i], &head[i], sizeof(spt_prim)) == 0;
+    double top = -INFINITY;
+    for (int i = 7; ok && i < n_prims; ++i) {
+      const double* g = prims[i].geom;
+      ok = prims[i].kind == SPT_SPHERE && std::isfinite(g[0]) && std::isfinite(g[1]) &&
+           std::isfinite(g[2]) && std::isfinite(g[3]);
+      top = std::max(top, g[2] + std::fabs(g[0]));
+      // the fp32 rounding argument of early_room_proven holds for |op| < 200 (and r < 200): every
+      // sphere centre within 190 of every room corner, so no vertex in the room is farther away
+      for (int c = 0; ok && c < 8; ++c) {
+        const double cx = (c & 1) ? 99.0 : 1.0, cy = (c & 2) ? 81.6 : 0.0, cz = (c & 4) ? 170.0 : 0.0;
+        ok = std::sqrt((g[1] - cx) * (g[1] - cx) + (g[2] - cy) * (g[2] - cy) +
+                       (g[3] - cz) * (g[3] - cz)) < 190.0 && std::fabs(g[0]) < 190.0;
+      }
+    }
+    if (ok && top + 1.0 < 81.0) {
+      float y0 = (float)(top + 1.0);
+      if ((double)y0 < top + 1.0) y0 = std::nextafter(y0, INFINITY);
+      K.early_y0 = y0;
+    }
+  }
+  // The uploaded-geometry HEAD-topology NEE kernel's early resolve (early_geo_proven): the room,
+  // the light and two boxes with the margins early_geo_setup checks, the clauses it picks (oracle
+  // c_find_early_clauses). Anything else: no clause, nothing resolved early.
+  early_geo_setup(g, light_pos, kv == KV_CORNELL_NEE || kv == KV_UPBOX_NEE_CAM || kv == KV_UPLIGHT_NEE_CAM, &K);
+  {
+    // (read only by the UPLIGHT NEE kernels, whose box clauses early_geo_setup leaves unsatisfiable
+    // unless the light plane lies >= 1 above the HEAD floor at +0: y_L >= 1, no sign bit)
+    const float yl = light_pos >= 0 ? g.rect[light_pos].k : 0.0f;
+    std::memcpy(&K.ul_ybits, &yl, 4);
+  }
+  // the room HEAD's: at the auto level the kernel with the room literal (the light, the boxes and
+  // the estimator's constants uploaded / literal); the const level keeps the uploaded-geometry one
+  if (kv == KV_CORNELL_NEE && kcap >= 3 && cornell_room_match(g)) kv = light_head ? KV_UPBOX_NEE : KV_UPLIGHT_NEE;
+  return kv;
+}
+
+// Does the variant resolve shadow rays without a trace under these parameters? The literal HEAD NEE
+// kernels always (early_nee_proven), the sphere NEE kernels with a finite threshold, the kernels
+// with uploaded boxes when early_geo_setup found the scene inside its margins (a clause is set).
+static int early_resolve_of(int kv, const KParams& K) {
+  switch (kv) {
+    case KV_CONST_NEE: case KV_CONST_NEE_REF: case KV_CONST_NEE_CAM:
+      return 1;
+    case KV_SPHDIFF_NEE: case KV_SPHDIFF_NEE_REF:
+      return std::isfinite(K.early_y0) ? 1 : 0;
+    case KV_CORNELL_NEE: case KV_UPBOX_NEE: case KV_UPBOX_NEE_CAM: case KV_UPLIGHT_NEE:
+    case KV_UPLIGHT_NEE_CAM:
+      return (K.er_span[0] | K.er_span[1] | K.er_span[2]) != 0 ? 1 : 0;
+    default:
+      return 0;
+  }
+}
+
+// Variant of the calling thread's last spt_render() launch (the one-shot call owns its context).
+static thread_local int g_dropin_kv = -1;
+
+extern "C" int32_t spt_kernel_count(void) { return KV_COUNT; }
+
+extern "C" const char* spt_kernel_name(int32_t id) {
+  return id >= 0 && id < KV_COUNT ? kKernelNames[id] : nullptr;
+}
+
+extern "C" spt_status spt_select_kernel(const spt_prim* prims, int32_t n_prims, const spt_camera* cam,
+                                        const spt_params* p, spt_kernel_choice* out) {
+  if (!out) return fail(SPT_ERR_INVALID_ARG, "null out");
+  spt_status st = validate(prims, n_prims, cam, p);
+  if (st != SPT_OK) return st;
+  std::unique_ptr<SceneGeo> g(new SceneGeo);
+  int light_pos = -1;
+  build_geo(prims, n_prims, g.get(), p->light_id, &light_pos);
+  KParams K{};
+  const int kv = select_variant(prims, n_prims, cam, p, *g, light_pos, &K);
+  out->kernel = kv;
+  out->leak_end = K.leak_end;
+  out->early_resolve = early_resolve_of(kv, K);
+  return SPT_OK;
+}
+
+extern "C" const char* spt_context_kernel(spt_context* c) {
+  const int kv = c ? c->last_kv : g_dropin_kv;
+  return kv >= 0 && kv < KV_COUNT ? kKernelNames[kv] : nullptr;
 }
 
 extern "C" spt_status spt_context_create(int32_t device, spt_context** out) {
@@ -2337,6 +2543,7 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
   if (rows == 0) {  // a shard that owns no rows (more shards than row tiles): nothing to render
     c->samples = 0;
     c->nee_by_identity = false;
+    c->last_kv = -1;
     c->scene_flop = 0;
     SPT_HIP(hipMemsetAsync(c->stats, 0, sizeof(unsigned long long) * kStatWords, stream));
     SPT_HIP(hipEventRecord(c->ev0, stream));
@@ -2349,123 +2556,8 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
     return SPT_OK;
   }
   K.n_local_pix = rows * p->width;
-  K.light_black = light_pos >= 0 && c->h_prims[p->light_id].pmax == 0.0f ? 1 : 0;
-  // Topology specialisation: the HEAD Cornell box (6 XY, 5 XZ, 6 YZ rects, light at grouped
-  // position 8) runs a fully unrolled intersect; anything else the generic loops.
-  const SceneGeo& g = *c->h_geo;
-  bool all_diff = true;
-  for (int i = 0; i < n_prims; ++i) all_diff = all_diff && prims[i].refl == SPT_DIFF;
-  // The HEAD-topology kernels are all-DIFF, cosine-scatter specialisations; anything else (SPEC/
-  // REFR, the uniform hemisphere) runs the generic kernel.
-  // spt_params.flags SPT_FLAG_KERNEL_LEVEL (A/B and tests; never changes results): cap the
-  // specialisation level. 0 = auto (the most specialised kernel the host can prove).
-  const uint32_t klevel = (p->flags & SPT_FLAG_KERNEL_LEVEL_MASK) >> 8;
-  const int kcap = klevel == SPT_KERNEL_LEVEL_GENERIC   ? 0
-                   : klevel == SPT_KERNEL_LEVEL_CORNELL ? 1
-                   : klevel == SPT_KERNEL_LEVEL_CONST   ? 2
-                                                        : 3;
-  const bool cornell = kcap >= 1 && all_diff && !(p->flags & SPT_FLAG_UNIFORM_SCATTER) &&
-                       g.n_xy == 6 && g.n_xz == 5 && g.n_yz == 6 && g.n_sph == 0 && light_pos == 8 &&
-                       g.n_txy == 0 && g.n_txz == 1 && g.n_tyz == 0 && g.has_room && g.n_box == 2;
-  const bool cconst = cornell && kcap >= 2 && cornell_const_match(g, light_pos);
-  // Estimator specialisations of the HEAD-geometry kernel (Cfg): the reference's own settings.
-  // axis-aligned camera (Cfg CAMAX): horizontal.y/z and vertical.x/z zero, origin nonzero
-  // (the contract-v5 terms L = llc - origin and Au_x, Av_y nonzero: the zero products then vanish
-  // exactly, see the kernel's camera ray)
-  bool cam_axis = K.cam[7] == 0.0f && K.cam[8] == 0.0f && K.cam[9] == 0.0f && K.cam[11] == 0.0f;
-  for (int c = 0; c < 3; ++c) cam_axis = cam_axis && (K.cam[3 + c] - K.cam[c]) != 0.0f;
-  cam_axis = cam_axis && K.cam[6] * (1.0f / (float)p->width) != 0.0f &&
-             K.cam[10] * (1.0f / (float)p->height) != 0.0f;
-  for (int i = 0; i < 12; ++i) cam_axis = cam_axis && std::isfinite(K.cam[i]);
-  const bool lref = p->rr_depth == kRefRrDepth && p->light_id == kRefLightId &&
-                    p->light_x0 == kRefLx0 && p->light_dx == 36.0f && p->light_z0 == kRefLz0 &&
-                    p->light_dz == 36.0f && p->light_y == kRefLy && p->light_area == kRefLarea;
-  K.leak_end = (p->flags & SPT_FLAG_REFERENCE_LEAKS) ? 0 : leak_end_of(prims, n_prims, g);
-  // (each estimator kernel in two forms: the leak-end rule, or leaked paths as the reference's)
-  const bool ref_est = K.light_black && p->max_depth == 0 && p->rr_depth >= 1 && cam_axis && lref;
-  const bool head_est = cconst && kcap >= 3 && ref_est;
-  // any other camera (finite): the literal kernels' CAMAX 2 forms (round 6; leak-end rule only)
-  bool cam_fin = true;
-  for (int i = 0; i < 12; ++i) cam_fin = cam_fin && std::isfinite(K.cam[i]);
-  const bool ref_est_cam = K.light_black && p->max_depth == 0 && p->rr_depth >= 1 && cam_fin && lref &&
-                           !cam_axis && K.leak_end;
-  const bool head_est_cam = cconst && kcap >= 3 && ref_est_cam;
-  const bool upbox_cam = cornell && !cconst && kcap >= 3 && ref_est_cam && cornell_room_match(g);
-  const bool wrap_nee = p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP;
-  // the HEAD topology with uploaded geometry (an edited rect[]: a box moved, a wall resized) and
-  // the reference's estimator: geometry from LDS, the estimator's branches compile-time
-  const bool cornell_est = cornell && !cconst && kcap >= 2 && ref_est && K.leak_end;
-  int kv = g.n_sph_wide > 0 ? KV_WIDE : KV_GENERIC;  // (only the wide kernel has the fp64 loop)
-  if (head_est && p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP)
-    kv = K.leak_end ? KV_CONST_NEE : KV_CONST_NEE_REF;
-  else if (head_est && p->nee_prob <= 0.0f) kv = K.leak_end ? KV_CONST_COS : KV_CONST_COS_REF;
-  else if (head_est_cam && wrap_nee) kv = KV_CONST_NEE_CAM;
-  else if (head_est_cam && p->nee_prob <= 0.0f) kv = KV_CONST_COS_CAM;
-  else if (cconst) kv = KV_CONST;
-  else if (upbox_cam && wrap_nee) kv = KV_UPBOX_NEE_CAM;
-  else if (upbox_cam && p->nee_prob <= 0.0f) kv = KV_UPBOX_COS_CAM;
-  else if (cornell_est && p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP) kv = KV_CORNELL_NEE;
-  else if (cornell_est && p->nee_prob <= 0.0f) kv = KV_CORNELL_COS;
-  else if (cornell) kv = KV_CORNELL;
-  else if (kv == KV_GENERIC && kcap >= 1 && all_diff && !(p->flags & SPT_FLAG_UNIFORM_SCATTER))
-    kv = g.n_sph == 0
-             // any other rect-only DIFF scene: run-time loops over the uploaded tests; with the
-             // reference's estimator its branches compile-time as well
-             ? (kcap >= 2 && ref_est && K.leak_end && p->nee_prob >= 1.0f &&
-                        p->light_mode == SPT_LIGHT_GLIBC_WRAP
-                    ? KV_RECTDIFF_NEE
-                    : kcap >= 2 && ref_est && K.leak_end && p->nee_prob <= 0.0f ? KV_RECTDIFF_COS
-                                                                                 : KV_RECTDIFF)
-         : kcap >= 3 && K.light_black && lref && p->nee_prob >= 1.0f &&
-                 p->light_mode == SPT_LIGHT_GLIBC_WRAP && light_pos >= 0 &&
-                 prims[p->light_id].kind == SPT_RECT_XZ
-             ? (K.leak_end ? KV_SPHDIFF_NEE : KV_SPHDIFF_NEE_REF)
-             : KV_SPHDIFF;
-  // the room HEAD's: the room literal, the boxes uploaded, the light literal when it is HEAD's too
-  const bool light_head = cornell_light_match(g, light_pos);
-  if (kv == KV_CORNELL_COS && kcap >= 3 && cornell_room_match(g)) kv = light_head ? KV_UPBOX_COS : KV_UPLIGHT_COS;
-  if (kv == KV_UPBOX_NEE_CAM && !light_head) kv = KV_UPLIGHT_NEE_CAM;
-  if (kv == KV_UPBOX_COS_CAM && !light_head) kv = KV_UPLIGHT_COS_CAM;
-  // The sphere NEE kernel's early resolve needs the HEAD room (rect[] :287-294, light at index 6)
-  // as prims 0..6, nothing else but narrow spheres, and a threshold above every sphere's top
-  // (early_room_proven); otherwise it stays off (+inf) and every shadow ray is traced.
-  K.early_y0 = INFINITY;
-  if ((kv == KV_SPHDIFF_NEE || kv == KV_SPHDIFF_NEE_REF) && n_prims > 7 && g.n_sph_wide == 0) {
-    spt_prim head[17];
-    int32_t nh = 0;
-    bool ok = spt_scene_cornell(head, 17, &nh) == SPT_OK;
-    for (int i = 0; ok && i < 7; ++i) ok = std::memcmp(&prims[i], &head[i], sizeof(spt_prim)) == 0;
-    double top = -INFINITY;
-    for (int i = 7; ok && i < n_prims; ++i) {
-      const double* g = prims[i].geom;
-      ok = prims[i].kind == SPT_SPHERE && std::isfinite(g[0]) && std::isfinite(g[1]) &&
-           std::isfinite(g[2]) && std::isfinite(g[3]);
-      top = std::max(top, g[2] + std::fabs(g[0]));
-      // the fp32 rounding argument of early_room_proven holds for |op| < 200 (and r < 200): every
-      // sphere centre within 190 of every room corner, so no vertex in the room is farther away
-      for (int c = 0; ok && c < 8; ++c) {
-        const double cx = (c & 1) ? 99.0 : 1.0, cy = (c & 2) ? 81.6 : 0.0, cz = (c & 4) ? 170.0 : 0.0;
-        ok = std::sqrt((g[1] - cx) * (g[1] - cx) + (g[2] - cy) * (g[2] - cy) +
-                       (g[3] - cz) * (g[3] - cz)) < 190.0 && std::fabs(g[0]) < 190.0;
-      }
-    }
-    if (ok && top + 1.0 < 81.0) {
-      float y0 = (float)(top + 1.0);
-      if ((double)y0 < top + 1.0) y0 = std::nextafter(y0, INFINITY);
-      K.early_y0 = y0;
-    }
-  }
-  // The uploaded-geometry HEAD-topology NEE kernel's early resolve (early_geo_proven): the room,
-  // the light and two boxes with the margins early_geo_setup checks, the clauses it picks (oracle
-  // c_find_early_clauses). Anything else: no clause, nothing resolved early.
-  early_geo_setup(g, light_pos, kv == KV_CORNELL_NEE || kv == KV_UPBOX_NEE_CAM || kv == KV_UPLIGHT_NEE_CAM, &K);
-  {
-    const float yl = light_pos >= 0 ? g.rect[light_pos].k : 0.0f;
-    std::memcpy(&K.ul_ybits, &yl, 4);
-  }
-  // the room HEAD's: at the auto level the kernel with the room literal (the light, the boxes and
-  // the estimator's constants uploaded / literal); the const level keeps the uploaded-geometry one
-  if (kv == KV_CORNELL_NEE && kcap >= 3 && cornell_room_match(g)) kv = light_head ? KV_UPBOX_NEE : KV_UPLIGHT_NEE;
+  // the kernel variant, with the early-resolve clauses and the leak-end rule it runs under
+  const int kv = select_variant(prims, n_prims, cam, p, *c->h_geo, light_pos, &K);
   // Unit size: SPT_UNITS_PER_LANE (8) units per resident lane (C3: 96 samples); never changes
   // results (integer accumulation). Round 1 chose 16 (25.0 ms vs 26.0 ms at 8 units/lane, before
   // in-wave stealing); re-measured in round 4 with stealing, unit slots and two frames in flight
@@ -2613,6 +2705,7 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
   SPT_HIP(hipEventRecord(c->ev2, stream));
   c->pending = true;
   c->launched = true;
+  c->last_kv = kv;
   return SPT_OK;
 }
 
@@ -2705,6 +2798,7 @@ extern "C" spt_status spt_render(const spt_prim* prims, int32_t n_prims, const s
   if (st != SPT_OK) return st;
   if (p->device < 0 || p->device >= kMaxDropInDevices) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
   const size_t n = 3ull * (size_t)spt_shard_row_count(p) * (size_t)p->width;
+  g_dropin_kv = -1;
   if (n == 0) {  // this shard owns no rows: nothing to render, no context or device memory
     if (stats) std::memset(stats, 0, sizeof *stats);
     return SPT_OK;
@@ -2727,6 +2821,7 @@ extern "C" spt_status spt_render(const spt_prim* prims, int32_t n_prims, const s
     D.out_cap = n;
   }
   st = spt_render_async(D.ctx, prims, n_prims, cam, p, D.out, nullptr);
+  if (st == SPT_OK) g_dropin_kv = D.ctx->last_kv;
   if (st == SPT_OK) {
     spt_stats tmp;
     st = spt_context_stats(D.ctx, stats ? stats : &tmp);

@@ -27,6 +27,16 @@ def _render_both(spt, oracle, prims, params, rows=None):
     return gpu, gst, cpu, cst
 
 
+def _assert_kernel(spt, gst, prims, p, want, cam=None):
+    """The launch ran the variant `want` (a literal at the call site), and spt_select_kernel, the
+    host-only query, names the same one: a scene that falls back to a less specialised kernel
+    computes the same bits, so only this shows it."""
+    if cam is None:
+        cam = spt.Camera(aspect=float(np.float32(p.width) / np.float32(p.height)))
+    assert gst["kernel"] == want, (gst["kernel"], want)
+    assert spt.select_kernel(prims, cam, p)["name"] == gst["kernel"]
+
+
 def _assert_exact(gpu, cpu):
     rmse = np.sqrt(((gpu.astype(np.float64) - cpu) ** 2).mean(axis=(0, 1)))
     assert (rmse < 1e-3).all(), rmse
@@ -86,18 +96,22 @@ def test_smallpt_classic_scene_bit_exact(spt, oracle, scene, case):
     _assert_exact(gpu, cpu)
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
     assert gpu.mean() > 0.05 and gst["misses"] == 0  # a closed box: light reaches the image
+    _assert_kernel(spt, gst, prims, p, "wide")
 
 
 @pytest.mark.parametrize("kernel", ["generic", "default"])
 @pytest.mark.parametrize("fl", [0, 1])
 def test_sphere_scene_bit_exact(spt, oracle, fl, kernel):
-    """The 32-sphere scene: by default the all-DIFF sphere kernel (TopoSphDiff), the generic kernel
-    when capped or with the uniform-hemisphere flag; same contract, same bits."""
+    """The 32-sphere scene: by default the all-DIFF sphere kernel's NEE form (TopoSphDiff, CfgSphNee:
+    the default params are the reference's estimator), the generic kernel when capped or with the
+    uniform-hemisphere flag; same contract, same bits."""
     kf = spt.kernel_flag("generic") if kernel == "generic" else 0
     p = spt.default_params(width=48, height=48, spp=8, seed=3, max_depth=16, flags=fl | kf)
     gpu, gst, cpu, cst = _render_both(spt, oracle, spt.spheres32_scene(), p)
     _assert_exact(gpu, cpu)
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+    _assert_kernel(spt, gst, spt.spheres32_scene(), p,
+                   "sphdiff_nee" if (kernel, fl) == ("default", 0) else "generic")
 
 
 @pytest.mark.parametrize("case", [
@@ -126,6 +140,9 @@ def test_every_kernel_specialisation_bit_exact(spt, oracle, kernel, est, q, fl):
     _assert_exact(gpu, cpu)
     assert hashlib.md5(gpu.tobytes()).hexdigest() == GOLD["counter_md5"][est]
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+    want = {"generic": "generic", "cornell": "cornell", "const": "const",
+            "head": {"nee": "const_nee", "cos": "const_cos"}[est]}[kernel]
+    _assert_kernel(spt, gst, spt.cornell_scene(), p, want)
 
 
 TILTED = dict(lookfrom=(40, 55, 160), lookat=(55, 35, 10), vup=(0.1, 1, 0))
@@ -138,8 +155,9 @@ def test_tilted_camera_bit_exact(spt, oracle, est, q, flags, scene):
     """A camera whose horizontal/vertical vectors are not axis-aligned (Camera :262-275 with another
     lookat and vup). Round 6: the literal kernels' any-camera forms (Cfg CAMAX 2: KV_CONST_*_CAM on
     the HEAD scene, KV_UPBOX_*_CAM with a box moved, KV_UPLIGHT_*_CAM with the light edited) keep
-    the early shadow-ray resolve; flags 4 (the reference's leaks) and the cornell cap (2 << 8) take the run-time camera
-    kernels. Same contract, same bits, and (NEE, auto) shadow rays resolved without a trace."""
+    the early shadow-ray resolve; flags 4 (the reference's leaks) and the cornell cap (2 << 8) take the
+    run-time camera kernels (KV_CONST with the leaks on the HEAD scene, KV_CORNELL otherwise). Same
+    contract, same bits, and (NEE, auto) shadow rays resolved without a trace."""
     import test_oracle as to
 
     prims = (spt.cornell_scene() if scene == "head" else
@@ -153,6 +171,11 @@ def test_tilted_camera_bit_exact(spt, oracle, est, q, flags, scene):
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
     if est == "nee":
         assert (gst["shadow_proven"] > 0) == (flags == 0), gst["shadow_proven"]
+    if flags == 0:
+        want = {"head": "const_", "movebox": "upbox_", "edited": "uplight_"}[scene] + est + "_cam"
+    else:
+        want = "const" if (scene, flags) == ("head", 4) else "cornell"
+    _assert_kernel(spt, gst, prims, p, want, cam)
 
 
 def test_specialisation_needs_all_diff(spt, oracle):
@@ -266,6 +289,7 @@ def test_early_nee_resolve_matches_oracle_proof(spt, oracle, seed, ref_leaks):
         assert gst[k] == cst[k], k
     assert bad == 0 and claims > 0.4 * cst["nee_light_hits"], (claims, bad, cst["nee_light_hits"])
     assert gst["shadow_proven"] == claims, (gst["shadow_proven"], claims)
+    _assert_kernel(spt, gst, spt.cornell_scene(), p, "const_nee_ref" if ref_leaks else "const_nee")
 
 
 @pytest.mark.parametrize("ref_leaks", [False, True])
@@ -286,16 +310,16 @@ def test_early_nee_resolve_spheres_matches_oracle_proof(spt, oracle, ref_leaks):
         assert gst[k] == cst[k], k
     assert bad == 0 and claims > 0, (claims, bad)
     assert gst["shadow_proven"] == claims, (gst["shadow_proven"], claims)
+    _assert_kernel(spt, gst, spt.spheres32_scene(), p, "sphdiff_nee_ref" if ref_leaks else "sphdiff_nee")
 
 
-@pytest.mark.parametrize("seed", [11, 12, 13, 14])
-def test_early_nee_resolve_random_low_spheres(spt, oracle, seed):
-    """Randomised sphere-only, all-DIFF scenes in the HEAD room (:287-294) whose spheres all lie
-    below y = 80 -- radii up to 99, centres below the floor and outside the room included: the host
-    enables the sphere kernel's early resolve above y0 = max top + 1 only when every centre is within
-    190 of every room corner (the fp32 rounding argument of early_room_proven). Enabled: the kernel's
-    count equals the oracle's claims, none contradicted by its own intersect; disabled: nothing is
-    resolved early. Image and statistics bit-exact either way."""
+LOW_SPHERE_SEEDS = [11, 12, 13, 14]
+
+
+def low_sphere_scene(spt, seed):
+    """(prims, near, y0): the HEAD room and light (:287-294) with 1-6 random DIFF spheres below
+    y = 80; near = every centre within 190 of every room corner; y0 = the fp32 threshold above the
+    highest top + 1."""
     rng = np.random.default_rng(seed)
     prims = list(spt.cornell_scene())[:7]
     tops, near = [], True
@@ -317,8 +341,20 @@ def test_early_nee_resolve_random_low_spheres(spt, oracle, seed):
     y0 = np.float32(max(tops) + 1.0)
     if float(y0) < max(tops) + 1.0:
         y0 = np.nextafter(y0, np.float32(np.inf))
+    return prims, near, float(y0)
+
+
+@pytest.mark.parametrize("seed", LOW_SPHERE_SEEDS)
+def test_early_nee_resolve_random_low_spheres(spt, oracle, seed):
+    """Randomised sphere-only, all-DIFF scenes in the HEAD room (:287-294) whose spheres all lie
+    below y = 80 -- radii up to 99, centres below the floor and outside the room included: the host
+    enables the sphere kernel's early resolve above y0 = max top + 1 only when every centre is within
+    190 of every room corner (the fp32 rounding argument of early_room_proven). Enabled: the kernel's
+    count equals the oracle's claims, none contradicted by its own intersect; disabled: nothing is
+    resolved early. Image and statistics bit-exact either way."""
+    prims, near, y0 = low_sphere_scene(spt, seed)
     params = spt.default_params(width=96, height=72, spp=8, seed=seed, max_depth=12)
-    oracle.proof_check(True, sphere_y0=float(y0))
+    oracle.proof_check(True, sphere_y0=y0)
     try:
         gpu, gst, cpu, cst = _render_both(spt, oracle, prims, params)
         claims, bad = oracle.proof_counts()
@@ -332,6 +368,8 @@ def test_early_nee_resolve_random_low_spheres(spt, oracle, seed):
         assert gst["shadow_proven"] == claims, (gst["shadow_proven"], claims)
     else:
         assert gst["shadow_proven"] == 0
+    _assert_kernel(spt, gst, prims, params, "sphdiff_nee")
+    assert spt.select_kernel(prims, spt.Camera(aspect=96 / 72), params)["early_resolve"] == near
 
 
 def test_c4_geometry_pixel_indices_beyond_2p24(spt, oracle):
@@ -518,8 +556,9 @@ def test_context_stats_before_any_render_is_an_error(spt):
 def test_leak_end_off_when_the_miss_vertex_emits(spt, oracle, nee):
     """Contract v6's leak-end rule needs a non-emitting prim 0 (a missed ray's vertex, :373-374):
     with an emissive front wall, leaked paths go on from the miss vertex as the reference's, on the
-    run-time HEAD kernel (the LREF kernels are launched only where the rule holds) -- the image and
-    statistics still equal the oracle's, and there are more misses than leaked paths."""
+    literal kernels' reference-leak forms (KV_CONST_NEE_REF / KV_CONST_COS_REF; the leak-end forms
+    are launched only where the rule holds) -- the image and statistics still equal the oracle's,
+    and there are more misses than leaked paths."""
     prims = list(spt.cornell_scene())
     prims[0].e[:] = [0.05, 0.05, 0.05]
     p = spt.default_params(width=48, height=36, spp=8, seed=4, nee_prob=nee)
@@ -527,6 +566,7 @@ def test_leak_end_off_when_the_miss_vertex_emits(spt, oracle, nee):
     _assert_exact(gpu, cpu)
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
     assert gst["misses"] / gst["samples"] > 0.1  # the reference's repeated misses, not first ones
+    _assert_kernel(spt, gst, prims, p, "const_nee_ref" if nee else "const_cos_ref")
 
 
 @pytest.mark.parametrize("kernel", ["head", "const", "generic"])
@@ -542,6 +582,9 @@ def test_reference_leaks_flag_bit_exact(spt, oracle, kernel, nee):
     gpu, gst, cpu, cst = _render_both(spt, oracle, spt.cornell_scene(), p)
     _assert_exact(gpu, cpu)
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+    want = {"head": "const_nee_ref" if nee else "const_cos_ref", "const": "const",
+            "generic": "generic"}[kernel]
+    _assert_kernel(spt, gst, spt.cornell_scene(), p, want)
     p0 = spt.default_params(width=64, height=48, spp=16, seed=1, nee_prob=nee,
                             flags=spt.kernel_flag(kernel))
     cam = spt.Camera(aspect=64 / 48)
@@ -580,6 +623,8 @@ def test_other_topology_rect_scene_bit_exact(spt, oracle, kernel, nee):
     gpu, gst, cpu, cst = _render_both(spt, oracle, prims, p)
     _assert_exact(gpu, cpu)
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+    want = "generic" if kernel == "generic" else ("rectdiff_nee" if nee else "rectdiff_cos")
+    _assert_kernel(spt, gst, prims, p, want)
 
 
 @pytest.mark.parametrize("kernel", ["auto", "const", "cornell"])
@@ -597,6 +642,9 @@ def test_edited_cornell_scene_bit_exact(spt, oracle, kernel, nee):
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
     base = spt.render(spt.cornell_scene(), spt.Camera(aspect=64 / 48), p)
     assert not np.array_equal(base, gpu)  # the edit is visible
+    est = "nee" if nee else "cos"
+    want = {"auto": "upbox_" + est, "const": "cornell_" + est, "cornell": "cornell"}[kernel]
+    _assert_kernel(spt, gst, prims, p, want)
 
 
 @pytest.mark.parametrize("scene", ["head", "light_tilted"])
@@ -618,9 +666,12 @@ def test_full_size_scheduling_never_changes_results(spt, flags, scene):
         prims = to.edited_scene(spt, light=dict(y=81.4))
         cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)), **TILTED)
     runs = []
+    want = {("head", 0): "const_nee", ("head", 4): "const_nee_ref",
+            ("light_tilted", 0): "uplight_nee_cam", ("light_tilted", 4): "cornell"}[scene, flags]
     for chunk in (0, 64):
         p = spt.default_params(width=w, height=h, spp=spp, seed=7, flags=flags, chunk=chunk)
         runs.append(spt.render(prims, cam, p, return_stats=True))
+        _assert_kernel(spt, runs[-1][1], prims, p, want, cam)
     (a, sa), (b, sb) = runs
     assert np.array_equal(a, b)
     assert {k: sa[k] for k in spt.STAT_KEYS} == {k: sb[k] for k in spt.STAT_KEYS}
@@ -648,14 +699,23 @@ def test_edited_scene_early_resolve_matches_oracle_proof(spt, oracle, edit, kern
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
     assert bad == 0 and claims > 0, (claims, bad)
     assert gst["shadow_proven"] == claims, (gst["shadow_proven"], claims)
+    _assert_kernel(spt, gst, prims, p, "upbox_nee" if kernel == "auto" else "cornell_nee")
+
+
+# The variant each test_oracle.EDITS_LR scene runs at the auto level: the light edited (the room
+# HEAD's) -> the room-literal kernel with the light uploaded; the room edited -> everything
+# uploaded; only a box edited -> the room and the light literal.
+EDITS_LR_AUTO = ["uplight_nee", "uplight_nee", "cornell_nee", "cornell_nee", "cornell_nee",
+                 "uplight_nee", "upbox_nee", "upbox_nee", "uplight_nee"]
 
 
 @pytest.mark.parametrize("kernel", ["auto", "const"])
 @pytest.mark.parametrize("edit", range(9))
 def test_edited_light_and_room_early_resolve_matches_oracle_proof(spt, oracle, edit, kernel):
     """Round 6: the light and the room edited as well (test_oracle.EDITS_LR). auto: the room HEAD's
-    -> the room-literal kernel with the light and boxes from LDS (KV_UPBOX_NEE), else the
-    uploaded-geometry one (KV_CORNELL_NEE); const: KV_CORNELL_NEE. Bit-exact image and statistics,
+    -> the room-literal kernel with the boxes from LDS and the light uploaded where it was edited
+    (KV_UPLIGHT_NEE; KV_UPBOX_NEE where only a box was), else the uploaded-geometry one
+    (KV_CORNELL_NEE), EDITS_LR_AUTO; const: KV_CORNELL_NEE. Bit-exact image and statistics,
     and the shadow rays resolved without a trace are exactly the oracle's claims (none where the
     scene is outside the clause margins)."""
     import test_oracle as to
@@ -673,12 +733,13 @@ def test_edited_light_and_room_early_resolve_matches_oracle_proof(spt, oracle, e
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
     assert bad == 0 and (claims > 0) == on, (claims, bad)
     assert gst["shadow_proven"] == claims, (gst["shadow_proven"], claims)
+    _assert_kernel(spt, gst, prims, p, EDITS_LR_AUTO[edit] if kernel == "auto" else "cornell_nee")
 
 
 @pytest.mark.parametrize("edit", [0, 1, 3])
 def test_edited_light_cosine_bit_exact(spt, oracle, edit):
-    """The cosine-only estimator on an edited light / room (KV_UPBOX_COS when the room is HEAD's,
-    KV_CORNELL_COS otherwise): equal to the oracle."""
+    """The cosine-only estimator on an edited light / room (KV_UPLIGHT_COS when the room is HEAD's
+    and the light is not, KV_CORNELL_COS with the room edited): equal to the oracle."""
     import test_oracle as to
 
     prims = to.edited_scene(spt, **to.EDITS_LR[edit][0])
@@ -686,6 +747,7 @@ def test_edited_light_cosine_bit_exact(spt, oracle, edit):
     gpu, gst, cpu, cst = _render_both(spt, oracle, prims, p)
     _assert_exact(gpu, cpu)
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+    _assert_kernel(spt, gst, prims, p, {0: "uplight_cos", 1: "uplight_cos", 3: "cornell_cos"}[edit])
 
 
 def test_material_edits_keep_the_literal_kernel(spt, oracle):
@@ -701,3 +763,177 @@ def test_material_edits_keep_the_literal_kernel(spt, oracle):
     _assert_exact(gpu, cpu)
     assert {k: gst[k] for k in spt.STAT_KEYS} == cst
     assert gst["shadow_proven"] > 0
+    _assert_kernel(spt, gst, prims, p, "const_nee")
+
+
+# ---- which kernel ran (tests/test_dispatch.py holds the table; the query needs no device) ----
+@pytest.mark.parametrize("name", [
+    "generic", "cornell", "const", "const_nee", "const_cos", "sphdiff", "wide", "sphdiff_nee",
+    "rectdiff", "const_nee_ref", "const_cos_ref", "sphdiff_nee_ref", "cornell_nee", "cornell_cos",
+    "rectdiff_nee", "rectdiff_cos", "upbox_nee", "upbox_cos", "const_nee_cam", "const_cos_cam",
+    "upbox_nee_cam", "upbox_cos_cam", "uplight_nee", "uplight_cos", "uplight_nee_cam",
+    "uplight_cos_cam"])
+def test_every_variant_runs_and_is_bit_exact(spt, oracle, name):
+    """One launch of every kernel variant (the first row of test_dispatch.TABLE that names it),
+    48x36 @ 8: the context reports that variant, and the image and statistics are the oracle's."""
+    import test_dispatch as td
+
+    assert sorted(td.ONE_PER_NAME) == sorted(spt.kernel_names())  # a new variant needs a row
+    prims, cam, p = td.recipe(spt, td.ONE_PER_NAME[name])
+    gpu, gst = spt.render(prims, cam, p, return_stats=True)
+    cpu, cst = oracle.counter_render(prims, cam._c, p)
+    assert gst["kernel"] == name
+    assert spt.select_kernel(prims, cam, p)["name"] == name
+    _assert_exact(gpu, cpu)
+    assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+
+
+def test_context_reports_its_last_launch(spt):
+    """spt_context_kernel: None before any launch and for a shard without rows, else the variant of
+    the last launch of that context."""
+    import torch
+
+    r = spt.Renderer(0)
+    try:
+        assert r.kernel() is None
+        out = torch.empty((12, 16, 3), dtype=torch.float32, device="cuda")
+        cam = spt.Camera(aspect=16 / 12)
+        for prims, want in ((spt.cornell_scene(), "const_nee"),
+                            (spt.drop_short_box(spt.cornell_scene()), "rectdiff_nee")):
+            r.render_async(prims, cam, spt.default_params(width=16, height=12, spp=2), out.data_ptr())
+            assert r.kernel() == want
+            r.stats()
+        p = spt.default_params(width=16, height=5, spp=2, shard_index=5, shard_count=8, tile_rows=4)
+        r.render_async(spt.cornell_scene(), spt.Camera(aspect=16 / 5), p, out.data_ptr())
+        assert r.stats()["samples"] == 0 and r.kernel() is None
+    finally:
+        r.close()
+    _, st = spt.render(spt.cornell_scene(), spt.Camera(aspect=16 / 5), p, return_stats=True)
+    assert st["kernel"] is None and st["samples"] == 0
+
+
+# Scheduling edges beyond the literal HEAD kernels: each topology has its own refill and retire
+# code (Topo / Cfg). (row of test_dispatch's recipes, expected variant)
+SCHED = {
+    "upbox_nee": ("movebox", False, dict(nee_prob=1.0)),
+    "uplight_nee_cam": ("edit_lr0", True, dict(nee_prob=1.0)),
+    "cornell_nee": ("movebox", False, dict(level="const", nee_prob=1.0)),
+    "rectdiff_nee": ("dropbox", False, dict(nee_prob=1.0)),
+    "sphdiff_nee": ("spheres32", False, dict(max_depth=12, nee_prob=1.0)),
+    "wide": ("smallpt_classic", False, dict(nee_prob=0.0)),
+}
+
+
+def _sched_case(spt, name, w, h, **size):
+    import test_dispatch as td
+
+    scene, tilted, kw = SCHED[name]
+    p = td.params(spt, **kw)
+    for k, v in dict(width=w, height=h, **size).items():
+        setattr(p, k, v)
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)), **(td.TILTED if tilted else {}))
+    return td.scene(spt, scene), cam, p
+
+
+@pytest.mark.parametrize("name", ["upbox_nee", "uplight_nee_cam", "cornell_nee", "rectdiff_nee",
+                                  "sphdiff_nee", "wide"])
+def test_in_wave_stealing_other_kernels(spt, oracle, name):
+    """test_in_wave_stealing_bit_exact's case (one unit per pixel on 2x2 pixels: four units for a
+    whole GPU, the samples spread by in-wave stealing alone) on the uploaded-box, uploaded-light,
+    uploaded-geometry, rect-only, sphere and wide-sphere kernels."""
+    prims, cam, p = _sched_case(spt, name, 2, 2, spp=2048, chunk=2048)
+    gpu, gst = spt.render(prims, cam, p, return_stats=True)
+    cpu, cst = oracle.counter_render(prims, cam._c, p)
+    assert gst["kernel"] == name
+    _assert_exact(gpu, cpu)
+    assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+
+
+@pytest.mark.parametrize("name", ["upbox_nee", "uplight_nee_cam", "cornell_nee", "rectdiff_nee",
+                                  "sphdiff_nee", "wide"])
+def test_small_shards_reassemble_other_kernels(spt, name):
+    """16x20 in 3 shards of 4-row tiles (shards of 8, 8 and 4 rows) on the same kernels: every shard
+    runs the variant of the whole image and the rows reassemble bitwise."""
+    prims, cam, p = _sched_case(spt, name, 16, 20)
+    full, fst = spt.render(prims, cam, p, return_stats=True)
+    assert fst["kernel"] == name
+    out = np.full_like(full, -1.0)
+    for k in range(3):
+        _, _, pk = _sched_case(spt, name, 16, 20, shard_index=k, shard_count=3, tile_rows=4)
+        img, st = spt.render(prims, cam, pk, return_stats=True)
+        assert st["kernel"] == name
+        out[spt.shard_rows(pk)] = img
+    assert np.array_equal(out, full)
+
+
+def _mat_geo_scene(spt, which):
+    """Material edits on top of geometry edits (the room-literal kernels compare geometry only)."""
+    import test_dispatch as td
+    import test_oracle as to
+
+    prims = td.recoloured(spt, spt.move_short_box(spt.cornell_scene(), 1.0))
+    if which == "light":
+        prims = spt.edit_light(prims, **to.EDITS_LR[0][0]["light"])
+    if which == "wall_emits":
+        prims[1].e[:] = [1.0, 1.0, 1.0]  # the back wall (:289)
+    return prims
+
+
+@pytest.mark.parametrize("est,q", [("nee", 1.0), ("cos", 0.0)])
+@pytest.mark.parametrize("which,kern,early", [
+    ("box", "upbox_", True),
+    ("light", "uplight_", True),
+    # An emitting back wall lies ON the room's box, not strictly inside it: the leak-end rule
+    # cannot be proven (leak_end_of), and every estimator-specialised uploaded-geometry kernel
+    # needs it. So the run-time Cornell kernel, which resolves nothing early.
+    ("wall_emits", None, False),
+])
+def test_material_and_geometry_edits_together(spt, oracle, which, kern, early, est, q):
+    """The short box moved 1 unit, the left wall blue and the light's emission 15 (and the light
+    moved; and the back wall emitting): the variant is picked from the geometry alone, materials
+    come from the uploaded primitives. Image and statistics the oracle's; with NEE, every shadow
+    ray resolved without a trace is one of the oracle's claims, none contradicted."""
+    prims = _mat_geo_scene(spt, which)
+    p = spt.default_params(width=64, height=48, spp=16, seed=27, nee_prob=q)
+    oracle.proof_check(True, edited=True)
+    try:
+        gpu, gst, cpu, cst = _render_both(spt, oracle, prims, p)
+        claims, bad = oracle.proof_counts()
+    finally:
+        oracle.proof_check(False)
+    _assert_exact(gpu, cpu)
+    assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+    _assert_kernel(spt, gst, prims, p, kern + est if kern else "cornell")
+    sel = spt.select_kernel(prims, spt.Camera(aspect=64 / 48), p)
+    assert sel["leak_end"] == (0 if which == "wall_emits" else 1)
+    assert sel["early_resolve"] == (early and est == "nee")
+    if est == "nee":
+        assert bad == 0 and claims > 0, (claims, bad)
+        assert gst["shadow_proven"] == (claims if early else 0), (gst["shadow_proven"], claims)
+    else:
+        assert gst["shadow_proven"] == 0
+
+
+@pytest.mark.parametrize("kernel", ["auto", "const"])
+@pytest.mark.parametrize("walls", ["front", "floor", "both"])
+def test_negative_zero_walls_bit_exact(spt, oracle, walls, kernel):
+    """The HEAD scene with the front wall's and / or the floor's plane at -0.0: not the literal room
+    (other bits), so KV_CORNELL_NEE with its room clause from KParams. The clause's lower bound is
+    taken as +0.0 (early_geo_setup); as -0.0 its span wrapped and vertices that had rounded through
+    the wall were resolved as lit (test_oracle's proof test has the counts). Image and statistics
+    the oracle's, the shadow rays resolved early exactly its claims, none contradicted."""
+    import test_dispatch as td
+
+    prims = td.neg_zero_walls(spt, front=walls in ("front", "both"), floor=walls in ("floor", "both"))
+    p = spt.default_params(width=96, height=72, spp=16, seed=7, flags=spt.kernel_flag(kernel))
+    oracle.proof_check(True, edited=True)
+    try:
+        gpu, gst, cpu, cst = _render_both(spt, oracle, prims, p)
+        claims, bad = oracle.proof_counts()
+    finally:
+        oracle.proof_check(False)
+    _assert_kernel(spt, gst, prims, p, "cornell_nee")
+    _assert_exact(gpu, cpu)
+    assert {k: gst[k] for k in spt.STAT_KEYS} == cst
+    assert bad == 0 and claims > 0, (claims, bad)
+    assert gst["shadow_proven"] == claims, (gst["shadow_proven"], claims)

@@ -574,6 +574,33 @@ def test_early_nee_resolve_proof_holds_edited_light_and_room(oracle, spt, edit):
         assert claims == 0 and st["nee_light_hits"] > 0, (claims, st["nee_light_hits"])
 
 
+@pytest.mark.parametrize("walls", ["front", "floor", "both"])
+def test_early_nee_resolve_proof_holds_negative_zero_walls(oracle, spt, walls):
+    """A room wall at -0.0 (the front wall's plane, prim 0; the floor's, prim 4) passes the clause
+    setup's lo >= 0 with the bits 0x80000000. Taken as they are, the room clause's span wraps and
+    the uint compare holds for every negative coordinate, so vertices that rounded through the wall
+    are claimed although the wall blocks them (128x96 @ 32, seed 7: 213 contradicted claims of
+    211,321 with the front wall at -0.0, 1,179 of 212,287 with the floor as well; 0 of 211,108 at
+    +0.0). c_find_early_clauses and the host's early_geo_setup take a zero bound as +0.0: the clause
+    stays on, and a vertex at exactly -0.0 fails the compare and is traced."""
+    import test_dispatch as td
+
+    prims = td.neg_zero_walls(spt, front=walls in ("front", "both"), floor=walls in ("floor", "both"))
+    assert np.signbit(prims[0].geom[4]) == (walls != "floor")
+    assert np.signbit(prims[4].geom[4]) == (walls != "front")
+    p = oracle.default_params(width=128, height=96, spp=32, seed=7)
+    assert oracle.scene_boxes(prims, p) == 2
+    oracle.proof_check(True, edited=True)
+    try:
+        _, st = oracle.counter_render(prims, oracle.camera(128 / 96), p)
+        claims, bad = oracle.proof_counts()
+    finally:
+        oracle.proof_check(False)
+    print(f"{walls}: {claims} claims, {bad} contradicted, {st['nee_light_hits']} light hits")
+    assert bad == 0, (claims, bad)
+    assert claims > 0.3 * st["nee_light_hits"], (claims, st["nee_light_hits"])
+
+
 def test_shadow_census_accounts_for_every_traced_shadow_ray(oracle):
     """The slot model's census (tools/shadow_census.py): every light-accepted shadow
     ray the HEAD early resolve does not prove is counted once, as reached or blocked, and the
