@@ -29,7 +29,9 @@ extern "C" {
                              3: shadow_proven; 4: spt_gather_plan, spt_deinterleave_source,
                              spt_gather_staging_floats, spt_shutdown; 5: SPT_FLAG_REFERENCE_LEAKS;
                              6: spt_kernel_count, spt_kernel_name, spt_select_kernel,
-                             spt_context_kernel */
+                             spt_context_kernel. Added since, with no change to an existing struct or
+                             entry point (so the version stays): SPT_HAS_FILM, the spt_film_* calls */
+#define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -238,6 +240,60 @@ spt_status spt_select_kernel(const spt_prim* prims, int32_t n_prims, const spt_c
 /* Name of the variant of the context's last launch; NULL before any launch and after a render of a
  * shard without rows. ctx == NULL: the calling thread's last spt_render() (which owns its context). */
 const char* spt_context_kernel(spt_context* ctx);
+
+/* ---- progressive rendering: sample windows and the resumable integer film (SPT_HAS_FILM) ----
+ * A render draws the sample indices [0, spp) of every pixel, converts each sample to 1.31 fixed point
+ * with the one scale 2^31 / spp and sums in uint64. A film keeps those sums on the device between
+ * launches: uint64[rows * w][3] in image pixel order (rows = the shard's compact rows, the row layout
+ * of rgb_dev). A pass renders the window [sample_base, sample_base + sample_count) of the SAME
+ * spp-sample image (the counter RNG is keyed by the absolute sample index, the scale stays
+ * 2^31 / spp) and adds it. Once every index of [0, spp) has been added exactly once, the film's sums
+ * are the one-shot render's, and its resolved image equals spt_render's bit for bit -- whatever the
+ * split, the order of the windows, the contexts, processes or GPUs that rendered them.
+ * Keeping the windows disjoint is the caller's duty: a film only counts samples (samples_done), it
+ * does not record which indices it holds, so that films filled elsewhere can be merged. Calls on one
+ * film must be serialised by the caller and enqueued on one stream (or ordered by the caller). */
+typedef struct spt_film spt_film;
+typedef struct spt_film_info {
+  int32_t width, rows, spp_total; /* rows = the shard's row count (the image's height unsharded) */
+  int64_t samples_done;           /* samples per pixel added so far, 0 .. spp_total */
+} spt_film_info;
+/* A zeroed film on `device` for renders with p's width, height, spp (= spp_total) and shard fields. */
+spt_status spt_film_create(int32_t device, const spt_params* p, spt_film** out);
+spt_status spt_film_destroy(spt_film* film);
+spt_status spt_film_info_get(const spt_film* film, spt_film_info* out);
+spt_status spt_film_clear(spt_film* film, void* stream); /* sums and samples_done back to 0 */
+/* Enqueue the render of the window on `stream` and its add into the film. p's width, height, spp
+ * and shard fields must equal the film's, the window must lie in [0, spp) with sample_count >= 1, and
+ * samples_done + sample_count must not exceed spp: SPT_ERR_INVALID_ARG otherwise, and a rejected call
+ * queues nothing and leaves the film untouched. rgb_dev_or_null: if given (DEVICE, rows*w*3 floats),
+ * the same pass also writes the film resolved after the add (what spt_film_resolve would give).
+ * ctx and film must be on one device. spt_context_stats(ctx) afterwards reports this pass alone
+ * (samples = pixels * sample_count; the integer fields of the passes sum to the one-shot's). A pass
+ * that hit the runaway-iteration guard adds nothing: the film's sums are unchanged, a given rgb_dev is
+ * all NaN, and spt_context_stats returns SPT_ERR_HIP and takes the pass out of samples_done. A shard
+ * without rows renders nothing (its film has no sums) and only counts the samples. */
+spt_status spt_film_render_async(spt_context* ctx, spt_film* film, const spt_prim* prims,
+                                 int32_t n_prims, const spt_camera* cam, const spt_params* p,
+                                 int32_t sample_base, int32_t sample_count, float* rgb_dev_or_null,
+                                 void* stream);
+/* Film -> float image (DEVICE, rows*w*3). A full film (samples_done == spp_total):
+ * min((float)sum * 2^-31, 1), the one-shot render's image. A partial one (a preview):
+ * min(((float)sum * 2^-31) * r, 1) with r = (float)((double)spp_total / samples_done), two separate
+ * multiplies. samples_done == 0: zeros. */
+spt_status spt_film_resolve(const spt_film* film, float* rgb_dev, void* stream);
+/* dst += src, dst.samples_done += src.samples_done: films of equal width, rows and spp_total on one
+ * device (a film from another process or GPU arrives through spt_film_upload). Rejected, with
+ * dst untouched, when they differ or the sum of their samples_done exceeds spp_total. */
+spt_status spt_film_merge(spt_film* dst, const spt_film* src, void* stream);
+/* The sums to and from HOST memory (rows*w*3 uint64, pixel order): a checkpoint. Both wait for their
+ * copy on `stream`, so the host buffer is complete (download) or free again (upload) on return. */
+spt_status spt_film_download(const spt_film* film, uint64_t* host_sums, void* stream);
+spt_status spt_film_upload(spt_film* film, const uint64_t* host_sums, int64_t samples_done,
+                           void* stream);
+/* The resolve as a pure host function (no device): the CPU statement of spt_film_resolve, for
+ * checkpoints and tests. Uses info's width, rows, spp_total and samples_done. */
+spt_status spt_film_resolve_host(const uint64_t* sums, const spt_film_info* info, float* rgb_out);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

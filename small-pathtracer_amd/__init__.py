@@ -92,6 +92,11 @@ class spt_kernel_choice(ctypes.Structure):
                 ("early_resolve", ctypes.c_int32)]
 
 
+class spt_film_info(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("rows", ctypes.c_int32), ("spp_total", ctypes.c_int32),
+                ("samples_done", ctypes.c_int64)]
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -113,7 +118,9 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_gather_framebuffer", "spt_deinterleave_rows", "spt_render_multi", "spt_shutdown",
            "spt_gather_plan", "spt_gather_staging_floats", "spt_deinterleave_source",
            "spt_build_sources_sha16", "spt_kernel_count", "spt_kernel_name", "spt_select_kernel",
-           "spt_context_kernel"]
+           "spt_context_kernel", "spt_film_create", "spt_film_destroy", "spt_film_info_get",
+           "spt_film_clear", "spt_film_render_async", "spt_film_resolve", "spt_film_merge",
+           "spt_film_download", "spt_film_upload", "spt_film_resolve_host"]
 IMAGE_FORMATS = {"p3": 0, "p6": 1, "pfm": 2}
 FLAG_UNIFORM_SCATTER = 1  # spt_params.flags: random_scattering from the uniform code of :352-359
 # spt_params.flags: leaked paths go on from the miss vertex as the reference's (:371-377) instead of
@@ -207,6 +214,21 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_select_kernel.restype = I32
     lib.spt_context_kernel.argtypes = [VP]
     lib.spt_context_kernel.restype = ctypes.c_char_p
+    I64 = ctypes.c_int64
+    lib.spt_film_create.argtypes = [I32, P(spt_params), P(VP)]
+    lib.spt_film_destroy.argtypes = [VP]
+    lib.spt_film_info_get.argtypes = [VP, P(spt_film_info)]
+    lib.spt_film_clear.argtypes = [VP, VP]
+    lib.spt_film_render_async.argtypes = [VP, VP, P(spt_prim), I32, P(spt_camera), P(spt_params),
+                                          I32, I32, VP, VP]
+    lib.spt_film_resolve.argtypes = [VP, VP, VP]
+    lib.spt_film_merge.argtypes = [VP, VP, VP]
+    lib.spt_film_download.argtypes = [VP, VP, VP]
+    lib.spt_film_upload.argtypes = [VP, VP, I64, VP]
+    lib.spt_film_resolve_host.argtypes = [VP, P(spt_film_info), VP]
+    for name in EXPORTS:
+        if name.startswith("spt_film_"):
+            getattr(lib, name).restype = I32
     for name in ("spt_comm_unique_id", "spt_comm_create", "spt_comm_destroy", "spt_comm_reserve",
                  "spt_gather_framebuffer", "spt_deinterleave_rows", "spt_render_multi",
                  "spt_deinterleave_source", "spt_shutdown"):
@@ -230,7 +252,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
 # profile committed under profiles/ can say which kernel it measured (bench.py omits hardware-counter
 # figures whose profile was taken on other sources).
 KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_device.h", "csrc/spt_cornell.h", "csrc/spt_diag.h",
-                  "csrc/Makefile", "../include/spt.h", "../include/spt_flops.h")
+                  "csrc/Makefile", "../include/spt.h", "../include/spt_flops.h", "csrc/spt_film.hip",
+                  "csrc/spt_film.h")
 
 
 def kernel_sources_sha16() -> str:
@@ -554,6 +577,177 @@ class Renderer:
         """spt_context_kernel(): the variant of the last launch (None before any, and for a shard
         without rows)."""
         return _kernel_of(self._ctx)
+
+
+# ---------------------------------------------------------------------------------------------
+# Progressive rendering: sample windows into a resumable integer film (spt_film_*)
+# ---------------------------------------------------------------------------------------------
+FILM_MAGIC = b"SPTFILM1"
+_FILM_HEADER = "<8siiiiq"  # magic, width, rows, spp_total, 0, samples_done: 32 bytes, then the sums
+
+
+def sample_windows(spp: int, passes: int) -> list:
+    """[0, spp) cut into `passes` near-equal windows [(base, count), ...] (empty ones dropped)."""
+    if passes < 1:
+        raise ValueError("passes must be >= 1")
+    edges = [spp * i // passes for i in range(passes + 1)]
+    return [(a, b - a) for a, b in zip(edges, edges[1:]) if b > a]
+
+
+def film_resolve_host(sums: np.ndarray, width: int, rows: int, spp_total: int,
+                      samples_done: int) -> np.ndarray:
+    """spt_film_resolve_host(): the CPU statement of the film's resolve (no device)."""
+    a = np.ascontiguousarray(sums, dtype=np.uint64)
+    info = spt_film_info(int(width), int(rows), int(spp_total), int(samples_done))
+    if a.size != 3 * max(info.rows, 0) * max(info.width, 0):
+        raise SptError(1, "sums do not have rows * width * 3 elements")
+    out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
+    _check(load_library().spt_film_resolve_host(a.ctypes.data, ctypes.byref(info), out.ctypes.data))
+    return out
+
+
+def write_film_file(path: str, sums: np.ndarray, width: int, rows: int, spp_total: int,
+                    samples_done: int) -> None:
+    """The film file: a 32-byte header (FILM_MAGIC, width, rows, spp_total, 0, samples_done; little
+    endian) and the rows * width * 3 sums as raw little-endian uint64."""
+    import struct
+    a = np.ascontiguousarray(sums, dtype="<u8")
+    if a.size != 3 * rows * width:
+        raise SptError(1, "sums do not have rows * width * 3 elements")
+    with open(path, "wb") as f:
+        f.write(struct.pack(_FILM_HEADER, FILM_MAGIC, width, rows, spp_total, 0, samples_done))
+        f.write(a.tobytes())
+
+
+def read_film_file(path: str):
+    """-> (sums (rows, width, 3) uint64, {"width", "rows", "spp_total", "samples_done"})."""
+    import struct
+    data = open(path, "rb").read()
+    n = struct.calcsize(_FILM_HEADER)
+    if len(data) < n:
+        raise SptError(1, f"{path}: not a film file")
+    magic, w, rows, spp, _, done = struct.unpack(_FILM_HEADER, data[:n])
+    if magic != FILM_MAGIC or w <= 0 or rows < 0 or spp <= 0 or not 0 <= done <= spp \
+            or len(data) != n + 24 * rows * w:
+        raise SptError(1, f"{path}: not a film file")
+    sums = np.frombuffer(data, dtype="<u8", offset=n).astype(np.uint64).reshape(rows, w, 3)
+    return sums, {"width": w, "rows": rows, "spp_total": spp, "samples_done": done}
+
+
+class Film:
+    """spt_film: the uint64 sums of the samples rendered so far, on the device. Passes over disjoint
+    sample windows of one spp-sample image add up to the one-shot render bit for bit."""
+
+    def __init__(self, params: spt_params, device: int = 0):
+        self.lib = load_library()
+        self._f = ctypes.c_void_p()
+        _check(self.lib.spt_film_create(int(device), ctypes.byref(params), ctypes.byref(self._f)))
+        self.device = device
+
+    def close(self):
+        if self._f:
+            self.lib.spt_film_destroy(self._f)
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def info(self) -> dict:
+        i = spt_film_info()
+        _check(self.lib.spt_film_info_get(self._f, ctypes.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in i._fields_}
+
+    def clear(self, stream_ptr: int = 0):
+        _check(self.lib.spt_film_clear(self._f, ctypes.c_void_p(stream_ptr or None)))
+
+    def render(self, renderer: "Renderer", prims, cam: Camera, params: spt_params, base: int,
+               count: int, rgb_dev_ptr: int = 0, stream_ptr: int = 0):
+        """Enqueue samples [base, base + count) of the params.spp-sample image and add them;
+        rgb_dev_ptr (optional): the film resolved after the add, written by the same pass."""
+        renderer._prims = _scene_array(prims)
+        _check(self.lib.spt_film_render_async(renderer._ctx, self._f, renderer._prims, len(prims),
+                                              ctypes.byref(cam._c), ctypes.byref(params), int(base),
+                                              int(count), ctypes.c_void_p(rgb_dev_ptr or None),
+                                              ctypes.c_void_p(stream_ptr or None)))
+
+    def resolve(self, rgb_dev_ptr: int = 0, stream_ptr: int = 0):
+        """Film -> float image. With rgb_dev_ptr: enqueued into that device buffer. Without: into a
+        buffer of this call's own, returned on the host as (rows, width, 3) float32."""
+        if rgb_dev_ptr:
+            _check(self.lib.spt_film_resolve(self._f, ctypes.c_void_p(rgb_dev_ptr),
+                                             ctypes.c_void_p(stream_ptr or None)))
+            return None
+        import torch
+        i = self.info()
+        with torch.cuda.device(self.device):
+            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
+                              device=f"cuda:{self.device}")
+            _check(self.lib.spt_film_resolve(self._f, ctypes.c_void_p(buf.data_ptr()),
+                                             ctypes.c_void_p(stream_ptr or None)))
+            torch.cuda.synchronize(self.device)
+        return buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+
+    def merge(self, other: "Film", stream_ptr: int = 0):
+        """self += other (equal width, rows, spp_total; one device)."""
+        _check(self.lib.spt_film_merge(self._f, other._f, ctypes.c_void_p(stream_ptr or None)))
+
+    def to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
+        """The sums on the host: (rows, width, 3) uint64."""
+        i = self.info()
+        out = np.zeros((i["rows"], i["width"], 3), dtype=np.uint64)
+        _check(self.lib.spt_film_download(self._f, out.ctypes.data,
+                                          ctypes.c_void_p(stream_ptr or None)))
+        return out
+
+    def from_numpy(self, sums: np.ndarray, samples_done: int, stream_ptr: int = 0):
+        """Replace the sums (rows * width * 3 uint64) and samples_done: resume from a checkpoint."""
+        i = self.info()
+        a = np.ascontiguousarray(sums, dtype=np.uint64)
+        if a.size != i["rows"] * i["width"] * 3:
+            raise SptError(1, "sums do not have rows * width * 3 elements")
+        _check(self.lib.spt_film_upload(self._f, a.ctypes.data, int(samples_done),
+                                        ctypes.c_void_p(stream_ptr or None)))
+
+    def save(self, path: str):
+        i = self.info()
+        write_film_file(path, self.to_numpy(), i["width"], i["rows"], i["spp_total"], i["samples_done"])
+
+
+def render_progressive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, passes,
+                       return_stats=False):
+    """params.spp samples rendered as several launches through a Film: `passes` = a number of
+    near-equal windows (sample_windows) or a list of (base, count). Returns the host image, equal to
+    render()'s bit for bit when the windows cover [0, spp) once; return_stats: also the integer
+    spt_stats fields summed over the passes (kernel_ms summed too)."""
+    import torch
+    windows = sample_windows(params.spp, passes) if isinstance(passes, int) else list(passes)
+    dev = params.device
+    r, film = Renderer(dev), Film(params, dev)
+    try:
+        i = film.info()
+        total = dict.fromkeys(STAT_KEYS + ["shadow_proven"], 0)
+        total["kernel_ms"] = 0.0
+        with torch.cuda.device(dev):
+            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
+                              device=f"cuda:{dev}")
+            stream = torch.cuda.current_stream().cuda_stream
+            for k, (base, count) in enumerate(windows):
+                last = k == len(windows) - 1
+                film.render(r, prims, cam, params, base, count, buf.data_ptr() if last else 0, stream)
+                st = r.stats()
+                for key in total:
+                    total[key] += st[key]
+            if not windows:
+                film.resolve(buf.data_ptr(), stream)
+            torch.cuda.synchronize(dev)
+        out = buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+    finally:
+        film.close()
+        r.close()
+    return (out, total) if return_stats else out
 
 
 def render_multi(prims: Sequence[spt_prim], cam: Camera, params: spt_params, devices,

@@ -13,16 +13,109 @@
 //   --devices N: row tiles sharded over GPUs 0..N-1, one RCCL gather to GPU 0 (spt_render_multi)
 //   --repeat N: render N times (spt_render keeps its device context between calls) and print
 //               each call's wall time beside its kernel time (tools/dropin_e2e.py)
+//   --passes K: render the SPP samples as K near-equal sample windows through a film (spt_film_*):
+//               the same file as without it, bit for bit
+//   --film PATH [--add N]: progressive rendering with a checkpoint. Loads the film PATH if it exists
+//               (it must match W H SPP; else starts empty), renders the next N samples of the SPP
+//               (default: all that remain; the film holds the samples [0, samples_done)), saves the
+//               film and writes the image resolved from it (a preview while samples remain). Fails
+//               when the film is full. Film file: 32-byte header (magic "SPTFILM1", int32 width,
+//               rows, spp_total, 0, int64 samples_done; little endian), then the raw uint64 sums.
 // Same scene, camera (:521), clamp/toInt and P3 output; the pixel loop is one spt_render() call.
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
+
+#include <hip/hip_runtime_api.h>
 
 #include "smallpt.hpp"
 
 using namespace smallpt_amd;
+
+namespace {
+
+struct FilmHeader {  // the film file's first 32 bytes (little endian)
+  char magic[8];
+  int32_t width, rows, spp_total, zero;
+  int64_t samples_done;
+};
+static_assert(sizeof(FilmHeader) == 32, "film file header");
+const char kFilmMagic[8] = {'S', 'P', 'T', 'F', 'I', 'L', 'M', '1'};
+
+void check(spt_status s) {
+  if (s != SPT_OK) throw std::runtime_error(std::string(spt_status_string(s)) + ": " + spt_last_error());
+}
+
+// SPP samples through a film: `passes` near-equal windows of the samples to render -- all of them,
+// or with film_path the next `add` after those the film file holds. Returns the DEVICE image.
+float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
+                   int passes, const char* film_path, int add, spt_stats* total) {
+  spt_context* ctx = nullptr;
+  spt_film* film = nullptr;
+  check(spt_context_create(p.device, &ctx));
+  check(spt_film_create(p.device, &p, &film));
+  spt_film_info info{};
+  check(spt_film_info_get(film, &info));
+  const size_t n = 3ull * (size_t)info.rows * (size_t)info.width;
+  std::vector<uint64_t> sums(n);
+  if (film_path) {
+    std::ifstream in(film_path, std::ios::binary);
+    if (in) {
+      FilmHeader h{};
+      in.read((char*)&h, sizeof h);
+      if (!in || std::memcmp(h.magic, kFilmMagic, 8) != 0)
+        throw std::runtime_error(std::string(film_path) + ": not a film file");
+      if (h.width != info.width || h.rows != info.rows || h.spp_total != info.spp_total)
+        throw std::runtime_error(std::string(film_path) + ": the film is not W H SPP");
+      in.read((char*)sums.data(), (std::streamsize)(n * sizeof(uint64_t)));
+      if (!in || in.peek() != std::ifstream::traits_type::eof())
+        throw std::runtime_error(std::string(film_path) + ": truncated or oversized film file");
+      check(spt_film_upload(film, sums.data(), h.samples_done, nullptr));
+      info.samples_done = h.samples_done;
+    }
+  }
+  const int left = p.spp - (int)info.samples_done;
+  if (left <= 0) throw std::runtime_error("the film is full: all SPP samples are in it");
+  if (add > left) throw std::runtime_error("--add asks for more samples than the film has room for");
+  const int todo = add > 0 ? add : left, base0 = (int)info.samples_done;
+  float* dev = nullptr;
+  if (hipMalloc(&dev, std::max<size_t>(n, 1) * sizeof(float)) != hipSuccess)
+    throw std::runtime_error("device allocation failed");
+  passes = std::max(1, passes);
+  std::memset(total, 0, sizeof *total);
+  for (int k = 0; k < passes; ++k) {
+    const int a = (int)((int64_t)todo * k / passes), b = (int)((int64_t)todo * (k + 1) / passes);
+    if (b == a) continue;
+    check(spt_film_render_async(ctx, film, scene.data(), (int32_t)scene.size(), &cam.abi(), &p,
+                                base0 + a, b - a, b == todo ? dev : nullptr, nullptr));
+    spt_stats st{};
+    check(spt_context_stats(ctx, &st));
+    total->samples += st.samples;
+    total->vertices += st.vertices;
+    total->kernel_ms += st.kernel_ms;
+  }
+  if (film_path) {
+    check(spt_film_download(film, sums.data(), nullptr));
+    check(spt_film_info_get(film, &info));
+    FilmHeader h{};
+    std::memcpy(h.magic, kFilmMagic, 8);
+    h.width = info.width; h.rows = info.rows; h.spp_total = info.spp_total;
+    h.samples_done = info.samples_done;
+    std::ofstream o(film_path, std::ios::binary | std::ios::trunc);
+    o.write((const char*)&h, sizeof h);
+    o.write((const char*)sums.data(), (std::streamsize)(n * sizeof(uint64_t)));
+    if (!o) throw std::runtime_error(std::string("cannot write ") + film_path);
+    std::cout << "FILM : " << info.samples_done << " / " << info.spp_total << " samples" << std::endl;
+  }
+  check(spt_film_destroy(film));
+  check(spt_context_destroy(ctx));
+  return dev;
+}
+
+}  // namespace
 
 int main(int argc, char* argv[]) {
   int pos[4] = {512, 512, 16, 1};  // :507-508 defaults, seed 1
@@ -30,6 +123,8 @@ int main(int argc, char* argv[]) {
   bool cosine = false, uniform = false, specular = false, classic = false, mirror_glass = false;
   bool spheres = false, ref_leaks = false;
   int device = 0, devices = 0, max_depth = 0, npos = 0, format = SPT_IMAGE_P3, repeat = 1;
+  int passes = 0, add = 0;
+  const char* film_path = nullptr;
   float q = -1.0f;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--cos")) cosine = true;
@@ -44,6 +139,9 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) devices = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--repeat") && i + 1 < argc) repeat = std::max(1, std::atoi(argv[++i]));
+    else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) passes = std::max(1, std::atoi(argv[++i]));
+    else if (!std::strcmp(argv[i], "--film") && i + 1 < argc) film_path = argv[++i];
+    else if (!std::strcmp(argv[i], "--add") && i + 1 < argc) add = std::max(1, std::atoi(argv[++i]));
     else if (!std::strcmp(argv[i], "--p6")) format = SPT_IMAGE_P6;
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
     else if (npos < 4) pos[npos++] = std::atoi(argv[i]);
@@ -62,12 +160,18 @@ int main(int argc, char* argv[]) {
   Camera cam(LOOKFROM, Vec(50, 40, 5), Vec(0, 1, 0), 65, float(p.width) / float(p.height));  // :521
   spt_stats st{};
   std::vector<float> c;
+  const float* image = nullptr;  // what the writer reads: c's data, or the film's device image
   try {
     const std::vector<spt_prim> scene = classic ? smallpt_classic_scene()
                                         : mirror_glass ? smallpt_mirror_glass_scene()
                                         : specular ? cornell_specular_scene()
                                         : spheres ? spheres32_scene()
                                                   : cornell_scene();
+    if (passes > 0 || film_path) {
+      if (devices > 0 || repeat > 1) throw std::runtime_error("--passes / --film go with one device and no --repeat");
+      image = render_film(scene, cam, p, passes, film_path, add, &st);
+      repeat = 0;
+    }
     for (int k = 0; k < repeat; ++k) {
       const auto c0 = std::chrono::high_resolution_clock::now();
       if (devices > 0) {
@@ -86,8 +190,9 @@ int main(int argc, char* argv[]) {
     std::cerr << "render failed: " << e.what() << std::endl;
     return 1;
   }
+  if (!image) image = c.data();
   const auto w0 = std::chrono::high_resolution_clock::now();
-  if (write_ppm(out, p.width, p.height, c.data(), device, format)) {
+  if (write_ppm(out, p.width, p.height, image, device, format)) {
     std::cerr << "cannot write " << out << ": " << spt_last_error() << std::endl;
     return 1;
   }

@@ -1,0 +1,39 @@
+// spt_film.h — what spt_kernel.hip (the render launch) and spt_film.hip (the film) share. Internal:
+// the public statement is include/spt.h.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "../../include/spt.h"
+
+// The resumable integer film: the 1.31 fixed-point sums of the samples rendered so far, in image
+// pixel order (the row layout of rgb_dev: a shard's film holds its compact rows).
+struct spt_film {
+  int device = 0;
+  int32_t width = 0, rows = 0, spp_total = 0;
+  int64_t samples_done = 0;
+  // the params the film was created for (a pass must bring the same ones)
+  int32_t height = 0, tile_rows = 0, shard_index = 0, shard_count = 1;
+  unsigned long long* sums = nullptr;  // [rows * width][3], device
+  size_t n = 0;                        // elements (3 * rows * width)
+  spt_context* last_ctx = nullptr;     // the context of the last pass (it takes a guarded pass back)
+};
+
+// spt_kernel.hip: one render launch over a sample window (film == nullptr: the one-shot finalize).
+spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
+                             const spt_camera* cam, const spt_params* p, int32_t s_base,
+                             int32_t s_count, float* rgb_dev, spt_film* film, void* stream);
+void spt_context_forget_film(spt_context* c, const spt_film* film);
+
+// spt_film.hip: enqueue the accumulate pass behind a render launch of `c` (the launch's stolen-range
+// sums, unit slots and statistics words) and count its s_count samples into the film.
+spt_status spt_film_accumulate(spt_film* film, spt_context* c, const unsigned long long* accum,
+                               const unsigned long long* slots, float* rgb_dev, uint32_t npix,
+                               uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
+                               const unsigned long long* stats, int32_t s_count, void* stream);
+// The pass of `c` hit the runaway guard and added nothing: samples_done goes back by s_count.
+void spt_film_rollback(spt_film* film, const spt_context* c, int32_t s_count);
+void spt_film_forget_context(spt_film* film, const spt_context* c);
+
+void spt_set_last_error(const std::string& msg);

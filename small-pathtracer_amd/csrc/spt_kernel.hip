@@ -36,6 +36,7 @@
 #include "spt_device.h"
 #include "spt_cornell.h"
 #include "spt_diag.h"
+#include "spt_film.h"
 
 #define SPT_STR_(x) #x
 #define SPT_XSTR(x) SPT_STR_(x)
@@ -176,7 +177,10 @@ struct KParams {  // in device memory, read through a laundered constant-space p
   const SceneGeo* geo;
   int n_prims;
   float cam[12];  // origin, lower_left_corner, horizontal, vertical
-  int width, height, spp;
+  int width, height, spp;  // spp: the whole image's sample count (fix_scale), not the launch's
+  // the launch's sample window [s_base, s_base + s_count) of those spp samples (s_lim = its end):
+  // one-shot renders launch [0, spp), a film pass (spt_film.hip) any window
+  uint32_t s_base, s_count, s_lim;
   uint32_t seed;
   float nee_prob;
   int rr_depth, max_depth, light_id;
@@ -1138,8 +1142,8 @@ render_kernel(const KParams* __restrict__ Pg) {
         // per-wave work varies less (the image does not change: every pixel-sample is still done
         // once and summed in integers)
         lp = (lp & ((1u << Q->scr_k) - 1u)) * Q->scr_q + (lp >> Q->scr_k);
-        s = j * (uint32_t)Q->chunk;
-        s_end = min(s + (uint32_t)Q->chunk, (uint32_t)Q->spp);
+        s = Q->s_base + j * (uint32_t)Q->chunk;  // absolute sample index: the Philox sample word
+        s_end = min(s + (uint32_t)Q->chunk, Q->s_lim);
         pixel_terms(Q, lp, pk, fx, fy);
         if constexpr (CF::CAMAX == 1) {  // the per-pixel P_x, P_y of the camera ray (jitter_f)
           fx = fmaf(ck.aux, fx, ck.lx);
@@ -1671,7 +1675,7 @@ render_kernel(const KParams* __restrict__ Pg) {
     }
     if (!TP::MAT && blockIdx.x == 0 && threadIdx.x == 0) {  // one camera ray per sample
       const SPT_CONST KParams* C = cptr(Pg);
-      const unsigned long long samples = (unsigned long long)C->n_local_pix * (unsigned long long)C->spp;
+      const unsigned long long samples = (unsigned long long)C->n_local_pix * (unsigned long long)C->s_count;
       atomicAdd(st + 1, samples);
       atomicAdd(st + 3, samples);
     }
@@ -1816,6 +1820,8 @@ struct spt_context {
   bool nee_by_identity = false;  // the last kernel derives nee_events from vertices - samples
   int last_kv = -1;          // variant of the last launch (-1: none yet, or a shard without rows)
   double scene_flop = 0;     // FLOP-model cost of one ray against the scene
+  spt_film* last_film = nullptr;  // the film of the last launch (nullptr: a plain render)
+  int32_t last_film_count = 0;    // ... and the samples that pass added to its samples_done
 };
 
 extern "C" int32_t spt_shard_rows(const spt_params* p, int32_t* rows_out, int32_t cap);
@@ -2483,6 +2489,7 @@ extern "C" spt_status spt_context_destroy(spt_context* c) {
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
   if (c->h_stats) (void)hipHostFree(c->h_stats);
+  if (c->last_film) spt_film_forget_context(c->last_film, c);
   delete c;
   return SPT_OK;
 }
@@ -2502,12 +2509,30 @@ extern "C" spt_status spt_context_reserve(spt_context* c, int32_t n_prims, const
   return SPT_OK;
 }
 
-extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, int32_t n_prims,
-                                       const spt_camera* cam, const spt_params* p, float* rgb_dev,
-                                       void* stream_v) {
-  if (!c || !rgb_dev) return fail(SPT_ERR_INVALID_ARG, "null context/output");
+// The film of the context's last launch and that film's last context name each other and nobody
+// else, so whichever is destroyed first can tell the other (spt_film_forget_context).
+static void set_last_film(spt_context* c, spt_film* film, int32_t count) {
+  if (c->last_film && c->last_film != film) spt_film_forget_context(c->last_film, c);
+  c->last_film = film;
+  c->last_film_count = count;
+}
+
+// One launch over the sample window [s_base, s_base + s_count) of the p->spp-sample image. With
+// film == nullptr the window's sums become the clamped floats of rgb_dev (finalize_slots_kernel:
+// the one-shot render, window [0, spp)); with a film they are added to it (spt_film.hip) and
+// rgb_dev, if given, receives the film resolved after the pass. Every size of the launch comes
+// from s_count; the fixed-point scale stays 2^31 / p->spp, so the windows' integers sum to the
+// one-shot's.
+spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
+                             const spt_camera* cam, const spt_params* p, int32_t s_base,
+                             int32_t s_count, float* rgb_dev, spt_film* film, void* stream_v) {
+  if (!c || (!rgb_dev && !film)) return fail(SPT_ERR_INVALID_ARG, "null context/output");
   spt_status st = validate(prims, n_prims, cam, p);
   if (st != SPT_OK) return st;
+  if (s_base < 0 || s_count < 1 || (int64_t)s_base + s_count > p->spp)
+    return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
+  if (film && film->device != c->device)
+    return fail(SPT_ERR_INVALID_ARG, "the film and the context are on different devices");
   st = spt_context_reserve(c, n_prims, p);
   if (st != SPT_OK) return st;
   SPT_HIP(hipSetDevice(c->device));
@@ -2531,6 +2556,7 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
     K.cam[9 + i] = (float)cam->vertical[i];
   }
   K.width = p->width; K.height = p->height; K.spp = p->spp;
+  K.s_base = (uint32_t)s_base; K.s_count = (uint32_t)s_count; K.s_lim = (uint32_t)(s_base + s_count);
   K.seed = p->seed;
   K.nee_prob = p->nee_prob; K.rr_depth = p->rr_depth; K.max_depth = p->max_depth;
   K.light_id = p->light_id;
@@ -2544,6 +2570,7 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
     c->samples = 0;
     c->nee_by_identity = false;
     c->last_kv = -1;
+    set_last_film(c, nullptr, 0);
     c->scene_flop = 0;
     SPT_HIP(hipMemsetAsync(c->stats, 0, sizeof(unsigned long long) * kStatWords, stream));
     SPT_HIP(hipEventRecord(c->ev0, stream));
@@ -2566,7 +2593,7 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
   // 11.68 / 11.70 ms -- fewer refills and retires, and the next frame fills the longer tail.
   int chunk = p->chunk;
   const double rays_per_sample = p->nee_prob > 0.0f ? 5.3 : 8.9;  // HEAD: NEE / cosine only
-  const double lane_iters = (double)K.n_local_pix * p->spp * rays_per_sample /
+  const double lane_iters = (double)K.n_local_pix * s_count * rays_per_sample /
                             ((double)c->n_cu * c->bpc[kv] * kBlock);
   const bool small_launch = lane_iters < SPT_SMALL_ITERS;
   // A short launch takes at most SPT_SMALL_BPC blocks per CU (half the chip's wave slots): its tail
@@ -2582,16 +2609,16 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
       // and let the in-wave stealing and guided grabs balance the rest (C2: chunk 23 -> 64,
       // 4.6 -> 4.0 ms; measured, scripts/ab_r02e.sh).
       const double units_per_pix = std::max(1.0, std::ceil(SPT_SMALL_UNITS * lanes / std::max(1, K.n_local_pix)));
-      chunk = (int)std::ceil(p->spp / units_per_pix);
+      chunk = (int)std::ceil(s_count / units_per_pix);
     } else {
       // SPT_UNITS_PER_LANE units per resident lane (above)...
       const double per_pix = std::max(1.0, SPT_UNITS_PER_LANE * lanes / std::max(1, K.n_local_pix));
-      chunk = (int)std::max(4.0, std::ceil(p->spp / per_pix));
+      chunk = (int)std::max(4.0, std::ceil(s_count / per_pix));
     }
     // ...but a unit should last >= ~200 lane-iterations: every unit costs a refill (~35 VALU +
     // ~40 SALU for the whole wave) and a retire (C2: 6 -> 23 samples per unit, 4.73 -> ~4.6 ms).
     chunk = std::max(chunk, (int)std::ceil(200.0 / rays_per_sample));
-    chunk = std::min(chunk, p->spp);
+    chunk = std::min(chunk, s_count);
   }
   {
     const uint32_t waves = (uint32_t)(c->n_cu * bpc * (kBlock / 64));
@@ -2604,7 +2631,7 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
   K.young_block = 0xFFFFFFFFu;
   K.young_cut = 0xFFFFFFFFu;
   K.steal_min = small_launch ? SPT_STEAL_MIN_SMALL : SPT_STEAL_MIN;
-  const uint64_t n_chunks = ((uint64_t)p->spp + chunk - 1) / chunk;
+  const uint64_t n_chunks = ((uint64_t)s_count + chunk - 1) / chunk;
   const uint64_t n_units = n_chunks * (uint64_t)K.n_local_pix;
   if (n_units >= 0x80000000ull) return fail(SPT_ERR_INVALID_ARG, "too many work units; raise chunk");
   K.n_units = (uint32_t)n_units;
@@ -2669,7 +2696,7 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
   K.nee_c = (float)((double)p->light_area / 3.14159265358979323846);
   c->n_prims = n_prims;
   c->last = K;
-  c->samples = (uint64_t)K.n_local_pix * (uint64_t)p->spp;
+  c->samples = (uint64_t)K.n_local_pix * (uint64_t)s_count;
   c->scene_flop = 0;
   for (int i = 0; i < n_prims; ++i)
     c->scene_flop += prims[i].kind == SPT_SPHERE ? SPT_FLOP_SPHERE : SPT_FLOP_RECT;
@@ -2695,11 +2722,18 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
   SPT_HIP(hipGetLastError());
   SPT_HIP(hipEventRecord(c->ev1, stream));
   const uint32_t np = (uint32_t)K.n_local_pix;
-  hipLaunchKernelGGL(finalize_slots_kernel, dim3((np + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
-                     (const unsigned long long*)c->accum, (const unsigned long long*)c->slots,
-                     rgb_dev, np, (uint32_t)n_chunks, K.scr_k, K.scr_q,
-                     (const unsigned long long*)c->stats);
-  SPT_HIP(hipGetLastError());
+  if (film) {  // add the window's sums to the film (and resolve it into rgb_dev, if given)
+    st = spt_film_accumulate(film, c, c->accum, c->slots, rgb_dev, np, (uint32_t)n_chunks, K.scr_k,
+                             K.scr_q, c->stats, s_count, stream);
+    if (st != SPT_OK) return st;
+  } else {
+    hipLaunchKernelGGL(finalize_slots_kernel, dim3((np + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
+                       (const unsigned long long*)c->accum, (const unsigned long long*)c->slots,
+                       rgb_dev, np, (uint32_t)n_chunks, K.scr_k, K.scr_q,
+                       (const unsigned long long*)c->stats);
+    SPT_HIP(hipGetLastError());
+  }
+  set_last_film(c, film, film ? s_count : 0);
   SPT_HIP(hipMemcpyAsync(c->h_stats, c->stats, sizeof(unsigned long long) * kStatWords,
                          hipMemcpyDeviceToHost, stream));
   SPT_HIP(hipEventRecord(c->ev2, stream));
@@ -2707,6 +2741,19 @@ extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, in
   c->launched = true;
   c->last_kv = kv;
   return SPT_OK;
+}
+
+extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, int32_t n_prims,
+                                       const spt_camera* cam, const spt_params* p, float* rgb_dev,
+                                       void* stream) {
+  if (!c || !rgb_dev) return fail(SPT_ERR_INVALID_ARG, "null context/output");
+  if (!p) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  return spt_render_window(c, prims, n_prims, cam, p, 0, p->spp, rgb_dev, nullptr, stream);
+}
+
+// A film whose last pass this context rendered is going away (spt_film_destroy).
+void spt_context_forget_film(spt_context* c, const spt_film* film) {
+  if (c && c->last_film == film) c->last_film = nullptr;
 }
 
 extern "C" spt_status spt_context_stats(spt_context* c, spt_stats* out) {
@@ -2740,6 +2787,9 @@ extern "C" spt_status spt_context_stats(spt_context* c, spt_stats* out) {
 #endif
   if (h[0] != 0) {
     c->pending = false;
+    // a film pass that hit the guard added nothing (spt_film.hip): take its samples back
+    if (c->last_film) spt_film_rollback(c->last_film, c, c->last_film_count);
+    set_last_film(c, nullptr, 0);
     return fail(SPT_ERR_HIP, "render kernel hit its iteration cap in " + std::to_string(h[0]) +
                                  " waves (a path did not terminate); the image is incomplete");
   }
