@@ -285,6 +285,81 @@ def sincos2pi(xi: float):
     return s.value, c.value
 
 
+def intersect_batch(prims, params, o, d):
+    """The contract's nearest hit (c_intersect) for rays o, d: (n, 3) float32 each. Returns
+    (t float32 (n,), id int32 (n,)); a miss is t = 1e20, id = -1."""
+    o = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    assert o.shape == d.shape
+    arr = (_spt.spt_prim * len(prims))(*prims)
+    t = np.empty(len(o), dtype=np.float32)
+    ids = np.empty(len(o), dtype=np.int32)
+    L = lib()
+    L.spt_oracle_intersect_batch.argtypes = [
+        ctypes.POINTER(_spt.spt_prim), ctypes.c_int, ctypes.POINTER(_spt.spt_params),
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    rc = L.spt_oracle_intersect_batch(arr, len(prims), ctypes.byref(params), o.ctypes.data,
+                                      d.ctypes.data, len(o), t.ctypes.data, ids.ctypes.data)
+    assert rc == 0
+    return t, ids
+
+
+def zero_dir_counts() -> tuple:
+    """(rays traced with an exactly zero direction component, of those missed) by c_intersect since
+    the last call (spt_oracle_zero_dir_counts); resets the counts."""
+    out = (ctypes.c_uint64 * 2)()
+    lib().spt_oracle_zero_dir_counts(out)
+    return int(out[0]), int(out[1])
+
+
+# spt_oracle_map's ops, in the order of its enum
+MAP_OPS = ["rcp_nr", "rsq_nr", "rsq_nr1", "rsq_nr2", "u01", "u16i", "u16", "jitter", "disk_dir",
+           "cosine", "fix", "philox", "normalize", "normalize_free"]
+
+
+def map_words(op: str, words) -> np.ndarray:
+    """spt_oracle_map: the contract's building block `op` (MAP_OPS) over an (n, width_in) uint32
+    array -- floats as their bits -- giving (n, width_out) uint32."""
+    L = lib()
+    L.spt_oracle_map.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+    k = MAP_OPS.index(op)
+    wi, wo = L.spt_oracle_map_width(k, 0), L.spt_oracle_map_width(k, 1)
+    a = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, wi)
+    out = np.empty((len(a), wo), dtype=np.uint32)
+    assert L.spt_oracle_map(k, a.ctypes.data, out.ctypes.data, len(a)) == 0
+    return out
+
+
+def map_f32(op: str, x) -> np.ndarray:
+    """rcp_nr / rsq_nr / rsq_nr1 / rsq_nr2 of a float32 array, as float32."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    return map_words(op, x.view(np.uint32)).view(np.float32).reshape(x.shape)
+
+
+def disk_dir_batch(ra):
+    """(cos, sin) float32 arrays of the contract's azimuth for the words ra."""
+    r = map_words("disk_dir", ra).view(np.float32)
+    return r[:, 0], r[:, 1]
+
+
+def cosine_batch(nl, ra, rb, uniform: bool, unit: bool) -> np.ndarray:
+    """c_cosine (normalized) for the normal nl (3 floats) and word pairs (ra, rb): (n, 3) float32."""
+    ra = np.ascontiguousarray(ra, dtype=np.uint32)
+    w = np.empty((len(ra), 6), dtype=np.uint32)
+    w[:, :3] = np.asarray(nl, dtype=np.float32).view(np.uint32)
+    w[:, 3], w[:, 4], w[:, 5] = ra, rb, int(bool(uniform)) | (int(bool(unit)) << 1)
+    return map_words("cosine", w).view(np.float32)
+
+
+def fix_batch(L, inv_spp) -> np.ndarray:
+    """c_fix(L, inv_spp) for float32 arrays: uint32."""
+    L = np.ascontiguousarray(L, dtype=np.float32)
+    w = np.empty((len(L), 2), dtype=np.uint32)
+    w[:, 0] = L.view(np.uint32)
+    w[:, 1] = np.broadcast_to(np.asarray(inv_spp, dtype=np.float32), L.shape).copy().view(np.uint32)
+    return map_words("fix", w)[:, 0]
+
+
 def threads() -> int:
     return lib().spt_oracle_threads()
 

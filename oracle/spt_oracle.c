@@ -515,7 +515,8 @@ float spt_oracle_rsq_nr2(float x) {
   return y;
 }
 /* Contract v7: the free-scale contract's normalize of the path directions takes ONE Newton step
- * (relative error < 1.8e-3, from below; rounds 1-4 took two). The scale places no geometry, it
+ * (relative error < 1.8e-3, from below up to its own roundings: at most 1.25e-7 above the root,
+ * tests/test_contract_math.py; rounds 1-4 took two). The scale places no geometry, it
  * only moves the roundings behind the self-hit / leak statistics: measured on this oracle, 128x96
  * @ 16, 12 seeds, NEE, first misses +0.25 % (0.6 sigma); with the bare seed (3.4e-2) +2.3 % (5
  * sigma), so not that. The cosine sample's R keeps two steps: its error biases the sampled
@@ -1228,7 +1229,32 @@ void spt_oracle_proof_counts(uint64_t out[2]) {
  *  - spheres: key(t, position) of the nearest root beyond the epsilon (0 = no root, ranked last).
  * The hit's t is the winner's own t, recomputed from its plane / sphere (the same bits as in its
  * key). id is left untouched on a miss; returns 1 on hit, *t = 1e20f on a miss. */
+/* rcp_nr(+-0) is NaN. A single rectangle (or pair) parallel to the ray gets a NaN distance, fails its
+ * in-plane compares and is not hit, like 1/0 = inf. The room and box slabs below take min / max over
+ * all three axes' keys as signed integers, so one NaN axis voids the whole slab: a ray with an
+ * exactly zero direction component misses the room and every box altogether (here the NaN is
+ * x86's 0xFFC00000: en <= ex holds and the candidate ranks above C_KEY_NONE; a positive NaN makes
+ * en > ex; both end in no hit). DESIGN.md section 3 "Zero direction components";
+ * tests/test_contract_rays.py F2. spt_oracle_zero_dir_counts counts such rays (test hook). */
+static uint64_t g_zero_dir[2]; /* traced rays with a zero direction component; of those, missed */
+void spt_oracle_zero_dir_counts(uint64_t out[2]) { /* since the last call; resets */
+  int i;
+  for (i = 0; i < 2; i++) { out[i] = g_zero_dir[i]; g_zero_dir[i] = 0; }
+}
+static int c_intersect_1(const c_ctx* C, fv o, fv d, float* t, int* id);
 static int c_intersect(const c_ctx* C, fv o, fv d, float* t, int* id) {
+  const int hit = c_intersect_1(C, o, d, t, id);
+  if (d.x == 0.0f || d.y == 0.0f || d.z == 0.0f) { /* ~2^-21 of the rays: the atomics are rare */
+#pragma omp atomic
+    g_zero_dir[0]++;
+    if (!hit) {
+#pragma omp atomic
+      g_zero_dir[1]++;
+    }
+  }
+  return hit;
+}
+static int c_intersect_1(const c_ctx* C, fv o, fv d, float* t, int* id) {
   const float ix = spt_oracle_rcp_nr(d.x), iy = spt_oracle_rcp_nr(d.y), iz = spt_oracle_rcp_nr(d.z);
   uint32_t tmin = C_KEY_NONE;
   int i, pos;
@@ -1640,6 +1666,63 @@ static fv c_path(const c_ctx* C, uint32_t pix, uint32_t s, int px, int py, const
 static inline uint64_t c_fix(float L, float inv_spp) {
   const float v = fminf(L * inv_spp, 1.0f) * 2147483648.0f;
   return v >= 0.0f ? (uint64_t)(uint32_t)v : 0u;
+}
+
+/* Test hook: the contract's scalar building blocks over arrays of 32-bit words (floats travel as
+ * their bits), so a 2^24-point sweep is one call. Element i reads spt_oracle_map_width(op, 0) words
+ * at in + i * that and writes spt_oracle_map_width(op, 1) words. Returns 0, or -1 for an unknown op.
+ *   RCP, RSQ, RSQ1, RSQ2, U01: x -> f(x).   U16I, U16, JITTER: (lo, hi) -> the 16-bit draw as an
+ *   integer, as a float in [0, 1), as the camera's float 2^23 + j.   DISK: word -> (cos, sin).
+ *   COSINE: (nl.x, nl.y, nl.z, ra, rb, mode) -> c_cosine, normalized; mode bit 0 = uniform,
+ *   bit 1 = unit.   FIX: (L, inv_spp) -> c_fix.   PHILOX: (c0, c1, c2, c3) -> c_philox with the
+ *   contract's key.   NORM, NORM_FREE: v -> fnormalize(v), fnormalize_free(v). */
+enum { C_MAP_RCP, C_MAP_RSQ, C_MAP_RSQ1, C_MAP_RSQ2, C_MAP_U01, C_MAP_U16I, C_MAP_U16, C_MAP_JITTER,
+       C_MAP_DISK, C_MAP_COSINE, C_MAP_FIX, C_MAP_PHILOX, C_MAP_NORM, C_MAP_NORM_FREE, C_MAP_OPS };
+int spt_oracle_map_width(int op, int out) {
+  static const int w[C_MAP_OPS][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}, {2, 1}, {2, 1}, {2, 1},
+                                      {1, 2}, {6, 3}, {2, 1}, {4, 4}, {3, 3}, {3, 3}};
+  return op < 0 || op >= C_MAP_OPS ? -1 : w[op][out != 0];
+}
+int spt_oracle_map(int op, const uint32_t* in, uint32_t* out, int64_t n) {
+  const int wi = spt_oracle_map_width(op, 0), wo = spt_oracle_map_width(op, 1);
+  const uint32_t key[2] = {SPT_PHILOX_KEY0, SPT_PHILOX_KEY1};
+  int64_t i;
+  if (wi < 0) return -1;
+#pragma omp parallel for schedule(static)
+  for (i = 0; i < n; i++) {
+    const uint32_t* a = in + i * wi;
+    uint32_t* o = out + i * wo;
+    switch (op) {
+      case C_MAP_RCP: o[0] = asu(spt_oracle_rcp_nr(asf(a[0]))); break;
+      case C_MAP_RSQ: o[0] = asu(spt_oracle_rsq_nr(asf(a[0]))); break;
+      case C_MAP_RSQ1: o[0] = asu(spt_oracle_rsq_nr1(asf(a[0]))); break;
+      case C_MAP_RSQ2: o[0] = asu(spt_oracle_rsq_nr2(asf(a[0]))); break;
+      case C_MAP_U01: o[0] = asu(u01(a[0])); break;
+      case C_MAP_U16I: o[0] = u16i(a[0], a[1]); break;
+      case C_MAP_U16: o[0] = asu(u16(a[0], a[1])); break;
+      case C_MAP_JITTER: o[0] = 0x4B000000u | u16i(a[0], a[1]); break; /* c_path's Fu, Fv */
+      case C_MAP_DISK: {
+        float c, s;
+        spt_oracle_disk_dir(a[0], &c, &s);
+        o[0] = asu(c); o[1] = asu(s);
+        break;
+      }
+      case C_MAP_COSINE: {
+        const fv r = c_cosine(fv3(asf(a[0]), asf(a[1]), asf(a[2])), a[3], a[4], (int)(a[5] & 1u),
+                              (int)((a[5] >> 1) & 1u));
+        o[0] = asu(r.x); o[1] = asu(r.y); o[2] = asu(r.z);
+        break;
+      }
+      case C_MAP_FIX: o[0] = (uint32_t)c_fix(asf(a[0]), asf(a[1])); break;
+      case C_MAP_PHILOX: c_philox(a, key, o); break;
+      default: {
+        const fv v = fv3(asf(a[0]), asf(a[1]), asf(a[2]));
+        const fv r = op == C_MAP_NORM ? fnormalize(v) : fnormalize_free(v);
+        o[0] = asu(r.x); o[1] = asu(r.y); o[2] = asu(r.z);
+      }
+    }
+  }
+  return 0;
 }
 
 /* Contract: the fp32 plane coordinate of a rectangle. The reference has no epsilon on rectangles

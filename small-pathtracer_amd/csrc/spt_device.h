@@ -101,10 +101,22 @@ __device__ __forceinline__ uint32_t u16i(uint32_t lo, uint32_t hi) {
   return __builtin_amdgcn_perm(hi, lo, 0x0C0C0400u);
 }
 __device__ __forceinline__ float u16(uint32_t lo, uint32_t hi) { return (float)u16i(lo, hi) * 0x1p-16f; }
+// The camera jitter's 16-bit draw j as the float 2^23 + j (bits 0x4B000000 | j; the camera ray of
+// contract v5 in spt_kernel.hip, oracle c_path's Fu, Fv).
+__device__ __forceinline__ float jitter_f(uint32_t lo, uint32_t hi) {
+  return __uint_as_float(u16i(lo, hi) | 0x4B000000u);
+}
 
 // ---- deterministic reciprocal / reciprocal square root (contract): integer seed + 3 Newton
-// steps; max relative error 6e-8 / 1.3e-7 (oracle tests). rcp_nr(+-0) is NaN, which the
-// intersection treats exactly like 1/0 = inf (no hit on a parallel plane).
+// steps; max relative error 6e-8 / 1.33e-7 over the normal range (measured over every float of
+// [1, 4): 5.965e-8 / 1.3242e-7, tests/test_contract_math.py; the device functions bit for bit,
+// tests/test_gpu_primitives.py). rcp_nr(+-0) is NaN. A single rectangle (or parallel
+// pair) whose plane the ray runs parallel to gets a NaN distance, fails its in-plane compares and
+// is not hit, as with 1/0 = inf. The room and the boxes are slabs whose entry / exit are min / max
+// over all three axes' keys as signed integers (box_keys, oracle c_intersect): one NaN axis voids
+// the whole slab, so a ray with an exactly zero direction component misses the room and every box
+// altogether, where the reference would hit the walls it is not parallel to (DESIGN.md section 3,
+// "Zero direction components"; pinned by tests/test_contract_rays.py and tests/test_gpu_rays.py).
 __device__ __forceinline__ float rcp_nr(float x) {
   float y = __uint_as_float(0x7EF311C3u - __float_as_uint(x));
 #pragma unroll
@@ -125,7 +137,8 @@ __device__ __forceinline__ float rsq_nr(float x) {
   return y;
 }
 
-// The same with one Newton step (relative error < 1.8e-3, always below the root): the free-scale
+// The same with one Newton step (relative error < 1.8e-3; below the root except where the seed is
+// within ~1e-4 of it, there at most 1.25e-7 above: the step's own roundings): the free-scale
 // contract's normalize of the path directions (contract v7, oracle c_unit_dirs). Not the cosine
 // sample's R, whose error would bias the sampled distribution.
 __device__ __forceinline__ float rsq_nr1(float x) {

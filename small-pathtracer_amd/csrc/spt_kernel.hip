@@ -908,10 +908,8 @@ constexpr float kRefNeeC = (float)(1296.0 / 3.14159265358979323846);  // kRefLar
 // P_c = fma(Au_c, fx, fma(Av_c, fy, llc_c - origin_c)), Au_c = hor_c (1/w), Av_c = ver_c (1/h),
 // fx = (x - 0.5) - 128, fy = (h - y - 1 - 0.5) - 128 (the -128 cancels 2^23 2^-16 in Fu Cu).
 // The axis-aligned camera kernels keep P_x, P_y per work unit: one fma per component per ray
-// (rounds 1-4: the jitter sum, a scale, an fma and a subtract per component).
-__device__ __forceinline__ float jitter_f(uint32_t lo, uint32_t hi) {
-  return __uint_as_float(u16i(lo, hi) | 0x4B000000u);
-}
+// (rounds 1-4: the jitter sum, a scale, an fma and a subtract per component). Fu, Fv are jitter_f
+// (spt_device.h).
 
 __device__ __forceinline__ uint32_t div_magic(uint32_t n, uint32_t m, uint32_t sh) {
   return (uint32_t)(((uint64_t)n * m) >> sh);
