@@ -2,8 +2,8 @@
 // as compile-time intersection geometry, in the kernel's grouped order (XY, XZ, YZ; index order
 // inside a kind). The render kernel specialised on it reads every rectangle bound as an
 // instruction literal: no scalar loads or waits in the intersect loop. The host runs that kernel
-// only when the uploaded scene's grouped geometry equals this table bit for bit (spt_kernel.hip,
-// cornell_const_match), so the table is an optimisation, never a substitute for the caller's scene.
+// only when the uploaded scene's grouped geometry equals this table bit for bit (spt_dispatch.cpp,
+// head_literal_match), so the table is an optimisation, never a substitute for the caller's scene.
 #pragma once
 #include <stdint.h>
 

@@ -1,4 +1,4 @@
-// spt_film.h — what spt_kernel.hip (the render launch) and spt_film.hip (the film) share. Internal:
+// spt_film.h — what spt_context.cpp (the render launch) and spt_film.hip (the film) share. Internal:
 // the public statement is include/spt.h.
 #pragma once
 #include <cstddef>
@@ -20,7 +20,7 @@ struct spt_film {
   spt_context* last_ctx = nullptr;     // the context of the last pass (it takes a guarded pass back)
 };
 
-// spt_kernel.hip: one render launch over a sample window (film == nullptr: the one-shot finalize).
+// spt_context.cpp: one render launch over a sample window (film == nullptr: the one-shot finalize).
 spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
                              const spt_camera* cam, const spt_params* p, int32_t s_base,
                              int32_t s_count, float* rgb_dev, spt_film* film, void* stream);

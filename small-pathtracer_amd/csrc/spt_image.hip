@@ -418,7 +418,7 @@ struct spt_encoder {
   uint64_t* h_total = nullptr;   // pinned mirror
 };
 
-void spt_set_last_error(const std::string& msg);  // spt_kernel.hip: spt_last_error() text
+void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp: spt_last_error() text
 static spt_status img_fail(spt_status s, const std::string& m) {
   spt_set_last_error(m);
   return s;

@@ -1,5 +1,7 @@
-// spt_kernel.hip — MI355X (gfx950) render kernel for the smallpt per-pixel sampling loop,
-// and the C ABI of include/spt.h.
+// spt_kernel.hip — MI355X (gfx950) render kernel for the smallpt per-pixel sampling loop: device
+// code only, plus the launchers the host side needs (the end of the file). The C ABI of
+// include/spt.h is spt_dispatch.cpp (scene grouping, kernel choice, launch sizing: no HIP) and
+// spt_context.cpp (contexts and launches).
 //
 // Replaces /root/reference/src/smallpt.cpp:528-542 (pixel x sample loop) and :419-480
 // (recursive radiance()) with one persistent-lane kernel:
@@ -21,96 +23,21 @@
 //     of unit size, lane order, queue order, stealing and GPU count.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <mutex>
-#include <string>
 #include <utility>
 
 #include "../../include/spt.h"
-#include "../../include/spt_flops.h"
 #include "spt_device.h"
 #include "spt_cornell.h"
 #include "spt_diag.h"
-#include "spt_film.h"
+#include "spt_kparams.h"
+#include "spt_variants.h"
+#include "spt_launch.h"
 
 #define SPT_STR_(x) #x
 #define SPT_XSTR(x) SPT_STR_(x)
 
 namespace spt {
 
-constexpr int kMaxPrims = 64;
-constexpr int kBlock = 256;
-// Units fetched per queue atomic. Measured (1 GPU): 8/16/32 slower (C2 5.6/5.0/4.7 ms vs 4.6:
-// atomics), 128/256 slower for C3 (16.7/17.3 vs 16.0 ms: work hoarded in one wave's pool when the
-// queue drains) though faster for C2 (4.45 ms); a guided scheme (static first slice per wave, then
-// shares of what is left, 16..256) was 6 % slower on C3-C5.
-#ifndef SPT_GRAB
-#define SPT_GRAB 64
-#endif
-constexpr uint32_t kGrab = SPT_GRAB;
-// Guided grabs of short launches: left >> (log2(2 x waves) + SPT_GUIDED_EXTRA) units, at least
-// SPT_GRAB_MIN. Round 3 (C2, 8 rounds on two boxes): 16 / +0 -> 8 / +1 cut the kernel 1.0-1.6 %;
-// 8 / +0, 4 / +0, 16 / +1 and 4 / +2 did not (profiles/r03_ab.txt session 10).
-#ifndef SPT_GRAB_MIN
-#define SPT_GRAB_MIN 8
-#endif
-#ifndef SPT_GUIDED_EXTRA
-#define SPT_GUIDED_EXTRA 1
-#endif
-constexpr uint32_t kGrabMin = SPT_GRAB_MIN;  // guided grabs never take fewer (bounds the queue atomics)
-// Launches with fewer lane-iterations per resident lane than SPT_SMALL_ITERS deal their units
-// almost all at once (SPT_SMALL_UNITS per lane) and balance by stealing (host, spt_render_async).
-#ifndef SPT_SMALL_ITERS
-#define SPT_SMALL_ITERS 2000.0
-#endif
-#ifndef SPT_SMALL_UNITS
-#define SPT_SMALL_UNITS 1.5
-#endif
-#ifndef SPT_SMALL_BPC
-#define SPT_SMALL_BPC 4  // resident blocks per CU of a short launch (host, spt_render_async)
-#endif
-// Units per resident lane of a long launch (host, spt_render_async): 8 since round 4 (was 16)
-#ifndef SPT_UNITS_PER_LANE
-#define SPT_UNITS_PER_LANE 8.0
-#endif
-// Young blocks of a long launch (host, spt_render_async): the waves of the blocks a CU received
-// last (blockIdx >= SPT_YOUNG_RANK x n_cu at 8 blocks per CU) take no new pool once SPT_YOUNG_CUT per
-// mille of the units are handed out. The SIMD issues oldest-first, so these waves get the fewest
-// slots (C3: the two youngest of a CU's 8 blocks do ~4 % of the work) and the units they hold end
-// the launch. Round 5 A/B (profiles/r05_young_cut_ab.json): C3 isolated kernel -1.3 to -1.6 %,
-// C4 -0.8 %, values flat; applied to the literal HEAD NEE kernels (and their any-camera forms) and
-// the room-literal edited-scene NEE kernels (KV_UPBOX_NEE: -4 %; KV_UPLIGHT_NEE, round 6) only (the
-// others lost). It assumes the dispatcher hands
-// each CU its blocks in blockIdx order, so blockIdx >= SPT_YOUNG_RANK x n_cu are the blocks a CU
-// received last; that holds only with every CU full at 8 blocks, so the host applies it at bpc == 8.
-#ifndef SPT_YOUNG_CUT
-#define SPT_YOUNG_CUT 300
-#endif
-#ifndef SPT_YOUNG_RANK
-#define SPT_YOUNG_RANK 6
-#endif
-#ifndef SPT_SCRAMBLE_K
-#define SPT_SCRAMBLE_K 8  // pixel-order spreading factor of the work units (1 = off; A/B in DESIGN.md §4)
-#endif
-// Unit slots: a unit's owner lane stores its three sums to the unit's own slot (plain stores, no
-// atomics); only stolen ranges add into the per-pixel accumulator; finalize_slots_kernel sums both
-// (rounds 1-2 added every unit's sums atomically)
-#ifndef SPT_STEAL_MIN
-#define SPT_STEAL_MIN 8  // unstarted samples a donor must hold (in-wave stealing; A/B in DESIGN.md §4)
-#endif
-#ifndef SPT_STEAL_MIN_SMALL
-#define SPT_STEAL_MIN_SMALL 16  // the same for short launches (C2: +2-3 %, profiles/r04_ab.txt s. 9)
-#endif
-#ifdef SPT_WAVE_TIMES
-constexpr int kStatWords = 32 + 3 * 32768;  // diagnostic: per-wave start, end, iterations
-#else
-constexpr int kStatWords = 32;
-#endif
 // Lane states of the render loop (render_kernel).
 constexpr uint32_t kStIdle = 0;    // no work unit
 constexpr uint32_t kStCam = 1;     // next: a camera ray (a new sample; retire the unit at s_end)
@@ -123,121 +50,7 @@ constexpr uint32_t kStEarly = 7;   // a NEE shadow ray proven to reach the light
 // Exit condition every wave reaches even if a path never terminated: a C3 wave runs ~4e3
 // iterations and a 1-GPU C5 wave ~3e6; stats[0] counts waves that hit the cap.
 constexpr uint32_t kMaxWaveIters = 1u << 26;
-// stats[]: [0] waves that hit kMaxWaveIters, [1,8) path statistics (spt_stats order), [8] shadow
-// rays that passed the light pre-test, [9] sphere vertices, [10] shadow rays of those resolved
-// without a trace (early_nee_proven), [12,32) region stats (diagnostic build)
-[[maybe_unused]] constexpr int kStatShadowTraced = 8, kStatSphereVertices = 9, kStatShadowProven = 10,
-                               kStatRegion = 12;
-
-// 64-byte device primitive. rect: w1..w5 = k, b1, b2, c1, c2 (in-plane bounds of the two free
-// axes in (x,y,z) order); sphere: w1..w5 = px, py, pz, rad^2, 1/rad.
-struct alignas(16) DevPrim {
-  int kind;
-  float w1, w2, w3, w4, w5;
-  int refl;  // spt_refl
-  float ip;  // 1/pmax, correctly rounded on the host (the RR reweighting f * (1/p) of :451)
-  float ex, ey, ez, pmax;
-  float cx, cy, cz;
-  // Russian roulette as integers (host): INT_MIN when pmax == 0 (RR always applies, :448), else
-  // ceil(pmax * 2^16) (0 for pmax <= 0, 2^16 for pmax >= 1), so that `u16 * 2^-16 < pmax` (:449,
-  // with alive only for pmax > 0) is `(int)u16 < rr_t`: the same decision with no conversion
-  int32_t rr_t;
-};
-static_assert(sizeof(DevPrim) == 64, "DevPrim layout");
-
-// Intersection geometry, grouped by kind (XY, XZ, YZ rects, then spheres; index order inside a
-// group) and read through the constant address space so every load in the intersect loop is a
-// wave-uniform s_load (scalar cache broadcast) — never a per-lane memory access.
-// rect bounds as |a - ma| <= ha, |b - mb| <= hb (c_rect_mid in the oracle): per axis one
-// subtract + one compare, each reading a single SGPR (the VALU constant-bus limit on gfx950).
-struct GeoRect { float k, ma, ha, mb, hb; int idx; int pad0, pad1; };   // 32 B
-struct GeoSph { float px, py, pz, rad2; int idx; int wide, pad1, pad2; };  // 32 B
-// fp64 geometry of a wide sphere (radius >= SPT_WIDE_SPHERE_RADIUS: the 1e5 walls of the classic
-// smallpt box), tested in double (oracle c_sphere_wide).
-struct GeoSphD { double px, py, pz, rad2; };
-// A rect test of the contract (oracle c_test): a parallel pair (k0 < k1, shared bounds) or a single
-// (k0 == k1, pos0 == pos1); pos* are grouped positions in rect[].
-struct GeoTest { float k0, k1, ma, ha, mb, hb; int pos0, pos1; };      // 32 B
-struct SceneGeo {
-  int n_xy, n_xz, n_yz, n_sph;
-  int n_txy, n_txz, n_tyz, n_sph_wide;  // rect tests per kind; wide spheres = the last n_sph_wide
-  // contract v5's room (oracle c_find_room): its three pair tests follow the per-kind lists in
-  // test[] (XY, XZ, YZ); box = mid, half + 2^-8 for x, y, z
-  int has_room, n_box, pad_[2];  // n_box: boxes of contract v6 (their tests follow the room's)
-  float pad2_[8];
-  GeoRect rect[kMaxPrims];  // [0,n_xy) XY, [n_xy, n_xy+n_xz) XZ, then YZ
-  GeoSph sph[kMaxPrims];
-  GeoSphD sphd[kMaxPrims];
-  GeoTest test[kMaxPrims];  // [0,n_txy) XY, then XZ, then YZ (room tests excluded), then the room
-};
 #define SPT_CONST __attribute__((address_space(4)))
-
-struct KParams {  // in device memory, read through a laundered constant-space pointer
-  const DevPrim* prims;
-  const SceneGeo* geo;
-  int n_prims;
-  float cam[12];  // origin, lower_left_corner, horizontal, vertical
-  int width, height, spp;  // spp: the whole image's sample count (fix_scale), not the launch's
-  // the launch's sample window [s_base, s_base + s_count) of those spp samples (s_lim = its end):
-  // one-shot renders launch [0, spp), a film pass (spt_film.hip) any window
-  uint32_t s_base, s_count, s_lim;
-  uint32_t seed;
-  float nee_prob;
-  int rr_depth, max_depth, light_id;
-  float lx0, ldx, lz0, ldz, ly, larea;
-  int light_mode;
-  uint32_t ldxi, ldzi;
-  int tile_rows, shard_index, shard_count;
-  int chunk, n_local_pix;
-  uint32_t n_units;
-  // n / d = (n * m) >> sh for every n < 2^31 (Granlund-Montgomery, host-computed): the refill's
-  // divisions by n_local_pix, width and tile_rows without the ~25-instruction integer divide.
-  uint32_t m_npix, sh_npix, m_w, sh_w, m_tile, sh_tile;
-  // Guided grabs (small launches only, sh_guided < 32): a wave takes min(kGrab, max(units its
-  // lanes need, kGrabMin, left >> sh_guided)) units per queue atomic, left = units not yet handed
-  // out, so no wave hoards a full pool while the queue runs dry. sh_guided = 32: always kGrab.
-  uint32_t sh_guided;
-  // young blocks (SPT_YOUNG_CUT): blockIdx >= young_block take no new pool once the queue is at
-  // young_cut; young_block = UINT32_MAX: off
-  uint32_t young_block, young_cut;
-  uint32_t scr_k, scr_q;  // pixel-order spreading of the units: K = 2^scr_k, scr_q = npix / K
-  float inv_spp, inv_w, inv_h;
-  float fix_scale;  // inv_spp * 2^31 (fix31)
-  // camera of contract v5 (jitter_f): Au, Av, Cu = Au 2^-16, Cv = Av 2^-16, L = llc - origin per axis
-  float cam_au[3], cam_av[3], cam_cu[3], cam_cv[3], cam_l[3];
-  // light sample of contract v5 (oracle c_wrap_sample): GLIBC_WRAP with dx = 2^a odd, 1 <= a <= 24:
-  // x0 - 1 + (r >> (7 + a)) 2^(a - 24); else (lattice 0) the rounds-1-4 wrapped multiply
-  int lx_lattice, lz_lattice;
-  uint32_t lx_shift, lz_shift;
-  float lx_scale, lz_scale, lx0m1, lz0m1;
-  // Shadow-ray specialisation: when the light is black (c == 0, HEAD :294) a path that reaches it
-  // always ends there (RR with p == 0, :448), so the NEE test only needs "is the nearest hit the
-  // light" — an occlusion query without id bookkeeping.
-  int light_black, light_kind, light_pos;
-  int scatter_uniform;  // SPT_FLAG_UNIFORM_SCATTER
-  int leak_end;         // contract v6: a leaked path ends at its first miss (host leak_end_of)
-  uint32_t steal_min;   // SPT_STEAL_MIN or, for a short launch, SPT_STEAL_MIN_SMALL
-  // Sphere NEE kernel: vertices above early_y0 (every sphere's top + 1) in the HEAD room resolve
-  // their light-accepted shadow rays early (early_room_proven); +inf when the host cannot prove it
-  float early_y0;
-  // The uploaded-geometry HEAD-topology NEE kernel's early resolve (early_geo_proven): per box, a
-  // vertex at or above eb_top[b] or with sgn * x[axis] <= eb_bnd[b] (axis x, or z where eb_z[b]) has
-  // a shadow segment that cannot meet the box; eb_top = +inf and eb_bnd = -inf: no clause (the
-  // host could not prove one, or the predicate is off)
-  float eb_top[2], eb_sgn[2], eb_bnd[2];
-  uint32_t eb_z[2];
-  // ... and its room clause (early_geo_setup): the vertex in the room's box below the light plane,
-  // per axis (bits(v) - er_lo) <= er_span on the float bits (HEAD: x in [1, 99], y in [0, 81.5),
-  // z in [0, 170], the literal early_room_ok); er_lo = 0, er_span = 0 with no clause
-  uint32_t er_lo[3], er_span[3];
-  uint32_t ul_ybits;  // the room-literal light-uploaded kernel's y bound: bits(y) < bits(y_L)
-  int unit_dirs;  // oracle c_unit_dirs: the scene has a sphere or a REFR primitive
-  float nee_c;    // light_area / pi rounded once (the free-scale NEE weight, nee_weight)
-  unsigned long long* accum;  // [n_local_pix][3] 1.31 fixed point (stolen ranges; every unit without slots)
-  unsigned long long* slots;  // [n_units][3] one owner store per unit, unit order (unit slots)
-  uint32_t* queue;            // [0] = next unit
-  unsigned long long* stats;  // [8]
-};
 
 // Re-derive a wave-uniform pointer as opaque so uniform loads are re-issued (s_load) where used
 // instead of being hoisted into long-lived SGPRs (which spill to VGPR lanes).
@@ -255,96 +68,6 @@ struct CornellRectPtr {
   __device__ constexpr const CRect* operator->() const { return &kCornellRects[i]; }
 };
 
-// Scene topology the kernel is specialised for: rect counts per kind (-1 = runtime loop), whether
-// spheres exist (runtime loop), the light's grouped position (-1 = runtime), and whether the rect
-// bounds are the compile-time HEAD scene (CONSTGEO) or read from the uploaded scene (s_load).
-// MAT: SPEC/REFR materials and the uniform-hemisphere flag may occur (generic kernel); the
-// specialisations are all-DIFF, cosine-scatter scenes (keeps their cosine block branch-free).
-// NT*: rect tests per kind (parallel pairs count once).
-template <int NXY_, int NXZ_, int NYZ_, bool SPH_, int LPOS_, bool CONSTGEO_ = false,
-          int NTXY_ = -1, int NTXZ_ = -1, int NTYZ_ = -1, bool MAT_ = SPH_, bool WIDE_ = false,
-          int NBOX_ = -1, bool UPBOX_ = false, bool UPLIGHT_ = false>
-struct Topo {
-  static constexpr int NBOX = NBOX_;  // boxes of contract v6 (uploaded geometry; -1 = run time)
-  // CONSTGEO with the two boxes uploaded (an edited rect[] whose room and light are HEAD's): the
-  // room and light as literals, the boxes' slab tests from LDS, the early resolve's box clauses
-  // from KParams (early_geo_proven)
-  static constexpr bool UPBOX = UPBOX_;
-  // UPBOX with the light uploaded as well (an edited light; the room literal): the light's test from
-  // the uploaded scene through scalar loads, its plane's y bound of the early resolve from KParams
-  static constexpr bool UPLIGHT = UPLIGHT_;
-  static constexpr int NXY = NXY_, NXZ = NXZ_, NYZ = NYZ_, LPOS = LPOS_;
-  static constexpr int NTXY = NTXY_, NTXZ = NTXZ_, NTYZ = NTYZ_;
-  static constexpr bool SPH = SPH_, CONSTGEO = CONSTGEO_, MAT = MAT_;
-  static constexpr bool WIDE = WIDE_;  // fp64 wide spheres may occur (their own kernel: VGPRs)
-  // Ray-direction contract (oracle c_unit_dirs): 1 = unit directions (spheres, REFR), 0 = free-scale
-  // (rect-only DIFF scenes: path directions normalised with rsq_nr1, the NEE vector not at all),
-  // -1 = KParams::unit_dirs at run time (the generic kernels)
-  static constexpr int DIRS = MAT_ ? -1 : (SPH_ ? 1 : 0);
-};
-// rect[] of :287-311 (light = XZ #3 -> pos 8); tests besides the room (contract v5): 2 XY box
-// pairs; light + 2 box tops; 2 YZ box pairs
-using TopoCornell = Topo<6, 5, 6, false, 8, false, 0, 1, 0, false, false, 2>;
-using TopoCornellConst = Topo<kCornellNXY, kCornellNXZ, kCornellNYZ, false, kCornellLightPos, true>;
-// the same with the boxes uploaded (a box moved or resized; room, light and topology HEAD's)
-using TopoCornellUpBox = Topo<kCornellNXY, kCornellNXZ, kCornellNYZ, false, kCornellLightPos, true, -1, -1,
-                              -1, false, false, 2, true>;
-// ... and with the light uploaded too (the light moved or resized; the room HEAD's)
-using TopoCornellUpLight = Topo<kCornellNXY, kCornellNXZ, kCornellNYZ, false, kCornellLightPos, true, -1, -1,
-                                -1, false, false, 2, true, true>;
-using TopoGeneric = Topo<-1, -1, -1, true, -1>;
-// Any scene with spheres but only DIFF materials and cosine scattering (the C5 32-sphere scene):
-// no SPEC/REFR stack and branch words, 8 waves/SIMD instead of the generic kernel's 6.
-using TopoSphDiff = Topo<-1, -1, -1, true, -1, false, -1, -1, -1, false>;
-// Any other rect-only, all-DIFF, cosine-scatter scene (uploaded geometry, run-time loops): the
-// free-scale direction contract at compile time (Topo::DIRS 0), no sphere loop.
-using TopoRectDiff = Topo<-1, -1, -1, false, -1>;
-// Scenes with wide spheres (radius >= SPT_WIDE_SPHERE_RADIUS, tested in fp64: the classic smallpt
-// box): the generic kernel plus the fp64 sphere loop, kept apart because the doubles cost VGPRs.
-using TopoGenericWide = Topo<-1, -1, -1, true, -1, false, -1, -1, -1, true, true>;
-
-// Estimator configuration the kernel is specialised for (compile-time where the host can prove
-// it, -1 = read from KParams at run time). Only wave-uniform branches and parameter loads go away;
-// per lane the arithmetic is the same contract.
-//   NEE:   1 = nee_prob >= 1 (HEAD :464), 0 = nee_prob <= 0 (cosine only, :474-477)
-//   LMODE: light sampling (SPT_LIGHT_GLIBC_WRAP / SPT_LIGHT_UNIFORM)
-//   BLACK: 1 = the light's colour is 0, so a path reaching it ends there (RR with p == 0, :448)
-//   MAXD0: 1 = no hard depth cap (max_depth == 0, the reference)
-//   NOS1:  1 = no vertex-1 stream-1 draws (rr_depth >= 1 and nee_prob is 0 or 1)
-//   CAMAX: 1 = axis-aligned camera (horizontal = (h,0,0), vertical = (0,v,0) up to the sign of
-//          zero, origin components nonzero, as the reference's :521 camera): the zero products of
-//          the camera's fma chain vanish exactly, so the ray is the same bits with 5 fewer VALU;
-//          2 = any camera (Camera :262-275 with any lookat/vup, round 6), its per-pixel P_x, P_y,
-//          P_z per work unit and the jitter's Cu, Cv in SGPRs: 6 fmas per camera ray (1: 2,
-//          0/-1: 12 and scalar loads); the same bits as the general form (contract v5)
-//   LREF:  1 = the reference's light sampling and RR constants (light x0/dx 32/36, z0/dz 63/36,
-//          y 81.6, area 1296 :365-367,:471; light id 6 :467; rr_depth 5 :448): literals instead
-//          of scalar loads in the loop
-//   LEAK:  1 = contract v6's leak-end rule (a leaked path ends at its first miss; the host proves
-//          it applies, leak_end_of), 0 = leaked paths go on from the miss vertex as the reference's
-//          (SPT_FLAG_REFERENCE_LEAKS, or a scene the rule does not hold for), -1 = KParams::leak_end
-template <int NEE_, int LMODE_, int BLACK_, int MAXD0_, int NOS1_, int CAMAX_, int LREF_ = 0,
-          int LEAK_ = -1>
-struct Cfg {
-  static constexpr int NEE = NEE_, LMODE = LMODE_, BLACK = BLACK_, MAXD0 = MAXD0_, NOS1 = NOS1_;
-  static constexpr int CAMAX = CAMAX_, LREF = LREF_, LEAK = LEAK_;
-};
-using CfgRuntime = Cfg<-1, -1, -1, -1, -1, -1>;
-// C3/C4: the reference's HEAD estimator; C2: cosine-weighted only (leak-end rule / reference leaks)
-using CfgHeadNee = Cfg<1, SPT_LIGHT_GLIBC_WRAP, 1, 1, 1, 1, 1, 1>;
-using CfgHeadCos = Cfg<0, SPT_LIGHT_GLIBC_WRAP, 1, 1, 1, 1, 1, 1>;
-using CfgHeadNeeRef = Cfg<1, SPT_LIGHT_GLIBC_WRAP, 1, 1, 1, 1, 1, 0>;
-// the same estimators with any camera (a tilted lookat)
-using CfgHeadNeeCam = Cfg<1, SPT_LIGHT_GLIBC_WRAP, 1, 1, 1, 2, 1, 1>;
-using CfgHeadCosCam = Cfg<0, SPT_LIGHT_GLIBC_WRAP, 1, 1, 1, 2, 1, 1>;
-using CfgHeadCosRef = Cfg<0, SPT_LIGHT_GLIBC_WRAP, 1, 1, 1, 1, 1, 0>;
-// Sphere scenes with the reference's NEE estimator and black light (C5): early NEE resolve
-using CfgSphNee = Cfg<1, SPT_LIGHT_GLIBC_WRAP, 1, -1, -1, -1, 1, 1>;
-using CfgSphNeeRef = Cfg<1, SPT_LIGHT_GLIBC_WRAP, 1, -1, -1, -1, 1, 0>;
-// The LREF constants (the host checks spt_params against them before it picks an LREF kernel).
-constexpr int kRefLightId = 6, kRefRrDepth = 5;
-constexpr float kRefLx0 = 32.0f, kRefLz0 = 63.0f, kRefLy = 81.6f, kRefLarea = 1296.0f;
-constexpr uint32_t kRefLdxi = 36u, kRefLdzi = 36u;
 template <class CF> __device__ __forceinline__ int light_id_of(const SPT_CONST KParams* P) {
   if constexpr (CF::LREF == 1) return kRefLightId; else return P->light_id;
 }
@@ -1055,20 +778,10 @@ render_kernel(const KParams* __restrict__ Pg) {
   uint32_t n_path = 0, n_cos = 0;
   // Per-lane counts of events that happen inside divergent blocks, incremented in place and
   // summed once at the end (a boolean per event carried to a convergent ballot cost 3 VALU each).
-  // NEE events need no counter in the HEAD NEE kernels: with NEE always on and no SPEC/REFR, every
-  // non-terminal vertex takes one (nee_events = vertices - samples, added by the host).
-  constexpr bool kNeeByIdentity = CF::NEE == 1 && !TP::MAT;
-  // Early NEE resolve (early_nee_proven): the HEAD NEE kernel only. The shadow-ray resolve then
-  // runs after the shading block, for the rays traced in this iteration and the proven ones.
-  constexpr bool kEarlyNee = TP::CONSTGEO && !TP::MAT && !TP::SPH && CF::NEE == 1 &&
-                             CF::BLACK == 1 && CF::LREF == 1 && CF::MAXD0 == 1;
-  // The sphere NEE kernel (C5): the same early resolve with the sphere-scene predicate.
-  constexpr bool kEarlySph = !kEarlyNee && TP::SPH && !TP::MAT && !TP::WIDE && CF::NEE == 1 &&
-                             CF::BLACK == 1 && CF::LREF == 1;
-  // The uploaded-geometry HEAD-topology NEE kernel (an edited rect[]): early_geo_proven.
-  constexpr bool kEarlyGeo = !kEarlyNee && !TP::SPH && !TP::MAT && TP::NBOX == 2 && CF::NEE == 1 &&
-                             CF::BLACK == 1 && CF::LREF == 1 && CF::MAXD0 == 1;
-  constexpr bool kEarly = kEarlyNee || kEarlySph || kEarlyGeo;
+  // What the variant's types imply (spt_variants.h, where the host reads the same values).
+  using KT = KernelTraits<TP, CF>;
+  constexpr bool kNeeByIdentity = KT::kNeeByIdentity, kEarlyNee = KT::kEarlyNee,
+                 kEarlySph = KT::kEarlySph, kEarlyGeo = KT::kEarlyGeo, kEarly = KT::kEarly;
   uint32_t l_early = 0;  // shadow rays resolved early (stats[kStatShadowProven])
   uint32_t l_miss = 0, l_nee = 0, l_hit = 0;
   // Shadow rays traced (NEE samples that passed light_accepts()): per lane in the rect kernels,
@@ -1735,1171 +1448,28 @@ finalize_slots_kernel(const unsigned long long* __restrict__ accum,
   rgb[3ull * p + 2] = f2 > 1.0f ? 1.0f : f2;
 }
 
-}  // namespace spt
-
-// =====================================================================================
-// C ABI
-// =====================================================================================
-using namespace spt;
-
-static thread_local std::string g_last_error;
-void spt_set_last_error(const std::string& msg) { g_last_error = msg; }
-static spt_status fail(spt_status s, const std::string& msg) {
-  g_last_error = msg;
-  return s;
-}
-#define SPT_HIP(call)                                                                    \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                 \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                    \
-  } while (0)
-
-// Kernel variants, from the most general to the most specialised (SPT_FLAG_KERNEL_LEVEL caps the
-// level).
+// ---- The launchers (spt_launch.h): everything else about a launch is the host files'.
 using RenderFn = void (*)(const KParams*);
-enum { KV_GENERIC, KV_CORNELL, KV_CONST, KV_CONST_NEE, KV_CONST_COS, KV_SPHDIFF, KV_WIDE,
-       KV_SPHDIFF_NEE, KV_RECTDIFF, KV_CONST_NEE_REF, KV_CONST_COS_REF, KV_SPHDIFF_NEE_REF,
-       KV_CORNELL_NEE, KV_CORNELL_COS, KV_RECTDIFF_NEE, KV_RECTDIFF_COS, KV_UPBOX_NEE, KV_UPBOX_COS,
-       KV_CONST_NEE_CAM, KV_CONST_COS_CAM, KV_UPBOX_NEE_CAM, KV_UPBOX_COS_CAM, KV_UPLIGHT_NEE,
-       KV_UPLIGHT_COS, KV_UPLIGHT_NEE_CAM, KV_UPLIGHT_COS_CAM, KV_COUNT };
-static const RenderFn kRenderKernels[KV_COUNT] = {
-    render_kernel<TopoGeneric, CfgRuntime>, render_kernel<TopoCornell, CfgRuntime>,
-    render_kernel<TopoCornellConst, CfgRuntime>, render_kernel<TopoCornellConst, CfgHeadNee>,
-    render_kernel<TopoCornellConst, CfgHeadCos>, render_kernel<TopoSphDiff, CfgRuntime>,
-    render_kernel<TopoGenericWide, CfgRuntime>, render_kernel<TopoSphDiff, CfgSphNee>,
-    render_kernel<TopoRectDiff, CfgRuntime>, render_kernel<TopoCornellConst, CfgHeadNeeRef>,
-    render_kernel<TopoCornellConst, CfgHeadCosRef>, render_kernel<TopoSphDiff, CfgSphNeeRef>,
-    render_kernel<TopoCornell, CfgHeadNee>, render_kernel<TopoCornell, CfgHeadCos>,
-    render_kernel<TopoRectDiff, CfgHeadNee>, render_kernel<TopoRectDiff, CfgHeadCos>,
-    render_kernel<TopoCornellUpBox, CfgHeadNee>, render_kernel<TopoCornellUpBox, CfgHeadCos>,
-    render_kernel<TopoCornellConst, CfgHeadNeeCam>, render_kernel<TopoCornellConst, CfgHeadCosCam>,
-    render_kernel<TopoCornellUpBox, CfgHeadNeeCam>, render_kernel<TopoCornellUpBox, CfgHeadCosCam>,
-    render_kernel<TopoCornellUpLight, CfgHeadNee>, render_kernel<TopoCornellUpLight, CfgHeadCos>,
-    render_kernel<TopoCornellUpLight, CfgHeadNeeCam>, render_kernel<TopoCornellUpLight, CfgHeadCosCam>};
-// The variants' public names (spt_kernel_name, spt_context_kernel), in the enum's order.
-static const char* const kKernelNames[] = {
-    "generic", "cornell", "const", "const_nee", "const_cos", "sphdiff", "wide",
-    "sphdiff_nee", "rectdiff", "const_nee_ref", "const_cos_ref", "sphdiff_nee_ref",
-    "cornell_nee", "cornell_cos", "rectdiff_nee", "rectdiff_cos", "upbox_nee", "upbox_cos",
-    "const_nee_cam", "const_cos_cam", "upbox_nee_cam", "upbox_cos_cam", "uplight_nee",
-    "uplight_cos", "uplight_nee_cam", "uplight_cos_cam"};
-static_assert(sizeof kKernelNames / sizeof kKernelNames[0] == KV_COUNT, "one name per kernel variant");
+#define SPT_X_FN(id, name, TP, CF, level, young) render_kernel<TP, CF>,
+static const RenderFn kRenderKernels[KV_COUNT] = {SPT_KERNEL_VARIANTS(SPT_X_FN)};
+#undef SPT_X_FN
 
-struct spt_context {
-  int device = 0;
-  int n_cu = 0, blocks_per_cu = 0;      // generic kernel
-  int bpc[KV_COUNT] = {};               // resident blocks per CU of each variant
-  DevPrim* prims = nullptr;
-  SceneGeo* geo = nullptr;
-  unsigned long long* accum = nullptr;
-  size_t accum_cap = 0;  // elements
-  unsigned long long* slots = nullptr;  // [n_units][3] unit slots, grown on demand
-  size_t slots_cap = 0;                 // elements
-  uint32_t* queue = nullptr;
-  unsigned long long* stats = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // the launch's statistics words, copied to pinned host memory on the launch's stream after the
-  // finalize (ev2 marks the copy): spt_context_stats() waits for that launch only, never for work
-  // queued behind it on the stream
-  unsigned long long* h_stats = nullptr;
-  hipEvent_t ev2 = nullptr;
-  bool pending = false;
-  bool launched = false;  // a render has been enqueued (spt_context_stats has events to read)
-  int n_prims = 0;
-  KParams last{};
-  // Pinned staging for the async scene upload; reused only after the previous upload completed.
-  DevPrim* h_prims = nullptr;
-  SceneGeo* h_geo = nullptr;
-  KParams* d_kp = nullptr;   // kernel parameters in device memory (read via s_load)
-  KParams* h_kp = nullptr;   // pinned staging
-  uint64_t samples = 0;      // pixel-samples of the last render (exact, not counted in-kernel)
-  bool nee_by_identity = false;  // the last kernel derives nee_events from vertices - samples
-  int last_kv = -1;          // variant of the last launch (-1: none yet, or a shard without rows)
-  double scene_flop = 0;     // FLOP-model cost of one ray against the scene
-  spt_film* last_film = nullptr;  // the film of the last launch (nullptr: a plain render)
-  int32_t last_film_count = 0;    // ... and the samples that pass added to its samples_done
-};
-
-extern "C" int32_t spt_shard_rows(const spt_params* p, int32_t* rows_out, int32_t cap);
-int spt_shard_row_count(const spt_params* p);  // spt_host.cpp
-
-static spt_status validate(const spt_prim* prims, int32_t n, const spt_camera* cam,
-                           const spt_params* p) {
-  if (!prims || !cam || !p) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  if (n <= 0 || n > kMaxPrims) return fail(SPT_ERR_INVALID_ARG, "n_prims must be in [1, 64]");
-  if (p->width <= 0 || p->height <= 0 || p->spp <= 0)
-    return fail(SPT_ERR_INVALID_ARG, "width/height/spp must be positive");
-  if ((uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull)
-    return fail(SPT_ERR_INVALID_ARG, "image too large for 32-bit pixel counters");
-  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count)
-    return fail(SPT_ERR_INVALID_ARG, "bad shard_index/shard_count");
-  if (p->tile_rows < 0 || p->chunk < 0) return fail(SPT_ERR_INVALID_ARG, "negative tile/chunk");
-  if (p->flags & ~(SPT_FLAG_UNIFORM_SCATTER | SPT_FLAG_REFERENCE_LEAKS | SPT_FLAG_KERNEL_LEVEL_MASK))
-    return fail(SPT_ERR_INVALID_ARG, "unknown flags");
-  if (((p->flags & SPT_FLAG_KERNEL_LEVEL_MASK) >> 8) > SPT_KERNEL_LEVEL_CONST)
-    return fail(SPT_ERR_INVALID_ARG, "bad kernel level");
-  if (p->light_mode != SPT_LIGHT_GLIBC_WRAP && p->light_mode != SPT_LIGHT_UNIFORM)
-    return fail(SPT_ERR_INVALID_ARG, "bad light_mode");
-  if (p->light_mode == SPT_LIGHT_GLIBC_WRAP &&
-      (p->light_dx != (float)(uint32_t)p->light_dx || p->light_dz != (float)(uint32_t)p->light_dz))
-    return fail(SPT_ERR_INVALID_ARG, "GLIBC_WRAP light sampling needs integral light_dx/dz");
-  for (int i = 0; i < n; ++i) {
-    if (prims[i].kind < SPT_RECT_XY || prims[i].kind > SPT_SPHERE)
-      return fail(SPT_ERR_INVALID_ARG, "bad primitive kind");
-    // Sphere::normal (:248) is (x - p).norm(); the contract's (x - p) * (1/r) equals it only for
-    // r > 0 (a negative radius would flip the geometric normal of the REFR test :485)
-    if (prims[i].kind == SPT_SPHERE && !(prims[i].geom[0] > 0.0 && std::isfinite(prims[i].geom[0])))
-      return fail(SPT_ERR_INVALID_ARG, "sphere radius must be positive and finite");
-    if (prims[i].refl < SPT_DIFF || prims[i].refl > SPT_REFR)
-      return fail(SPT_ERR_INVALID_ARG, "bad material");
-  }
-  // NEE (:464-472) weights shadow rays that reach prims[light_id] as light hits: that primitive
-  // must exist and emit, or the image is silently wrong (e.g. the classic sphere box with the HEAD
-  // light id 6, a ball).
-  if (p->nee_prob > 0.0f) {
-    if (p->light_id < 0 || p->light_id >= n)
-      return fail(SPT_ERR_INVALID_ARG, "nee_prob > 0 needs light_id in [0, n_prims)");
-    const double* e = prims[p->light_id].e;
-    if (!(e[0] != 0.0 || e[1] != 0.0 || e[2] != 0.0))
-      return fail(SPT_ERR_INVALID_ARG, "nee_prob > 0 but prims[light_id] emits nothing");
-  }
-  return SPT_OK;
+int render_kernel_occupancy(int kv) {
+  int bpc = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kRenderKernels[kv], kBlock, 0) != hipSuccess)
+    return 0;
+  return bpc;
 }
 
-// max(c) of a primitive's fp32 colour: the Russian-roulette survival probability (:447)
-static float prim_pmax(const spt_prim& s) {
-  const float cx = (float)s.c[0], cy = (float)s.c[1], cz = (float)s.c[2];
-  return cx > cy && cx > cz ? cx : cy > cz ? cy : cz;
+void launch_render_kernel(int kv, int grid, const KParams* kp_dev, void* stream) {
+  hipLaunchKernelGGL(kRenderKernels[kv], dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, kp_dev);
 }
 
-static void to_dev(const spt_prim* s, int n, DevPrim* out) {
-  for (int i = 0; i < n; ++i) {
-    DevPrim P;
-    std::memset(&P, 0, sizeof P);
-    P.kind = s[i].kind;
-    if (s[i].kind == SPT_SPHERE) {
-      const float r = (float)s[i].geom[0];
-      P.w1 = (float)s[i].geom[1]; P.w2 = (float)s[i].geom[2]; P.w3 = (float)s[i].geom[3];
-      P.w4 = r * r;
-      P.w5 = 1.0f / r;  // the normal as (x - p) * (1/r) (contract, oracle c_path)
-    } else {
-      P.w1 = plane_k(s[i].geom[4]);  // contract plane coordinate (spt_cornell.h)
-      P.w2 = (float)s[i].geom[0]; P.w3 = (float)s[i].geom[1];
-      P.w4 = (float)s[i].geom[2]; P.w5 = (float)s[i].geom[3];
-    }
-    P.ex = (float)s[i].e[0]; P.ey = (float)s[i].e[1]; P.ez = (float)s[i].e[2];
-    P.cx = (float)s[i].c[0]; P.cy = (float)s[i].c[1]; P.cz = (float)s[i].c[2];
-    P.pmax = prim_pmax(s[i]);
-    P.ip = 1.0f / P.pmax;  // IEEE single division, as the device's 1.0f / p
-    // u * 2^-16 < p (u < 2^16 an integer, p * 2^16 exact) <=> u < ceil(p * 2^16): the RR draw as
-    // one integer compare instead of a conversion, a scale and a float compare (same decision)
-    P.rr_t = P.pmax == 0.0f ? INT32_MIN
-             : !(P.pmax > 0.0f) ? 0
-             : P.pmax >= 1.0f   ? 65536
-                                : (int32_t)std::ceil((double)P.pmax * 65536.0);
-    P.refl = s[i].refl;
-    out[i] = P;
-  }
+void launch_finalize_slots(const unsigned long long* accum, const unsigned long long* slots,
+                           float* rgb, uint32_t npix, uint32_t n_chunks, uint32_t scr_k,
+                           uint32_t scr_q, const unsigned long long* stats, void* stream) {
+  hipLaunchKernelGGL(finalize_slots_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                     (hipStream_t)stream, accum, slots, rgb, npix, n_chunks, scr_k, scr_q, stats);
 }
 
-// Rect bounds [lo, hi] as |a - mid| <= half (contract; oracle c_rect_mid).
-static void rect_mid(double lo, double hi, float* mid, float* half) {
-  *mid = (float)((lo + hi) * 0.5);
-  *half = hi >= lo ? (float)((hi - lo) * 0.5) : -1.0f;
-}
-
-// Grouped geometry; *light_pos = position of prim `light` in rect[] / sph[] (-1 if absent).
-static void build_geo(const spt_prim* s, int n, SceneGeo* g, int light, int* light_pos) {
-  std::memset(g, 0, sizeof *g);
-  *light_pos = -1;
-  int r = 0;
-  const int kinds[3] = {SPT_RECT_XY, SPT_RECT_XZ, SPT_RECT_YZ};
-  int* counts[3] = {&g->n_xy, &g->n_xz, &g->n_yz};
-  for (int k = 0; k < 3; ++k) {
-    for (int i = 0; i < n; ++i) {
-      if (s[i].kind != kinds[k]) continue;
-      GeoRect& R = g->rect[r++];
-      R.k = plane_k(s[i].geom[4]);
-      rect_mid(s[i].geom[0], s[i].geom[1], &R.ma, &R.ha);
-      rect_mid(s[i].geom[2], s[i].geom[3], &R.mb, &R.hb);
-      R.idx = i;
-      if (i == light) *light_pos = r - 1;
-      ++*counts[k];
-    }
-  }
-  // Rect tests (oracle c_build_tests): inside each kind group, in order, a rectangle pairs with the
-  // first later unpaired one of bit-identical bounds on a different plane; the light never pairs.
-  {
-    bool used[kMaxPrims] = {};
-    const int grp[4] = {0, g->n_xy, g->n_xy + g->n_xz, g->n_xy + g->n_xz + g->n_yz};
-    int* tcounts[3] = {&g->n_txy, &g->n_txz, &g->n_tyz};
-    int nt = 0;
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    for (int k = 0; k < 3; ++k) {
-      for (int i = grp[k]; i < grp[k + 1]; ++i) {
-        if (used[i]) continue;
-        used[i] = true;
-        const GeoRect& A = g->rect[i];
-        GeoTest& T = g->test[nt++];
-        T = GeoTest{A.k, A.k, A.ma, A.ha, A.mb, A.hb, i, i};
-        ++*tcounts[k];
-        if (i == *light_pos) continue;
-        for (int j = i + 1; j < grp[k + 1]; ++j) {
-          const GeoRect& B = g->rect[j];
-          if (used[j] || j == *light_pos || bits(A.ma) != bits(B.ma) || bits(A.ha) != bits(B.ha) ||
-              bits(A.mb) != bits(B.mb) || bits(A.hb) != bits(B.hb) || bits(A.k) == bits(B.k) ||
-              !(A.k == A.k) || !(B.k == B.k))
-            continue;
-          used[j] = true;
-          if (A.k < B.k) { T.k1 = B.k; T.pos1 = j; }
-          else { T.k0 = B.k; T.pos0 = j; T.k1 = A.k; T.pos1 = i; }
-          break;
-        }
-      }
-    }
-  }
-  // Contract v5's room (oracle c_find_room): the first XY, XZ, YZ pair tests (test order) whose
-  // planes are exactly -- in the caller's doubles -- the other pairs' in-plane bounds (each pair's
-  // bounds read from its k0 member). Its tests move behind the per-kind lists (the nearest hit is a
-  // minimum of keys, so test order cannot matter).
-  {
-    const int nt = g->n_txy + g->n_txz + g->n_tyz;
-    auto member = [&](int pos) -> const spt_prim& { return s[g->rect[pos].idx]; };
-    auto same_range = [](double k1, double k2, double b1, double b2) {
-      return std::min(k1, k2) == b1 && std::max(k1, k2) == b2;
-    };
-    int room[3] = {-1, -1, -1};
-    for (int a = 0; a < g->n_txy && room[0] < 0; ++a) {
-      const GeoTest& A = g->test[a];
-      if (A.pos0 == A.pos1) continue;
-      for (int b = g->n_txy; b < g->n_txy + g->n_txz && room[0] < 0; ++b) {
-        const GeoTest& B = g->test[b];
-        if (B.pos0 == B.pos1) continue;
-        for (int c = g->n_txy + g->n_txz; c < nt; ++c) {
-          const GeoTest& D = g->test[c];
-          if (D.pos0 == D.pos1) continue;
-          const double* ga = member(A.pos0).geom, *gb = member(B.pos0).geom, *gd = member(D.pos0).geom;
-          const double zA = ga[4], zB = member(A.pos1).geom[4], yA = gb[4], yB = member(B.pos1).geom[4];
-          const double xA = gd[4], xB = member(D.pos1).geom[4];
-          if (!same_range(xA, xB, ga[0], ga[1]) || !same_range(xA, xB, gb[0], gb[1]) ||
-              !same_range(yA, yB, ga[2], ga[3]) || !same_range(yA, yB, gd[0], gd[1]) ||
-              !same_range(zA, zB, gb[2], gb[3]) || !same_range(zA, zB, gd[2], gd[3]))
-            continue;
-          room[0] = a; room[1] = b; room[2] = c;
-          break;
-        }
-      }
-    }
-    g->has_room = room[0] >= 0;
-    if (g->has_room) {
-      const GeoTest A = g->test[room[0]], B = g->test[room[1]], D = g->test[room[2]];
-      GeoTest rest[kMaxPrims];
-      int n = 0;
-      for (int i = 0; i < nt; ++i)
-        if (i != room[0] && i != room[1] && i != room[2]) rest[n++] = g->test[i];
-      for (int i = 0; i < n; ++i) g->test[i] = rest[i];
-      g->test[n] = A; g->test[n + 1] = B; g->test[n + 2] = D;
-      --g->n_txy; --g->n_txz; --g->n_tyz;
-    }
-  }
-  // Contract v6's boxes (oracle c_find_boxes): an XY pair, a YZ pair and an XZ top (not the light)
-  // closing a box on the room's floor, inside the floor's bounds, in the caller's doubles; searched
-  // in test order. Their tests move behind the room's, three per box (XY pair, YZ pair, top).
-  if (g->has_room) {
-    const int nt = g->n_txy + g->n_txz + g->n_tyz;
-    auto member = [&](int pos) -> const spt_prim& { return s[g->rect[pos].idx]; };
-    auto same_range = [](double k1, double k2, double b1, double b2) {
-      return std::min(k1, k2) == b1 && std::max(k1, k2) == b2;
-    };
-    const GeoTest& F = g->test[nt + 1];
-    const double floor_k = std::min(member(F.pos0).geom[4], member(F.pos1).geom[4]);
-    const double* gf = member(F.pos0).geom;
-    bool used[kMaxPrims] = {};
-    int box[kMaxPrims / 5][3], nb = 0;
-    for (int a = 0; a < g->n_txy && nb < kMaxPrims / 5; ++a) {  // (5 rects a box: <= 12 of them)
-      const GeoTest& A = g->test[a];
-      if (A.pos0 == A.pos1 || used[a]) continue;
-      for (int b = g->n_txy + g->n_txz; b < nt && !used[a]; ++b) {
-        const GeoTest& D = g->test[b];
-        if (D.pos0 == D.pos1 || used[b]) continue;
-        for (int c = g->n_txy; c < g->n_txy + g->n_txz; ++c) {
-          const GeoTest& T = g->test[c];
-          if (T.pos0 != T.pos1 || T.pos0 == *light_pos || used[c]) continue;
-          const double *ga = member(A.pos0).geom, *gd = member(D.pos0).geom, *gt = member(T.pos0).geom;
-          const double xA = gd[4], xB = member(D.pos1).geom[4], zA = ga[4], zB = member(A.pos1).geom[4];
-          if (!same_range(xA, xB, ga[0], ga[1]) || !same_range(xA, xB, gt[0], gt[1]) ||
-              !same_range(zA, zB, gd[2], gd[3]) || !same_range(zA, zB, gt[2], gt[3]) ||
-              !same_range(floor_k, gt[4], ga[2], ga[3]) || !same_range(floor_k, gt[4], gd[0], gd[1]) ||
-              !(gt[4] > floor_k))
-            continue;
-          if (!(gf[0] <= ga[0] && ga[1] <= gf[1] && gf[2] <= gd[2] && gd[3] <= gf[3])) continue;
-          used[a] = used[b] = used[c] = true;
-          box[nb][0] = a; box[nb][1] = b; box[nb][2] = c;
-          ++nb;
-          break;
-        }
-      }
-    }
-    if (nb > 0) {
-      GeoTest rest[kMaxPrims];
-      int n = 0, kind_n[3] = {0, 0, 0};
-      for (int i = 0; i < nt; ++i) {
-        if (used[i]) continue;
-        rest[n++] = g->test[i];
-        ++kind_n[i < g->n_txy ? 0 : (i < g->n_txy + g->n_txz ? 1 : 2)];
-      }
-      for (int r = 0; r < 3; ++r) rest[n + r] = g->test[nt + r];  // the room
-      for (int b = 0; b < nb; ++b)
-        for (int r = 0; r < 3; ++r) rest[n + 3 + 3 * b + r] = g->test[box[b][r]];
-      for (int i = 0; i < n + 3 + 3 * nb; ++i) g->test[i] = rest[i];
-      g->n_txy = kind_n[0]; g->n_txz = kind_n[1]; g->n_tyz = kind_n[2];
-      g->n_box = nb;
-    }
-  }
-  // Spheres in index order, the narrow (fp32) ones first, then the wide (fp64) ones (oracle
-  // c_intersect): the kernel's fp32 loop carries no per-sphere precision test.
-  for (int pass = 0; pass < 2; ++pass)
-  for (int i = 0; i < n; ++i) {
-    if (s[i].kind != SPT_SPHERE) continue;
-    if ((s[i].geom[0] >= SPT_WIDE_SPHERE_RADIUS) != (pass == 1)) continue;
-    g->n_sph_wide += pass;
-    GeoSph& S = g->sph[g->n_sph++];
-    const float rad = (float)s[i].geom[0];
-    S.px = (float)s[i].geom[1]; S.py = (float)s[i].geom[2]; S.pz = (float)s[i].geom[3];
-    S.rad2 = rad * rad;
-    S.idx = i;
-    S.wide = s[i].geom[0] >= SPT_WIDE_SPHERE_RADIUS ? 1 : 0;
-    GeoSphD& D = g->sphd[g->n_sph - 1];
-    D.px = s[i].geom[1]; D.py = s[i].geom[2]; D.pz = s[i].geom[3];
-    D.rad2 = s[i].geom[0] * s[i].geom[0];
-    if (i == light) *light_pos = g->n_sph - 1;
-  }
-}
-
-// Contract v6 (oracle c_find_leak_end): a leaked path ends at its first miss when the scene has a
-// room, the miss vertex (the origin, :373-374) lies strictly outside the room's box, prim 0 does
-// not emit and every emitter lies strictly inside the box -- compared on the caller's doubles.
-static int leak_end_of(const spt_prim* s, int n, const SceneGeo& g) {
-  if (!g.has_room) return 0;
-  const int nt = g.n_txy + g.n_txz + g.n_tyz;
-  double lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) {  // room tests: XY pair (planes z), XZ (y), YZ (x)
-    const GeoTest& T = g.test[nt + a];
-    const double k0 = s[g.rect[T.pos0].idx].geom[4], k1 = s[g.rect[T.pos1].idx].geom[4];
-    const int ax = a == 0 ? 2 : (a == 1 ? 1 : 0);
-    lo[ax] = std::min(k0, k1);
-    hi[ax] = std::max(k0, k1);
-  }
-  if (!(0.0 < lo[0] || 0.0 > hi[0] || 0.0 < lo[1] || 0.0 > hi[1] || 0.0 < lo[2] || 0.0 > hi[2])) return 0;
-  if (s[0].e[0] != 0.0 || s[0].e[1] != 0.0 || s[0].e[2] != 0.0) return 0;
-  for (int i = 0; i < n; ++i) {
-    const double* gm = s[i].geom;
-    if (s[i].e[0] == 0.0 && s[i].e[1] == 0.0 && s[i].e[2] == 0.0) continue;
-    if (s[i].kind == SPT_SPHERE) {
-      for (int a = 0; a < 3; ++a)
-        if (!(gm[1 + a] - gm[0] > lo[a] && gm[1 + a] + gm[0] < hi[a])) return 0;
-      continue;
-    }
-    const int pa = s[i].kind == SPT_RECT_XY ? 2 : (s[i].kind == SPT_RECT_XZ ? 1 : 0);
-    const int ua = s[i].kind == SPT_RECT_YZ ? 1 : 0, va = s[i].kind == SPT_RECT_XY ? 1 : 2;
-    if (!(gm[4] > lo[pa] && gm[4] < hi[pa] && gm[0] >= lo[ua] && gm[1] <= hi[ua] && gm[2] >= lo[va] &&
-          gm[3] <= hi[va]))
-      return 0;
-  }
-  return 1;
-}
-
-static int tile_rows_of(const spt_params* p) { return p->tile_rows > 0 ? p->tile_rows : 8; }
-
-// Multiply-shift reciprocal of d for 31-bit numerators: l = ceil(log2 d), m = floor(2^(31+l)/d) + 1
-// (< 2^32), n / d = (n * m) >> (31 + l) exactly for all n < 2^31 (Granlund & Montgomery 1994).
-static void magic31(uint32_t d, uint32_t* m, uint32_t* sh) {
-  uint32_t l = 0;
-  while ((1ull << l) < d) ++l;
-  *m = (uint32_t)(((unsigned __int128)1 << (31 + l)) / d + 1);
-  *sh = 31 + l;
-}
-
-// Does the uploaded scene's grouped geometry equal the compile-time HEAD scene bit for bit?
-static bool cornell_const_match(const SceneGeo& g, int light_pos) {
-  if (g.n_xy != kCornellNXY || g.n_xz != kCornellNXZ || g.n_yz != kCornellNYZ || g.n_sph != 0 ||
-      light_pos != kCornellLightPos || !g.has_room)
-    return false;
-  {  // the same room (tests behind the per-kind lists) and box as the compile-time kCornellRoom
-    const int nt = g.n_txy + g.n_txz + g.n_tyz;
-    for (int r = 0; r < 3; ++r) {
-      const CTest& C = kCornellTests.t[kCornellRoom[r]];
-      if (g.test[nt + r].pos0 != C.pos0 || g.test[nt + r].pos1 != C.pos1) return false;
-    }
-    if (g.n_box != kCornellBoxes.n) return false;  // and the same boxes (their tests behind the room's)
-    for (int b = 0; b < kCornellBoxes.n; ++b)
-      for (int r = 0; r < 3; ++r) {
-        const CTest& C = kCornellTests.t[kCornellBoxes.t[b][r]];
-        const GeoTest& T = g.test[nt + 3 + 3 * b + r];
-        if (T.pos0 != C.pos0 || T.pos1 != C.pos1) return false;
-      }
-  }
-  for (int i = 0; i < kCornellNXY + kCornellNXZ + kCornellNYZ; ++i) {
-    const GeoRect& R = g.rect[i];
-    const CRect& C = kCornellRects[i];
-    const float a[5] = {R.k, R.ma, R.ha, R.mb, R.hb}, b[5] = {C.k, C.ma, C.ha, C.mb, C.hb};
-    if (std::memcmp(a, b, sizeof a) != 0 || R.idx != C.idx) return false;
-  }
-  return true;
-}
-
-// The room of a HEAD-topology scene is the reference's (:288-293): its three pair tests at HEAD's
-// grouped positions with HEAD's fp32 geometry (materials may differ). The boxes-only-uploaded
-// kernels (TopoCornellUpBox) take the room as literals and everything else from LDS.
-static bool cornell_room_match(const SceneGeo& g) {
-  if (g.n_xy != kCornellNXY || g.n_xz != kCornellNXZ || g.n_yz != kCornellNYZ || g.n_sph != 0 ||
-      !g.has_room || g.n_txy != 0 || g.n_txz != 1 || g.n_tyz != 0 || g.n_box != 2)
-    return false;
-  const int nt = g.n_txy + g.n_txz + g.n_tyz;
-  for (int r = 0; r < 3; ++r) {
-    const CTest& C = kCornellTests.t[kCornellRoom[r]];
-    if (g.test[nt + r].pos0 != C.pos0 || g.test[nt + r].pos1 != C.pos1) return false;
-    for (const int pos : {C.pos0, C.pos1}) {
-      const GeoRect& R = g.rect[pos];
-      const CRect& H = kCornellRects[pos];
-      const float a[5] = {R.k, R.ma, R.ha, R.mb, R.hb}, b[5] = {H.k, H.ma, H.ha, H.mb, H.hb};
-      if (std::memcmp(a, b, sizeof a) != 0 || R.idx != H.idx) return false;
-    }
-  }
-  return true;
-}
-
-// The light of a HEAD-room scene is the reference's (:294, fp32 geometry at grouped position 8): the
-// boxes-only-uploaded kernels keep it literal, the UPLIGHT ones read it from the uploaded scene.
-static bool cornell_light_match(const SceneGeo& g, int light_pos) {
-  if (light_pos != kCornellLightPos) return false;
-  const GeoRect& R = g.rect[light_pos];
-  const CRect& H = kCornellRects[light_pos];
-  const float a[5] = {R.k, R.ma, R.ha, R.mb, R.hb}, b[5] = {H.k, H.ma, H.ha, H.mb, H.hb};
-  return std::memcmp(a, b, sizeof a) == 0 && R.idx == H.idx;
-}
-
-// The early resolve's clauses for a HEAD-topology scene with the reference's estimator (oracle
-// c_find_early_clauses, which the proof tests check claim by claim): the room's box with y below
-// the light plane (early_room_ok_k), the light's rectangle >= 1 inside the side walls and >= 1 above
-// the floor, its plane <= 81.5 (0.1 below the reference's sample plane :367) and >= 0.05 below the
-// ceiling, the room < 1000 across with X0, Y0, Z0 >= 0; per box a top >= 0.5 below the light plane
-// and the clause its position allows against the reference's wrapped samples (x in [31, 33), z in
-// [62, 64)). on = false, or a condition failing: no clause (+inf / -inf, nothing resolved early).
-static void early_geo_setup(const SceneGeo& g, int light_pos, bool on, KParams* K) {
-  for (int b = 0; b < 2; ++b) {
-    K->eb_top[b] = INFINITY; K->eb_sgn[b] = 1.0f; K->eb_bnd[b] = -INFINITY; K->eb_z[b] = 0;
-  }
-  for (int a = 0; a < 3; ++a) K->er_lo[a] = K->er_span[a] = 0;
-  bool ok = on && g.has_room && g.n_box == 2 && light_pos >= 0 && light_pos < g.n_xy + g.n_xz + g.n_yz &&
-            light_pos >= g.n_xy && light_pos < g.n_xy + g.n_xz;  // an XZ light
-  if (!ok) return;
-  const int nt = g.n_txy + g.n_txz + g.n_tyz;
-  float lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) {  // room tests: XY pair (planes z), XZ (y), YZ (x)
-    const GeoTest& R = g.test[nt + a];
-    const int ax = a == 0 ? 2 : (a == 1 ? 1 : 0);
-    lo[ax] = std::min(R.k0, R.k1);
-    hi[ax] = std::max(R.k0, R.k1);
-    ok = ok && lo[ax] >= 0.0f && hi[ax] - lo[ax] <= 1000.0f;
-    // a wall at -0.0 passes lo >= 0 with the bits 0x80000000: the span below would wrap and the
-    // uint compare hold for every negative coordinate. +0.0 instead: a vertex at exactly -0.0 then
-    // fails the compare and is traced, which is exact
-    if (lo[ax] == 0.0f) lo[ax] = 0.0f;
-  }
-  const GeoRect& L = g.rect[light_pos];
-  const float yl = L.k;
-  ok = ok && L.ha >= 0.0f && L.hb >= 0.0f && L.ma - L.ha >= lo[0] + 1.0f && L.ma + L.ha <= hi[0] - 1.0f &&
-       L.mb - L.hb >= lo[2] + 1.0f && L.mb + L.hb <= hi[2] - 1.0f && yl >= lo[1] + 1.0f && yl <= 81.5f &&
-       hi[1] >= yl + 0.05f;
-  for (int b = 0; ok && b < 2; ++b) {
-    const GeoTest &XY = g.test[nt + 3 + 3 * b], &YZ = g.test[nt + 4 + 3 * b], &T = g.test[nt + 5 + 3 * b];
-    const float z0 = std::min(XY.k0, XY.k1), z1 = std::max(XY.k0, XY.k1);
-    const float x0 = std::min(YZ.k0, YZ.k1), x1 = std::max(YZ.k0, YZ.k1);
-    // the box top at least 0.5 below the light plane (a top just under the plane left
-    // the box's y-slab exit within rounding of the light crossing)
-    if (!(T.k0 <= yl - 0.5f)) { ok = false; break; }
-    K->eb_top[b] = T.k0;
-    if (x0 >= 33.0f) { K->eb_sgn[b] = 1.0f; K->eb_bnd[b] = x0; K->eb_z[b] = 0; }
-    else if (x1 <= 31.0f) { K->eb_sgn[b] = -1.0f; K->eb_bnd[b] = -x1; K->eb_z[b] = 0; }
-    else if (z0 >= 64.0f) { K->eb_sgn[b] = 1.0f; K->eb_bnd[b] = z0; K->eb_z[b] = 1; }
-    else if (z1 <= 62.0f) { K->eb_sgn[b] = -1.0f; K->eb_bnd[b] = -z1; K->eb_z[b] = 1; }
-  }
-  if (!ok) {
-    for (int b = 0; b < 2; ++b) { K->eb_top[b] = INFINITY; K->eb_sgn[b] = 1.0f; K->eb_bnd[b] = -INFINITY; }
-    return;
-  }
-  for (int a = 0; a < 3; ++a) {
-    const float top = a == 1 ? std::nextafter(yl, 0.0f) : hi[a];  // y < y_L
-    uint32_t blo, btop;
-    std::memcpy(&blo, &lo[a], 4);
-    std::memcpy(&btop, &top, 4);
-    K->er_lo[a] = blo;
-    K->er_span[a] = btop - blo;
-  }
-}
-
-// The kernel variant of a render, a pure host decision (no device, no context: spt_select_kernel
-// answers it for any validated scene, spt_render_async launches what it returns). g, light_pos: the
-// scene's grouped geometry (build_geo). Also sets what the variant runs under in *K: light_black,
-// leak_end, the sphere kernel's early_y0, the uploaded-geometry kernels' clauses (early_geo_setup)
-// and ul_ybits.
-static int select_variant(const spt_prim* prims, int n_prims, const spt_camera* cam_in,
-                          const spt_params* p, const SceneGeo& g, int light_pos, KParams* Kp) {
-  KParams& K = *Kp;
-  float cam[12];  // the kernel's fp32 camera (KParams::cam)
-  for (int i = 0; i < 3; ++i) {
-    cam[i] = (float)cam_in->origin[i];
-    cam[3 + i] = (float)cam_in->lower_left_corner[i];
-    cam[6 + i] = (float)cam_in->horizontal[i];
-    cam[9 + i] = (float)cam_in->vertical[i];
-  }
-  K.light_black = light_pos >= 0 && prim_pmax(prims[p->light_id]) == 0.0f ? 1 : 0;
-  // Topology specialisation: the HEAD Cornell box (6 XY, 5 XZ, 6 YZ rects, light at grouped
-  // position 8) runs a fully unrolled intersect; anything else the generic loops.
-  bool all_diff = true;
-  for (int i = 0; i < n_prims; ++i) all_diff = all_diff && prims[i].refl == SPT_DIFF;
-  // The HEAD-topology kernels are all-DIFF, cosine-scatter specialisations; anything else (SPEC/
-  // REFR, the uniform hemisphere) runs the generic kernel.
-  // spt_params.flags SPT_FLAG_KERNEL_LEVEL (A/B and tests; never changes results): cap the
-  // specialisation level. 0 = auto (the most specialised kernel the host can prove).
-  const uint32_t klevel = (p->flags & SPT_FLAG_KERNEL_LEVEL_MASK) >> 8;
-  const int kcap = klevel == SPT_KERNEL_LEVEL_GENERIC   ? 0
-                   : klevel == SPT_KERNEL_LEVEL_CORNELL ? 1
-                   : klevel == SPT_KERNEL_LEVEL_CONST   ? 2
-                                                        : 3;
-  const bool cornell = kcap >= 1 && all_diff && !(p->flags & SPT_FLAG_UNIFORM_SCATTER) &&
-                       g.n_xy == 6 && g.n_xz == 5 && g.n_yz == 6 && g.n_sph == 0 && light_pos == 8 &&
-                       g.n_txy == 0 && g.n_txz == 1 && g.n_tyz == 0 && g.has_room && g.n_box == 2;
-  const bool cconst = cornell && kcap >= 2 && cornell_const_match(g, light_pos);
-  // Estimator specialisations of the HEAD-geometry kernel (Cfg): the reference's own settings.
-  // axis-aligned camera (Cfg CAMAX): horizontal.y/z and vertical.x/z zero, origin nonzero
-  // (the contract-v5 terms L = llc - origin and Au_x, Av_y nonzero: the zero products then vanish
-  // exactly, see the kernel's camera ray)
-  bool cam_axis = cam[7] == 0.0f && cam[8] == 0.0f && cam[9] == 0.0f && cam[11] == 0.0f;
-  for (int c = 0; c < 3; ++c) cam_axis = cam_axis && (cam[3 + c] - cam[c]) != 0.0f;
-  cam_axis = cam_axis && cam[6] * (1.0f / (float)p->width) != 0.0f &&
-             cam[10] * (1.0f / (float)p->height) != 0.0f;
-  for (int i = 0; i < 12; ++i) cam_axis = cam_axis && std::isfinite(cam[i]);
-  const bool lref = p->rr_depth == kRefRrDepth && p->light_id == kRefLightId &&
-                    p->light_x0 == kRefLx0 && p->light_dx == 36.0f && p->light_z0 == kRefLz0 &&
-                    p->light_dz == 36.0f && p->light_y == kRefLy && p->light_area == kRefLarea;
-  K.leak_end = (p->flags & SPT_FLAG_REFERENCE_LEAKS) ? 0 : leak_end_of(prims, n_prims, g);
-  // (each estimator kernel in two forms: the leak-end rule, or leaked paths as the reference's)
-  const bool ref_est = K.light_black && p->max_depth == 0 && p->rr_depth >= 1 && cam_axis && lref;
-  const bool head_est = cconst && kcap >= 3 && ref_est;
-  // any other camera (finite): the literal kernels' CAMAX 2 forms (round 6; leak-end rule only)
-  bool cam_fin = true;
-  for (int i = 0; i < 12; ++i) cam_fin = cam_fin && std::isfinite(cam[i]);
-  const bool ref_est_cam = K.light_black && p->max_depth == 0 && p->rr_depth >= 1 && cam_fin && lref &&
-                           !cam_axis && K.leak_end;
-  const bool head_est_cam = cconst && kcap >= 3 && ref_est_cam;
-  const bool upbox_cam = cornell && !cconst && kcap >= 3 && ref_est_cam && cornell_room_match(g);
-  const bool wrap_nee = p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP;
-  // the HEAD topology with uploaded geometry (an edited rect[]: a box moved, a wall resized) and
-  // the reference's estimator: geometry from LDS, the estimator's branches compile-time
-  const bool cornell_est = cornell && !cconst && kcap >= 2 && ref_est && K.leak_end;
-  int kv = g.n_sph_wide > 0 ? KV_WIDE : KV_GENERIC;  // (only the wide kernel has the fp64 loop)
-  if (head_est && p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP)
-    kv = K.leak_end ? KV_CONST_NEE : KV_CONST_NEE_REF;
-  else if (head_est && p->nee_prob <= 0.0f) kv = K.leak_end ? KV_CONST_COS : KV_CONST_COS_REF;
-  else if (head_est_cam && wrap_nee) kv = KV_CONST_NEE_CAM;
-  else if (head_est_cam && p->nee_prob <= 0.0f) kv = KV_CONST_COS_CAM;
-  else if (cconst) kv = KV_CONST;
-  else if (upbox_cam && wrap_nee) kv = KV_UPBOX_NEE_CAM;
-  else if (upbox_cam && p->nee_prob <= 0.0f) kv = KV_UPBOX_COS_CAM;
-  else if (cornell_est && p->nee_prob >= 1.0f && p->light_mode == SPT_LIGHT_GLIBC_WRAP) kv = KV_CORNELL_NEE;
-  else if (cornell_est && p->nee_prob <= 0.0f) kv = KV_CORNELL_COS;
-  else if (cornell) kv = KV_CORNELL;
-  else if (kv == KV_GENERIC && kcap >= 1 && all_diff && !(p->flags & SPT_FLAG_UNIFORM_SCATTER))
-    kv = g.n_sph == 0
-             // any other rect-only DIFF scene: run-time loops over the uploaded tests; with the
-             // reference's estimator its branches compile-time as well
-             ? (kcap >= 2 && ref_est && K.leak_end && p->nee_prob >= 1.0f &&
-                        p->light_mode == SPT_LIGHT_GLIBC_WRAP
-                    ? KV_RECTDIFF_NEE
-                    : kcap >= 2 && ref_est && K.leak_end && p->nee_prob <= 0.0f ? KV_RECTDIFF_COS
-                                                                                 : KV_RECTDIFF)
-         : kcap >= 3 && K.light_black && lref && p->nee_prob >= 1.0f &&
-                 p->light_mode == SPT_LIGHT_GLIBC_WRAP && light_pos >= 0 &&
-                 prims[p->light_id].kind == SPT_RECT_XZ
-             ? (K.leak_end ? KV_SPHDIFF_NEE : KV_SPHDIFF_NEE_REF)
-             : KV_SPHDIFF;
-  // the room HEAD's: the room literal, the boxes uploaded, the light literal when it is HEAD's too
-  const bool light_head = cornell_light_match(g, light_pos);
-  if (kv == KV_CORNELL_COS && kcap >= 3 && cornell_room_match(g)) kv = light_head ? KV_UPBOX_COS : KV_UPLIGHT_COS;
-  if (kv == KV_UPBOX_NEE_CAM && !light_head) kv = KV_UPLIGHT_NEE_CAM;
-  if (kv == KV_UPBOX_COS_CAM && !light_head) kv = KV_UPLIGHT_COS_CAM;
-  // The sphere NEE kernel's early resolve needs the HEAD room (rect[] :287-294, light at index 6)
-  // as prims 0..6, nothing else but narrow spheres, and a threshold above every sphere's top
-  // (early_room_proven); otherwise it stays off (+inf) and every shadow ray is traced.
-  K.early_y0 = INFINITY;
-  if ((kv == KV_SPHDIFF_NEE || kv == KV_SPHDIFF_NEE_REF) && n_prims > 7 && g.n_sph_wide == 0) {
-    spt_prim head[17];
-    int32_t nh = 0;
-    bool ok = spt_scene_cornell(head, 17, &nh) == SPT_OK;
-    for (int i = 0; ok && i < 7; ++i) ok = std::memcmp(&prims[i], &head[i], sizeof(spt_prim)) == 0;
-    double top = -INFINITY;
-    for (int i = 7; ok && i < n_prims; ++i) {
-      const double* g = prims[i].geom;
-      ok = prims[i].kind == SPT_SPHERE && std::isfinite(g[0]) && std::isfinite(g[1]) &&
-           std::isfinite(g[2]) && std::isfinite(g[3]);
-      top = std::max(top, g[2] + std::fabs(g[0]));
-      // the fp32 rounding argument of early_room_proven holds for |op| < 200 (and r < 200): every
-      // sphere centre within 190 of every room corner, so no vertex in the room is farther away
-      for (int c = 0; ok && c < 8; ++c) {
-        const double cx = (c & 1) ? 99.0 : 1.0, cy = (c & 2) ? 81.6 : 0.0, cz = (c & 4) ? 170.0 : 0.0;
-        ok = std::sqrt((g[1] - cx) * (g[1] - cx) + (g[2] - cy) * (g[2] - cy) +
-                       (g[3] - cz) * (g[3] - cz)) < 190.0 && std::fabs(g[0]) < 190.0;
-      }
-    }
-    if (ok && top + 1.0 < 81.0) {
-      float y0 = (float)(top + 1.0);
-      if ((double)y0 < top + 1.0) y0 = std::nextafter(y0, INFINITY);
-      K.early_y0 = y0;
-    }
-  }
-  // The uploaded-geometry HEAD-topology NEE kernel's early resolve (early_geo_proven): the room,
-  // the light and two boxes with the margins early_geo_setup checks, the clauses it picks (oracle
-  // c_find_early_clauses). Anything else: no clause, nothing resolved early.
-  early_geo_setup(g, light_pos, kv == KV_CORNELL_NEE || kv == KV_UPBOX_NEE_CAM || kv == KV_UPLIGHT_NEE_CAM, &K);
-  {
-    // (read only by the UPLIGHT NEE kernels, whose box clauses early_geo_setup leaves unsatisfiable
-    // unless the light plane lies >= 1 above the HEAD floor at +0: y_L >= 1, no sign bit)
-    const float yl = light_pos >= 0 ? g.rect[light_pos].k : 0.0f;
-    std::memcpy(&K.ul_ybits, &yl, 4);
-  }
-  // the room HEAD's: at the auto level the kernel with the room literal (the light, the boxes and
-  // the estimator's constants uploaded / literal); the const level keeps the uploaded-geometry one
-  if (kv == KV_CORNELL_NEE && kcap >= 3 && cornell_room_match(g)) kv = light_head ? KV_UPBOX_NEE : KV_UPLIGHT_NEE;
-  return kv;
-}
-
-// Does the variant resolve shadow rays without a trace under these parameters? The literal HEAD NEE
-// kernels always (early_nee_proven), the sphere NEE kernels with a finite threshold, the kernels
-// with uploaded boxes when early_geo_setup found the scene inside its margins (a clause is set).
-static int early_resolve_of(int kv, const KParams& K) {
-  switch (kv) {
-    case KV_CONST_NEE: case KV_CONST_NEE_REF: case KV_CONST_NEE_CAM:
-      return 1;
-    case KV_SPHDIFF_NEE: case KV_SPHDIFF_NEE_REF:
-      return std::isfinite(K.early_y0) ? 1 : 0;
-    case KV_CORNELL_NEE: case KV_UPBOX_NEE: case KV_UPBOX_NEE_CAM: case KV_UPLIGHT_NEE:
-    case KV_UPLIGHT_NEE_CAM:
-      return (K.er_span[0] | K.er_span[1] | K.er_span[2]) != 0 ? 1 : 0;
-    default:
-      return 0;
-  }
-}
-
-// Variant of the calling thread's last spt_render() launch (the one-shot call owns its context).
-static thread_local int g_dropin_kv = -1;
-
-extern "C" int32_t spt_kernel_count(void) { return KV_COUNT; }
-
-extern "C" const char* spt_kernel_name(int32_t id) {
-  return id >= 0 && id < KV_COUNT ? kKernelNames[id] : nullptr;
-}
-
-extern "C" spt_status spt_select_kernel(const spt_prim* prims, int32_t n_prims, const spt_camera* cam,
-                                        const spt_params* p, spt_kernel_choice* out) {
-  if (!out) return fail(SPT_ERR_INVALID_ARG, "null out");
-  spt_status st = validate(prims, n_prims, cam, p);
-  if (st != SPT_OK) return st;
-  std::unique_ptr<SceneGeo> g(new SceneGeo);
-  int light_pos = -1;
-  build_geo(prims, n_prims, g.get(), p->light_id, &light_pos);
-  KParams K{};
-  const int kv = select_variant(prims, n_prims, cam, p, *g, light_pos, &K);
-  out->kernel = kv;
-  out->leak_end = K.leak_end;
-  out->early_resolve = early_resolve_of(kv, K);
-  return SPT_OK;
-}
-
-extern "C" const char* spt_context_kernel(spt_context* c) {
-  const int kv = c ? c->last_kv : g_dropin_kv;
-  return kv >= 0 && kv < KV_COUNT ? kKernelNames[kv] : nullptr;
-}
-
-extern "C" spt_status spt_context_create(int32_t device, spt_context** out) {
-  if (!out) return fail(SPT_ERR_INVALID_ARG, "null out");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail(SPT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= count) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
-  SPT_HIP(hipSetDevice(device));
-  hipDeviceProp_t prop;
-  SPT_HIP(hipGetDeviceProperties(&prop, device));
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(SPT_ERR_NO_DEVICE, std::string("built for gfx950, device is ") + prop.gcnArchName);
-  spt_context* c = new spt_context();
-  c->device = device;
-  c->n_cu = prop.multiProcessorCount;
-  for (int v = 0; v < KV_COUNT; ++v) {
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kRenderKernels[v], kBlock, 0) !=
-            hipSuccess || bpc <= 0)
-      bpc = 4;
-    c->bpc[v] = bpc;
-  }
-  c->blocks_per_cu = c->bpc[KV_GENERIC];
-
-  hipError_t e = hipMalloc(&c->prims, sizeof(DevPrim) * kMaxPrims);
-  if (e == hipSuccess) e = hipMalloc(&c->geo, sizeof(SceneGeo));
-  if (e == hipSuccess) e = hipHostMalloc(&c->h_prims, sizeof(DevPrim) * kMaxPrims, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc(&c->h_geo, sizeof(SceneGeo), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&c->d_kp, sizeof(KParams));
-  if (e == hipSuccess) e = hipHostMalloc(&c->h_kp, sizeof(KParams), hipHostMallocDefault);
-
-  if (e == hipSuccess) e = hipMalloc(&c->queue, sizeof(uint32_t) * 64);
-  if (e == hipSuccess) e = hipMalloc(&c->stats, sizeof(unsigned long long) * kStatWords);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev1);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev2);
-  if (e == hipSuccess) e = hipHostMalloc(&c->h_stats, sizeof(unsigned long long) * kStatWords, hipHostMallocDefault);
-  if (e == hipSuccess) std::memset(c->h_stats, 0, sizeof(unsigned long long) * kStatWords);  // stats before any launch: zeros
-  if (e != hipSuccess) {
-    spt_context_destroy(c);
-    return fail(SPT_ERR_OOM, std::string("context alloc: ") + hipGetErrorString(e));
-  }
-  *out = c;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_context_destroy(spt_context* c) {
-  if (!c) return SPT_OK;
-  (void)hipSetDevice(c->device);
-  if (c->prims) (void)hipFree(c->prims);
-  if (c->geo) (void)hipFree(c->geo);
-  if (c->h_prims) (void)hipHostFree(c->h_prims);
-  if (c->h_geo) (void)hipHostFree(c->h_geo);
-  if (c->d_kp) (void)hipFree(c->d_kp);
-  if (c->h_kp) (void)hipHostFree(c->h_kp);
-
-  if (c->accum) (void)hipFree(c->accum);
-  if (c->slots) (void)hipFree(c->slots);
-  if (c->queue) (void)hipFree(c->queue);
-  if (c->stats) (void)hipFree(c->stats);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->ev2) (void)hipEventDestroy(c->ev2);
-  if (c->h_stats) (void)hipHostFree(c->h_stats);
-  if (c->last_film) spt_film_forget_context(c->last_film, c);
-  delete c;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_context_reserve(spt_context* c, int32_t n_prims, const spt_params* p) {
-  if (!c || !p) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  (void)n_prims;
-  const size_t need = 3ull * (size_t)spt_shard_row_count(p) * (size_t)p->width;
-  if (need > c->accum_cap) {
-    SPT_HIP(hipSetDevice(c->device));
-    if (c->accum) SPT_HIP(hipFree(c->accum));
-    c->accum = nullptr;
-    c->accum_cap = 0;
-    SPT_HIP(hipMalloc(&c->accum, need * sizeof(unsigned long long)));
-    c->accum_cap = need;
-  }
-  return SPT_OK;
-}
-
-// The film of the context's last launch and that film's last context name each other and nobody
-// else, so whichever is destroyed first can tell the other (spt_film_forget_context).
-static void set_last_film(spt_context* c, spt_film* film, int32_t count) {
-  if (c->last_film && c->last_film != film) spt_film_forget_context(c->last_film, c);
-  c->last_film = film;
-  c->last_film_count = count;
-}
-
-// One launch over the sample window [s_base, s_base + s_count) of the p->spp-sample image. With
-// film == nullptr the window's sums become the clamped floats of rgb_dev (finalize_slots_kernel:
-// the one-shot render, window [0, spp)); with a film they are added to it (spt_film.hip) and
-// rgb_dev, if given, receives the film resolved after the pass. Every size of the launch comes
-// from s_count; the fixed-point scale stays 2^31 / p->spp, so the windows' integers sum to the
-// one-shot's.
-spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
-                             const spt_camera* cam, const spt_params* p, int32_t s_base,
-                             int32_t s_count, float* rgb_dev, spt_film* film, void* stream_v) {
-  if (!c || (!rgb_dev && !film)) return fail(SPT_ERR_INVALID_ARG, "null context/output");
-  spt_status st = validate(prims, n_prims, cam, p);
-  if (st != SPT_OK) return st;
-  if (s_base < 0 || s_count < 1 || (int64_t)s_base + s_count > p->spp)
-    return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
-  if (film && film->device != c->device)
-    return fail(SPT_ERR_INVALID_ARG, "the film and the context are on different devices");
-  st = spt_context_reserve(c, n_prims, p);
-  if (st != SPT_OK) return st;
-  SPT_HIP(hipSetDevice(c->device));
-  hipStream_t stream = (hipStream_t)stream_v;
-
-  KParams K{};
-  if (c->pending) SPT_HIP(hipEventSynchronize(c->ev0));  // staging still read by a prior upload
-  to_dev(prims, n_prims, c->h_prims);
-  int light_pos = -1;
-  build_geo(prims, n_prims, c->h_geo, p->light_id, &light_pos);
-  SPT_HIP(hipMemcpyAsync(c->prims, c->h_prims, sizeof(DevPrim) * n_prims, hipMemcpyHostToDevice,
-                         stream));
-  SPT_HIP(hipMemcpyAsync(c->geo, c->h_geo, sizeof(SceneGeo), hipMemcpyHostToDevice, stream));
-  K.prims = c->prims;
-  K.geo = c->geo;
-  K.n_prims = n_prims;
-  for (int i = 0; i < 3; ++i) {
-    K.cam[i] = (float)cam->origin[i];
-    K.cam[3 + i] = (float)cam->lower_left_corner[i];
-    K.cam[6 + i] = (float)cam->horizontal[i];
-    K.cam[9 + i] = (float)cam->vertical[i];
-  }
-  K.width = p->width; K.height = p->height; K.spp = p->spp;
-  K.s_base = (uint32_t)s_base; K.s_count = (uint32_t)s_count; K.s_lim = (uint32_t)(s_base + s_count);
-  K.seed = p->seed;
-  K.nee_prob = p->nee_prob; K.rr_depth = p->rr_depth; K.max_depth = p->max_depth;
-  K.light_id = p->light_id;
-  K.lx0 = p->light_x0; K.ldx = p->light_dx; K.lz0 = p->light_z0; K.ldz = p->light_dz;
-  K.ly = p->light_y; K.larea = p->light_area; K.light_mode = p->light_mode;
-  K.ldxi = p->light_mode == SPT_LIGHT_GLIBC_WRAP ? (uint32_t)p->light_dx : 0u;
-  K.ldzi = p->light_mode == SPT_LIGHT_GLIBC_WRAP ? (uint32_t)p->light_dz : 0u;
-  K.tile_rows = tile_rows_of(p); K.shard_index = p->shard_index; K.shard_count = p->shard_count;
-  const int rows = spt_shard_row_count(p);
-  if (rows == 0) {  // a shard that owns no rows (more shards than row tiles): nothing to render
-    c->samples = 0;
-    c->nee_by_identity = false;
-    c->last_kv = -1;
-    set_last_film(c, nullptr, 0);
-    c->scene_flop = 0;
-    SPT_HIP(hipMemsetAsync(c->stats, 0, sizeof(unsigned long long) * kStatWords, stream));
-    SPT_HIP(hipEventRecord(c->ev0, stream));
-    SPT_HIP(hipEventRecord(c->ev1, stream));
-    SPT_HIP(hipMemcpyAsync(c->h_stats, c->stats, sizeof(unsigned long long) * kStatWords,
-                           hipMemcpyDeviceToHost, stream));
-    SPT_HIP(hipEventRecord(c->ev2, stream));
-    c->pending = true;
-    c->launched = true;
-    return SPT_OK;
-  }
-  K.n_local_pix = rows * p->width;
-  // the kernel variant, with the early-resolve clauses and the leak-end rule it runs under
-  const int kv = select_variant(prims, n_prims, cam, p, *c->h_geo, light_pos, &K);
-  // Unit size: SPT_UNITS_PER_LANE (8) units per resident lane (C3: 96 samples); never changes
-  // results (integer accumulation). Round 1 chose 16 (25.0 ms vs 26.0 ms at 8 units/lane, before
-  // in-wave stealing); re-measured in round 4 with stealing, unit slots and two frames in flight
-  // (profiles/r04_ab.txt session 6, 3 rounds): bench value 35.7 / 36.1 / 36.3 / 36.4 / 36.5
-  // Gsamples/s at 48 / 64 / 80 / 96 / 112 samples per unit, isolated kernel 11.67 / 11.60 / 11.60 /
-  // 11.68 / 11.70 ms -- fewer refills and retires, and the next frame fills the longer tail.
-  int chunk = p->chunk;
-  const double rays_per_sample = p->nee_prob > 0.0f ? 5.3 : 8.9;  // HEAD: NEE / cosine only
-  const double lane_iters = (double)K.n_local_pix * s_count * rays_per_sample /
-                            ((double)c->n_cu * c->bpc[kv] * kBlock);
-  const bool small_launch = lane_iters < SPT_SMALL_ITERS;
-  // A short launch takes at most SPT_SMALL_BPC blocks per CU (half the chip's wave slots): its tail
-  // is most of it, and the frame behind it (frames in flight) then runs beside it on the other half
-  // instead of only in its tail. C2, round 5 (profiles/r05_blocks_per_cu_ab.json, 4 rounds): bench
-  // value 17.9-18.8 -> 21.4-22.1 Gsamples/s, isolated kernel 2.88-2.95 -> 2.84-2.88 ms. Long launches
-  // keep every slot (C3 at 4 blocks: isolated +8 %, value within 1 %).
-  const int bpc = small_launch ? std::min(c->bpc[kv], SPT_SMALL_BPC) : c->bpc[kv];
-  const double lanes = (double)c->n_cu * bpc * kBlock;  // resident lanes of THIS launch
-  if (chunk <= 0) {
-    if (small_launch) {
-      // A short launch (C2: ~860 lane-iterations per lane): deal ~SPT_SMALL_UNITS units per lane
-      // and let the in-wave stealing and guided grabs balance the rest (C2: chunk 23 -> 64,
-      // 4.6 -> 4.0 ms; measured, scripts/ab_r02e.sh).
-      const double units_per_pix = std::max(1.0, std::ceil(SPT_SMALL_UNITS * lanes / std::max(1, K.n_local_pix)));
-      chunk = (int)std::ceil(s_count / units_per_pix);
-    } else {
-      // SPT_UNITS_PER_LANE units per resident lane (above)...
-      const double per_pix = std::max(1.0, SPT_UNITS_PER_LANE * lanes / std::max(1, K.n_local_pix));
-      chunk = (int)std::max(4.0, std::ceil(s_count / per_pix));
-    }
-    // ...but a unit should last >= ~200 lane-iterations: every unit costs a refill (~35 VALU +
-    // ~40 SALU for the whole wave) and a retire (C2: 6 -> 23 samples per unit, 4.73 -> ~4.6 ms).
-    chunk = std::max(chunk, (int)std::ceil(200.0 / rays_per_sample));
-    chunk = std::min(chunk, s_count);
-  }
-  {
-    const uint32_t waves = (uint32_t)(c->n_cu * bpc * (kBlock / 64));
-    uint32_t sh = 1;  // 2^sh >= 2 x waves
-    while ((1u << sh) < 2u * waves && sh < 31) ++sh;
-    sh = std::min(31u, sh + (uint32_t)SPT_GUIDED_EXTRA);
-    K.sh_guided = small_launch ? sh : 32u;  // guided grabs cost C3 ~1 % (A/B), help C2
-  }
-  K.chunk = chunk;
-  K.young_block = 0xFFFFFFFFu;
-  K.young_cut = 0xFFFFFFFFu;
-  K.steal_min = small_launch ? SPT_STEAL_MIN_SMALL : SPT_STEAL_MIN;
-  const uint64_t n_chunks = ((uint64_t)s_count + chunk - 1) / chunk;
-  const uint64_t n_units = n_chunks * (uint64_t)K.n_local_pix;
-  if (n_units >= 0x80000000ull) return fail(SPT_ERR_INVALID_ARG, "too many work units; raise chunk");
-  K.n_units = (uint32_t)n_units;
-  // the literal HEAD NEE kernels (and the boxes-only-uploaded one: edited scene -4 %) at 8 blocks
-  // per CU only (the measured shape): the sphere kernel (C5) lost 3.6 %, the uploaded-geometry
-  // kernels 0.5-2.4 % of kernel time or ~1.5 % of pipelined value (profiles/r05_young_cut_ab.json)
-  if (!small_launch && bpc == 8 &&
-      (kv == KV_CONST_NEE || kv == KV_CONST_NEE_REF || kv == KV_UPBOX_NEE || kv == KV_CONST_NEE_CAM ||
-       kv == KV_UPBOX_NEE_CAM || kv == KV_UPLIGHT_NEE || kv == KV_UPLIGHT_NEE_CAM) &&
-      SPT_YOUNG_CUT > 0) {
-    K.young_block = (uint32_t)(SPT_YOUNG_RANK * c->n_cu);
-    K.young_cut = (uint32_t)(n_units * (uint64_t)SPT_YOUNG_CUT / 1000u);
-  }
-  magic31((uint32_t)K.n_local_pix, &K.m_npix, &K.sh_npix);
-  // pixel-order spreading: the largest K = 2^k <= SPT_SCRAMBLE_K dividing n_local_pix
-  K.scr_k = 0;
-  while ((1 << (K.scr_k + 1)) <= SPT_SCRAMBLE_K && K.n_local_pix % (1 << (K.scr_k + 1)) == 0) ++K.scr_k;
-  K.scr_q = (uint32_t)K.n_local_pix >> K.scr_k;
-  magic31((uint32_t)p->width, &K.m_w, &K.sh_w);
-  magic31((uint32_t)K.tile_rows, &K.m_tile, &K.sh_tile);
-  K.inv_spp = 1.0f / (float)p->spp;
-  K.fix_scale = K.inv_spp * 2147483648.0f;
-  K.inv_w = 1.0f / (float)p->width;
-  K.inv_h = 1.0f / (float)p->height;
-  for (int c = 0; c < 3; ++c) {  // camera of contract v5 (oracle c_path)
-    K.cam_au[c] = K.cam[6 + c] * K.inv_w;
-    K.cam_av[c] = K.cam[9 + c] * K.inv_h;
-    K.cam_cu[c] = K.cam_au[c] * 0x1p-16f;
-    K.cam_cv[c] = K.cam_av[c] * 0x1p-16f;
-    K.cam_l[c] = K.cam[3 + c] - K.cam[c];
-  }
-  {  // light sample lattice of contract v5 (oracle c_wrap_sample)
-    auto lattice = [](uint32_t dx, float x0, int* on, uint32_t* shift, float* scale, float* x0m1) {
-      int a = 0;
-      while (a < 32 && dx != 0 && !((dx >> a) & 1u)) ++a;
-      *on = dx != 0 && a >= 1 && a <= 24;
-      *shift = *on ? 7u + (uint32_t)a : 0u;
-      *scale = std::ldexp(1.0f, a - 24);
-      *x0m1 = x0 - 1.0f;
-    };
-    lattice(K.ldxi, K.lx0, &K.lx_lattice, &K.lx_shift, &K.lx_scale, &K.lx0m1);
-    lattice(K.ldzi, K.lz0, &K.lz_lattice, &K.lz_shift, &K.lz_scale, &K.lz0m1);
-  }
-  K.accum = c->accum;
-  if (3ull * n_units > c->slots_cap) {  // one owner store per unit (24 B): C3 208 MB, C4/C5 ~400 MB
-    if (c->slots) SPT_HIP(hipFree(c->slots));
-    c->slots = nullptr;
-    c->slots_cap = 0;
-    SPT_HIP(hipMalloc(&c->slots, 3ull * n_units * sizeof(unsigned long long)));
-    c->slots_cap = 3ull * n_units;
-  }
-  K.slots = c->slots;
-  K.queue = c->queue;
-  K.stats = c->stats;
-  K.light_kind = light_pos >= 0 ? prims[p->light_id].kind : 0;
-  K.light_pos = light_pos;
-  K.scatter_uniform = (p->flags & SPT_FLAG_UNIFORM_SCATTER) ? 1 : 0;
-  // Ray-direction contract (oracle c_unit_dirs): unit directions iff a sphere or a REFR primitive
-  K.unit_dirs = 0;
-  for (int i = 0; i < n_prims; ++i)
-    if (prims[i].kind == SPT_SPHERE || prims[i].refl == SPT_REFR) K.unit_dirs = 1;
-  K.nee_c = (float)((double)p->light_area / 3.14159265358979323846);
-  c->n_prims = n_prims;
-  c->last = K;
-  c->samples = (uint64_t)K.n_local_pix * (uint64_t)s_count;
-  c->scene_flop = 0;
-  for (int i = 0; i < n_prims; ++i)
-    c->scene_flop += prims[i].kind == SPT_SPHERE ? SPT_FLOP_SPHERE : SPT_FLOP_RECT;
-
-  SPT_HIP(hipMemsetAsync(c->accum, 0, sizeof(unsigned long long) * 3 * (size_t)K.n_local_pix,
-                         stream));
-  SPT_HIP(hipMemsetAsync(c->queue, 0, sizeof(uint32_t), stream));
-  SPT_HIP(hipMemsetAsync(c->stats, 0, sizeof(unsigned long long) * kStatWords, stream));
-#ifdef SPT_WAVE_TIMES
-  SPT_HIP(hipMemsetAsync(c->stats + 14, 0xFF, sizeof(unsigned long long), stream));
-#endif
-  c->nee_by_identity = kv == KV_CONST_NEE_CAM || kv == KV_UPBOX_NEE_CAM || kv == KV_UPLIGHT_NEE ||
-                       kv == KV_UPLIGHT_NEE_CAM ||
-                       kv == KV_CONST_NEE || kv == KV_SPHDIFF_NEE || kv == KV_CONST_NEE_REF ||
-                       kv == KV_SPHDIFF_NEE_REF || kv == KV_CORNELL_NEE || kv == KV_RECTDIFF_NEE ||
-                       kv == KV_UPBOX_NEE;
-  const int grid = c->n_cu * bpc;
-  *c->h_kp = K;
-  SPT_HIP(hipMemcpyAsync(c->d_kp, c->h_kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
-  SPT_HIP(hipEventRecord(c->ev0, stream));
-  hipLaunchKernelGGL(kRenderKernels[kv], dim3(grid), dim3(kBlock), 0, stream,
-                     (const KParams*)c->d_kp);
-  SPT_HIP(hipGetLastError());
-  SPT_HIP(hipEventRecord(c->ev1, stream));
-  const uint32_t np = (uint32_t)K.n_local_pix;
-  if (film) {  // add the window's sums to the film (and resolve it into rgb_dev, if given)
-    st = spt_film_accumulate(film, c, c->accum, c->slots, rgb_dev, np, (uint32_t)n_chunks, K.scr_k,
-                             K.scr_q, c->stats, s_count, stream);
-    if (st != SPT_OK) return st;
-  } else {
-    hipLaunchKernelGGL(finalize_slots_kernel, dim3((np + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
-                       (const unsigned long long*)c->accum, (const unsigned long long*)c->slots,
-                       rgb_dev, np, (uint32_t)n_chunks, K.scr_k, K.scr_q,
-                       (const unsigned long long*)c->stats);
-    SPT_HIP(hipGetLastError());
-  }
-  set_last_film(c, film, film ? s_count : 0);
-  SPT_HIP(hipMemcpyAsync(c->h_stats, c->stats, sizeof(unsigned long long) * kStatWords,
-                         hipMemcpyDeviceToHost, stream));
-  SPT_HIP(hipEventRecord(c->ev2, stream));
-  c->pending = true;
-  c->launched = true;
-  c->last_kv = kv;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, int32_t n_prims,
-                                       const spt_camera* cam, const spt_params* p, float* rgb_dev,
-                                       void* stream) {
-  if (!c || !rgb_dev) return fail(SPT_ERR_INVALID_ARG, "null context/output");
-  if (!p) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  return spt_render_window(c, prims, n_prims, cam, p, 0, p->spp, rgb_dev, nullptr, stream);
-}
-
-// A film whose last pass this context rendered is going away (spt_film_destroy).
-void spt_context_forget_film(spt_context* c, const spt_film* film) {
-  if (c && c->last_film == film) c->last_film = nullptr;
-}
-
-extern "C" spt_status spt_context_stats(spt_context* c, spt_stats* out) {
-  if (!c || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  if (!c->launched) return fail(SPT_ERR_INVALID_ARG, "no render has been enqueued on this context");
-  SPT_HIP(hipSetDevice(c->device));
-  SPT_HIP(hipEventSynchronize(c->ev2));
-  const unsigned long long* h = c->h_stats;
-#ifdef SPT_WAVE_TIMES
-  std::fprintf(stderr, "SPT_WAVE_TIMES sum=%llu sumsq=%llu first=%llu last=%llu iters=%llu maxiters=%llu "
-               "sumstart16=%llu sumend16=%llu smid=%llu\n",
-               h[12], h[13], h[14], h[15], h[16], h[17], h[18], h[19], h[20]);
-  if (const char* path = std::getenv("SPT_WAVE_DUMP")) {  // diagnostic build only
-    if (FILE* f = std::fopen(path, "wb")) {
-      std::fwrite(h + 32, sizeof(unsigned long long), 3 * 32768, f);
-      std::fclose(f);
-    }
-  }
-#endif
-#ifdef SPT_REGION_STATS
-  {
-    static const char* names[10] = {"iteration", "unit_retire", "refill", "camera", "path_isect",
-                                    "diff_shading", "shadow_test", "nee_light_hit", "cosine",
-                                    "path_end"};
-    std::fprintf(stderr, "SPT_REGION_STATS");
-    for (int r = 0; r < 10; ++r)
-      std::fprintf(stderr, " %s=%llu/%llu", names[r], h[kStatRegion + 2 * r],
-                   h[kStatRegion + 1 + 2 * r]);
-    std::fprintf(stderr, "\n");
-  }
-#endif
-  if (h[0] != 0) {
-    c->pending = false;
-    // a film pass that hit the guard added nothing (spt_film.hip): take its samples back
-    if (c->last_film) spt_film_rollback(c->last_film, c, c->last_film_count);
-    set_last_film(c, nullptr, 0);
-    return fail(SPT_ERR_HIP, "render kernel hit its iteration cap in " + std::to_string(h[0]) +
-                                 " waves (a path did not terminate); the image is incomplete");
-  }
-  float ms = 0.0f;
-  SPT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  std::memset(out, 0, sizeof *out);
-  out->samples = c->samples; out->path_rays = h[1]; out->shadow_rays = h[2]; out->vertices = h[3];
-  out->nee_events = h[4]; out->nee_light_hits = h[5]; out->cosine_samples = h[6];
-  out->misses = h[7];
-  out->shadow_traced = h[kStatShadowTraced];
-  out->sphere_vertices = h[kStatSphereVertices];
-  out->shadow_proven = h[kStatShadowProven];
-  if (c->nee_by_identity) {  // HEAD NEE kernels: one NEE event per non-terminal vertex
-    out->nee_events = out->vertices - out->samples;
-    out->shadow_rays = out->nee_events;
-  }
-  // FLOP model (include/spt_flops.h): scene cost per ray from the primitive mix. `flop` charges
-  // a full scene test for every shadow ray of the reference (:466); `flop_executed` only for the
-  // shadow rays the kernel traced (the others are rejected exactly by the light pre-test or
-  // resolved by early_nee_proven()).
-  const double scene = c->scene_flop;
-  const double common = (double)out->samples * SPT_FLOP_SAMPLE +
-                        (double)out->path_rays * scene + (double)out->vertices * SPT_FLOP_VERTEX +
-                        (double)out->sphere_vertices * SPT_FLOP_SPHERE_NORMAL +
-                        (double)(out->vertices - out->samples) * SPT_FLOP_COMBINE +
-                        (double)out->cosine_samples * SPT_FLOP_COSINE +
-                        (double)out->nee_events * SPT_FLOP_NEE +
-                        (double)out->nee_light_hits * SPT_FLOP_NEE_HIT;
-  out->flop = common + (double)out->shadow_rays * scene;
-  out->flop_executed = common + (double)(out->shadow_traced - out->shadow_proven) * scene;
-  out->kernel_ms = ms;
-  c->pending = false;
-  return SPT_OK;
-}
-
-// The one-shot drop-in (spt_render) keeps one context and one device output buffer per device for
-// the life of the process (or until spt_shutdown), so a caller that renders repeatedly -- the
-// reference's main() replaced by smallpt_amd, or a Python loop over spt.render -- pays context
-// creation, the unit-slot allocation (~200 MB at C3) and the cold first launch once, not per call.
-// Calls on one device are serialised by that device's mutex; different devices run concurrently.
-namespace {
-constexpr int kMaxDropInDevices = 64;
-struct DropIn {
-  std::mutex mu;
-  spt_context* ctx = nullptr;
-  float* out = nullptr;  // device output, grown on demand
-  size_t out_cap = 0;    // floats
-};
-DropIn g_dropin[kMaxDropInDevices];
-}  // namespace
-
-extern "C" spt_status spt_render(const spt_prim* prims, int32_t n_prims, const spt_camera* cam,
-                                 const spt_params* p, float* rgb_out, spt_stats* stats) {
-  if (!rgb_out) return fail(SPT_ERR_INVALID_ARG, "null rgb_out");
-  spt_status st = validate(prims, n_prims, cam, p);
-  if (st != SPT_OK) return st;
-  if (p->device < 0 || p->device >= kMaxDropInDevices) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
-  const size_t n = 3ull * (size_t)spt_shard_row_count(p) * (size_t)p->width;
-  g_dropin_kv = -1;
-  if (n == 0) {  // this shard owns no rows: nothing to render, no context or device memory
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    return SPT_OK;
-  }
-  DropIn& D = g_dropin[p->device];
-  std::lock_guard<std::mutex> lock(D.mu);
-  if (!D.ctx) {
-    st = spt_context_create(p->device, &D.ctx);
-    if (st != SPT_OK) {
-      D.ctx = nullptr;
-      return st;
-    }
-  }
-  SPT_HIP(hipSetDevice(p->device));
-  if (n > D.out_cap) {
-    if (D.out) SPT_HIP(hipFree(D.out));
-    D.out = nullptr;
-    D.out_cap = 0;
-    SPT_HIP(hipMalloc(&D.out, n * sizeof(float)));
-    D.out_cap = n;
-  }
-  st = spt_render_async(D.ctx, prims, n_prims, cam, p, D.out, nullptr);
-  if (st == SPT_OK) g_dropin_kv = D.ctx->last_kv;
-  if (st == SPT_OK) {
-    spt_stats tmp;
-    st = spt_context_stats(D.ctx, stats ? stats : &tmp);
-  }
-  if (st == SPT_OK) SPT_HIP(hipMemcpy(rgb_out, D.out, n * sizeof(float), hipMemcpyDeviceToHost));
-  return st;
-}
-
-extern "C" spt_status spt_shutdown(void) {
-  for (DropIn& D : g_dropin) {
-    std::lock_guard<std::mutex> lock(D.mu);
-    if (D.ctx) {
-      const int dev = D.ctx->device;
-      spt_context_destroy(D.ctx);
-      D.ctx = nullptr;
-      if (D.out) {
-        (void)hipSetDevice(dev);
-        (void)hipFree(D.out);
-      }
-    }
-    D.out = nullptr;
-    D.out_cap = 0;
-  }
-  return SPT_OK;
-}
-
-extern "C" int32_t spt_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-extern "C" const char* spt_last_error(void) { return g_last_error.c_str(); }
+}  // namespace spt

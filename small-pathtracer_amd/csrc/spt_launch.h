@@ -1,0 +1,50 @@
+// spt_launch.h — the seams of the render path (internal; the public statement is include/spt.h):
+//   spt_dispatch.cpp  pure host code, no HIP: validation, scene grouping, the kernel choice, the
+//                     launch sizing, the last-error text
+//   spt_kernel.hip    the kernels, and the three launchers below: hipLaunchKernelGGL on a template
+//                     instantiation is the one thing a plain C++ file cannot do
+//   spt_context.cpp   contexts, uploads, launches and statistics (HIP runtime calls)
+#pragma once
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/spt.h"
+#include "spt_kparams.h"
+#include "spt_variants.h"
+
+namespace spt {
+
+// ---- spt_dispatch.cpp
+spt_status fail(spt_status s, const std::string& msg);  // sets spt_last_error()'s text, returns s
+spt_status validate(const spt_prim* prims, int32_t n, const spt_camera* cam, const spt_params* p);
+void to_dev(const spt_prim* s, int n, DevPrim* out);
+// Grouped geometry; *light_pos = position of prim `light` in rect[] / sph[] (-1 if absent).
+void build_geo(const spt_prim* s, int n, SceneGeo* g, int light, int* light_pos);
+// The kernel variant of a render (KV_*). Also sets what the variant runs under in *K: the fp32
+// camera, light_black, leak_end, early_y0, the early_geo_setup clauses and ul_ybits.
+int select_variant(const spt_prim* prims, int n_prims, const spt_camera* cam, const spt_params* p,
+                   const SceneGeo& g, int light_pos, KParams* K);
+
+// The sizes of one launch that are not KParams fields.
+struct LaunchPlan {
+  bool small_launch;  // fewer than SPT_SMALL_ITERS lane-iterations per resident lane
+  int bpc, grid;      // resident blocks per CU of this launch, blocks
+  uint32_t n_chunks;  // units per pixel
+};
+// Launch sizing, plain arithmetic: from the device's CU count, the variant kv and its resident
+// blocks per CU, the params, the sample window's length and the shard's pixels to the unit size,
+// the grid, the queue policy (guided grabs, stealing, young cut), the pixel spreading, the magic
+// divisors, the camera terms (from K->cam: select_variant first) and the light lattice. Fills *K
+// and *plan; fails when the launch would have 2^31 units or more.
+spt_status plan_launch(int n_cu, int variant_bpc, int kv, const spt_params* p, int32_t s_count,
+                       int n_local_pix, KParams* K, LaunchPlan* plan);
+
+// ---- spt_kernel.hip (stream: a hipStream_t; errors are left to the caller's hipGetLastError)
+int render_kernel_occupancy(int kv);  // resident blocks per CU of variant kv; <= 0: query failed
+void launch_render_kernel(int kv, int grid, const KParams* kp_dev, void* stream);
+void launch_finalize_slots(const unsigned long long* accum, const unsigned long long* slots,
+                           float* rgb, uint32_t npix, uint32_t n_chunks, uint32_t scr_k,
+                           uint32_t scr_q, const unsigned long long* stats, void* stream);
+
+}  // namespace spt

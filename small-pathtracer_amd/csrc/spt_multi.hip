@@ -24,7 +24,7 @@
 
 #include "../../include/spt.h"
 
-void spt_set_last_error(const std::string& msg);  // spt_kernel.hip
+void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp
 int spt_shard_row_count(const spt_params* p);     // spt_host.cpp
 
 namespace {

@@ -1,0 +1,196 @@
+// spt_dispatch_check.cpp — TEST INFRASTRUCTURE ONLY: a stand-alone host program over the pure host
+// half of the render path (spt_dispatch.cpp, with spt_host.cpp for the scenes), built with
+// -fsanitize=address,undefined by tests/probe/Makefile and run by tests/test_dispatch_host.py.
+// No HIP, no device, never loaded into Python.
+//   * build_geo / spt_select_kernel on scenes at the sizes where the kMaxPrims arrays and
+//     test[nt + 3 + 3*b + r] could overrun;
+//   * plan_launch on four shapes whose sizes were worked out by hand from the expressions.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../small-pathtracer_amd/csrc/spt_launch.h"
+
+using namespace spt;
+
+static int g_failed = 0;
+#define CHECK(cond)                                                          \
+  do {                                                                       \
+    if (!(cond)) {                                                           \
+      std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
+      ++g_failed;                                                            \
+    }                                                                        \
+  } while (0)
+
+static spt_prim rect(int kind, double a, double b, double c, double d, double k, double e = 0,
+                     double col = 0.75) {
+  spt_prim p;
+  std::memset(&p, 0, sizeof p);
+  p.kind = kind;
+  p.refl = SPT_DIFF;
+  p.geom[0] = a; p.geom[1] = b; p.geom[2] = c; p.geom[3] = d; p.geom[4] = k;
+  p.e[0] = p.e[1] = p.e[2] = e;
+  p.c[0] = p.c[1] = p.c[2] = col;
+  return p;
+}
+
+static std::vector<spt_prim> head() {
+  std::vector<spt_prim> s(17);
+  int32_t n = 0;
+  CHECK(spt_scene_cornell(s.data(), 17, &n) == SPT_OK && n == 17);
+  return s;
+}
+
+static spt_camera camera(bool tilted) {
+  const double from[3] = {tilted ? 40.0 : 50.0, tilted ? 55.0 : 40.0, tilted ? 160.0 : 168.0};
+  const double at[3] = {tilted ? 55.0 : 50.0, tilted ? 35.0 : 40.0, tilted ? 10.0 : 5.0};
+  const double up[3] = {tilted ? 0.1 : 0.0, 1.0, 0.0};
+  spt_camera c;
+  CHECK(spt_camera_init(&c, from, at, up, 65.0f, 4.0f / 3.0f) == SPT_OK);
+  return c;
+}
+
+// build_geo and the kernel choice of one scene, under NEE and cosine params, both cameras, every
+// level; `want`: the name at the auto level, axis camera, NEE (nullptr: not asserted).
+static void run_scene(const char* what, const std::vector<spt_prim>& s, int light_id, const char* want,
+                      int want_boxes = -1) {
+  auto g = std::make_unique<SceneGeo>();
+  int light_pos = -1;
+  build_geo(s.data(), (int)s.size(), g.get(), light_id, &light_pos);
+  const int nt = g->n_txy + g->n_txz + g->n_tyz + (g->has_room ? 3 : 0) + 3 * g->n_box;
+  CHECK(g->n_xy + g->n_xz + g->n_yz + g->n_sph == (int)s.size());
+  CHECK(nt >= 0 && nt <= kMaxPrims);
+  if (want_boxes >= 0) CHECK(g->n_box == want_boxes);
+  std::vector<DevPrim> dev(s.size());
+  to_dev(s.data(), (int)s.size(), dev.data());
+  for (int tilted = 0; tilted < 2; ++tilted) {
+    const spt_camera cam = camera(tilted != 0);
+    for (int level = 0; level < 4; ++level) {
+      for (int est = 0; est < 2; ++est) {
+        spt_params p;
+        spt_default_params(&p);
+        p.light_id = light_id;
+        p.nee_prob = est == 0 ? 1.0f : 0.0f;
+        p.flags = SPT_FLAG_KERNEL_LEVEL(level);
+        spt_kernel_choice ch{-1, -1, -1};
+        const spt_status st = spt_select_kernel(s.data(), (int32_t)s.size(), &cam, &p, &ch);
+        if (st != SPT_OK) {
+          std::fprintf(stderr, "%s: spt_select_kernel: %s\n", what, spt_last_error());
+          ++g_failed;
+          continue;
+        }
+        CHECK(ch.kernel >= 0 && ch.kernel < spt_kernel_count());
+        if (want && !tilted && level == 0 && est == 0 &&
+            std::string(spt_kernel_name(ch.kernel)) != want) {
+          std::fprintf(stderr, "%s: kernel %s, expected %s\n", what, spt_kernel_name(ch.kernel), want);
+          ++g_failed;
+        }
+      }
+    }
+  }
+}
+
+static void scenes() {
+  run_scene("head", head(), 6, "const_nee", 2);
+  {  // the short box moved by 1 along x
+    std::vector<spt_prim> s = head();
+    for (int i : {12, 13, 16}) { s[i].geom[0] += 1.0; s[i].geom[1] += 1.0; }
+    for (int i : {14, 15}) s[i].geom[4] += 1.0;
+    run_scene("box moved", s, 6, "upbox_nee", 2);
+  }
+  {  // the short box dropped
+    std::vector<spt_prim> s = head();
+    s.resize(12);
+    run_scene("box dropped", s, 6, "rectdiff_nee", 1);
+  }
+  run_scene("one primitive", {rect(SPT_RECT_XZ, 0, 10, 0, 10, 5, 12, 0)}, 0, "rectdiff", 0);
+  {  // the HEAD room and light plus spheres up to exactly kMaxPrims primitives
+    std::vector<spt_prim> s = head();
+    s.resize(7);
+    for (int i = 0; (int)s.size() < kMaxPrims; ++i) {
+      spt_prim p;
+      std::memset(&p, 0, sizeof p);
+      p.kind = SPT_SPHERE;
+      p.refl = SPT_DIFF;
+      p.geom[0] = 3.0;
+      p.geom[1] = 6.0 + 8.0 * (i % 11); p.geom[2] = 3.0; p.geom[3] = 20.0 + 25.0 * (i / 11);
+      p.c[0] = p.c[1] = p.c[2] = 0.5;
+      s.push_back(p);
+    }
+    CHECK((int)s.size() == kMaxPrims);
+    run_scene("64 with spheres", s, 6, "sphdiff_nee", 0);
+  }
+  {  // 64 rectangles of one kind, all with their own bounds: 64 single tests
+    std::vector<spt_prim> s;
+    for (int i = 0; i < kMaxPrims; ++i) s.push_back(rect(SPT_RECT_XY, 0, 10 + i, 0, 10, i, i == 0 ? 12 : 0, i == 0 ? 0 : 0.75));
+    run_scene("64 single XY", s, 0, "rectdiff", 0);
+  }
+  {  // ... and with shared bounds: 32 pair tests (the light never pairs)
+    std::vector<spt_prim> s;
+    for (int i = 0; i < kMaxPrims; ++i) s.push_back(rect(SPT_RECT_YZ, 0, 10, 0, 10, i, i == 63 ? 12 : 0, i == 63 ? 0 : 0.75));
+    run_scene("64 paired YZ", s, 63, "rectdiff", 0);
+  }
+  {  // a room, a light and 11 boxes (62 primitives): the most tests behind the room's
+    std::vector<spt_prim> s = head();
+    s.resize(7);
+    for (int b = 0; b < 11; ++b) {
+      const double x0 = 5 + 8 * b, x1 = x0 + 5, z0 = 10, z1 = 15, h = 10 + b;
+      s.push_back(rect(SPT_RECT_XY, x0, x1, 0, h, z0));
+      s.push_back(rect(SPT_RECT_XY, x0, x1, 0, h, z1));
+      s.push_back(rect(SPT_RECT_YZ, 0, h, z0, z1, x0));
+      s.push_back(rect(SPT_RECT_YZ, 0, h, z0, z1, x1));
+      s.push_back(rect(SPT_RECT_XZ, x0, x1, z0, z1, h));
+    }
+    run_scene("11 boxes", s, 6, "rectdiff_nee", 11);
+  }
+}
+
+// One plan_launch on an n_cu = 256 device.
+struct Sized { KParams K; LaunchPlan plan; };
+static Sized size(int w, int h, int spp, float nee_prob, int kv, int variant_bpc) {
+  spt_params p;
+  spt_default_params(&p);
+  p.width = w; p.height = h; p.spp = spp; p.nee_prob = nee_prob;
+  Sized s;
+  std::memset(&s, 0, sizeof s);
+  CHECK(plan_launch(256, variant_bpc, kv, &p, spp, w * h, &s.K, &s.plan) == SPT_OK);
+  return s;
+}
+
+static void sizing() {
+  for (int pass = 0; pass < 2; ++pass) {  // C3: 1024x768, 512 spp, NEE; const_nee, then cornell_nee
+    const Sized s = size(1024, 768, 512, 1.0f, pass == 0 ? KV_CONST_NEE : KV_CORNELL_NEE, 8);
+    CHECK(s.K.chunk == 96 && s.K.n_units == 4718592u && s.plan.n_chunks == 6u);
+    CHECK(!s.plan.small_launch && s.plan.bpc == 8 && s.plan.grid == 2048);
+    CHECK(s.K.sh_guided == 32u && s.K.steal_min == 8u);
+    if (pass == 0) CHECK(s.K.young_block == 1536u && s.K.young_cut == 1415577u);
+    else CHECK(s.K.young_block == 0xFFFFFFFFu && s.K.young_cut == 0xFFFFFFFFu);  // no young cut
+    CHECK(s.K.scr_k == 3u && s.K.scr_q == 98304u);
+    CHECK(s.K.n_local_pix == 786432 && s.K.tile_rows == 8);
+  }
+  {  // C2: 1024x768, 64 spp, cosine only, const_cos: a short launch
+    const Sized s = size(1024, 768, 64, 0.0f, KV_CONST_COS, 8);
+    CHECK(s.K.chunk == 64 && s.K.n_units == 786432u && s.plan.n_chunks == 1u);
+    CHECK(s.plan.small_launch && s.plan.bpc == 4 && s.plan.grid == 1024);
+    CHECK(s.K.sh_guided == 14u && s.K.steal_min == 16u);
+    CHECK(s.K.young_block == 0xFFFFFFFFu && s.K.young_cut == 0xFFFFFFFFu);
+  }
+  {  // 64x48, 16 spp, NEE
+    const Sized s = size(64, 48, 16, 1.0f, KV_CONST_NEE, 8);
+    CHECK(s.K.chunk == 16 && s.K.n_units == 3072u && s.plan.bpc == 4);
+  }
+}
+
+int main() {
+  scenes();
+  sizing();
+  if (g_failed) {
+    std::fprintf(stderr, "spt_dispatch_check: %d checks failed\n", g_failed);
+    return 1;
+  }
+  std::puts("spt_dispatch_check ok");
+  return 0;
+}

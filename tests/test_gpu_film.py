@@ -177,7 +177,7 @@ def test_short_and_long_launch_in_one_image(spt, torch_dev):
     first window is a short launch and the second a long one; together they are the one-shot."""
     w, h, spp = 1024, 768, 512
     n_cu = torch_dev.cuda.get_device_properties(0).multi_processor_count
-    # spt_kernel.hip: pixels * samples * 5.3 rays per NEE sample / (CUs * 8 blocks * 256 lanes)
+    # plan_launch (spt_dispatch.cpp): pixels * samples * 5.3 rays per NEE sample / (CUs * 8 blocks * 256 lanes)
     iters = lambda count: w * h * count * 5.3 / (n_cu * 8 * 256)  # noqa: E731
     assert iters(200) < 2000.0 <= iters(312), (n_cu, iters(200), iters(312))
     p = spt.default_params(width=w, height=h, spp=spp, seed=1, device=0)
