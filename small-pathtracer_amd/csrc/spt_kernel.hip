@@ -653,6 +653,15 @@ __device__ __forceinline__ void pixel_terms(const SPT_CONST KParams* Q, uint32_t
   fy = ((float)(Q->height - py - 1) - 0.5f) - 128.0f;
 }
 
+// Orders one wave's own LDS accesses: what its lanes wrote before this point is what any of its
+// lanes reads after it. No instruction on gfx950 (a wave's LDS operations complete in order); it
+// binds the compiler.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                    __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -709,6 +718,12 @@ render_kernel(const KParams* __restrict__ Pg) {
   // Shadow rays resolved early, per wave, in the sphere kernels (same reason: no VGPR counter)
   __shared__ uint32_t s_nearly[TP::SPH ? kBlock / 64 : 1];
   if (TP::SPH && threadIdx.x < kBlock / 64) s_nearly[threadIdx.x] = 0;
+  // The set-up of the units of each wave's pool (spt_kparams.h, SPT_POOL_LDS): 64 entries per wave,
+  // written and read by that wave alone. The generic kernels keep the per-lane set-up: the REFR
+  // stack fills their LDS (5 blocks per CU), and 8 KB more would cost them a block.
+  constexpr bool kPoolLds = kPoolLdsBuild && !TP::MAT;
+  __shared__ PoolEntryA s_pool_a[kPoolLds ? kBlock : 1];
+  __shared__ PoolEntryB s_pool_b[kPoolLds ? kBlock : 1];
   {
     const SPT_CONST KParams* P = cptr(Pg);
     const SPT_CONST SceneGeo* G = cptr(P->geo);
@@ -769,6 +784,35 @@ render_kernel(const KParams* __restrict__ Pg) {
     cg = CamG{C->cam[0], C->cam[1], C->cam[2], C->cam_cu[0], C->cam_cu[1], C->cam_cu[2],
               C->cam_cv[0], C->cam_cv[1], C->cam_cv[2], C->fix_scale};
   }
+  // The terms of unit u (chunk-major units, pixel order spread by scr_k): its sample range, the
+  // Philox key and the camera terms of its pixel. One lane's set-up of its own unit, or lane i's of
+  // unit pool_next + i at the pool fill: the same arithmetic either way.
+  auto unit_setup = [&](uint32_t u, uint32_t& us, uint32_t& us_end, PxKey& upk, float& ufx, float& ufy,
+                        float& ufz) {
+    const SPT_CONST KParams* Q = cptr(Pg);
+    const uint32_t npix = (uint32_t)Q->n_local_pix;
+    const uint32_t j = div_magic(u, Q->m_npix, Q->sh_npix);  // chunk-major
+    uint32_t up = u - j * npix;
+    // Spread the pixel order (scr_k > 0): unit pixel lp = b * K + a -> a * (npix / K) + b, so a
+    // wave's run of consecutive units samples the whole image instead of one row segment, and
+    // per-wave work varies less (the image does not change: every pixel-sample is still done
+    // once and summed in integers)
+    up = (up & ((1u << Q->scr_k) - 1u)) * Q->scr_q + (up >> Q->scr_k);
+    us = Q->s_base + j * (uint32_t)Q->chunk;  // absolute sample index: the Philox sample word
+    us_end = min(us + (uint32_t)Q->chunk, Q->s_lim);
+    pixel_terms(Q, up, upk, ufx, ufy);
+    if constexpr (CF::CAMAX == 1) {  // the per-pixel P_x, P_y of the camera ray (jitter_f)
+      ufx = fmaf(ck.aux, ufx, ck.lx);
+      ufy = fmaf(ck.avy, ufy, ck.ly);
+    } else if constexpr (CF::CAMAX == 2) {  // P_c = fma(Au_c, fx, fma(Av_c, fy, L_c)), c = x, y, z
+      const float rx = ufx, ry = ufy;
+      ufx = fmaf(Q->cam_au[0], rx, fmaf(Q->cam_av[0], ry, Q->cam_l[0]));
+      ufy = fmaf(Q->cam_au[1], rx, fmaf(Q->cam_av[1], ry, Q->cam_l[1]));
+      ufz = fmaf(Q->cam_au[2], rx, fmaf(Q->cam_av[2], ry, Q->cam_l[2]));
+    }
+  };
+  // the wave's region of s_pool_a / s_pool_b starts at its first thread's index (wave-uniform)
+  const uint32_t pool_lds = kPoolLds ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) : 0u;
   uint32_t pool_next = 0, pool_end = 0, grab_at = 0;  // grab_at: the wave's last queue position
   bool exhausted = false, capped = false;
   // Wave-uniform event counters (SGPRs), fed by ballots at convergent points of the loop: per-lane
@@ -840,32 +884,49 @@ render_kernel(const KParams* __restrict__ Pg) {
         if (b >= Q->n_units) { exhausted = true; break; }
         pool_next = b;
         pool_end = min(b + want, Q->n_units);
+        if constexpr (kPoolLds) {
+          // Fill: lane i sets up unit b + i into entry (b + i) mod 64, all lanes at once (the branch
+          // is wave-uniform). The region is the wave's own, so the order that matters is this wave's:
+          // its earlier fetches before these writes, these writes before its later fetches.
+          wave_lds_order();
+          const uint32_t u = b + lane;
+          if (u < pool_end) {
+            uint32_t us, us_end;
+            PxKey upk;
+            float ufx, ufy, ufz = 0.0f;
+            unit_setup(u, us, us_end, upk, ufx, ufy, ufz);
+            s_pool_a[pool_lds + (u & 63u)] = PoolEntryA{us, upk.qhi, upk.qlo, upk.lo};
+            // (the third word: P_z where the kernel holds one, else the owner's lp = u | 2^31, so
+            // that every kernel reads the entry as two whole 128-bit words)
+            if constexpr (CF::CAMAX != 2) ufz = __uint_as_float(u | 0x80000000u);
+            s_pool_b[pool_lds + (u & 63u)] = PoolEntryB{ufx, ufy, ufz, us_end};
+          }
+          wave_lds_order();
+        }
       }
       const uint32_t rank = lane_rank(need);
       const uint32_t avail = pool_end - pool_next;
       if (needs_unit && rank < avail) {
         const uint32_t u = pool_next + rank;
-        const uint32_t npix = (uint32_t)Q->n_local_pix;
-        const uint32_t j = div_magic(u, Q->m_npix, Q->sh_npix);  // chunk-major
-        lp = u - j * npix;
-        // Spread the pixel order (scr_k > 0): unit pixel lp = b * K + a -> a * (npix / K) + b, so a
-        // wave's run of consecutive units samples the whole image instead of one row segment, and
-        // per-wave work varies less (the image does not change: every pixel-sample is still done
-        // once and summed in integers)
-        lp = (lp & ((1u << Q->scr_k) - 1u)) * Q->scr_q + (lp >> Q->scr_k);
-        s = Q->s_base + j * (uint32_t)Q->chunk;  // absolute sample index: the Philox sample word
-        s_end = min(s + (uint32_t)Q->chunk, Q->s_lim);
-        pixel_terms(Q, lp, pk, fx, fy);
-        if constexpr (CF::CAMAX == 1) {  // the per-pixel P_x, P_y of the camera ray (jitter_f)
-          fx = fmaf(ck.aux, fx, ck.lx);
-          fy = fmaf(ck.avy, fy, ck.ly);
-        } else if constexpr (CF::CAMAX == 2) {  // P_c = fma(Au_c, fx, fma(Av_c, fy, L_c)), c = x, y, z
-          const float rx = fx, ry = fy;
-          fx = fmaf(Q->cam_au[0], rx, fmaf(Q->cam_av[0], ry, Q->cam_l[0]));
-          fy = fmaf(Q->cam_au[1], rx, fmaf(Q->cam_av[1], ry, Q->cam_l[1]));
-          fz = fmaf(Q->cam_au[2], rx, fmaf(Q->cam_av[2], ry, Q->cam_l[2]));
+        if constexpr (kPoolLds) {  // the entry the fill wrote for unit u
+          const PoolEntryA ea = s_pool_a[pool_lds + (u & 63u)];
+          const PoolEntryB eb = s_pool_b[pool_lds + (u & 63u)];
+          s = ea.s;
+          pk = PxKey{ea.qhi, ea.qlo, ea.lo};
+          fx = eb.fx;
+          fy = eb.fy;
+          s_end = eb.s_end;
+          // the owner keeps its unit index: the sums go to the unit's slot
+          if constexpr (CF::CAMAX == 2) {
+            fz = eb.fz;
+            lp = u | 0x80000000u;
+          } else {
+            lp = __float_as_uint(eb.fz);
+          }
+        } else {
+          unit_setup(u, s, s_end, pk, fx, fy, fz);
+          lp = u | 0x80000000u;
         }
-        lp = u | 0x80000000u;  // the owner keeps its unit index: the sums go to the unit's slot
         ls = kStCam;
         needs_unit = false;
       }

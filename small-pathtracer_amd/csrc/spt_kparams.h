@@ -29,6 +29,22 @@ constexpr uint32_t kGrab = SPT_GRAB;
 #define SPT_GUIDED_EXTRA 1
 #endif
 constexpr uint32_t kGrabMin = SPT_GRAB_MIN;  // guided grabs never take fewer (bounds the queue atomics)
+// Pool set-up through LDS (render_kernel, refill): the wave that grabs a pool computes the terms of
+// all its units at once, lane i those of unit pool_next + i, into a region of LDS of its own, and a
+// lane that takes a unit reads its entry where it used to compute it (the whole wave paid ~60
+// issue slots for the 1.2 lanes an average refill serves). 0: every lane sets its own unit up, as
+// rounds 1-6 did. The generic kernels (Topo::MAT: the REFR stack holds their LDS) always do.
+#ifndef SPT_POOL_LDS
+#define SPT_POOL_LDS 1
+#endif
+// An entry: two 16-byte halves, kept in two arrays so that both the fill (consecutive entries) and
+// the fetch read and write whole 128-bit words at a 16-byte stride (no bank conflict). The entry
+// of unit u is u mod 64: a pool is at most 64 consecutive units, one per lane of the fill (a build
+// with a larger SPT_GRAB keeps the per-lane set-up).
+constexpr bool kPoolLdsBuild = SPT_POOL_LDS != 0 && kGrab <= 64;
+struct alignas(16) PoolEntryA { uint32_t s, qhi, qlo, lo; };  // first sample; the Philox pixel key (PxKey)
+struct alignas(16) PoolEntryB { float fx, fy, fz; uint32_t s_end; };  // camera terms; end of the sample range
+static_assert(sizeof(PoolEntryA) == 16 && sizeof(PoolEntryB) == 16, "pool entry layout");
 // Launches with fewer lane-iterations per resident lane than SPT_SMALL_ITERS deal their units
 // almost all at once (SPT_SMALL_UNITS per lane) and balance by stealing (host, plan_launch).
 #ifndef SPT_SMALL_ITERS
