@@ -30,8 +30,10 @@ extern "C" {
                              spt_gather_staging_floats, spt_shutdown; 5: SPT_FLAG_REFERENCE_LEAKS;
                              6: spt_kernel_count, spt_kernel_name, spt_select_kernel,
                              spt_context_kernel. Added since, with no change to an existing struct or
-                             entry point (so the version stays): SPT_HAS_FILM, the spt_film_* calls */
+                             entry point (so the version stays): SPT_HAS_FILM, the spt_film_* calls;
+                             SPT_HAS_FILM_NOISE, the spt_film_noise_* calls */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
+#define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -294,6 +296,64 @@ spt_status spt_film_upload(spt_film* film, const uint64_t* host_sums, int64_t sa
 /* The resolve as a pure host function (no device): the CPU statement of spt_film_resolve, for
  * checkpoints and tests. Uses info's width, rows, spp_total and samples_done. */
 spt_status spt_film_resolve_host(const uint64_t* sums, const spt_film_info* info, float* rgb_out);
+
+/* ---- the noise-aware film: batch moments, error map, RMSE estimate (SPT_HAS_FILM_NOISE) ----
+ * A noise film takes its samples in B = spp_total / batch passes of exactly `batch` samples each.
+ * Beside the sums S it keeps the moment plane M2: uint64[rows * w * 3][2], element e the 128-bit
+ * integer (lo, hi) = the sum over the passes of P^2, P = the pass's 1.31 window sum of that pixel and
+ * channel (what the pass adds to S). Exact integers: P <= batch * 2^31, so B * M2 <= spp^2 * 2^62
+ * < 2^128; like the sums, M2 does not depend on the order of the passes, the contexts or the GPUs.
+ * From the two the standard error of every resolved value follows (the passes are independent
+ * estimates of the same pixel: the counter RNG is keyed by the absolute sample index):
+ *   D  = B * M2 - S^2                (128-bit, >= 0 by Cauchy-Schwarz), d = (double)hi * 2^64 + (double)lo
+ *   se = (float)(sqrt(d) * k),       k = spp_total / (batch * 2^31 * B * sqrt(B - 1)) in double
+ *   se = 0 where the channel's resolved value (spt_film_resolve's rule) is the clamp 1.0f
+ * with B = batches_done >= 2; se estimates the standard error of the resolved (preview or full) value.
+ * The clamp rule makes the figures those of the clamped image, the project's metric: an edge pixel
+ * of the light has a large unclamped error and a clamped error of 0. */
+typedef struct spt_film_noise_info {
+  int32_t enabled, batch; /* enabled = 0: a plain film (batch and batches_done 0) */
+  int64_t batches_done;
+} spt_film_noise_info;
+typedef struct spt_noise_summary {
+  double rmse[3];       /* per channel: sqrt(mean over ALL pixels of d * k^2), clamped channels 0 */
+  double rmse_all;      /* the same over the three channels together */
+  float se_max;         /* the largest se of the map */
+  uint64_t clamped;     /* channels whose resolved value is the clamp (se = 0 by rule) */
+  int64_t batches_done; /* B */
+} spt_noise_summary;
+/* Allocates and zeroes M2. Only on an empty film (samples_done == 0), with batch >= 1,
+ * spp_total % batch == 0 and spp_total / batch >= 2: SPT_ERR_INVALID_ARG otherwise, film untouched.
+ * From then on spt_film_render_async accepts only windows with sample_count == batch and
+ * sample_base % batch == 0 (rejected otherwise: nothing queued, film untouched); the accumulate pass
+ * also does M2 += P^2. A pass that hit the runaway guard adds nothing to M2 either and its batch is
+ * taken back with its samples. spt_film_clear also zeroes M2 and the batch count. spt_film_merge
+ * wants both films plain (as above) or both noise films of equal batch (dst.M2 += src.M2 with carry,
+ * the batch counts add); a mixed pair or unequal batches are rejected with dst untouched.
+ * spt_film_upload on a noise film requires samples_done % batch == 0. */
+spt_status spt_film_noise_enable(spt_film* film, int32_t batch);
+spt_status spt_film_noise_info_get(const spt_film* film, spt_film_noise_info* out);
+/* M2 to and from HOST memory (rows*w*3 pairs (lo, hi) of uint64, pixel order); both wait for their
+ * copy. upload: 0 <= batches_done <= spp_total / batch. Keeping spt_film_upload's samples_done and
+ * this batches_done consistent (samples_done == batches_done * batch) is the caller's duty, as
+ * keeping windows disjoint is. Rejected on a plain film. */
+spt_status spt_film_noise_download(const spt_film* film, uint64_t* host_m2, void* stream);
+spt_status spt_film_noise_upload(spt_film* film, const uint64_t* host_m2, int64_t batches_done,
+                                 void* stream);
+/* The error map: se of every value of the film, rows*w*3 floats (DEVICE), enqueued on `stream`.
+ * Rejected on a plain film and while batches_done < 2. */
+spt_status spt_film_noise_map(const spt_film* film, float* se_dev, void* stream);
+/* The image figures. Waits on `stream`. A two-stage reduction in a fixed order (per-block partials,
+ * then one block; no floating-point atomics): the same film gives the same bits every time. */
+spt_status spt_film_noise_summary(spt_film* film, spt_noise_summary* out, void* stream);
+/* Both as pure host functions (no device): sums and m2 as downloaded, info and noise from the
+ * *_info_get calls (width, rows, spp_total, samples_done; batch, batches_done). */
+spt_status spt_film_noise_map_host(const uint64_t* sums, const uint64_t* m2,
+                                   const spt_film_info* info, const spt_film_noise_info* noise,
+                                   float* se_out);
+spt_status spt_film_noise_summary_host(const uint64_t* sums, const uint64_t* m2,
+                                       const spt_film_info* info, const spt_film_noise_info* noise,
+                                       spt_noise_summary* out);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

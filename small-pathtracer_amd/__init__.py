@@ -97,6 +97,22 @@ class spt_film_info(ctypes.Structure):
                 ("samples_done", ctypes.c_int64)]
 
 
+class spt_film_noise_info(ctypes.Structure):
+    _fields_ = [("enabled", ctypes.c_int32), ("batch", ctypes.c_int32),
+                ("batches_done", ctypes.c_int64)]
+
+
+class spt_noise_summary(ctypes.Structure):
+    _fields_ = [("rmse", ctypes.c_double * 3), ("rmse_all", ctypes.c_double),
+                ("se_max", ctypes.c_float), ("clamped", ctypes.c_uint64),
+                ("batches_done", ctypes.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {"rmse": [float(x) for x in self.rmse], "rmse_all": float(self.rmse_all),
+                "se_max": float(self.se_max), "clamped": int(self.clamped),
+                "batches_done": int(self.batches_done)}
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -120,7 +136,10 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_build_sources_sha16", "spt_kernel_count", "spt_kernel_name", "spt_select_kernel",
            "spt_context_kernel", "spt_film_create", "spt_film_destroy", "spt_film_info_get",
            "spt_film_clear", "spt_film_render_async", "spt_film_resolve", "spt_film_merge",
-           "spt_film_download", "spt_film_upload", "spt_film_resolve_host"]
+           "spt_film_download", "spt_film_upload", "spt_film_resolve_host",
+           "spt_film_noise_enable", "spt_film_noise_info_get", "spt_film_noise_download",
+           "spt_film_noise_upload", "spt_film_noise_map", "spt_film_noise_summary",
+           "spt_film_noise_map_host", "spt_film_noise_summary_host"]
 IMAGE_FORMATS = {"p3": 0, "p6": 1, "pfm": 2}
 FLAG_UNIFORM_SCATTER = 1  # spt_params.flags: random_scattering from the uniform code of :352-359
 # spt_params.flags: leaked paths go on from the miss vertex as the reference's (:371-377) instead of
@@ -226,6 +245,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_film_download.argtypes = [VP, VP, VP]
     lib.spt_film_upload.argtypes = [VP, VP, I64, VP]
     lib.spt_film_resolve_host.argtypes = [VP, P(spt_film_info), VP]
+    lib.spt_film_noise_enable.argtypes = [VP, I32]
+    lib.spt_film_noise_info_get.argtypes = [VP, P(spt_film_noise_info)]
+    lib.spt_film_noise_download.argtypes = [VP, VP, VP]
+    lib.spt_film_noise_upload.argtypes = [VP, VP, I64, VP]
+    lib.spt_film_noise_map.argtypes = [VP, VP, VP]
+    lib.spt_film_noise_summary.argtypes = [VP, P(spt_noise_summary), VP]
+    lib.spt_film_noise_map_host.argtypes = [VP, VP, P(spt_film_info), P(spt_film_noise_info), VP]
+    lib.spt_film_noise_summary_host.argtypes = [VP, VP, P(spt_film_info), P(spt_film_noise_info),
+                                                P(spt_noise_summary)]
     for name in EXPORTS:
         if name.startswith("spt_film_"):
             getattr(lib, name).restype = I32
@@ -585,6 +613,10 @@ class Renderer:
 # ---------------------------------------------------------------------------------------------
 FILM_MAGIC = b"SPTFILM1"
 _FILM_HEADER = "<8siiiiq"  # magic, width, rows, spp_total, 0, samples_done: 32 bytes, then the sums
+# a noise film's file: the same 32 bytes under its own magic, then batch, 0, batches_done (48 bytes),
+# the sums, and the moment plane M2 (rows * width * 3 pairs (lo, hi) of uint64)
+FILM_MAGIC_NOISE = b"SPTFILM2"
+_FILM_HEADER_NOISE = "<8siiiiqiiq"
 
 
 def sample_windows(spp: int, passes: int) -> list:
@@ -607,32 +639,99 @@ def film_resolve_host(sums: np.ndarray, width: int, rows: int, spp_total: int,
     return out
 
 
+def film_noise_map_host(sums: np.ndarray, m2: np.ndarray, width: int, rows: int, spp_total: int,
+                        samples_done: int, batch: int, batches_done: int) -> np.ndarray:
+    """spt_film_noise_map_host(): the CPU statement of the error map (no device). m2: rows * width
+    * 3 pairs (lo, hi) of uint64. -> (rows, width, 3) float32 standard errors."""
+    a, m, info, noise = _noise_host_args(sums, m2, width, rows, spp_total, samples_done, batch,
+                                         batches_done)
+    out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
+    _check(load_library().spt_film_noise_map_host(a.ctypes.data, m.ctypes.data, ctypes.byref(info),
+                                                  ctypes.byref(noise), out.ctypes.data))
+    return out
+
+
+def film_noise_summary_host(sums: np.ndarray, m2: np.ndarray, width: int, rows: int, spp_total: int,
+                            samples_done: int, batch: int, batches_done: int) -> dict:
+    """spt_film_noise_summary_host(): the CPU statement of the image figures -> {"rmse": [r, g, b],
+    "rmse_all", "se_max", "clamped", "batches_done"}."""
+    a, m, info, noise = _noise_host_args(sums, m2, width, rows, spp_total, samples_done, batch,
+                                         batches_done)
+    out = spt_noise_summary()
+    _check(load_library().spt_film_noise_summary_host(a.ctypes.data, m.ctypes.data,
+                                                      ctypes.byref(info), ctypes.byref(noise),
+                                                      ctypes.byref(out)))
+    return out.as_dict()
+
+
+def _noise_host_args(sums, m2, width, rows, spp_total, samples_done, batch, batches_done):
+    a = np.ascontiguousarray(sums, dtype=np.uint64)
+    m = np.ascontiguousarray(m2, dtype=np.uint64)
+    info = spt_film_info(int(width), int(rows), int(spp_total), int(samples_done))
+    noise = spt_film_noise_info(1, int(batch), int(batches_done))
+    n = 3 * max(info.rows, 0) * max(info.width, 0)
+    if a.size != n or m.size != 2 * n:
+        raise SptError(1, "sums / m2 do not have rows * width * 3 elements / pairs")
+    return a, m, info, noise
+
+
 def write_film_file(path: str, sums: np.ndarray, width: int, rows: int, spp_total: int,
-                    samples_done: int) -> None:
+                    samples_done: int, m2: np.ndarray | None = None, batch: int = 0,
+                    batches_done: int = 0) -> None:
     """The film file: a 32-byte header (FILM_MAGIC, width, rows, spp_total, 0, samples_done; little
-    endian) and the rows * width * 3 sums as raw little-endian uint64."""
+    endian) and the rows * width * 3 sums as raw little-endian uint64. With m2 (a noise film): the
+    magic is FILM_MAGIC_NOISE, the header goes on with batch, 0, batches_done (48 bytes), and the
+    moment plane (rows * width * 3 pairs (lo, hi) of uint64) follows the sums."""
     import struct
     a = np.ascontiguousarray(sums, dtype="<u8")
     if a.size != 3 * rows * width:
         raise SptError(1, "sums do not have rows * width * 3 elements")
+    if m2 is None:
+        with open(path, "wb") as f:
+            f.write(struct.pack(_FILM_HEADER, FILM_MAGIC, width, rows, spp_total, 0, samples_done))
+            f.write(a.tobytes())
+        return
+    m = np.ascontiguousarray(m2, dtype="<u8")
+    if m.size != 6 * rows * width or batch < 1 or batches_done < 0:
+        raise SptError(1, "m2 does not have rows * width * 3 pairs, or a bad batch")
     with open(path, "wb") as f:
-        f.write(struct.pack(_FILM_HEADER, FILM_MAGIC, width, rows, spp_total, 0, samples_done))
+        f.write(struct.pack(_FILM_HEADER_NOISE, FILM_MAGIC_NOISE, width, rows, spp_total, 0,
+                            samples_done, batch, 0, batches_done))
         f.write(a.tobytes())
+        f.write(m.tobytes())
 
 
-def read_film_file(path: str):
-    """-> (sums (rows, width, 3) uint64, {"width", "rows", "spp_total", "samples_done"})."""
+def read_film_file(path: str, with_noise: bool = False):
+    """-> (sums (rows, width, 3) uint64, {"width", "rows", "spp_total", "samples_done"}).
+    with_noise: -> (sums, m2, info), for a noise film's file m2 = (rows, width, 3, 2) uint64 and info
+    also holds "batch" and "batches_done"; for a plain film's m2 is None. Without with_noise a noise
+    film's file is refused (its moments would be dropped)."""
     import struct
     data = open(path, "rb").read()
     n = struct.calcsize(_FILM_HEADER)
     if len(data) < n:
         raise SptError(1, f"{path}: not a film file")
     magic, w, rows, spp, _, done = struct.unpack(_FILM_HEADER, data[:n])
+    if magic == FILM_MAGIC_NOISE and with_noise:
+        n2 = struct.calcsize(_FILM_HEADER_NOISE)
+        if len(data) < n2:
+            raise SptError(1, f"{path}: not a film file")
+        batch, _, bdone = struct.unpack("<iiq", data[n:n2])
+        if w <= 0 or rows < 0 or spp <= 0 or not 0 <= done <= spp or batch < 1 or spp % batch \
+                or spp // batch < 2 or not 0 <= bdone <= spp // batch or done % batch \
+                or len(data) != n2 + 72 * rows * w:
+            raise SptError(1, f"{path}: not a film file")
+        words = np.frombuffer(data, dtype="<u8", offset=n2).astype(np.uint64)
+        sums = words[: 3 * rows * w].reshape(rows, w, 3)
+        m2 = words[3 * rows * w:].reshape(rows, w, 3, 2)
+        return sums, m2, {"width": w, "rows": rows, "spp_total": spp, "samples_done": done,
+                          "batch": batch, "batches_done": bdone}
     if magic != FILM_MAGIC or w <= 0 or rows < 0 or spp <= 0 or not 0 <= done <= spp \
             or len(data) != n + 24 * rows * w:
         raise SptError(1, f"{path}: not a film file")
     sums = np.frombuffer(data, dtype="<u8", offset=n).astype(np.uint64).reshape(rows, w, 3)
-    return sums, {"width": w, "rows": rows, "spp_total": spp, "samples_done": done}
+    info = {"width": w, "rows": rows, "spp_total": spp, "samples_done": done}
+    return (sums, None, info) if with_noise else (sums, info)
 
 
 class Film:
@@ -713,8 +812,66 @@ class Film:
                                         ctypes.c_void_p(stream_ptr or None)))
 
     def save(self, path: str):
+        i, n = self.info(), self.noise_info()
+        if not n["enabled"]:
+            write_film_file(path, self.to_numpy(), i["width"], i["rows"], i["spp_total"],
+                            i["samples_done"])
+        else:
+            write_film_file(path, self.to_numpy(), i["width"], i["rows"], i["spp_total"],
+                            i["samples_done"], self.noise_to_numpy(), n["batch"], n["batches_done"])
+
+    # ---- the noise film (spt_film_noise_*) ----
+    def enable_noise(self, batch: int):
+        """Keep the moment plane from now on (an empty film only): every pass is then one batch of
+        `batch` samples at a base that is a multiple of it; batch must divide spp into >= 2."""
+        _check(self.lib.spt_film_noise_enable(self._f, int(batch)))
+
+    def noise_info(self) -> dict:
+        i = spt_film_noise_info()
+        _check(self.lib.spt_film_noise_info_get(self._f, ctypes.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in i._fields_}
+
+    def noise_to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
+        """The moment plane on the host: (rows, width, 3, 2) uint64, [..., 0] = lo, [..., 1] = hi."""
         i = self.info()
-        write_film_file(path, self.to_numpy(), i["width"], i["rows"], i["spp_total"], i["samples_done"])
+        out = np.zeros((i["rows"], i["width"], 3, 2), dtype=np.uint64)
+        _check(self.lib.spt_film_noise_download(self._f, out.ctypes.data,
+                                                ctypes.c_void_p(stream_ptr or None)))
+        return out
+
+    def noise_from_numpy(self, m2: np.ndarray, batches_done: int, stream_ptr: int = 0):
+        """Replace the moment plane and batches_done (beside from_numpy: a checkpoint's other half)."""
+        i = self.info()
+        a = np.ascontiguousarray(m2, dtype=np.uint64)
+        if a.size != i["rows"] * i["width"] * 6:
+            raise SptError(1, "m2 does not have rows * width * 3 pairs")
+        _check(self.lib.spt_film_noise_upload(self._f, a.ctypes.data, int(batches_done),
+                                              ctypes.c_void_p(stream_ptr or None)))
+
+    def noise_map(self, se_dev_ptr: int = 0, stream_ptr: int = 0):
+        """The standard error of every resolved value. With se_dev_ptr: enqueued into that device
+        buffer (rows * width * 3 floats). Without: returned on the host as (rows, width, 3) float32."""
+        if se_dev_ptr:
+            _check(self.lib.spt_film_noise_map(self._f, ctypes.c_void_p(se_dev_ptr),
+                                               ctypes.c_void_p(stream_ptr or None)))
+            return None
+        import torch
+        i = self.info()
+        with torch.cuda.device(self.device):
+            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
+                              device=f"cuda:{self.device}")
+            _check(self.lib.spt_film_noise_map(self._f, ctypes.c_void_p(buf.data_ptr()),
+                                               ctypes.c_void_p(stream_ptr or None)))
+            torch.cuda.synchronize(self.device)
+        return buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+
+    def noise_summary(self, stream_ptr: int = 0) -> dict:
+        """spt_film_noise_summary(): {"rmse": [r, g, b], "rmse_all", "se_max", "clamped",
+        "batches_done"} of the clamped image; waits for the stream."""
+        out = spt_noise_summary()
+        _check(self.lib.spt_film_noise_summary(self._f, ctypes.byref(out),
+                                               ctypes.c_void_p(stream_ptr or None)))
+        return out.as_dict()
 
 
 def render_progressive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, passes,
@@ -749,6 +906,49 @@ def render_progressive(prims: Sequence[spt_prim], cam: Camera, params: spt_param
         film.close()
         r.close()
     return (out, total) if return_stats else out
+
+
+def render_until(prims: Sequence[spt_prim], cam: Camera, params: spt_params, target_rmse: float,
+                 batch: int | None = None, min_batches: int = 2, return_info=False):
+    """Render until the image's estimated RMSE is at most target_rmse: batches of `batch` samples in
+    index order into a noise film, params.spp the cap. After each batch from min_batches (>= 2) on the
+    film's summary is read, and the render stops once max(rmse) <= target_rmse. Returns the resolved
+    image (a preview when it stopped early; render()'s image bit for bit when every batch was
+    rendered); return_info: also {"samples_done", "batches_done", "rmse"}.
+    batch defaults to spp / 8 when 8 divides spp and must be given otherwise."""
+    import torch
+    spp = int(params.spp)
+    if batch is None:
+        if spp % 8:
+            raise ValueError("render_until: spp is no multiple of 8, give batch")
+        batch = spp // 8
+    dev = params.device
+    r, film = Renderer(dev), Film(params, dev)
+    try:
+        film.enable_noise(batch)
+        i = film.info()
+        need = max(2, int(min_batches))
+        rmse = None
+        with torch.cuda.device(dev):
+            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
+                              device=f"cuda:{dev}")
+            stream = torch.cuda.current_stream().cuda_stream
+            for k in range(spp // batch):
+                film.render(r, prims, cam, params, k * batch, batch, 0, stream)
+                r.stats()  # a pass that hit the runaway guard raises here
+                if k + 1 >= need:
+                    rmse = film.noise_summary(stream)["rmse"]
+                    if max(rmse) <= target_rmse:
+                        break
+            film.resolve(buf.data_ptr(), stream)
+            torch.cuda.synchronize(dev)
+        out = buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+        info = {"samples_done": film.info()["samples_done"],
+                "batches_done": film.noise_info()["batches_done"], "rmse": rmse}
+    finally:
+        film.close()
+        r.close()
+    return (out, info) if return_info else out
 
 
 def render_multi(prims: Sequence[spt_prim], cam: Camera, params: spt_params, devices,

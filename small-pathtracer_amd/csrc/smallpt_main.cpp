@@ -1,7 +1,7 @@
 // smallpt_main.cpp — the reference's main() (smallpt.cpp:502-557) on the MI355X:
 //   smallpt_amd [W H SPP [SEED [OUT.ppm]]] [--cos] [--uniform] [--reference-leaks] [--q Q]
 //               [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]
-//               [--device N | --devices N] [--p6 | --pfm]
+//               [--device N | --devices N] [--p6 | --pfm] [--noise T [--batch B]]
 //   --uniform: random_scattering from the commented-out uniform hemisphere code (:352-359)
 //   --reference-leaks: leaked paths go on from the miss vertex as the reference's (:371-377)
 //                      instead of ending at their first miss (SPT_FLAG_REFERENCE_LEAKS)
@@ -21,6 +21,14 @@
 //               film and writes the image resolved from it (a preview while samples remain). Fails
 //               when the film is full. Film file: 32-byte header (magic "SPTFILM1", int32 width,
 //               rows, spp_total, 0, int64 samples_done; little endian), then the raw uint64 sums.
+//   --noise T [--batch B]: render until the image's estimated RMSE (spt_film_noise_summary: the
+//               largest of the three channels') is at most T, in batches of B samples (default SPP / 8
+//               when 8 divides SPP, else --batch is required; B must divide SPP into >= 2 batches),
+//               at least two batches and at most SPP samples. Prints "NOISE : r g b after N / SPP".
+//               --noise 0 renders every batch: the same file as without it, bit for bit. With --film
+//               the checkpoint is a noise film's ("SPTFILM2": the header goes on with int32 batch, 0,
+//               int64 batches_done -- 48 bytes --, and the moment plane, rows*width*3 pairs (lo, hi)
+//               of uint64, follows the sums) and --add N (a multiple of B) caps this run's samples.
 // Same scene, camera (:521), clamp/toInt and P3 output; the pixel loop is one spt_render() call.
 #include <algorithm>
 #include <chrono>
@@ -44,15 +52,30 @@ struct FilmHeader {  // the film file's first 32 bytes (little endian)
 };
 static_assert(sizeof(FilmHeader) == 32, "film file header");
 const char kFilmMagic[8] = {'S', 'P', 'T', 'F', 'I', 'L', 'M', '1'};
+struct NoiseHeader {  // a noise film's file goes on with these 16 bytes
+  int32_t batch, zero;
+  int64_t batches_done;
+};
+static_assert(sizeof(NoiseHeader) == 16, "noise film file header");
+const char kFilmMagicNoise[8] = {'S', 'P', 'T', 'F', 'I', 'L', 'M', '2'};
+
+struct NoiseOpts {
+  bool on = false;
+  double target = 0.0;
+  int batch = 0;  // 0: SPP / 8
+};
 
 void check(spt_status s) {
   if (s != SPT_OK) throw std::runtime_error(std::string(spt_status_string(s)) + ": " + spt_last_error());
 }
 
 // SPP samples through a film: `passes` near-equal windows of the samples to render -- all of them,
-// or with film_path the next `add` after those the film file holds. Returns the DEVICE image.
+// or with film_path the next `add` after those the film file holds. With noise.on the film keeps
+// its moment plane, the passes are the batches in index order, and the run ends early once the
+// estimated RMSE is at most noise.target. Returns the DEVICE image.
 float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
-                   int passes, const char* film_path, int add, spt_stats* total) {
+                   int passes, const char* film_path, int add, const NoiseOpts& noise,
+                   spt_stats* total) {
   spt_context* ctx = nullptr;
   spt_film* film = nullptr;
   check(spt_context_create(p.device, &ctx));
@@ -60,20 +83,39 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
   spt_film_info info{};
   check(spt_film_info_get(film, &info));
   const size_t n = 3ull * (size_t)info.rows * (size_t)info.width;
-  std::vector<uint64_t> sums(n);
+  std::vector<uint64_t> sums(n), m2(noise.on ? 2 * n : 0);
+  int batch = 0;
+  if (noise.on) {
+    if (noise.batch <= 0 && p.spp % 8 != 0)
+      throw std::runtime_error("--noise: SPP is no multiple of 8, give --batch");
+    batch = noise.batch > 0 ? noise.batch : p.spp / 8;
+    check(spt_film_noise_enable(film, batch));
+  }
+  const char* magic = noise.on ? kFilmMagicNoise : kFilmMagic;
   if (film_path) {
     std::ifstream in(film_path, std::ios::binary);
     if (in) {
       FilmHeader h{};
       in.read((char*)&h, sizeof h);
-      if (!in || std::memcmp(h.magic, kFilmMagic, 8) != 0)
+      if (in && std::memcmp(h.magic, noise.on ? kFilmMagic : kFilmMagicNoise, 8) == 0)
+        throw std::runtime_error(std::string(film_path) + (noise.on ? ": a plain film (no --noise)"
+                                                                    : ": a noise film (--noise)"));
+      if (!in || std::memcmp(h.magic, magic, 8) != 0)
         throw std::runtime_error(std::string(film_path) + ": not a film file");
+      NoiseHeader nh{};
+      if (noise.on) {
+        in.read((char*)&nh, sizeof nh);
+        if (!in) throw std::runtime_error(std::string(film_path) + ": truncated or oversized film file");
+        if (nh.batch != batch) throw std::runtime_error(std::string(film_path) + ": the film has another --batch");
+      }
       if (h.width != info.width || h.rows != info.rows || h.spp_total != info.spp_total)
         throw std::runtime_error(std::string(film_path) + ": the film is not W H SPP");
       in.read((char*)sums.data(), (std::streamsize)(n * sizeof(uint64_t)));
+      if (noise.on) in.read((char*)m2.data(), (std::streamsize)(2 * n * sizeof(uint64_t)));
       if (!in || in.peek() != std::ifstream::traits_type::eof())
         throw std::runtime_error(std::string(film_path) + ": truncated or oversized film file");
       check(spt_film_upload(film, sums.data(), h.samples_done, nullptr));
+      if (noise.on) check(spt_film_noise_upload(film, m2.data(), nh.batches_done, nullptr));
       info.samples_done = h.samples_done;
     }
   }
@@ -86,6 +128,33 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
     throw std::runtime_error("device allocation failed");
   passes = std::max(1, passes);
   std::memset(total, 0, sizeof *total);
+  if (noise.on) {  // the batches in index order, the summary after each from the second on
+    if (todo % batch != 0 || base0 % batch != 0)
+      throw std::runtime_error("--add and the film's samples must be multiples of the batch");
+    spt_film_noise_info ni{};
+    spt_noise_summary sm{};
+    bool measured = false;
+    for (int k = 0; k < todo / batch; ++k) {
+      check(spt_film_render_async(ctx, film, scene.data(), (int32_t)scene.size(), &cam.abi(), &p,
+                                  base0 + k * batch, batch, nullptr, nullptr));
+      spt_stats st{};
+      check(spt_context_stats(ctx, &st));
+      total->samples += st.samples;
+      total->vertices += st.vertices;
+      total->kernel_ms += st.kernel_ms;
+      check(spt_film_noise_info_get(film, &ni));
+      measured = ni.batches_done >= 2;
+      if (!measured) continue;
+      check(spt_film_noise_summary(film, &sm, nullptr));
+      if (std::max(sm.rmse[0], std::max(sm.rmse[1], sm.rmse[2])) <= noise.target) break;
+    }
+    check(spt_film_resolve(film, dev, nullptr));
+    check(spt_film_info_get(film, &info));
+    if (measured)
+      std::cout << "NOISE : " << sm.rmse[0] << " " << sm.rmse[1] << " " << sm.rmse[2] << " after "
+                << info.samples_done << " / " << info.spp_total << std::endl;
+    passes = 0;
+  }
   for (int k = 0; k < passes; ++k) {
     const int a = (int)((int64_t)todo * k / passes), b = (int)((int64_t)todo * (k + 1) / passes);
     if (b == a) continue;
@@ -101,12 +170,20 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
     check(spt_film_download(film, sums.data(), nullptr));
     check(spt_film_info_get(film, &info));
     FilmHeader h{};
-    std::memcpy(h.magic, kFilmMagic, 8);
+    std::memcpy(h.magic, magic, 8);
     h.width = info.width; h.rows = info.rows; h.spp_total = info.spp_total;
     h.samples_done = info.samples_done;
     std::ofstream o(film_path, std::ios::binary | std::ios::trunc);
     o.write((const char*)&h, sizeof h);
+    if (noise.on) {
+      spt_film_noise_info ni{};
+      check(spt_film_noise_info_get(film, &ni));
+      check(spt_film_noise_download(film, m2.data(), nullptr));
+      const NoiseHeader nh{ni.batch, 0, ni.batches_done};
+      o.write((const char*)&nh, sizeof nh);
+    }
     o.write((const char*)sums.data(), (std::streamsize)(n * sizeof(uint64_t)));
+    if (noise.on) o.write((const char*)m2.data(), (std::streamsize)(2 * n * sizeof(uint64_t)));
     if (!o) throw std::runtime_error(std::string("cannot write ") + film_path);
     std::cout << "FILM : " << info.samples_done << " / " << info.spp_total << " samples" << std::endl;
   }
@@ -125,6 +202,7 @@ int main(int argc, char* argv[]) {
   int device = 0, devices = 0, max_depth = 0, npos = 0, format = SPT_IMAGE_P3, repeat = 1;
   int passes = 0, add = 0;
   const char* film_path = nullptr;
+  NoiseOpts noise;
   float q = -1.0f;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--cos")) cosine = true;
@@ -142,6 +220,8 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) passes = std::max(1, std::atoi(argv[++i]));
     else if (!std::strcmp(argv[i], "--film") && i + 1 < argc) film_path = argv[++i];
     else if (!std::strcmp(argv[i], "--add") && i + 1 < argc) add = std::max(1, std::atoi(argv[++i]));
+    else if (!std::strcmp(argv[i], "--noise") && i + 1 < argc) { noise.on = true; noise.target = std::atof(argv[++i]); }
+    else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) noise.batch = std::max(1, std::atoi(argv[++i]));
     else if (!std::strcmp(argv[i], "--p6")) format = SPT_IMAGE_P6;
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
     else if (npos < 4) pos[npos++] = std::atoi(argv[i]);
@@ -167,9 +247,10 @@ int main(int argc, char* argv[]) {
                                         : specular ? cornell_specular_scene()
                                         : spheres ? spheres32_scene()
                                                   : cornell_scene();
-    if (passes > 0 || film_path) {
-      if (devices > 0 || repeat > 1) throw std::runtime_error("--passes / --film go with one device and no --repeat");
-      image = render_film(scene, cam, p, passes, film_path, add, &st);
+    if (passes > 0 || film_path || noise.on) {
+      if (devices > 0 || repeat > 1)
+        throw std::runtime_error("--passes / --film / --noise go with one device and no --repeat");
+      image = render_film(scene, cam, p, passes, film_path, add, noise, &st);
       repeat = 0;
     }
     for (int k = 0; k < repeat; ++k) {

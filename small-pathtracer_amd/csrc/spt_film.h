@@ -18,6 +18,12 @@ struct spt_film {
   unsigned long long* sums = nullptr;  // [rows * width][3], device
   size_t n = 0;                        // elements (3 * rows * width)
   spt_context* last_ctx = nullptr;     // the context of the last pass (it takes a guarded pass back)
+  // the noise film (spt_film_noise_enable): every pass is one batch of `batch` samples
+  int32_t batch = 0;                   // 0: a plain film
+  int64_t batches_done = 0;
+  unsigned long long* m2 = nullptr;    // [rows * width * 3][2]: (lo, hi) of the sum of P^2, device
+  void* partials = nullptr;            // the summary's per-block partials and its result, device
+  unsigned n_partials = 0;             // blocks of the summary's first stage
 };
 
 // spt_context.cpp: one render launch over a sample window (film == nullptr: the one-shot finalize).

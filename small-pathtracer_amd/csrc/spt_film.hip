@@ -11,12 +11,15 @@
 //   resolve     film -> float: min((float)sum * 2^-31 [* r], 1), r = spp_total / samples_done
 //               rounded once on the host (a preview; no factor for a full film)
 //   merge       dst += src
+//   noise       a noise film's moment plane (accumulate also does M2 += P^2, 128 bits), its error map
+//               and the image's RMSE estimate (a two-stage reduction in a fixed order)
 //
 // All three stream: one pass over the sums at 16 bytes per access (two sums, or four floats),
 // 256 threads per block, no reuse -- HBM-bound. -ffp-contract=off (the Makefile) keeps the preview two
 // separate multiplies, as spt_film_resolve_host and a numpy restatement compute it.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -48,15 +51,43 @@ __device__ __forceinline__ void loads_landed(ulonglong2& a, ulonglong2& b) {
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y)::"memory");
 }
 
+// 64 x 64 -> high 64 bits.
+__host__ __device__ __forceinline__ u64 mulhi64(u64 a, u64 b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(a, b);
+#else
+  return (u64)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
+// m += p^2 in 128 bits, m = (lo, hi). Exact: p <= batch * 2^31 (the moment plane's bound, spt.h).
+__host__ __device__ __forceinline__ void m2_add_square(ulonglong2& m, u64 p) {
+  const u64 lo = p * p, nl = m.x + lo;
+  m.y += mulhi64(p, p) + (u64)(nl < lo);
+  m.x = nl;
+}
+
+// The same wait for one 16-byte load (an element of the moment plane).
+__device__ __forceinline__ void load_landed(ulonglong2& a) {
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(a.x), "+v"(a.y)::"memory");
+}
+
 // One sum of the accumulate's phase 2 (a run's unaligned head or tail).
+template <bool NOISE>
 __device__ __forceinline__ void acc_one(u64* __restrict__ film, const u64* __restrict__ accum,
-                                        float* __restrict__ rgb, size_t e, u64 add, bool capped,
-                                        float r, int full) {
+                                        ulonglong2* __restrict__ m2, float* __restrict__ rgb,
+                                        size_t e, u64 add, bool capped, float r, int full) {
   float f = __builtin_nanf("");
   if (!capped) {
     const u64 v = film[e] + add + accum[e];
     film[e] = v;
     f = film_resolve1(v, r, full);
+    if constexpr (NOISE) {  // the pass's own sum, squared into the moment plane
+      ulonglong2 m = m2[e];
+      load_landed(m);
+      m2_add_square(m, add + accum[e]);
+      m2[e] = m;
+    }
   }
   if (rgb) rgb[e] = f;
 }
@@ -75,11 +106,19 @@ __device__ __forceinline__ void acc_one(u64* __restrict__ film, const u64* __res
 // Every thread reads the launch's runaway-guard word first: when the launch dropped units its slots
 // hold an earlier launch's sums, so nothing is added and a given rgb is all NaN (never a partial
 // image); the host takes the pass's samples back (spt_context_stats).
+//
+// NOISE (a noise film, m2 = its moment plane): the pass's own sum P = slots + accumulator of every
+// element is also squared into m2[e] (+= P^2, 128 bits): one more 16-byte load and store per sum,
+// as a group of its own behind the film's (loads, the full wait, stores). m2 is the last parameter
+// and every NOISE step is compiled out of the <false> instantiation, the one a plain film launches:
+// its instructions are what they were before the moment plane existed.
+template <bool NOISE>
 __global__ void __launch_bounds__(kBlock)
 film_accumulate_kernel(const u64* __restrict__ accum, const u64* __restrict__ slots,
                        u64* __restrict__ film, float* __restrict__ rgb, uint32_t npix,
                        uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
-                       const u64* __restrict__ stats, float r, int full, int rgb_vec) {
+                       const u64* __restrict__ stats, float r, int full, int rgb_vec,
+                       ulonglong2* __restrict__ m2) {
   __shared__ u64 s_sum[3 * kBlock];
   const bool capped = stats[0] != 0;
   const uint32_t R = (uint32_t)kBlock >> scr_k;
@@ -126,6 +165,19 @@ film_accumulate_kernel(const u64* __restrict__ accum, const u64* __restrict__ sl
       v1.y = f1.y + a1.y + s[3];
       *(ulonglong2*)(film + e) = v0;
       *(ulonglong2*)(film + e + 2) = v1;
+      if constexpr (NOISE) {  // a second group of the same shape: four loads, the full wait, four stores
+        ulonglong2 q0 = m2[e], q1 = m2[e + 1], q2 = m2[e + 2], q3 = m2[e + 3];
+        loads_landed(q0, q1);
+        loads_landed(q2, q3);
+        m2_add_square(q0, a0.x + s[0]);
+        m2_add_square(q1, a0.y + s[1]);
+        m2_add_square(q2, a1.x + s[2]);
+        m2_add_square(q3, a1.y + s[3]);
+        m2[e] = q0;
+        m2[e + 1] = q1;
+        m2[e + 2] = q2;
+        m2[e + 3] = q3;
+      }
       f = make_float4(film_resolve1(v0.x, r, full), film_resolve1(v0.y, r, full),
                       film_resolve1(v1.x, r, full), film_resolve1(v1.y, r, full));
     }
@@ -145,10 +197,21 @@ film_accumulate_kernel(const u64* __restrict__ accum, const u64* __restrict__ sl
     const uint32_t h = min((0u - (uint32_t)e0) & 3u, n);
     const uint32_t body_end = h + ((n - h) & ~3u);
     const u64* s = s_sum + 3u * a * R;
-    for (uint32_t idx = 0; idx < h; ++idx)
-      acc_one(film, accum, rgb, e0 + idx, capped ? 0ull : s[idx], capped, r, full);
-    for (uint32_t idx = body_end; idx < n; ++idx)
-      acc_one(film, accum, rgb, e0 + idx, capped ? 0ull : s[idx], capped, r, full);
+    if constexpr (NOISE) {  // at most three sums at either end: unrolled, no loop around a 16-byte load
+#pragma unroll
+      for (uint32_t u = 0; u < 3; ++u)
+        if (u < h) acc_one<true>(film, accum, m2, rgb, e0 + u, capped ? 0ull : s[u], capped, r, full);
+#pragma unroll
+      for (uint32_t u = 0; u < 3; ++u) {
+        const uint32_t idx = body_end + u;
+        if (idx < n) acc_one<true>(film, accum, m2, rgb, e0 + idx, capped ? 0ull : s[idx], capped, r, full);
+      }
+    } else {
+      for (uint32_t idx = 0; idx < h; ++idx)
+        acc_one<false>(film, accum, m2, rgb, e0 + idx, capped ? 0ull : s[idx], capped, r, full);
+      for (uint32_t idx = body_end; idx < n; ++idx)
+        acc_one<false>(film, accum, m2, rgb, e0 + idx, capped ? 0ull : s[idx], capped, r, full);
+    }
   }
 }
 
@@ -200,6 +263,129 @@ __global__ void __launch_bounds__(kBlock)
 film_merge_tail_kernel(u64* dst, const u64* src, size_t begin, size_t n) {
   const size_t e = begin + (size_t)blockIdx.x * kBlock + threadIdx.x;
   if (e < n) dst[e] += src[e];
+}
+
+// dst.M2 += src.M2 with carry: one 128-bit element per thread, 16-byte loads and store.
+__global__ void __launch_bounds__(kBlock)
+film_merge_m2_kernel(ulonglong2* dst, const ulonglong2* src, size_t n) {
+  const size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e < n) {
+    ulonglong2 d = dst[e], s = src[e];
+    loads_landed(d, s);
+    const u64 lo = d.x + s.x;
+    d.y += s.y + (u64)(lo < s.x);
+    d.x = lo;
+    dst[e] = d;
+  }
+}
+
+// What the error map and the summary take from the host: B = batches_done, the factor k of spt.h
+// and its square (both rounded once, in double), the resolve's factor for the clamp rule.
+struct NoiseArgs {
+  u64 B;
+  double k, k2;
+  float r;
+  int full;
+};
+
+// One element: D = B * M2 - S^2 in 128 bits as a double, or 0 with *clamped set where the resolved
+// value is the clamp. se = (float)(sqrt(d) * k); the summary adds d * k2.
+__host__ __device__ __forceinline__ double noise_d(u64 S, ulonglong2 m, const NoiseArgs& A,
+                                                   bool* clamped) {
+  *clamped = film_resolve1(S, A.r, A.full) == 1.0f;
+  if (*clamped) return 0.0;
+  const u64 blo = A.B * m.x, bhi = A.B * m.y + mulhi64(A.B, m.x);
+  const u64 slo = S * S, shi = mulhi64(S, S);
+  const u64 lo = blo - slo, hi = bhi - shi - (u64)(blo < slo);
+  return (double)hi * 0x1p64 + (double)lo;
+}
+
+__global__ void __launch_bounds__(kBlock)
+film_noise_map_kernel(const u64* sums, const ulonglong2* m2, float* se, size_t n, NoiseArgs A) {
+  const size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e < n) {
+    ulonglong2 m = m2[e];
+    load_landed(m);
+    bool c;
+    se[e] = (float)(sqrt(noise_d(sums[e], m, A, &c)) * A.k);
+  }
+}
+
+// The summary's partial sums: of a block (stage 1), of the image (stage 2).
+struct NoisePartial {
+  double s[3];  // per channel: sum of d * k2
+  float se_max;
+  uint32_t pad;
+  u64 clamped;
+};
+
+// p[0] = the block's 256 partials combined pairwise, in an order fixed by the thread index alone.
+__device__ __forceinline__ void noise_block_reduce(NoisePartial* p) {
+  for (uint32_t w = kBlock / 2; w > 0; w >>= 1) {
+    __syncthreads();
+    if (threadIdx.x < w) {
+      NoisePartial& a = p[threadIdx.x];
+      const NoisePartial& b = p[threadIdx.x + w];
+      a.s[0] += b.s[0];
+      a.s[1] += b.s[1];
+      a.s[2] += b.s[2];
+      a.se_max = fmaxf(a.se_max, b.se_max);
+      a.clamped += b.clamped;
+    }
+  }
+  __syncthreads();
+}
+
+// Stage 1: one pixel per thread (three sums, three moments), one partial per block. The partials
+// are five planes of nb = gridDim.x 8-byte words (s[0], s[1], s[2], se_max as a double, clamped), so
+// that stage 2 reads them with 8-byte loads.
+__global__ void __launch_bounds__(kBlock)
+film_noise_partials_kernel(const u64* sums, const ulonglong2* m2, size_t npix, NoiseArgs A,
+                           double* out) {
+  __shared__ NoisePartial s_p[kBlock];
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  NoisePartial v{};
+  if (px < npix) {
+    ulonglong2 m0 = m2[3 * px], m1 = m2[3 * px + 1], mm = m2[3 * px + 2];
+    loads_landed(m0, m1);
+    load_landed(mm);
+    const ulonglong2 m[3] = {m0, m1, mm};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      bool cl;
+      const double d = noise_d(sums[3 * px + c], m[c], A, &cl);
+      v.s[c] = d * A.k2;
+      v.se_max = fmaxf(v.se_max, (float)(sqrt(d) * A.k));
+      v.clamped += cl ? 1u : 0u;
+    }
+  }
+  s_p[threadIdx.x] = v;
+  noise_block_reduce(s_p);
+  if (threadIdx.x == 0) {
+    const size_t nb = gridDim.x;
+    out[blockIdx.x] = s_p[0].s[0];
+    out[nb + blockIdx.x] = s_p[0].s[1];
+    out[2 * nb + blockIdx.x] = s_p[0].s[2];
+    out[3 * nb + blockIdx.x] = (double)s_p[0].se_max;
+    ((u64*)out)[4 * nb + blockIdx.x] = s_p[0].clamped;
+  }
+}
+
+// Stage 2, one block: thread t adds the partials t, t + 256, ... in that order; *total = the image's.
+__global__ void __launch_bounds__(kBlock)
+film_noise_total_kernel(const double* parts, uint32_t n, NoisePartial* total) {
+  __shared__ NoisePartial s_p[kBlock];
+  NoisePartial v{};
+  for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
+    v.s[0] += parts[i];
+    v.s[1] += parts[(size_t)n + i];
+    v.s[2] += parts[2 * (size_t)n + i];
+    v.se_max = fmaxf(v.se_max, (float)parts[3 * (size_t)n + i]);
+    v.clamped += ((const u64*)parts)[4 * (size_t)n + i];
+  }
+  s_p[threadIdx.x] = v;
+  noise_block_reduce(s_p);
+  if (threadIdx.x == 0) *total = s_p[0];
 }
 
 spt_status fail(spt_status s, const std::string& msg) {
@@ -267,10 +453,10 @@ extern "C" spt_status spt_film_create(int32_t device, const spt_params* p, spt_f
 extern "C" spt_status spt_film_destroy(spt_film* f) {
   if (!f) return SPT_OK;
   if (f->last_ctx) spt_context_forget_film(f->last_ctx, f);
-  if (f->sums) {
-    (void)hipSetDevice(f->device);
-    (void)hipFree(f->sums);
-  }
+  if (f->sums || f->m2 || f->partials) (void)hipSetDevice(f->device);
+  if (f->sums) (void)hipFree(f->sums);
+  if (f->m2) (void)hipFree(f->m2);
+  if (f->partials) (void)hipFree(f->partials);
   delete f;
   return SPT_OK;
 }
@@ -289,8 +475,10 @@ extern "C" spt_status spt_film_clear(spt_film* f, void* stream) {
   if (f->n) {
     FILM_HIP(hipSetDevice(f->device));
     FILM_HIP(hipMemsetAsync(f->sums, 0, f->n * sizeof(u64), (hipStream_t)stream));
+    if (f->m2) FILM_HIP(hipMemsetAsync(f->m2, 0, f->n * sizeof(ulonglong2), (hipStream_t)stream));
   }
   f->samples_done = 0;
+  f->batches_done = 0;
   return SPT_OK;
 }
 
@@ -301,18 +489,27 @@ spt_status spt_film_accumulate(spt_film* f, spt_context* c, const unsigned long 
   if (f->n != 3ull * npix) return fail(SPT_ERR_INVALID_ARG, "the film does not have the launch's pixels");
   int full = 0;
   const float r = resolve_factor(f->spp_total, f->samples_done + s_count, &full);
-  hipLaunchKernelGGL(film_accumulate_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0,
-                     (hipStream_t)stream, accum, slots, f->sums, rgb_dev, npix, n_chunks, scr_k, scr_q,
-                     stats, r, full, (int)aligned16(rgb_dev));
+  if (f->batch)  // a noise film: the same pass also squares its sums into the moment plane
+    hipLaunchKernelGGL(film_accumulate_kernel<true>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock),
+                       0, (hipStream_t)stream, accum, slots, f->sums, rgb_dev, npix, n_chunks, scr_k,
+                       scr_q, stats, r, full, (int)aligned16(rgb_dev), (ulonglong2*)f->m2);
+  else
+    hipLaunchKernelGGL(film_accumulate_kernel<false>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock),
+                       0, (hipStream_t)stream, accum, slots, f->sums, rgb_dev, npix, n_chunks, scr_k,
+                       scr_q, stats, r, full, (int)aligned16(rgb_dev), (ulonglong2*)nullptr);
   FILM_HIP(hipGetLastError());
   f->samples_done += s_count;
+  if (f->batch) f->batches_done += 1;
   if (f->last_ctx && f->last_ctx != c) spt_context_forget_film(f->last_ctx, f);
   f->last_ctx = c;
   return SPT_OK;
 }
 
 void spt_film_rollback(spt_film* f, const spt_context* c, int32_t s_count) {
-  if (f->last_ctx == c && f->samples_done >= s_count) f->samples_done -= s_count;
+  if (f->last_ctx == c && f->samples_done >= s_count) {
+    f->samples_done -= s_count;
+    if (f->batch && f->batches_done > 0) f->batches_done -= 1;  // a pass of a noise film is one batch
+  }
 }
 
 void spt_film_forget_context(spt_film* f, const spt_context* c) {
@@ -333,10 +530,15 @@ extern "C" spt_status spt_film_render_async(spt_context* ctx, spt_film* f, const
     return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
   if (f->samples_done + sample_count > f->spp_total)
     return fail(SPT_ERR_INVALID_ARG, "the film would hold more than spp samples");
+  if (f->batch && (sample_count != f->batch || sample_base % f->batch != 0))
+    return fail(SPT_ERR_INVALID_ARG, "a noise film takes whole batches: sample_count == batch, sample_base % batch == 0");
   const spt_status st = spt_render_window(ctx, prims, n_prims, cam, p, sample_base, sample_count,
                                           rgb_dev, f, stream);
   if (st != SPT_OK) return st;
-  if (f->rows == 0) f->samples_done += sample_count;  // a shard without rows: nothing to add, still counted
+  if (f->rows == 0) {  // a shard without rows: nothing to add, still counted
+    f->samples_done += sample_count;
+    if (f->batch) f->batches_done += 1;
+  }
   return SPT_OK;
 }
 
@@ -369,6 +571,8 @@ extern "C" spt_status spt_film_merge(spt_film* dst, const spt_film* src, void* s
     return fail(SPT_ERR_INVALID_ARG, "films on different devices: download one and upload it beside the other");
   if (dst->samples_done + src->samples_done > dst->spp_total)
     return fail(SPT_ERR_INVALID_ARG, "the merged film would hold more than spp samples");
+  if (dst->batch != src->batch)
+    return fail(SPT_ERR_INVALID_ARG, "merge needs two plain films or two noise films of equal batch");
   if (dst->n) {
     FILM_HIP(hipSetDevice(dst->device));
     const size_t body = dst->n & ~(size_t)3;
@@ -382,7 +586,13 @@ extern "C" spt_status spt_film_merge(spt_film* dst, const spt_film* src, void* s
                          (hipStream_t)stream, dst->sums, (const u64*)src->sums, body, dst->n);
       FILM_HIP(hipGetLastError());
     }
+    if (dst->batch) {
+      hipLaunchKernelGGL(film_merge_m2_kernel, dim3(tail_blocks(dst->n)), dim3(kBlock), 0,
+                         (hipStream_t)stream, (ulonglong2*)dst->m2, (const ulonglong2*)src->m2, dst->n);
+      FILM_HIP(hipGetLastError());
+    }
   }
+  dst->batches_done += src->batches_done;
   dst->samples_done += src->samples_done;
   return SPT_OK;
 }
@@ -403,6 +613,8 @@ extern "C" spt_status spt_film_upload(spt_film* f, const uint64_t* host_sums, in
   if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
   if (samples_done < 0 || samples_done > f->spp_total)
     return fail(SPT_ERR_INVALID_ARG, "samples_done outside [0, spp]");
+  if (f->batch && samples_done % f->batch != 0)
+    return fail(SPT_ERR_INVALID_ARG, "a noise film holds whole batches: samples_done % batch != 0");
   if (f->n) {
     if (!host_sums) return fail(SPT_ERR_INVALID_ARG, "null input");
     FILM_HIP(hipSetDevice(f->device));
@@ -426,5 +638,190 @@ extern "C" spt_status spt_film_resolve_host(const uint64_t* sums, const spt_film
   int full = 0;
   const float r = resolve_factor(info->spp_total, info->samples_done, &full);
   for (size_t k = 0; k < n; ++k) rgb_out[k] = film_resolve1((u64)sums[k], r, full);
+  return SPT_OK;
+}
+
+// ---- the noise film: moment plane, error map, image figures (include/spt.h SPT_HAS_FILM_NOISE) ----
+namespace {
+
+// The factor of the error map in double, rounded once: se = sqrt(d) * k. B >= 2.
+NoiseArgs noise_args(int32_t spp_total, int64_t samples_done, int32_t batch, int64_t B) {
+  NoiseArgs A;
+  A.B = (u64)B;
+  A.k = (double)spp_total / ((double)batch * 0x1p31 * (double)B * std::sqrt((double)(B - 1)));
+  A.k2 = A.k * A.k;
+  A.r = resolve_factor(spp_total, samples_done, &A.full);
+  return A;
+}
+
+void noise_finish(const NoisePartial& t, size_t npix, int64_t B, spt_noise_summary* out) {
+  const double n = npix ? (double)npix : 1.0;
+  for (int c = 0; c < 3; ++c) out->rmse[c] = std::sqrt(t.s[c] / n);
+  out->rmse_all = std::sqrt((t.s[0] + t.s[1] + t.s[2]) / (3.0 * n));
+  out->se_max = t.se_max;
+  out->clamped = t.clamped;
+  out->batches_done = B;
+}
+
+spt_status noise_host_args(const spt_film_info* info, const spt_film_noise_info* noise, size_t* n) {
+  if (!info || !noise) return fail(SPT_ERR_INVALID_ARG, "null info");
+  if (info->width <= 0 || info->rows < 0 || info->spp_total <= 0 || info->samples_done < 0 ||
+      info->samples_done > info->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "bad film info");
+  if (!noise->enabled || noise->batch < 1)
+    return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (noise->batches_done < 2)
+    return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
+  *n = 3ull * (size_t)info->rows * (size_t)info->width;
+  return SPT_OK;
+}
+
+}  // namespace
+
+extern "C" spt_status spt_film_noise_enable(spt_film* f, int32_t batch) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (f->batch) return fail(SPT_ERR_INVALID_ARG, "the film is a noise film already");
+  if (f->samples_done != 0) return fail(SPT_ERR_INVALID_ARG, "noise is enabled on an empty film only");
+  if (batch < 1 || f->spp_total % batch != 0 || f->spp_total / batch < 2)
+    return fail(SPT_ERR_INVALID_ARG, "batch must divide spp into at least two batches");
+  if (f->n) {
+    FILM_HIP(hipSetDevice(f->device));
+    const unsigned blocks = tail_blocks(f->n / 3);
+    unsigned long long* m2 = nullptr;
+    void* parts = nullptr;
+    hipError_t e = hipMalloc(&m2, f->n * sizeof(ulonglong2));
+    if (e == hipSuccess)  // five planes of 8-byte words, then the total
+      e = hipMalloc(&parts, 5 * (size_t)blocks * sizeof(double) + sizeof(NoisePartial));
+    if (e == hipSuccess) e = hipMemset(m2, 0, f->n * sizeof(ulonglong2));
+    if (e != hipSuccess) {
+      if (m2) (void)hipFree(m2);
+      if (parts) (void)hipFree(parts);
+      return fail(SPT_ERR_OOM, std::string("moment plane alloc: ") + hipGetErrorString(e));
+    }
+    f->m2 = m2;
+    f->partials = parts;
+    f->n_partials = blocks;
+  }
+  f->batch = batch;
+  f->batches_done = 0;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_info_get(const spt_film* f, spt_film_noise_info* out) {
+  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  out->enabled = f->batch != 0;
+  out->batch = f->batch;
+  out->batches_done = f->batches_done;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_download(const spt_film* f, uint64_t* host_m2, void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (f->n == 0) return SPT_OK;
+  if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null output");
+  FILM_HIP(hipSetDevice(f->device));
+  FILM_HIP(hipMemcpyAsync(host_m2, f->m2, f->n * sizeof(ulonglong2), hipMemcpyDeviceToHost,
+                          (hipStream_t)stream));
+  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_upload(spt_film* f, const uint64_t* host_m2, int64_t batches_done,
+                                            void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (batches_done < 0 || batches_done > f->spp_total / f->batch)
+    return fail(SPT_ERR_INVALID_ARG, "batches_done outside [0, spp / batch]");
+  if (f->n) {
+    if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null input");
+    FILM_HIP(hipSetDevice(f->device));
+    FILM_HIP(hipMemcpyAsync(f->m2, host_m2, f->n * sizeof(ulonglong2), hipMemcpyHostToDevice,
+                            (hipStream_t)stream));
+    FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  }
+  f->batches_done = batches_done;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_map(const spt_film* f, float* se_dev, void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
+  if (f->n == 0) return SPT_OK;
+  if (!se_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
+  FILM_HIP(hipSetDevice(f->device));
+  const NoiseArgs A = noise_args(f->spp_total, f->samples_done, f->batch, f->batches_done);
+  hipLaunchKernelGGL(film_noise_map_kernel, dim3(tail_blocks(f->n)), dim3(kBlock), 0,
+                     (hipStream_t)stream, (const u64*)f->sums, (const ulonglong2*)f->m2, se_dev, f->n, A);
+  FILM_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_summary(spt_film* f, spt_noise_summary* out, void* stream) {
+  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
+  NoisePartial total{};
+  if (f->n) {
+    FILM_HIP(hipSetDevice(f->device));
+    const NoiseArgs A = noise_args(f->spp_total, f->samples_done, f->batch, f->batches_done);
+    double* parts = (double*)f->partials;
+    NoisePartial* total_dev = (NoisePartial*)(parts + 5 * (size_t)f->n_partials);
+    hipLaunchKernelGGL(film_noise_partials_kernel, dim3(f->n_partials), dim3(kBlock), 0,
+                       (hipStream_t)stream, (const u64*)f->sums, (const ulonglong2*)f->m2, f->n / 3, A,
+                       parts);
+    FILM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(film_noise_total_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const double*)parts, (uint32_t)f->n_partials, total_dev);
+    FILM_HIP(hipGetLastError());
+    FILM_HIP(hipMemcpyAsync(&total, total_dev, sizeof total, hipMemcpyDeviceToHost,
+                            (hipStream_t)stream));
+  }
+  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  noise_finish(total, f->n / 3, f->batches_done, out);
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_map_host(const uint64_t* sums, const uint64_t* m2,
+                                              const spt_film_info* info,
+                                              const spt_film_noise_info* noise, float* se_out) {
+  size_t n = 0;
+  const spt_status st = noise_host_args(info, noise, &n);
+  if (st != SPT_OK) return st;
+  if (n == 0) return SPT_OK;
+  if (!sums || !m2 || !se_out) return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
+  const NoiseArgs A = noise_args(info->spp_total, info->samples_done, noise->batch, noise->batches_done);
+  for (size_t e = 0; e < n; ++e) {
+    ulonglong2 m;
+    m.x = m2[2 * e];
+    m.y = m2[2 * e + 1];
+    bool c;
+    se_out[e] = (float)(std::sqrt(noise_d((u64)sums[e], m, A, &c)) * A.k);
+  }
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_summary_host(const uint64_t* sums, const uint64_t* m2,
+                                                  const spt_film_info* info,
+                                                  const spt_film_noise_info* noise,
+                                                  spt_noise_summary* out) {
+  size_t n = 0;
+  const spt_status st = noise_host_args(info, noise, &n);
+  if (st != SPT_OK) return st;
+  if (!out || (n && (!sums || !m2))) return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
+  const NoiseArgs A = noise_args(info->spp_total, info->samples_done, noise->batch, noise->batches_done);
+  NoisePartial t{};
+  for (size_t e = 0; e < n; ++e) {
+    ulonglong2 m;
+    m.x = m2[2 * e];
+    m.y = m2[2 * e + 1];
+    bool c;
+    const double d = noise_d((u64)sums[e], m, A, &c);
+    t.s[e % 3] += d * A.k2;
+    t.se_max = std::fmax(t.se_max, (float)(std::sqrt(d) * A.k));
+    t.clamped += c ? 1u : 0u;
+  }
+  noise_finish(t, n / 3, noise->batches_done, out);
   return SPT_OK;
 }
