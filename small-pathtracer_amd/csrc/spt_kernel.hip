@@ -59,7 +59,16 @@ __device__ __forceinline__ const SPT_CONST T* cptr(const T* p) {
   asm volatile("" : "+s"(p));
   return (const SPT_CONST T*)p;
 }
-
+// The same at a site of the render loop where a variant's literals may fold every use of the pointer
+// away (CAMAX == 1, the LREF constants, light_slot_of of a CONSTGEO kernel): not volatile, so an
+// unused one leaves no copy of the pointer pair behind (an s_mov_b64 per site and iteration). It
+// takes the loop's counter, which changes every iteration, so it stays where it is written like the
+// volatile form, and its site's number, so two sites are never merged into one long-lived pointer.
+template <int SITE, typename T>
+__device__ __forceinline__ const SPT_CONST T* cptr_at(const T* p, uint32_t it) {
+  asm("" : "+s"(p) : "s"(it), "n"(SITE));
+  return (const SPT_CONST T*)p;
+}
 
 // Rect geometry with literal operands: kCornellRects[i] at a compile-time i (spt_cornell.h).
 struct CornellRectPtr {
@@ -814,12 +823,15 @@ render_kernel(const KParams* __restrict__ Pg) {
   // the wave's region of s_pool_a / s_pool_b starts at its first thread's index (wave-uniform)
   const uint32_t pool_lds = kPoolLds ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) : 0u;
   uint32_t pool_next = 0, pool_end = 0, grab_at = 0;  // grab_at: the wave's last queue position
-  bool exhausted = false, capped = false;
+  bool exhausted = false, capped = false;  // capped: the runaway guard ended the wave
   // Wave-uniform event counters (SGPRs), fed by ballots at convergent points of the loop: per-lane
   // counters incremented inside the divergent blocks cost ~40 VGPRs of copies.
   // (vertices = path rays + NEE light hits: every path ray shades a vertex, hit or miss, and a
   // shadow ray that reaches the light shades the light's)
-  uint32_t n_path = 0, n_cos = 0;
+  // n_gen (kernels without SPEC/REFR): the path rays, counted as the lanes that generate one. Each
+  // is a sample's camera ray or a cosine continuation, so the cosine rays are n_gen less the launch's
+  // samples, taken off once at the end. The generic kernel counts n_path and n_cos themselves.
+  uint32_t n_path = 0, n_cos = 0, n_gen = 0;
   // Per-lane counts of events that happen inside divergent blocks, incremented in place and
   // summed once at the end (a boolean per event carried to a convergent ballot cost 3 VALU each).
   // What the variant's types imply (spt_variants.h, where the host reads the same values).
@@ -841,97 +853,117 @@ render_kernel(const KParams* __restrict__ Pg) {
   const unsigned long long wave_t0 = __builtin_amdgcn_s_memrealtime();
   uint32_t wave_iters = 0;
 #endif
-  for (uint32_t iter = 0;; ++iter) {
+  // The loop's two exits share one scalar condition at the back edge. `left` counts the iterations
+  // down to the runaway guard, in every iteration whatever the lanes hold: a wave whose paths never
+  // end leaves after kMaxWaveIters with its work dropped (`capped`). A wave that finds no lane with
+  // work sets left = 1 (`live` tells the two apart): it runs the rest of that iteration with every
+  // block's lane mask empty and leaves at the same branch. (A lane-mask flag broken out of the
+  // nested refill branch was built, inverted and re-tested in every iteration: ~7 SALU.)
+  uint32_t left = kMaxWaveIters;
+  // (The sphere kernel with the run-time estimator, at 64 VGPRs, spills one with the exit at the back
+  // edge alone: it tests `live` after the refill as well and skips the empty pass.)
+  constexpr bool kExitAtRefill = TP::SPH && !TP::MAT && CF::NEE < 0;
+  bool live = true;  // wave-uniform: some lane holds work
+  for (;;) {
+    [[maybe_unused]] const uint32_t iter = kMaxWaveIters - left;  // (the diagnostic builds' count)
 #ifdef SPT_WAVE_TIMES
     wave_iters = iter;
 #endif
-    const SPT_CONST KParams* P = cptr(Pg);
+    const SPT_CONST KParams* P = cptr_at<0>(Pg, left);
     SPT_REGION(0);  // loop iteration
-    if (__builtin_expect(iter >= kMaxWaveIters, 0)) {  // runaway guard: drop the work, leave
-      capped = true;                // through the normal exit (a second loop exit would duplicate
-      exhausted = true;             // the loop state)
-      ls = kStIdle;
-    }
     // 1) (a unit is retired at the end of its last sample, in the path-end block below)
     // 2) refill idle lanes from the wave's pool (ballot + mbcnt prefix sum), pool from the queue.
-    //    Everything up to the loop exit test runs only when some lane is idle: most iterations
+    //    Everything up to the exit test runs only when some lane is idle: most iterations
     //    skip it with one wave-uniform branch (round 4: the loop-head bookkeeping was ~12 SALU per
     //    iteration when no lane needed a unit).
-    uint64_t need = __ballot(ls == kStIdle);
+    const uint64_t need = __ballot(ls == kStIdle);
     if (need != 0) {
-    bool needs_unit = ls == kStIdle;
-    while (need != 0 && !exhausted) {
+    // One pass, no loop: the idle lanes take what the pool holds, a fresh one if it is empty. When
+    // the pool's last units do not serve every idle lane, the others take theirs from the next pool
+    // in the next iteration. (A loop that served them at once carried the eight unit registers
+    // through its phis: 16 v_mov per refill around a body that changes them for one lane in fifty.
+    // Its second pass cannot be folded into one fetch after the loop either: a full pool's fill
+    // writes all 64 entries, the ones that lanes served from the old pool have yet to read among
+    // them.)
+    if (!exhausted) {
       SPT_REGION(2);
       const SPT_CONST KParams* Q = cptr(Pg);
       if (pool_next >= pool_end) {
         uint32_t want = kGrab;
         if (Q->sh_guided < 32u) {
-          const uint32_t left = Q->n_units - min(grab_at, (uint32_t)Q->n_units);
-          want = min(kGrab, max(max((uint32_t)__popcll(need), kGrabMin), left >> Q->sh_guided));
+          const uint32_t rest = Q->n_units - min(grab_at, (uint32_t)Q->n_units);
+          want = min(kGrab, max(max((uint32_t)__popcll(need), kGrabMin), rest >> Q->sh_guided));
         }
         // a young block's wave (SPT_YOUNG_CUT) past the cut takes no new pool: its lanes finish and
         // split what they hold (in-wave stealing) and the wave leaves
+        bool open = true;  // the queue has a pool for this wave
         if (blockIdx.x >= Q->young_block) {
           uint32_t q = 0;
           if (lane == 0) q = __hip_atomic_load(Q->queue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           q = __builtin_amdgcn_readfirstlane(q);
-          if (q >= Q->young_cut) { exhausted = true; break; }
+          open = q < Q->young_cut;
         }
-        uint32_t b = 0;
-        if (lane == 0) b = atomicAdd(Q->queue, want);
-        b = __builtin_amdgcn_readfirstlane(b);
-        grab_at = b + want;
-        if (b >= Q->n_units) { exhausted = true; break; }
-        pool_next = b;
-        pool_end = min(b + want, Q->n_units);
-        if constexpr (kPoolLds) {
-          // Fill: lane i sets up unit b + i into entry (b + i) mod 64, all lanes at once (the branch
-          // is wave-uniform). The region is the wave's own, so the order that matters is this wave's:
-          // its earlier fetches before these writes, these writes before its later fetches.
-          wave_lds_order();
-          const uint32_t u = b + lane;
-          if (u < pool_end) {
-            uint32_t us, us_end;
-            PxKey upk;
-            float ufx, ufy, ufz = 0.0f;
-            unit_setup(u, us, us_end, upk, ufx, ufy, ufz);
-            s_pool_a[pool_lds + (u & 63u)] = PoolEntryA{us, upk.qhi, upk.qlo, upk.lo};
-            // (the third word: P_z where the kernel holds one, else the owner's lp = u | 2^31, so
-            // that every kernel reads the entry as two whole 128-bit words)
-            if constexpr (CF::CAMAX != 2) ufz = __uint_as_float(u | 0x80000000u);
-            s_pool_b[pool_lds + (u & 63u)] = PoolEntryB{ufx, ufy, ufz, us_end};
+        if (open) {
+          uint32_t b = 0;
+          if (lane == 0) b = atomicAdd(Q->queue, want);
+          b = __builtin_amdgcn_readfirstlane(b);
+          grab_at = b + want;
+          open = b < Q->n_units;
+          if (open) {
+            pool_next = b;
+            pool_end = min(b + want, Q->n_units);
+            if constexpr (kPoolLds) {
+              // Fill: lane i sets up unit b + i into entry (b + i) mod 64, all lanes at once (the
+              // branch is wave-uniform). The region is the wave's own, so the order that matters is
+              // this wave's: its earlier fetches before these writes, these writes before its later
+              // fetches.
+              wave_lds_order();
+              const uint32_t u = b + lane;
+              if (u < pool_end) {
+                uint32_t us, us_end;
+                PxKey upk;
+                float ufx, ufy, ufz = 0.0f;
+                unit_setup(u, us, us_end, upk, ufx, ufy, ufz);
+                s_pool_a[pool_lds + (u & 63u)] = PoolEntryA{us, upk.qhi, upk.qlo, upk.lo};
+                // (the third word: P_z where the kernel holds one, else the owner's lp = u | 2^31,
+                // so that every kernel reads the entry as two whole 128-bit words)
+                if constexpr (CF::CAMAX != 2) ufz = __uint_as_float(u | 0x80000000u);
+                s_pool_b[pool_lds + (u & 63u)] = PoolEntryB{ufx, ufy, ufz, us_end};
+              }
+              wave_lds_order();
+            }
           }
-          wave_lds_order();
         }
+        exhausted = !open;
       }
-      const uint32_t rank = lane_rank(need);
-      const uint32_t avail = pool_end - pool_next;
-      if (needs_unit && rank < avail) {
-        const uint32_t u = pool_next + rank;
-        if constexpr (kPoolLds) {  // the entry the fill wrote for unit u
-          const PoolEntryA ea = s_pool_a[pool_lds + (u & 63u)];
-          const PoolEntryB eb = s_pool_b[pool_lds + (u & 63u)];
-          s = ea.s;
-          pk = PxKey{ea.qhi, ea.qlo, ea.lo};
-          fx = eb.fx;
-          fy = eb.fy;
-          s_end = eb.s_end;
-          // the owner keeps its unit index: the sums go to the unit's slot
-          if constexpr (CF::CAMAX == 2) {
-            fz = eb.fz;
-            lp = u | 0x80000000u;
+      if (!exhausted) {
+        const uint32_t rank = lane_rank(need);
+        const uint32_t avail = pool_end - pool_next;
+        if (ls == kStIdle && rank < avail) {
+          const uint32_t u = pool_next + rank;
+          if constexpr (kPoolLds) {  // the entry the fill wrote for unit u
+            const PoolEntryA ea = s_pool_a[pool_lds + (u & 63u)];
+            const PoolEntryB eb = s_pool_b[pool_lds + (u & 63u)];
+            s = ea.s;
+            pk = PxKey{ea.qhi, ea.qlo, ea.lo};
+            fx = eb.fx;
+            fy = eb.fy;
+            s_end = eb.s_end;
+            // the owner keeps its unit index: the sums go to the unit's slot
+            if constexpr (CF::CAMAX == 2) {
+              fz = eb.fz;
+              lp = u | 0x80000000u;
+            } else {
+              lp = __float_as_uint(eb.fz);
+            }
           } else {
-            lp = __float_as_uint(eb.fz);
+            unit_setup(u, s, s_end, pk, fx, fy, fz);
+            lp = u | 0x80000000u;
           }
-        } else {
-          unit_setup(u, s, s_end, pk, fx, fy, fz);
-          lp = u | 0x80000000u;
+          ls = kStCam;
         }
-        ls = kStCam;
-        needs_unit = false;
+        pool_next += min((uint32_t)__popcll(need), avail);
       }
-      pool_next += min((uint32_t)__popcll(need), avail);
-      need = __ballot(needs_unit);
     }
     // 2b) the queue is dry: an idle lane takes the upper half of a busy lane's unstarted samples
     //     (same pixel; each flushes its own sums and the accumulation is integer, so the image is
@@ -977,9 +1009,18 @@ render_kernel(const KParams* __restrict__ Pg) {
         }
       }
     }
-    if (__ballot(ls != kStIdle) == 0) break;
+    if (__ballot(ls != kStIdle) == 0) {  // no lane has work: the last iteration (the back edge)
+      live = false;
+      left = 1;
     }
-    n_cos += (uint32_t)__popcll(__ballot(ls == kStCos));
+    }
+    if constexpr (kExitAtRefill) {
+      if (!live) break;
+    }
+    // The generating lanes (the compare is the generate block's own), or in the generic kernel, whose
+    // SPEC/REFR rays generate too, the cosine ones (a v_cmp of their own).
+    if constexpr (TP::MAT) n_cos += (uint32_t)__popcll(__ballot(ls == kStCos));
+    else n_gen += (uint32_t)__popcll(__ballot(ls - kStCam < 3u));
 
     // 3) generate the path ray (kStCam, kStCos, kStSpec): the cosine continuation from the last
     //    vertex (random_scattering :337-347, its xi from that vertex's Philox words) or the camera
@@ -996,7 +1037,7 @@ render_kernel(const KParams* __restrict__ Pg) {
       const uint32_t ctr2 = (uint32_t)dp1 | (TP::MAT ? branch << 24 : 0u);
       r = philox_px(pk, s, ctr2);
       {
-        const SPT_CONST KParams* C = cptr(Pg);
+        const SPT_CONST KParams* C = cptr_at<1>(Pg, left);
         f3 vc;
         const float Fu = jitter_f(r.x, r.y), Fv = jitter_f(r.z, r.w);
         if constexpr (CF::CAMAX == 1) {
@@ -1026,9 +1067,11 @@ render_kernel(const KParams* __restrict__ Pg) {
       }
       ls = kStPath;
     }
+    // (opaque here: LLVM knows that a lane which skips the trace below is idle and would feed the
+    // state's phi a zero of its own, a v_mov and a second register for the state word)
+    ls = keep(ls);
 
-    // Path rays: counted here by the generic kernel only. Without SPEC/REFR every path ray is a
-    // sample's camera ray or a cosine continuation, so the others add n_cos + samples at the end.
+    // Path rays: counted here by the generic kernel only (the others: n_gen, above).
     if constexpr (TP::MAT) n_path += (uint32_t)__popcll(__ballot(ls == kStPath));
     if constexpr (TP::SPH) l_shadow += (uint32_t)__popcll(__ballot(ls == kStShadow));
     if (ls >= kStPath) {  // kStPath or kStShadow
@@ -1059,10 +1102,17 @@ render_kernel(const KParams* __restrict__ Pg) {
       //    cosine sample follows (:468-469, T = T*f). The weight is computed for every shadow lane
       //    and applied as T*1 (exact) where the light is not reached: no branch. (The HEAD NEE
       //    kernel resolves in 5') below instead, after the shading block.)
-      const bool traced_shadow = ls == kStShadow;
+      bool traced_shadow = ls == kStShadow;
+      if constexpr (kEarly) {
+        // as a lane mask taken here: compared where 5') reads it, the state word of before the
+        // shading stays live beside the new one (two v_mov per iteration)
+        uint64_t tsm = __ballot(ls == kStShadow);
+        asm volatile("" : "+s"(tsm));
+        traced_shadow = __builtin_amdgcn_inverse_ballot_w64(tsm);
+      }
       if (!kEarly && ls == kStShadow) {
         SPT_REGION(6);
-        const SPT_CONST KParams* D = cptr(Pg);
+        const SPT_CONST KParams* D = cptr_at<2>(Pg, left);
         const bool lh = id == light_slot_of<TP, CF>(D);
         if (lh) SPT_REGION(7);
         count_if(l_hit, lh);
@@ -1151,10 +1201,10 @@ render_kernel(const KParams* __restrict__ Pg) {
         f3 f = mk(H.cx, H.cy, H.cz);
         const f3 e = mk(H.ex, H.ey, H.ez);
         const int rr_t = H.rr_t;
-        const int depth = dp1++;  // this vertex's depth (1 = the first)
+        const int depth = dp1;  // this vertex's depth (1 = the first); dp1 moves on at the block's end
         u4 rl = r;  // RR / NEE-mix draws; at vertex 1 from stream 1 (only configs that need them)
         if (CF::NOS1 != 1 && depth == 1) {
-          const SPT_CONST KParams* C = cptr(Pg);
+          const SPT_CONST KParams* C = cptr_at<3>(Pg, left);
           if (C->rr_depth < 1 || (C->nee_prob > 0.0f && C->nee_prob < 1.0f))
             rl = philox_px(pk, s, 1u | 0x80000000u);
         }
@@ -1226,7 +1276,7 @@ render_kernel(const KParams* __restrict__ Pg) {
           // DIFF :457-480. T is T*f now; the NEE weight (if the light is reached) multiplies it
           // when the shadow ray resolves, so T = (T*f)*w exactly as the contract rounds it.
           // Computed for every vertex lane (a lane whose path ends here discards it): no branch.
-          const SPT_CONST KParams* D = cptr(Pg);
+          const SPT_CONST KParams* D = cptr_at<4>(Pg, left);
           bool nee;
           if constexpr (CF::NEE == 1) {
             nee = true;
@@ -1305,6 +1355,7 @@ render_kernel(const KParams* __restrict__ Pg) {
           }
         }
         ls = term ? kStTerm : nxt;
+        dp1 = depth + 1;  // (here: incremented where depth is read, it is copied at the block's end)
       }
       // 5') the HEAD NEE kernel resolves shadow rays here, after the shading block: the ones traced
       //    in this iteration and the ones early_nee_proven() has just resolved (t = the light's t,
@@ -1317,7 +1368,7 @@ render_kernel(const KParams* __restrict__ Pg) {
           const bool ea = ls == kStEarly;
           // a traced shadow ray that reached the light; never a proven lane (its path ray hit what
           // it shaded, not the black light, which would have ended the path)
-          const bool th = id == light_slot_of<TP, CF>(cptr(Pg));
+          const bool th = id == light_slot_of<TP, CF>(cptr_at<5>(Pg, left));
           const bool lh = ea | th;
           if (lh) SPT_REGION(7);
           count_if(l_hit, th);  // (+ the proven ones, l_early / s_nearly, at the end)
@@ -1333,7 +1384,7 @@ render_kernel(const KParams* __restrict__ Pg) {
           } else {
             // the light's t: the pre-test's for a proven lane, else the traced light hit's own
             // (k_L - o.y) / d.y as the trace ranked it (the light is an XZ rect)
-            const float kl = s_prims[light_slot_of<TP, CF>(cptr(Pg))].w1;
+            const float kl = s_prims[light_slot_of<TP, CF>(cptr_at<6>(Pg, left))].w1;
             const float tl = ea ? t : plane_t(kl - o.y, ia_hit);
             // (computed for every resolving lane: a branch around it cost exec-mask SALU)
             wl = keep(nee_weight(unit_dirs_of<TP>(Pg), d, nl, tl, kRefLarea, kRefNeeC));
@@ -1344,7 +1395,7 @@ render_kernel(const KParams* __restrict__ Pg) {
           // and >= 0 on a path that has not reached the light (one select, not three)
           const float wh = lh ? wl : 0.0f;
           const f3 Tw = mk(T.x * wh, T.y * wh, T.z * wh);
-          const DevPrim& H = s_prims[light_slot_of<TP, CF>(cptr(Pg))];
+          const DevPrim& H = s_prims[light_slot_of<TP, CF>(cptr_at<7>(Pg, left))];
           L = mk(fmaf(Tw.x, H.ex, L.x), fmaf(Tw.y, H.ey, L.y), fmaf(Tw.z, H.ez, L.z));
           ls = lh ? kStTerm : kStCos;
         }
@@ -1371,7 +1422,7 @@ render_kernel(const KParams* __restrict__ Pg) {
           T = mk(1, 1, 1);
           dp1 = 1;
           {
-            const SPT_CONST KParams* C = cptr(Pg);
+            const SPT_CONST KParams* C = cptr_at<8>(Pg, left);
             o = CF::CAMAX == 1   ? mk(ck.o0, ck.o1, ck.o2)
                 : CF::CAMAX == 2 ? mk(cg.o0, cg.o1, cg.o2)
                                  : mk(C->cam[0], C->cam[1], C->cam[2]);
@@ -1406,7 +1457,9 @@ render_kernel(const KParams* __restrict__ Pg) {
     }
     reg_flags = 0;
 #endif
+    if (--left == 0) break;  // no lane has work, or the runaway guard
   }
+  capped = live;  // left with work in hand: the guard (the units are dropped, the host reports it)
   {
     unsigned long long* st = cptr(Pg)->stats;  // wave-reduced by the atomic optimizer
 #ifdef SPT_WAVE_TIMES
@@ -1440,16 +1493,15 @@ render_kernel(const KParams* __restrict__ Pg) {
 #endif
     if (lane == 0) {  // wave-uniform counters: one lane adds them
       if (capped) atomicAdd(st + 0, 1ull);  // the host reports an error
-      const unsigned long long np = TP::MAT ? n_path : n_cos;  // (+ samples below, !MAT)
+      const unsigned long long np = TP::MAT ? n_path : n_gen;
       atomicAdd(st + 1, np);
       atomicAdd(st + 3, np);  // + the light hits, added per lane below
-      atomicAdd(st + 6, (unsigned long long)n_cos);
+      atomicAdd(st + 6, (unsigned long long)(TP::MAT ? n_cos : n_gen));
     }
-    if (!TP::MAT && blockIdx.x == 0 && threadIdx.x == 0) {  // one camera ray per sample
+    if (!TP::MAT && blockIdx.x == 0 && threadIdx.x == 0) {  // one camera ray per sample: not cosine rays
       const SPT_CONST KParams* C = cptr(Pg);
       const unsigned long long samples = (unsigned long long)C->n_local_pix * (unsigned long long)C->s_count;
-      atomicAdd(st + 1, samples);
-      atomicAdd(st + 3, samples);
+      atomicAdd(st + 6, 0ull - samples);  // (the word is whole again once every wave has added its n_gen)
     }
     {  // per-lane event counts (the atomic optimizer reduces each over the wave)
       if constexpr (!kNeeByIdentity) {
