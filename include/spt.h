@@ -31,9 +31,11 @@ extern "C" {
                              6: spt_kernel_count, spt_kernel_name, spt_select_kernel,
                              spt_context_kernel. Added since, with no change to an existing struct or
                              entry point (so the version stays): SPT_HAS_FILM, the spt_film_* calls;
-                             SPT_HAS_FILM_NOISE, the spt_film_noise_* calls */
+                             SPT_HAS_FILM_NOISE, the spt_film_noise_* calls; SPT_HAS_FILM_ADAPTIVE,
+                             the spt_film_adaptive_* calls */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
+#define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -354,6 +356,75 @@ spt_status spt_film_noise_map_host(const uint64_t* sums, const uint64_t* m2,
 spt_status spt_film_noise_summary_host(const uint64_t* sums, const uint64_t* m2,
                                        const spt_film_info* info, const spt_film_noise_info* noise,
                                        spt_noise_summary* out);
+
+/* ---- adaptive sampling: per-pixel batch counts and passes over a pixel list (SPT_HAS_FILM_ADAPTIVE) ----
+ * An adaptive film is a noise film whose pixels may stop taking batches. It keeps one more plane,
+ * cnt: uint32[rows * w], low 31 bits = the batches that pixel holds, bit 31 = retired. The film's
+ * front is batches_done. A pixel is either active (cnt == front) or retired (bit 31 set, batches <=
+ * front), and a retired pixel never returns; so pixel p always holds exactly the samples
+ * [0, batches(p) * batch) of the spp_total-sample image, and its sums and moments are those of a
+ * uniform noise film after batches(p) batches, bit for bit (samples are keyed by the global pixel
+ * index and the absolute sample index and summed in integers, whichever launch rendered them).
+ * Every per-pixel figure takes the pixel's own B = batches(p) through one table, computed once on the
+ * host in double and read by the kernels and the host statements alike:
+ *   r(B) = (float)((double)spp_total / (B * batch)), full iff B * batch == spp_total (the resolve)
+ *   k(B) = spp_total / (batch * 2^31 * B * sqrt(B - 1)), k2(B) = k(B)^2 (the error; 0 for B < 2) */
+typedef struct spt_film_adaptive_info {
+  int32_t enabled, reserved;
+  int64_t front;         /* batches_done */
+  int64_t n_active;      /* pixels the next pass would render */
+  int64_t samples_total; /* pixel-samples spent: the sum over the passes of n_active * batch */
+} spt_film_adaptive_info;
+/* Only on an empty noise film with spp_total / batch <= 4096: SPT_ERR_INVALID_ARG otherwise, film
+ * untouched. Allocates and zeroes cnt, the list and the scan scratch, uploads the table. From then on
+ * spt_film_render_async accepts only the next window (sample_base == front * batch, sample_count ==
+ * batch) and renders the active pixels: while nothing has retired through the ordinary launch (a
+ * noise film's pass, the counts implied), afterwards through a launch over the active list whose
+ * accumulate scatters (virtual pixel v -> g = list[v]: S[g] += P, M2[g] += P^2, cnt[g] += 1). With
+ * rgb_dev the adaptive resolve is enqueued behind the add. spt_context_stats then reports
+ * samples = n_active * batch. Rejected, nothing queued, film untouched: an out-of-order window, and a
+ * pass with no active pixel. A pass that hit the runaway guard adds nothing, increments no count and
+ * spt_context_stats restores the front. spt_film_info_get reports samples_done = front * batch.
+ * spt_film_resolve, spt_film_noise_map and spt_film_noise_summary use every pixel's own B (the summary
+ * stays the mean over ALL pixels, batches_done = the front). spt_film_clear resets counts and list.
+ * spt_film_merge with an adaptive film on either side is rejected with dst untouched; spt_film_upload
+ * and spt_film_noise_upload keep their meaning (sums, moments) and spt_film_adaptive_upload sets the
+ * front, so a checkpoint uploads all three with the counts last. */
+spt_status spt_film_adaptive_enable(spt_film* film);
+spt_status spt_film_adaptive_info_get(const spt_film* film, spt_film_adaptive_info* out);
+/* Retire pixels; the rest is the next pass's list. Requires front >= 2. A pixel stays active iff it is
+ * active, and keep is NULL or keep[p] != 0 (DEVICE, rows*w bytes), and se_threshold < 0 or some channel
+ * has d * k2(B) > se_threshold^2 (d of the error map: 0 for a clamped channel; the square taken once on
+ * the host in double; no square root, so host and device run the same IEEE operations). The pixels
+ * that leave get bit 31. The new list is ascending, built by a deterministic compaction (per-block
+ * counts from wave ballots, one scan, a scatter by lane rank: no atomic decides an order). Waits on
+ * `stream` and returns the count. Rejected: a NaN threshold, a plain or non-adaptive film, front < 2. */
+spt_status spt_film_adaptive_select(spt_film* film, double se_threshold, const uint8_t* keep_dev_or_null,
+                                    int64_t* n_active, void* stream);
+/* The counts plane to and from HOST memory (rows*w uint32); both wait for their copy. An upload
+ * rebuilds the list and the front: the active pixels must share one count (the front; with none active
+ * the front is the largest count) and no count may exceed spp_total / batch. */
+spt_status spt_film_adaptive_download(const spt_film* film, uint32_t* host_counts, void* stream);
+spt_status spt_film_adaptive_upload(spt_film* film, const uint32_t* host_counts, void* stream);
+/* The per-pixel forms as pure host functions (no device): sums, m2 and counts as downloaded; info's
+ * width, rows, spp_total; noise's batch (and batches_done = the front, which the summary reports). */
+spt_status spt_film_adaptive_resolve_host(const uint64_t* sums, const uint32_t* counts,
+                                          const spt_film_info* info, const spt_film_noise_info* noise,
+                                          float* rgb_out);
+spt_status spt_film_adaptive_noise_map_host(const uint64_t* sums, const uint64_t* m2,
+                                            const uint32_t* counts, const spt_film_info* info,
+                                            const spt_film_noise_info* noise, float* se_out);
+spt_status spt_film_adaptive_noise_summary_host(const uint64_t* sums, const uint64_t* m2,
+                                                const uint32_t* counts, const spt_film_info* info,
+                                                const spt_film_noise_info* noise,
+                                                spt_noise_summary* out);
+/* spt_film_adaptive_select on the host: counts_out (rows*w) = the new plane, list_out (rows*w
+ * capacity) = the new active list ascending, *n_active its length. keep: HOST bytes or NULL. */
+spt_status spt_film_adaptive_select_host(const uint64_t* sums, const uint64_t* m2,
+                                         const uint32_t* counts, const spt_film_info* info,
+                                         const spt_film_noise_info* noise, double se_threshold,
+                                         const uint8_t* keep_or_null, uint32_t* counts_out,
+                                         uint32_t* list_out, int64_t* n_active);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

@@ -113,6 +113,11 @@ class spt_noise_summary(ctypes.Structure):
                 "batches_done": int(self.batches_done)}
 
 
+class spt_film_adaptive_info(ctypes.Structure):
+    _fields_ = [("enabled", ctypes.c_int32), ("reserved", ctypes.c_int32), ("front", ctypes.c_int64),
+                ("n_active", ctypes.c_int64), ("samples_total", ctypes.c_int64)]
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -139,7 +144,13 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_film_download", "spt_film_upload", "spt_film_resolve_host",
            "spt_film_noise_enable", "spt_film_noise_info_get", "spt_film_noise_download",
            "spt_film_noise_upload", "spt_film_noise_map", "spt_film_noise_summary",
-           "spt_film_noise_map_host", "spt_film_noise_summary_host"]
+           "spt_film_noise_map_host", "spt_film_noise_summary_host",
+           "spt_film_adaptive_enable", "spt_film_adaptive_info_get", "spt_film_adaptive_select",
+           "spt_film_adaptive_download", "spt_film_adaptive_upload",
+           "spt_film_adaptive_resolve_host", "spt_film_adaptive_noise_map_host",
+           "spt_film_adaptive_noise_summary_host", "spt_film_adaptive_select_host"]
+COUNT_RETIRED = 0x80000000  # bit 31 of an adaptive film's counts: the pixel takes no more batches
+COUNT_MASK = 0x7FFFFFFF     # ... and the batches it holds
 IMAGE_FORMATS = {"p3": 0, "p6": 1, "pfm": 2}
 FLAG_UNIFORM_SCATTER = 1  # spt_params.flags: random_scattering from the uniform code of :352-359
 # spt_params.flags: leaked paths go on from the miss vertex as the reference's (:371-377) instead of
@@ -254,6 +265,18 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_film_noise_map_host.argtypes = [VP, VP, P(spt_film_info), P(spt_film_noise_info), VP]
     lib.spt_film_noise_summary_host.argtypes = [VP, VP, P(spt_film_info), P(spt_film_noise_info),
                                                 P(spt_noise_summary)]
+    lib.spt_film_adaptive_enable.argtypes = [VP]
+    lib.spt_film_adaptive_info_get.argtypes = [VP, P(spt_film_adaptive_info)]
+    lib.spt_film_adaptive_select.argtypes = [VP, ctypes.c_double, VP, P(I64), VP]
+    lib.spt_film_adaptive_download.argtypes = [VP, VP, VP]
+    lib.spt_film_adaptive_upload.argtypes = [VP, VP, VP]
+    lib.spt_film_adaptive_resolve_host.argtypes = [VP, VP, P(spt_film_info), P(spt_film_noise_info), VP]
+    lib.spt_film_adaptive_noise_map_host.argtypes = [VP, VP, VP, P(spt_film_info),
+                                                     P(spt_film_noise_info), VP]
+    lib.spt_film_adaptive_noise_summary_host.argtypes = [VP, VP, VP, P(spt_film_info),
+                                                         P(spt_film_noise_info), P(spt_noise_summary)]
+    lib.spt_film_adaptive_select_host.argtypes = [VP, VP, VP, P(spt_film_info), P(spt_film_noise_info),
+                                                  ctypes.c_double, VP, VP, VP, P(I64)]
     for name in EXPORTS:
         if name.startswith("spt_film_"):
             getattr(lib, name).restype = I32
@@ -675,6 +698,70 @@ def _noise_host_args(sums, m2, width, rows, spp_total, samples_done, batch, batc
     return a, m, info, noise
 
 
+def _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, front):
+    a = np.ascontiguousarray(sums, dtype=np.uint64)
+    m = None if m2 is None else np.ascontiguousarray(m2, dtype=np.uint64)
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    info = spt_film_info(int(width), int(rows), int(spp_total), int(front) * int(batch))
+    noise = spt_film_noise_info(1, int(batch), int(front))
+    npix = max(info.rows, 0) * max(info.width, 0)
+    if a.size != 3 * npix or c.size != npix or (m is not None and m.size != 6 * npix):
+        raise SptError(1, "sums / m2 / counts do not have the film's elements")
+    return a, m, c, info, noise
+
+
+def film_adaptive_resolve_host(sums, counts, width: int, rows: int, spp_total: int,
+                               batch: int) -> np.ndarray:
+    """spt_film_adaptive_resolve_host(): the resolve with every pixel's own count (no device)."""
+    a, _, c, info, noise = _adaptive_host_args(sums, None, counts, width, rows, spp_total, batch, 0)
+    out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
+    _check(load_library().spt_film_adaptive_resolve_host(a.ctypes.data, c.ctypes.data,
+                                                         ctypes.byref(info), ctypes.byref(noise),
+                                                         out.ctypes.data))
+    return out
+
+
+def film_adaptive_noise_map_host(sums, m2, counts, width: int, rows: int, spp_total: int,
+                                 batch: int) -> np.ndarray:
+    """spt_film_adaptive_noise_map_host(): the error map with every pixel's own count."""
+    a, m, c, info, noise = _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, 0)
+    out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
+    _check(load_library().spt_film_adaptive_noise_map_host(a.ctypes.data, m.ctypes.data, c.ctypes.data,
+                                                           ctypes.byref(info), ctypes.byref(noise),
+                                                           out.ctypes.data))
+    return out
+
+
+def film_adaptive_noise_summary_host(sums, m2, counts, width: int, rows: int, spp_total: int,
+                                     batch: int, front: int) -> dict:
+    """spt_film_adaptive_noise_summary_host(): the image figures (the mean over all pixels), each
+    pixel with its own count; batches_done reports `front`."""
+    a, m, c, info, noise = _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, front)
+    out = spt_noise_summary()
+    _check(load_library().spt_film_adaptive_noise_summary_host(a.ctypes.data, m.ctypes.data,
+                                                               c.ctypes.data, ctypes.byref(info),
+                                                               ctypes.byref(noise), ctypes.byref(out)))
+    return out.as_dict()
+
+
+def film_adaptive_select_host(sums, m2, counts, width: int, rows: int, spp_total: int, batch: int,
+                              front: int, threshold: float, keep=None):
+    """spt_film_adaptive_select_host(): -> (the new counts plane (rows, width) uint32, the new active
+    list ascending). keep: rows * width bytes or None."""
+    a, m, c, info, noise = _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, front)
+    k = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    if k is not None and k.size != c.size:
+        raise SptError(1, "keep does not have rows * width bytes")
+    out = np.zeros((max(info.rows, 0), max(info.width, 0)), dtype=np.uint32)
+    lst = np.zeros(max(1, c.size), dtype=np.uint32)
+    n = ctypes.c_int64(0)
+    _check(load_library().spt_film_adaptive_select_host(
+        a.ctypes.data, m.ctypes.data, c.ctypes.data, ctypes.byref(info), ctypes.byref(noise),
+        float(threshold), None if k is None else k.ctypes.data, out.ctypes.data, lst.ctypes.data,
+        ctypes.byref(n)))
+    return out, lst[: n.value].copy()
+
+
 def write_film_file(path: str, sums: np.ndarray, width: int, rows: int, spp_total: int,
                     samples_done: int, m2: np.ndarray | None = None, batch: int = 0,
                     batches_done: int = 0) -> None:
@@ -812,6 +899,9 @@ class Film:
                                         ctypes.c_void_p(stream_ptr or None)))
 
     def save(self, path: str):
+        if self.adaptive_info()["enabled"]:
+            raise SptError(1, "an adaptive film has no file format: checkpoint it with to_numpy, "
+                              "noise_to_numpy and counts_to_numpy")
         i, n = self.info(), self.noise_info()
         if not n["enabled"]:
             write_film_file(path, self.to_numpy(), i["width"], i["rows"], i["spp_total"],
@@ -872,6 +962,58 @@ class Film:
         _check(self.lib.spt_film_noise_summary(self._f, ctypes.byref(out),
                                                ctypes.c_void_p(stream_ptr or None)))
         return out.as_dict()
+
+
+    # ---- the adaptive film (spt_film_adaptive_*) ----
+    def enable_adaptive(self):
+        """Per-pixel batch counts from now on (an empty noise film with at most 4096 batches): passes
+        must come in window order and render the pixels still active (adaptive_select)."""
+        _check(self.lib.spt_film_adaptive_enable(self._f))
+
+    def adaptive_info(self) -> dict:
+        i = spt_film_adaptive_info()
+        _check(self.lib.spt_film_adaptive_info_get(self._f, ctypes.byref(i)))
+        return {k: int(getattr(i, k)) for k in ("enabled", "front", "n_active", "samples_total")}
+
+    def adaptive_select(self, threshold: float, keep=None, stream_ptr: int = 0) -> int:
+        """Retire the active pixels whose every channel has se <= threshold (threshold < 0: none by
+        the error) or whose keep entry is 0; -> the pixels still active. keep: None, a device pointer
+        (rows * width bytes), or an array (uploaded for this call)."""
+        n = ctypes.c_int64(0)
+        ptr, hold = None, None
+        if keep is not None and not isinstance(keep, int):
+            import torch
+            k = np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1)
+            i = self.info()
+            if k.size != i["rows"] * i["width"]:
+                raise SptError(1, "keep does not have rows * width bytes")
+            hold = torch.from_numpy(k).to(f"cuda:{self.device}")
+            torch.cuda.synchronize(self.device)
+            ptr = hold.data_ptr()
+        elif keep:
+            ptr = int(keep)
+        _check(self.lib.spt_film_adaptive_select(self._f, float(threshold), ctypes.c_void_p(ptr),
+                                                 ctypes.byref(n), ctypes.c_void_p(stream_ptr or None)))
+        del hold
+        return int(n.value)
+
+    def counts_to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
+        """The counts plane on the host: (rows, width) uint32 (COUNT_MASK, COUNT_RETIRED)."""
+        i = self.info()
+        out = np.zeros((i["rows"], i["width"]), dtype=np.uint32)
+        _check(self.lib.spt_film_adaptive_download(self._f, out.ctypes.data,
+                                                   ctypes.c_void_p(stream_ptr or None)))
+        return out
+
+    def counts_from_numpy(self, counts: np.ndarray, stream_ptr: int = 0):
+        """Replace the counts plane (the last of a checkpoint's three uploads): rebuilds the active
+        list and sets the front."""
+        i = self.info()
+        a = np.ascontiguousarray(counts, dtype=np.uint32)
+        if a.size != i["rows"] * i["width"]:
+            raise SptError(1, "counts do not have rows * width elements")
+        _check(self.lib.spt_film_adaptive_upload(self._f, a.ctypes.data,
+                                                 ctypes.c_void_p(stream_ptr or None)))
 
 
 def render_progressive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, passes,
@@ -945,6 +1087,56 @@ def render_until(prims: Sequence[spt_prim], cam: Camera, params: spt_params, tar
         out = buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
         info = {"samples_done": film.info()["samples_done"],
                 "batches_done": film.noise_info()["batches_done"], "rmse": rmse}
+    finally:
+        film.close()
+        r.close()
+    return (out, info) if return_info else out
+
+
+def render_adaptive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, target_rmse: float,
+                    batch: int | None = None, min_batches: int = 4, threshold_scale: float = 1.0,
+                    return_info=False):
+    """render_until with the samples going where the error is. Full batches until min_batches (at
+    least 2; pass a small value to retire earlier). After every pass from then on the film's summary
+    is read and the render stops once max(rmse) <= target_rmse; otherwise the pixels whose every
+    channel has se <= threshold_scale * target_rmse retire (adaptive_select) and the next pass renders
+    the rest, until nothing is active or every batch of params.spp is in. A pixel retired on its own
+    estimate may look converged by luck: min_batches is the guard. Returns the
+    resolved image; return_info: also {"front", "samples_total", "rmse", "counts"}."""
+    import torch
+    spp = int(params.spp)
+    if batch is None:
+        if spp % 8:
+            raise ValueError("render_adaptive: spp is no multiple of 8, give batch")
+        batch = spp // 8
+    dev = params.device
+    r, film = Renderer(dev), Film(params, dev)
+    try:
+        film.enable_noise(batch)
+        film.enable_adaptive()
+        i = film.info()
+        need = max(2, int(min_batches))
+        rmse = None
+        with torch.cuda.device(dev):
+            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
+                              device=f"cuda:{dev}")
+            stream = torch.cuda.current_stream().cuda_stream
+            for k in range(spp // batch):
+                film.render(r, prims, cam, params, k * batch, batch, 0, stream)
+                r.stats()  # a pass that hit the runaway guard raises here
+                if k + 1 >= need:
+                    rmse = film.noise_summary(stream)["rmse"]
+                    if max(rmse) <= target_rmse:
+                        break
+                    if k + 1 < spp // batch and \
+                            film.adaptive_select(threshold_scale * target_rmse, None, stream) == 0:
+                        break
+            film.resolve(buf.data_ptr(), stream)
+            torch.cuda.synchronize(dev)
+        out = buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+        a = film.adaptive_info()
+        info = {"front": a["front"], "samples_total": a["samples_total"], "rmse": rmse,
+                "counts": film.counts_to_numpy(stream)}
     finally:
         film.close()
         r.close()

@@ -1,7 +1,8 @@
 // smallpt_main.cpp — the reference's main() (smallpt.cpp:502-557) on the MI355X:
 //   smallpt_amd [W H SPP [SEED [OUT.ppm]]] [--cos] [--uniform] [--reference-leaks] [--q Q]
 //               [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]
-//               [--device N | --devices N] [--p6 | --pfm] [--noise T [--batch B]]
+//               [--device N | --devices N] [--p6 | --pfm]
+//               [--noise T [--batch B] [--adaptive [--min-batches M]]]
 //   --uniform: random_scattering from the commented-out uniform hemisphere code (:352-359)
 //   --reference-leaks: leaked paths go on from the miss vertex as the reference's (:371-377)
 //                      instead of ending at their first miss (SPT_FLAG_REFERENCE_LEAKS)
@@ -29,6 +30,12 @@
 //               the checkpoint is a noise film's ("SPTFILM2": the header goes on with int32 batch, 0,
 //               int64 batches_done -- 48 bytes --, and the moment plane, rows*width*3 pairs (lo, hi)
 //               of uint64, follows the sums) and --add N (a multiple of B) caps this run's samples.
+//   --adaptive (with --noise T): the samples go where the error is (spt_film_adaptive_*). Full
+//               batches until M (--min-batches, default 4, at least 2); after every pass from then on
+//               the run ends once the estimated RMSE is at most T, otherwise the pixels whose every
+//               channel has a standard error <= T retire and the next pass renders the rest, until
+//               none is left or every batch is in. Prints "SAMPLES_TOTAL : N" (the pixel-samples
+//               spent) beside DURATION. Not with --film: the counts plane has no file format.
 // Same scene, camera (:521), clamp/toInt and P3 output; the pixel loop is one spt_render() call.
 #include <algorithm>
 #include <chrono>
@@ -63,6 +70,9 @@ struct NoiseOpts {
   bool on = false;
   double target = 0.0;
   int batch = 0;  // 0: SPP / 8
+  bool adaptive = false;
+  int min_batches = 4;
+  int64_t samples_total = -1;  // out: the pixel-samples an adaptive run spent
 };
 
 void check(spt_status s) {
@@ -74,7 +84,7 @@ void check(spt_status s) {
 // its moment plane, the passes are the batches in index order, and the run ends early once the
 // estimated RMSE is at most noise.target. Returns the DEVICE image.
 float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
-                   int passes, const char* film_path, int add, const NoiseOpts& noise,
+                   int passes, const char* film_path, int add, NoiseOpts& noise,
                    spt_stats* total) {
   spt_context* ctx = nullptr;
   spt_film* film = nullptr;
@@ -90,6 +100,7 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
       throw std::runtime_error("--noise: SPP is no multiple of 8, give --batch");
     batch = noise.batch > 0 ? noise.batch : p.spp / 8;
     check(spt_film_noise_enable(film, batch));
+    if (noise.adaptive) check(spt_film_adaptive_enable(film));
   }
   const char* magic = noise.on ? kFilmMagicNoise : kFilmMagic;
   if (film_path) {
@@ -143,10 +154,20 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
       total->vertices += st.vertices;
       total->kernel_ms += st.kernel_ms;
       check(spt_film_noise_info_get(film, &ni));
-      measured = ni.batches_done >= 2;
+      measured = ni.batches_done >= (noise.adaptive ? std::max(2, noise.min_batches) : 2);
       if (!measured) continue;
       check(spt_film_noise_summary(film, &sm, nullptr));
       if (std::max(sm.rmse[0], std::max(sm.rmse[1], sm.rmse[2])) <= noise.target) break;
+      if (noise.adaptive && k + 1 < todo / batch) {  // retire what is below the target, render the rest
+        int64_t n_active = 0;
+        check(spt_film_adaptive_select(film, noise.target, nullptr, &n_active, nullptr));
+        if (n_active == 0) break;
+      }
+    }
+    if (noise.adaptive) {
+      spt_film_adaptive_info ai{};
+      check(spt_film_adaptive_info_get(film, &ai));
+      noise.samples_total = ai.samples_total;
     }
     check(spt_film_resolve(film, dev, nullptr));
     check(spt_film_info_get(film, &info));
@@ -222,6 +243,8 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--add") && i + 1 < argc) add = std::max(1, std::atoi(argv[++i]));
     else if (!std::strcmp(argv[i], "--noise") && i + 1 < argc) { noise.on = true; noise.target = std::atof(argv[++i]); }
     else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) noise.batch = std::max(1, std::atoi(argv[++i]));
+    else if (!std::strcmp(argv[i], "--adaptive")) noise.adaptive = true;
+    else if (!std::strcmp(argv[i], "--min-batches") && i + 1 < argc) noise.min_batches = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--p6")) format = SPT_IMAGE_P6;
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
     else if (npos < 4) pos[npos++] = std::atoi(argv[i]);
@@ -247,9 +270,12 @@ int main(int argc, char* argv[]) {
                                         : specular ? cornell_specular_scene()
                                         : spheres ? spheres32_scene()
                                                   : cornell_scene();
-    if (passes > 0 || film_path || noise.on) {
+    if (passes > 0 || film_path || noise.on || noise.adaptive) {
       if (devices > 0 || repeat > 1)
         throw std::runtime_error("--passes / --film / --noise go with one device and no --repeat");
+      if (noise.adaptive && !noise.on) throw std::runtime_error("--adaptive goes with --noise T");
+      if (noise.adaptive && film_path)
+        throw std::runtime_error("--adaptive does not go with --film: the counts plane has no file format");
       image = render_film(scene, cam, p, passes, film_path, add, noise, &st);
       repeat = 0;
     }
@@ -282,6 +308,7 @@ int main(int argc, char* argv[]) {
   const double samples = (double)p.width * p.height * p.spp;
   std::cout << "KERNEL_MS : " << st.kernel_ms << "  MSAMPLES/S : " << samples / (st.kernel_ms * 1e3)
             << "  VERTICES/SAMPLE : " << (double)st.vertices / samples << std::endl;
+  if (noise.samples_total >= 0) std::cout << "SAMPLES_TOTAL : " << noise.samples_total << std::endl;
   std::cout << " DURATION : " << std::chrono::duration_cast<std::chrono::milliseconds>(t2 - t1).count()
             << std::endl;  // :554-556
   return 0;

@@ -167,8 +167,11 @@ static void set_last_film(spt_context* c, spt_film* film, int32_t count) {
 // one-shot's.
 spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
                              const spt_camera* cam, const spt_params* p, int32_t s_base,
-                             int32_t s_count, float* rgb_dev, spt_film* film, void* stream_v) {
+                             int32_t s_count, float* rgb_dev, spt_film* film, void* stream_v,
+                             const uint32_t* list_dev, uint32_t n_list) {
   if (!c || (!rgb_dev && !film)) return fail(SPT_ERR_INVALID_ARG, "null context/output");
+  if (list_dev && (!film || n_list == 0))
+    return fail(SPT_ERR_INVALID_ARG, "a pixel list needs a film and at least one pixel");
   spt_status st = validate(prims, n_prims, cam, p);
   if (st != SPT_OK) return st;
   if (s_base < 0 || s_count < 1 || (int64_t)s_base + s_count > p->spp)
@@ -219,7 +222,12 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   // runs under; then the launch's sizes (both spt_dispatch.cpp)
   const int kv = select_variant(prims, n_prims, cam, p, *c->h_geo, light_pos, &K);
   LaunchPlan plan;
-  st = plan_launch(c->n_cu, c->bpc[kv], kv, p, s_count, rows * p->width, &K, &plan);
+  // over a pixel list the launch's local pixels are the virtual indices [0, n_list)
+  if (list_dev && (uint64_t)n_list > (uint64_t)rows * (uint64_t)p->width)
+    return fail(SPT_ERR_INVALID_ARG, "the pixel list is longer than the shard");
+  K.pix_list = list_dev;
+  st = plan_launch(c->n_cu, c->bpc[kv], kv, p, s_count, list_dev ? (int)n_list : rows * p->width, &K,
+                   &plan);
   if (st != SPT_OK) return st;
   const size_t n_units = K.n_units;
   K.accum = c->accum;
@@ -258,11 +266,15 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   *c->h_kp = K;
   SPT_HIP(hipMemcpyAsync(c->d_kp, c->h_kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
   SPT_HIP(hipEventRecord(c->ev0, stream));
-  launch_render_kernel(kv, plan.grid, c->d_kp, stream);
+  launch_render_kernel(kv, plan.grid, c->d_kp, stream, list_dev != nullptr);
   SPT_HIP(hipGetLastError());
   SPT_HIP(hipEventRecord(c->ev1, stream));
   const uint32_t np = (uint32_t)K.n_local_pix;
-  if (film) {  // add the window's sums to the film (and resolve it into rgb_dev, if given)
+  if (film && list_dev) {  // scatter the list's sums into the film's pixels
+    st = spt_film_accumulate_listed(film, c, c->accum, c->slots, rgb_dev, np, plan.n_chunks, K.scr_k,
+                                    K.scr_q, c->stats, s_count, stream);
+    if (st != SPT_OK) return st;
+  } else if (film) {  // add the window's sums to the film (and resolve it into rgb_dev, if given)
     st = spt_film_accumulate(film, c, c->accum, c->slots, rgb_dev, np, plan.n_chunks, K.scr_k,
                              K.scr_q, c->stats, s_count, stream);
     if (st != SPT_OK) return st;

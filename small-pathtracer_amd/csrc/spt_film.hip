@@ -13,6 +13,9 @@
 //   merge       dst += src
 //   noise       a noise film's moment plane (accumulate also does M2 += P^2, 128 bits), its error map
 //               and the image's RMSE estimate (a two-stage reduction in a fixed order)
+//   adaptive    an adaptive film's counts plane: passes over the active list scatter their sums, the
+//               selection retires pixels and compacts the rest, and the resolve, the map and the
+//               summary take every pixel's own batch count (the last section of this file)
 //
 // All three stream: one pass over the sums at 16 bytes per access (two sums, or four floats),
 // 256 threads per block, no reuse -- HBM-bound. -ffp-contract=off (the Makefile) keeps the preview two
@@ -20,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -408,6 +412,12 @@ float resolve_factor(int32_t spp_total, int64_t done, int* full) {
   return done > 0 ? (float)((double)spp_total / (double)done) : 0.0f;
 }
 
+// The adaptive film's forms of the calls above them (defined in the last section).
+void adaptive_sync_counts(const spt_film* f, hipStream_t stream);
+spt_status adaptive_resolve(const spt_film* f, float* rgb_dev, const u64* stats, hipStream_t stream);
+spt_status adaptive_noise_map(const spt_film* f, float* se_dev, hipStream_t stream);
+spt_status adaptive_noise_summary(spt_film* f, spt_noise_summary* out, hipStream_t stream);
+
 unsigned quad_blocks(size_t n) { return (unsigned)(((n + 3) / 4 + kBlock - 1) / kBlock); }
 unsigned tail_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -457,6 +467,11 @@ extern "C" spt_status spt_film_destroy(spt_film* f) {
   if (f->sums) (void)hipFree(f->sums);
   if (f->m2) (void)hipFree(f->m2);
   if (f->partials) (void)hipFree(f->partials);
+  if (f->cnt) (void)hipFree(f->cnt);
+  if (f->list) (void)hipFree(f->list);
+  if (f->scan) (void)hipFree(f->scan);
+  if (f->table) (void)hipFree(f->table);
+  std::free(f->h_table);
   delete f;
   return SPT_OK;
 }
@@ -476,6 +491,14 @@ extern "C" spt_status spt_film_clear(spt_film* f, void* stream) {
     FILM_HIP(hipSetDevice(f->device));
     FILM_HIP(hipMemsetAsync(f->sums, 0, f->n * sizeof(u64), (hipStream_t)stream));
     if (f->m2) FILM_HIP(hipMemsetAsync(f->m2, 0, f->n * sizeof(ulonglong2), (hipStream_t)stream));
+    if (f->cnt) FILM_HIP(hipMemsetAsync(f->cnt, 0, f->n / 3 * sizeof(uint32_t), (hipStream_t)stream));
+  }
+  if (f->adaptive) {  // every pixel active again at count 0; the list is rebuilt by the next select
+    f->any_retired = false;
+    f->cnt_front = 0;
+    f->n_active = (int64_t)(f->n / 3);
+    f->samples_total = 0;
+    f->last_pass_samples = 0;
   }
   f->samples_done = 0;
   f->batches_done = 0;
@@ -500,6 +523,10 @@ spt_status spt_film_accumulate(spt_film* f, spt_context* c, const unsigned long 
   FILM_HIP(hipGetLastError());
   f->samples_done += s_count;
   if (f->batch) f->batches_done += 1;
+  if (f->adaptive) {  // nothing has retired: every pixel took the batch, the counts stay implied
+    f->last_pass_samples = (int64_t)npix * s_count;
+    f->samples_total += f->last_pass_samples;
+  }
   if (f->last_ctx && f->last_ctx != c) spt_context_forget_film(f->last_ctx, f);
   f->last_ctx = c;
   return SPT_OK;
@@ -509,6 +536,11 @@ void spt_film_rollback(spt_film* f, const spt_context* c, int32_t s_count) {
   if (f->last_ctx == c && f->samples_done >= s_count) {
     f->samples_done -= s_count;
     if (f->batch && f->batches_done > 0) f->batches_done -= 1;  // a pass of a noise film is one batch
+    if (f->adaptive) {  // the front goes back; the guarded pass incremented no count
+      f->samples_total -= f->last_pass_samples;
+      f->last_pass_samples = 0;
+      if (!f->any_retired && f->cnt_front > f->batches_done) f->cnt_front = -1;
+    }
   }
 }
 
@@ -532,8 +564,17 @@ extern "C" spt_status spt_film_render_async(spt_context* ctx, spt_film* f, const
     return fail(SPT_ERR_INVALID_ARG, "the film would hold more than spp samples");
   if (f->batch && (sample_count != f->batch || sample_base % f->batch != 0))
     return fail(SPT_ERR_INVALID_ARG, "a noise film takes whole batches: sample_count == batch, sample_base % batch == 0");
+  if (f->adaptive) {
+    if ((int64_t)sample_base != f->batches_done * f->batch)
+      return fail(SPT_ERR_INVALID_ARG, "an adaptive film takes the next window only: sample_base == front * batch");
+    if (f->n && f->n_active == 0)
+      return fail(SPT_ERR_INVALID_ARG, "the adaptive film has no active pixel");
+  }
+  // once a pixel has retired the pass runs over the active list; until then it is a noise film's
+  const bool listed = f->adaptive && f->any_retired;
   const spt_status st = spt_render_window(ctx, prims, n_prims, cam, p, sample_base, sample_count,
-                                          rgb_dev, f, stream);
+                                          rgb_dev, f, stream, listed ? f->list : nullptr,
+                                          listed ? (uint32_t)f->n_active : 0u);
   if (st != SPT_OK) return st;
   if (f->rows == 0) {  // a shard without rows: nothing to add, still counted
     f->samples_done += sample_count;
@@ -547,6 +588,7 @@ extern "C" spt_status spt_film_resolve(const spt_film* f, float* rgb_dev, void* 
   if (f->n == 0) return SPT_OK;
   if (!rgb_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
   FILM_HIP(hipSetDevice(f->device));
+  if (f->adaptive) return adaptive_resolve(f, rgb_dev, nullptr, (hipStream_t)stream);
   int full = 0;
   const float r = resolve_factor(f->spp_total, f->samples_done, &full);
   const size_t body = aligned16(rgb_dev) ? f->n & ~(size_t)3 : 0;  // sums the 16-byte kernel takes
@@ -571,6 +613,8 @@ extern "C" spt_status spt_film_merge(spt_film* dst, const spt_film* src, void* s
     return fail(SPT_ERR_INVALID_ARG, "films on different devices: download one and upload it beside the other");
   if (dst->samples_done + src->samples_done > dst->spp_total)
     return fail(SPT_ERR_INVALID_ARG, "the merged film would hold more than spp samples");
+  if (dst->adaptive || src->adaptive)
+    return fail(SPT_ERR_INVALID_ARG, "an adaptive film cannot be merged: its pixels hold different sample ranges");
   if (dst->batch != src->batch)
     return fail(SPT_ERR_INVALID_ARG, "merge needs two plain films or two noise films of equal batch");
   if (dst->n) {
@@ -751,6 +795,7 @@ extern "C" spt_status spt_film_noise_map(const spt_film* f, float* se_dev, void*
   if (f->n == 0) return SPT_OK;
   if (!se_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
   FILM_HIP(hipSetDevice(f->device));
+  if (f->adaptive) return adaptive_noise_map(f, se_dev, (hipStream_t)stream);
   const NoiseArgs A = noise_args(f->spp_total, f->samples_done, f->batch, f->batches_done);
   hipLaunchKernelGGL(film_noise_map_kernel, dim3(tail_blocks(f->n)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const u64*)f->sums, (const ulonglong2*)f->m2, se_dev, f->n, A);
@@ -762,6 +807,7 @@ extern "C" spt_status spt_film_noise_summary(spt_film* f, spt_noise_summary* out
   if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
   if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
   if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
+  if (f->adaptive) return adaptive_noise_summary(f, out, (hipStream_t)stream);
   NoisePartial total{};
   if (f->n) {
     FILM_HIP(hipSetDevice(f->device));
@@ -823,5 +869,620 @@ extern "C" spt_status spt_film_noise_summary_host(const uint64_t* sums, const ui
     t.clamped += c ? 1u : 0u;
   }
   noise_finish(t, n / 3, noise->batches_done, out);
+  return SPT_OK;
+}
+
+// ---- the adaptive film: counts plane, listed accumulate, selection (spt.h SPT_HAS_FILM_ADAPTIVE) ----
+// New kernels throughout: the kernels above are launched by plain and noise films exactly as before.
+namespace {
+
+constexpr uint32_t kRetired = 0x80000000u, kCntMask = 0x7FFFFFFFu;
+constexpr int32_t kAdaptMaxBatches = 4096;
+
+// One row of the table, for a pixel that holds B batches: the resolve's factor and the error's.
+struct AdaptRow {
+  double k, k2;
+  float r;
+  int full;
+};
+
+// Computed once on the host in double; kernels and host statements read the same values.
+AdaptRow adapt_row(int32_t spp_total, int32_t batch, int64_t B) {
+  AdaptRow t{};
+  t.r = resolve_factor(spp_total, B * (int64_t)batch, &t.full);
+  if (B >= 2) {
+    const NoiseArgs A = noise_args(spp_total, B * (int64_t)batch, batch, B);
+    t.k = A.k;
+    t.k2 = A.k2;
+  }
+  return t;
+}
+
+__host__ __device__ __forceinline__ NoiseArgs adapt_args(const AdaptRow& t, uint32_t B) {
+  NoiseArgs A;
+  A.B = B;
+  A.k = t.k;
+  A.k2 = t.k2;
+  A.r = t.r;
+  A.full = t.full;
+  return A;
+}
+
+// Is some channel of the pixel above the threshold? d * k2 > thr2, no square root: the same IEEE
+// operations on the host and on the device (-ffp-contract=off).
+__host__ __device__ __forceinline__ bool adapt_noisy(const u64* S, const ulonglong2* m, const NoiseArgs& A,
+                                                     double thr2) {
+  bool noisy = false;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    bool cl;
+    const double d = noise_d(S[c], m[c], A, &cl);
+    noisy = noisy || d * A.k2 > thr2;
+  }
+  return noisy;
+}
+
+// The pass over the active list: thread t sums the slots of unit-order virtual pixel t (as the
+// unlisted kernel's phase 1), v = its spread virtual pixel (the accumulator's index), g = list[v]
+// the film's pixel. A scatter: 8-byte accesses of the sums, one 16-byte load and store per moment
+// (straight-line, the full wait before any register is used), the pixel's count + 1. No two threads
+// share a g (the list holds every pixel once). A guarded launch adds nothing.
+__global__ void __launch_bounds__(kBlock)
+film_accumulate_listed_kernel(const u64* __restrict__ accum, const u64* __restrict__ slots,
+                              u64* __restrict__ film, ulonglong2* __restrict__ m2,
+                              uint32_t* __restrict__ cnt, const uint32_t* __restrict__ list,
+                              uint32_t npix, uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
+                              const u64* __restrict__ stats) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (stats[0] != 0 || t >= npix) return;
+  u64 v0 = 0, v1 = 0, v2 = 0;
+  for (uint32_t j = 0; j < n_chunks; ++j) {
+    const u64* q = slots + 3ull * ((size_t)j * npix + t);
+    v0 += q[0];
+    v1 += q[1];
+    v2 += q[2];
+  }
+  const uint32_t v = ((uint32_t)t & ((1u << scr_k) - 1u)) * scr_q + ((uint32_t)t >> scr_k);
+  const size_t g = list[v];
+  v0 += accum[3ull * v];
+  v1 += accum[3ull * v + 1];
+  v2 += accum[3ull * v + 2];
+  ulonglong2 q0 = m2[3 * g], q1 = m2[3 * g + 1], q2 = m2[3 * g + 2];
+  loads_landed(q0, q1);
+  load_landed(q2);
+  film[3 * g] += v0;
+  film[3 * g + 1] += v1;
+  film[3 * g + 2] += v2;
+  m2_add_square(q0, v0);
+  m2_add_square(q1, v1);
+  m2_add_square(q2, v2);
+  m2[3 * g] = q0;
+  m2[3 * g + 1] = q1;
+  m2[3 * g + 2] = q2;
+  cnt[g] += 1u;
+}
+
+// film -> float with every pixel's own factor: one pixel per thread. stats (optional): the words of
+// the pass this resolve follows; a guarded pass leaves rgb all NaN, as the unlisted pass does.
+__global__ void __launch_bounds__(kBlock)
+film_adapt_resolve_kernel(const u64* __restrict__ sums, const uint32_t* __restrict__ cnt,
+                          const AdaptRow* __restrict__ tab, float* __restrict__ rgb, size_t npix,
+                          const u64* __restrict__ stats) {
+  const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= npix) return;
+  if (stats && stats[0] != 0) {
+    rgb[3 * p] = rgb[3 * p + 1] = rgb[3 * p + 2] = __builtin_nanf("");
+    return;
+  }
+  const uint32_t B = cnt[p] & kCntMask;
+  const float r = tab[B].r;
+  const int full = tab[B].full;
+  rgb[3 * p] = film_resolve1(sums[3 * p], r, full);
+  rgb[3 * p + 1] = film_resolve1(sums[3 * p + 1], r, full);
+  rgb[3 * p + 2] = film_resolve1(sums[3 * p + 2], r, full);
+}
+
+// The error map with the pixel's own B: one element per thread, as film_noise_map_kernel.
+__global__ void __launch_bounds__(kBlock)
+film_adapt_map_kernel(const u64* sums, const ulonglong2* m2, const uint32_t* cnt, const AdaptRow* tab,
+                      float* se, size_t n) {
+  const size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e < n) {
+    ulonglong2 m = m2[e];
+    load_landed(m);
+    const uint32_t B = cnt[e / 3] & kCntMask;
+    const NoiseArgs A = adapt_args(tab[B], B);
+    bool c;
+    se[e] = (float)(sqrt(noise_d(sums[e], m, A, &c)) * A.k);
+  }
+}
+
+// The summary's stage 1 with the pixel's own B (stage 2 is film_noise_total_kernel).
+__global__ void __launch_bounds__(kBlock)
+film_adapt_partials_kernel(const u64* sums, const ulonglong2* m2, const uint32_t* cnt,
+                           const AdaptRow* tab, size_t npix, double* out) {
+  __shared__ NoisePartial s_p[kBlock];
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  NoisePartial v{};
+  if (px < npix) {
+    ulonglong2 m0 = m2[3 * px], m1 = m2[3 * px + 1], mm = m2[3 * px + 2];
+    loads_landed(m0, m1);
+    load_landed(mm);
+    const ulonglong2 m[3] = {m0, m1, mm};
+    const uint32_t B = cnt[px] & kCntMask;
+    const NoiseArgs A = adapt_args(tab[B], B);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      bool cl;
+      const double d = noise_d(sums[3 * px + c], m[c], A, &cl);
+      v.s[c] = d * A.k2;
+      v.se_max = fmaxf(v.se_max, (float)(sqrt(d) * A.k));
+      v.clamped += cl ? 1u : 0u;
+    }
+  }
+  s_p[threadIdx.x] = v;
+  noise_block_reduce(s_p);
+  if (threadIdx.x == 0) {
+    const size_t nb = gridDim.x;
+    out[blockIdx.x] = s_p[0].s[0];
+    out[nb + blockIdx.x] = s_p[0].s[1];
+    out[2 * nb + blockIdx.x] = s_p[0].s[2];
+    out[3 * nb + blockIdx.x] = (double)s_p[0].se_max;
+    ((u64*)out)[4 * nb + blockIdx.x] = s_p[0].clamped;
+  }
+}
+
+// The selection's first step: an active pixel that the mask drops, or none of whose channels is above
+// the threshold, gets bit 31. One pixel per thread; the moments are loaded by every thread in range
+// (straight-line), used or not.
+__global__ void __launch_bounds__(kBlock)
+film_adapt_mark_kernel(const u64* sums, const ulonglong2* m2, uint32_t* cnt, const AdaptRow* tab,
+                       const uint8_t* keep, size_t npix, double thr2, int all) {
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (px >= npix) return;
+  ulonglong2 m0 = m2[3 * px], m1 = m2[3 * px + 1], mm = m2[3 * px + 2];
+  loads_landed(m0, m1);
+  load_landed(mm);
+  const uint32_t c = cnt[px];
+  if (c & kRetired) return;
+  bool stay = keep ? keep[px] != 0 : true;
+  if (stay && !all) {
+    const ulonglong2 m[3] = {m0, m1, mm};
+    const u64 S[3] = {sums[3 * px], sums[3 * px + 1], sums[3 * px + 2]};
+    stay = adapt_noisy(S, m, adapt_args(tab[c], c), thr2);
+  }
+  if (!stay) cnt[px] = c | kRetired;
+}
+
+// The compaction of the active pixels into the ascending list, in three kernels and without an
+// atomic: (1) every block counts its active pixels from its waves' ballots, (2) one block turns the
+// counts into exclusive offsets (counts[nblk] = the total), (3) every active pixel goes to its
+// block's offset + the waves before it + its rank among its wave's active lanes.
+__device__ __forceinline__ uint32_t ballot_rank(u64 b) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+}
+
+__global__ void __launch_bounds__(kBlock)
+film_adapt_count_kernel(const uint32_t* cnt, size_t npix, uint32_t* counts) {
+  __shared__ uint32_t s_w[kBlock / 64];
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool active = px < npix && !(cnt[px] & kRetired);
+  const u64 b = __ballot(active);
+  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ void __launch_bounds__(kBlock)
+film_adapt_scan_kernel(uint32_t* counts, uint32_t nblk) {
+  __shared__ uint32_t s_t[kBlock];
+  const uint32_t per = (nblk + kBlock - 1) / kBlock;  // a thread's run of consecutive blocks
+  const uint32_t b0 = min(threadIdx.x * per, nblk), b1 = min(b0 + per, nblk);
+  uint32_t sum = 0;
+  for (uint32_t i = b0; i < b1; ++i) sum += counts[i];
+  s_t[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t run = 0;
+    for (uint32_t i = 0; i < (uint32_t)kBlock; ++i) {
+      const uint32_t t = s_t[i];
+      s_t[i] = run;
+      run += t;
+    }
+    counts[nblk] = run;
+  }
+  __syncthreads();
+  uint32_t run = s_t[threadIdx.x];
+  for (uint32_t i = b0; i < b1; ++i) {
+    const uint32_t t = counts[i];
+    counts[i] = run;
+    run += t;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+film_adapt_scatter_kernel(const uint32_t* cnt, size_t npix, const uint32_t* offs, uint32_t* list) {
+  __shared__ uint32_t s_w[kBlock / 64];
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool active = px < npix && !(cnt[px] & kRetired);
+  const u64 b = __ballot(active);
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) s_w[wave] = (uint32_t)__popcll(b);
+  __syncthreads();
+  uint32_t at = offs[blockIdx.x];
+  for (uint32_t w = 0; w < wave; ++w) at += s_w[w];
+  if (active) list[at + ballot_rank(b)] = (uint32_t)px;  // at + rank < the total <= npix
+}
+
+// f->list = the active pixels ascending, *n_out their number. Waits on the stream.
+spt_status adaptive_rebuild_list(spt_film* f, hipStream_t stream, int64_t* n_out) {
+  const size_t npix = f->n / 3;
+  const unsigned nblk = tail_blocks(npix);
+  hipLaunchKernelGGL(film_adapt_count_kernel, dim3(nblk), dim3(kBlock), 0, stream,
+                     (const uint32_t*)f->cnt, npix, f->scan);
+  FILM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(film_adapt_scan_kernel, dim3(1), dim3(kBlock), 0, stream, f->scan, (uint32_t)nblk);
+  FILM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(film_adapt_scatter_kernel, dim3(nblk), dim3(kBlock), 0, stream,
+                     (const uint32_t*)f->cnt, npix, (const uint32_t*)f->scan, f->list);
+  FILM_HIP(hipGetLastError());
+  uint32_t total = 0;
+  FILM_HIP(hipMemcpyAsync(&total, f->scan + nblk, sizeof total, hipMemcpyDeviceToHost, stream));
+  FILM_HIP(hipStreamSynchronize(stream));
+  *n_out = (int64_t)total;
+  return SPT_OK;
+}
+
+// While nothing has retired the passes leave the counts plane alone (every count is the front):
+// write it before anything reads it.
+void adaptive_sync_counts(const spt_film* f, hipStream_t stream) {
+  if (!f->adaptive || f->any_retired || f->n == 0 || f->cnt_front == f->batches_done) return;
+  (void)hipMemsetD32Async((hipDeviceptr_t)f->cnt, (int)f->batches_done, f->n / 3, stream);
+  f->cnt_front = f->batches_done;
+}
+
+spt_status adaptive_resolve(const spt_film* f, float* rgb_dev, const u64* stats, hipStream_t stream) {
+  adaptive_sync_counts(f, stream);
+  hipLaunchKernelGGL(film_adapt_resolve_kernel, dim3(tail_blocks(f->n / 3)), dim3(kBlock), 0, stream,
+                     (const u64*)f->sums, (const uint32_t*)f->cnt, (const AdaptRow*)f->table, rgb_dev,
+                     f->n / 3, stats);
+  FILM_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+spt_status adaptive_noise_map(const spt_film* f, float* se_dev, hipStream_t stream) {
+  adaptive_sync_counts(f, stream);
+  hipLaunchKernelGGL(film_adapt_map_kernel, dim3(tail_blocks(f->n)), dim3(kBlock), 0, stream,
+                     (const u64*)f->sums, (const ulonglong2*)f->m2, (const uint32_t*)f->cnt,
+                     (const AdaptRow*)f->table, se_dev, f->n);
+  FILM_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+spt_status adaptive_noise_summary(spt_film* f, spt_noise_summary* out, hipStream_t stream) {
+  NoisePartial total{};
+  if (f->n) {
+    FILM_HIP(hipSetDevice(f->device));
+    adaptive_sync_counts(f, stream);
+    double* parts = (double*)f->partials;
+    NoisePartial* total_dev = (NoisePartial*)(parts + 5 * (size_t)f->n_partials);
+    hipLaunchKernelGGL(film_adapt_partials_kernel, dim3(f->n_partials), dim3(kBlock), 0, stream,
+                       (const u64*)f->sums, (const ulonglong2*)f->m2, (const uint32_t*)f->cnt,
+                       (const AdaptRow*)f->table, f->n / 3, parts);
+    FILM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(film_noise_total_kernel, dim3(1), dim3(kBlock), 0, stream, (const double*)parts,
+                       (uint32_t)f->n_partials, total_dev);
+    FILM_HIP(hipGetLastError());
+    FILM_HIP(hipMemcpyAsync(&total, total_dev, sizeof total, hipMemcpyDeviceToHost, stream));
+  }
+  FILM_HIP(hipStreamSynchronize(stream));
+  noise_finish(total, f->n / 3, f->batches_done, out);
+  return SPT_OK;
+}
+
+// The host statements' arguments: *n = the film's elements, tab = the table for noise->batch.
+spt_status adaptive_host_args(const uint32_t* counts, const spt_film_info* info,
+                              const spt_film_noise_info* noise, size_t* n, AdaptRow** tab) {
+  if (!info || !noise) return fail(SPT_ERR_INVALID_ARG, "null info");
+  if (info->width <= 0 || info->rows < 0 || info->spp_total <= 0)
+    return fail(SPT_ERR_INVALID_ARG, "bad film info");
+  if (!noise->enabled || noise->batch < 1 || info->spp_total % noise->batch != 0 ||
+      info->spp_total / noise->batch > kAdaptMaxBatches)
+    return fail(SPT_ERR_INVALID_ARG, "not an adaptive film's batch");
+  *n = 3ull * (size_t)info->rows * (size_t)info->width;
+  if (*n && !counts) return fail(SPT_ERR_INVALID_ARG, "null counts");
+  const int32_t b_max = info->spp_total / noise->batch;
+  for (size_t p = 0; p < *n / 3; ++p)
+    if ((counts[p] & kCntMask) > (uint32_t)b_max)
+      return fail(SPT_ERR_INVALID_ARG, "a count above spp_total / batch");
+  *tab = (AdaptRow*)std::malloc(sizeof(AdaptRow) * (size_t)(b_max + 1));
+  if (!*tab) return fail(SPT_ERR_OOM, "table alloc");
+  for (int32_t B = 0; B <= b_max; ++B) (*tab)[B] = adapt_row(info->spp_total, noise->batch, B);
+  return SPT_OK;
+}
+
+}  // namespace
+
+spt_status spt_film_accumulate_listed(spt_film* f, spt_context* c, const unsigned long long* accum,
+                                      const unsigned long long* slots, float* rgb_dev, uint32_t npix,
+                                      uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
+                                      const unsigned long long* stats, int32_t s_count, void* stream) {
+  if (!f->adaptive || !f->any_retired || (int64_t)npix != f->n_active)
+    return fail(SPT_ERR_INVALID_ARG, "the launch is not over the film's active list");
+  hipLaunchKernelGGL(film_accumulate_listed_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                     (hipStream_t)stream, accum, slots, f->sums, (ulonglong2*)f->m2, f->cnt,
+                     (const uint32_t*)f->list, npix, n_chunks, scr_k, scr_q, stats);
+  FILM_HIP(hipGetLastError());
+  f->samples_done += s_count;
+  f->batches_done += 1;
+  f->last_pass_samples = (int64_t)npix * s_count;
+  f->samples_total += f->last_pass_samples;
+  if (f->last_ctx && f->last_ctx != c) spt_context_forget_film(f->last_ctx, f);
+  f->last_ctx = c;
+  if (rgb_dev) return adaptive_resolve(f, rgb_dev, stats, (hipStream_t)stream);
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_enable(spt_film* f) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "adaptive sampling needs a noise film");
+  if (f->adaptive) return fail(SPT_ERR_INVALID_ARG, "the film is adaptive already");
+  if (f->samples_done != 0 || f->batches_done != 0)
+    return fail(SPT_ERR_INVALID_ARG, "adaptive sampling is enabled on an empty film only");
+  const int32_t b_max = f->spp_total / f->batch;
+  if (b_max > kAdaptMaxBatches)
+    return fail(SPT_ERR_INVALID_ARG, "adaptive sampling takes at most 4096 batches: raise batch");
+  AdaptRow* h = (AdaptRow*)std::malloc(sizeof(AdaptRow) * (size_t)(b_max + 1));
+  if (!h) return fail(SPT_ERR_OOM, "table alloc");
+  for (int32_t B = 0; B <= b_max; ++B) h[B] = adapt_row(f->spp_total, f->batch, B);
+  if (f->n) {
+    const size_t npix = f->n / 3;
+    const size_t tab_bytes = sizeof(AdaptRow) * (size_t)(b_max + 1);
+    uint32_t *cnt = nullptr, *list = nullptr, *scan = nullptr;
+    void* tab = nullptr;
+    hipError_t e = hipSetDevice(f->device);
+    if (e == hipSuccess) e = hipMalloc(&cnt, npix * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&list, npix * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&scan, ((size_t)tail_blocks(npix) + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&tab, tab_bytes);
+    if (e == hipSuccess) e = hipMemset(cnt, 0, npix * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(tab, h, tab_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      if (cnt) (void)hipFree(cnt);
+      if (list) (void)hipFree(list);
+      if (scan) (void)hipFree(scan);
+      if (tab) (void)hipFree(tab);
+      std::free(h);
+      return fail(SPT_ERR_OOM, std::string("adaptive planes alloc: ") + hipGetErrorString(e));
+    }
+    f->cnt = cnt;
+    f->list = list;
+    f->scan = scan;
+    f->table = tab;
+  }
+  f->h_table = h;
+  f->b_max = b_max;
+  f->adaptive = true;
+  f->any_retired = false;
+  f->cnt_front = 0;
+  f->n_active = (int64_t)(f->n / 3);
+  f->samples_total = 0;
+  f->last_pass_samples = 0;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_info_get(const spt_film* f, spt_film_adaptive_info* out) {
+  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  out->enabled = f->adaptive ? 1 : 0;
+  out->reserved = 0;
+  out->front = f->adaptive ? f->batches_done : 0;
+  out->n_active = f->adaptive ? f->n_active : 0;
+  out->samples_total = f->adaptive ? f->samples_total : 0;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_select(spt_film* f, double se_threshold,
+                                               const uint8_t* keep_dev, int64_t* n_active,
+                                               void* stream_v) {
+  if (!f || !n_active) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (!f->adaptive) return fail(SPT_ERR_INVALID_ARG, "not an adaptive film");
+  if (se_threshold != se_threshold) return fail(SPT_ERR_INVALID_ARG, "the threshold is NaN");
+  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (f->n == 0) {
+    *n_active = 0;
+    return SPT_OK;
+  }
+  FILM_HIP(hipSetDevice(f->device));
+  adaptive_sync_counts(f, stream);
+  const size_t npix = f->n / 3;
+  const int all = se_threshold < 0.0;
+  const double thr2 = se_threshold * se_threshold;  // once, in double
+  if (keep_dev || !all) {
+    hipLaunchKernelGGL(film_adapt_mark_kernel, dim3(tail_blocks(npix)), dim3(kBlock), 0, stream,
+                       (const u64*)f->sums, (const ulonglong2*)f->m2, f->cnt,
+                       (const AdaptRow*)f->table, keep_dev, npix, thr2, all);
+    FILM_HIP(hipGetLastError());
+  }
+  int64_t n = 0;
+  const spt_status st = adaptive_rebuild_list(f, stream, &n);
+  if (st != SPT_OK) return st;
+  f->n_active = n;
+  if ((size_t)n != npix) f->any_retired = true;
+  *n_active = n;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_download(const spt_film* f, uint32_t* host_counts,
+                                                 void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->adaptive) return fail(SPT_ERR_INVALID_ARG, "not an adaptive film");
+  if (f->n == 0) return SPT_OK;
+  if (!host_counts) return fail(SPT_ERR_INVALID_ARG, "null output");
+  FILM_HIP(hipSetDevice(f->device));
+  adaptive_sync_counts(f, (hipStream_t)stream);
+  FILM_HIP(hipMemcpyAsync(host_counts, f->cnt, f->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          (hipStream_t)stream));
+  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_upload(spt_film* f, const uint32_t* host_counts,
+                                               void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->adaptive) return fail(SPT_ERR_INVALID_ARG, "not an adaptive film");
+  if (f->n == 0) return SPT_OK;
+  if (!host_counts) return fail(SPT_ERR_INVALID_ARG, "null input");
+  const size_t npix = f->n / 3;
+  // the invariant: the active pixels share one count, the front; a retired one holds 2 .. front
+  int64_t front = -1, top = 0, total = 0;
+  size_t retired = 0;
+  for (size_t p = 0; p < npix; ++p) {
+    const int64_t B = host_counts[p] & kCntMask;
+    if (B > f->b_max) return fail(SPT_ERR_INVALID_ARG, "a count above spp_total / batch");
+    total += B;
+    top = B > top ? B : top;
+    if (host_counts[p] & kRetired) {
+      ++retired;
+    } else if (front < 0) {
+      front = B;
+    } else if (B != front) {
+      return fail(SPT_ERR_INVALID_ARG, "the active pixels do not share one count");
+    }
+  }
+  if (front < 0) front = top;
+  if (top > front) return fail(SPT_ERR_INVALID_ARG, "a retired pixel holds more batches than the front");
+  FILM_HIP(hipSetDevice(f->device));
+  FILM_HIP(hipMemcpyAsync(f->cnt, host_counts, npix * sizeof(uint32_t), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  f->batches_done = front;
+  f->samples_done = front * (int64_t)f->batch;
+  f->cnt_front = front;
+  f->any_retired = retired != 0;
+  f->n_active = (int64_t)(npix - retired);
+  f->samples_total = total * (int64_t)f->batch;  // what the counts imply
+  f->last_pass_samples = 0;
+  if (f->any_retired) {
+    int64_t n = 0;
+    const spt_status st = adaptive_rebuild_list(f, (hipStream_t)stream, &n);
+    if (st != SPT_OK) return st;
+    f->n_active = n;
+  }
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_resolve_host(const uint64_t* sums, const uint32_t* counts,
+                                                     const spt_film_info* info,
+                                                     const spt_film_noise_info* noise, float* rgb_out) {
+  size_t n = 0;
+  AdaptRow* tab = nullptr;
+  if (info && info->rows > 0 && info->width > 0 && (!sums || !rgb_out))
+    return fail(SPT_ERR_INVALID_ARG, "null sums/output");
+  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
+  if (st != SPT_OK) return st;
+  for (size_t e = 0; e < n; ++e) {
+    const AdaptRow& t = tab[counts[e / 3] & kCntMask];
+    rgb_out[e] = film_resolve1((u64)sums[e], t.r, t.full);
+  }
+  std::free(tab);
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_noise_map_host(const uint64_t* sums, const uint64_t* m2,
+                                                       const uint32_t* counts,
+                                                       const spt_film_info* info,
+                                                       const spt_film_noise_info* noise,
+                                                       float* se_out) {
+  size_t n = 0;
+  AdaptRow* tab = nullptr;
+  if (info && info->rows > 0 && info->width > 0 && (!sums || !m2 || !se_out))
+    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
+  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
+  if (st != SPT_OK) return st;
+  for (size_t e = 0; e < n; ++e) {
+    const uint32_t B = counts[e / 3] & kCntMask;
+    const NoiseArgs A = adapt_args(tab[B], B);
+    ulonglong2 m;
+    m.x = m2[2 * e];
+    m.y = m2[2 * e + 1];
+    bool c;
+    se_out[e] = (float)(std::sqrt(noise_d((u64)sums[e], m, A, &c)) * A.k);
+  }
+  std::free(tab);
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_noise_summary_host(const uint64_t* sums, const uint64_t* m2,
+                                                           const uint32_t* counts,
+                                                           const spt_film_info* info,
+                                                           const spt_film_noise_info* noise,
+                                                           spt_noise_summary* out) {
+  size_t n = 0;
+  AdaptRow* tab = nullptr;
+  if (!out || (info && info->rows > 0 && info->width > 0 && (!sums || !m2)))
+    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
+  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
+  if (st != SPT_OK) return st;
+  NoisePartial t{};
+  for (size_t e = 0; e < n; ++e) {
+    const uint32_t B = counts[e / 3] & kCntMask;
+    const NoiseArgs A = adapt_args(tab[B], B);
+    ulonglong2 m;
+    m.x = m2[2 * e];
+    m.y = m2[2 * e + 1];
+    bool c;
+    const double d = noise_d((u64)sums[e], m, A, &c);
+    t.s[e % 3] += d * A.k2;
+    t.se_max = std::fmax(t.se_max, (float)(std::sqrt(d) * A.k));
+    t.clamped += c ? 1u : 0u;
+  }
+  std::free(tab);
+  noise_finish(t, n / 3, noise->batches_done, out);
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_adaptive_select_host(const uint64_t* sums, const uint64_t* m2,
+                                                    const uint32_t* counts, const spt_film_info* info,
+                                                    const spt_film_noise_info* noise,
+                                                    double se_threshold, const uint8_t* keep,
+                                                    uint32_t* counts_out, uint32_t* list_out,
+                                                    int64_t* n_active) {
+  size_t n = 0;
+  AdaptRow* tab = nullptr;
+  if (!n_active) return fail(SPT_ERR_INVALID_ARG, "null n_active");
+  if (se_threshold != se_threshold) return fail(SPT_ERR_INVALID_ARG, "the threshold is NaN");
+  if (noise && noise->batches_done < 2)
+    return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
+  if (info && info->rows > 0 && info->width > 0 && (!sums || !m2 || !counts_out || !list_out))
+    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
+  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
+  if (st != SPT_OK) return st;
+  const bool all = se_threshold < 0.0;
+  const double thr2 = se_threshold * se_threshold;
+  int64_t na = 0;
+  for (size_t px = 0; px < n / 3; ++px) {
+    uint32_t c = counts[px];
+    if (!(c & kRetired)) {
+      bool stay = keep ? keep[px] != 0 : true;
+      if (stay && !all) {
+        ulonglong2 m[3];
+        u64 S[3];
+        for (int ch = 0; ch < 3; ++ch) {
+          S[ch] = (u64)sums[3 * px + ch];
+          m[ch].x = m2[2 * (3 * px + ch)];
+          m[ch].y = m2[2 * (3 * px + ch) + 1];
+        }
+        stay = adapt_noisy(S, m, adapt_args(tab[c], c), thr2);
+      }
+      if (stay)
+        list_out[na++] = (uint32_t)px;
+      else
+        c |= kRetired;
+    }
+    counts_out[px] = c;
+  }
+  std::free(tab);
+  *n_active = na;
   return SPT_OK;
 }

@@ -206,6 +206,10 @@ struct KParams {  // in device memory, read through a laundered constant-space p
   unsigned long long* slots;  // [n_units][3] one owner store per unit, unit order (unit slots)
   uint32_t* queue;            // [0] = next unit
   unsigned long long* stats;  // [8]
+  // A launch over a pixel list (an adaptive film's pass, spt_film.hip): local pixel lp of the launch
+  // is the real local pixel pix_list[lp] (ascending, row-tile shard order), n_local_pix = the list's
+  // length. nullptr: the launch's pixels are the shard's, as ever. Read in pixel_terms() only.
+  const uint32_t* pix_list;
 };
 
 }  // namespace spt

@@ -42,7 +42,8 @@ spt_status plan_launch(int n_cu, int variant_bpc, int kv, const spt_params* p, i
 
 // ---- spt_kernel.hip (stream: a hipStream_t; errors are left to the caller's hipGetLastError)
 int render_kernel_occupancy(int kv);  // resident blocks per CU of variant kv; <= 0: query failed
-void launch_render_kernel(int kv, int grid, const KParams* kp_dev, void* stream);
+// listed: the variant over KParams::pix_list (kp_dev->pix_list must be set)
+void launch_render_kernel(int kv, int grid, const KParams* kp_dev, void* stream, bool listed = false);
 void launch_finalize_slots(const unsigned long long* accum, const unsigned long long* slots,
                            float* rgb, uint32_t npix, uint32_t n_chunks, uint32_t scr_k,
                            uint32_t scr_q, const unsigned long long* stats, void* stream);
