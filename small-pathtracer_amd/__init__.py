@@ -23,6 +23,7 @@ from __future__ import annotations
 import atexit
 import ctypes
 import os
+from contextlib import contextmanager as _contextmanager
 from typing import Iterable, Sequence
 
 import numpy as np
@@ -305,7 +306,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
 KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_variants.h", "csrc/spt_kparams.h", "csrc/spt_launch.h",
                   "csrc/spt_dispatch.cpp", "csrc/spt_context.cpp",
                   "csrc/spt_device.h", "csrc/spt_cornell.h", "csrc/spt_diag.h", "csrc/Makefile", "../include/spt.h", "../include/spt_flops.h", "csrc/spt_film.hip",
-                  "csrc/spt_film.h")
+                  "csrc/spt_film.h", "csrc/spt_film_math.h", "csrc/spt_film_host.cpp")
 
 
 def kernel_sources_sha16() -> str:
@@ -666,8 +667,8 @@ def film_noise_map_host(sums: np.ndarray, m2: np.ndarray, width: int, rows: int,
                         samples_done: int, batch: int, batches_done: int) -> np.ndarray:
     """spt_film_noise_map_host(): the CPU statement of the error map (no device). m2: rows * width
     * 3 pairs (lo, hi) of uint64. -> (rows, width, 3) float32 standard errors."""
-    a, m, info, noise = _noise_host_args(sums, m2, width, rows, spp_total, samples_done, batch,
-                                         batches_done)
+    a, m, _, info, noise = _film_host_args(sums, m2, None, width, rows, spp_total, samples_done, batch,
+                                           batches_done)
     out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
     _check(load_library().spt_film_noise_map_host(a.ctypes.data, m.ctypes.data, ctypes.byref(info),
                                                   ctypes.byref(noise), out.ctypes.data))
@@ -678,8 +679,8 @@ def film_noise_summary_host(sums: np.ndarray, m2: np.ndarray, width: int, rows: 
                             samples_done: int, batch: int, batches_done: int) -> dict:
     """spt_film_noise_summary_host(): the CPU statement of the image figures -> {"rmse": [r, g, b],
     "rmse_all", "se_max", "clamped", "batches_done"}."""
-    a, m, info, noise = _noise_host_args(sums, m2, width, rows, spp_total, samples_done, batch,
-                                         batches_done)
+    a, m, _, info, noise = _film_host_args(sums, m2, None, width, rows, spp_total, samples_done, batch,
+                                           batches_done)
     out = spt_noise_summary()
     _check(load_library().spt_film_noise_summary_host(a.ctypes.data, m.ctypes.data,
                                                       ctypes.byref(info), ctypes.byref(noise),
@@ -687,33 +688,26 @@ def film_noise_summary_host(sums: np.ndarray, m2: np.ndarray, width: int, rows: 
     return out.as_dict()
 
 
-def _noise_host_args(sums, m2, width, rows, spp_total, samples_done, batch, batches_done):
-    a = np.ascontiguousarray(sums, dtype=np.uint64)
-    m = np.ascontiguousarray(m2, dtype=np.uint64)
-    info = spt_film_info(int(width), int(rows), int(spp_total), int(samples_done))
-    noise = spt_film_noise_info(1, int(batch), int(batches_done))
-    n = 3 * max(info.rows, 0) * max(info.width, 0)
-    if a.size != n or m.size != 2 * n:
-        raise SptError(1, "sums / m2 do not have rows * width * 3 elements / pairs")
-    return a, m, info, noise
-
-
-def _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, front):
+def _film_host_args(sums, m2, counts, width, rows, spp_total, samples_done, batch, batches_done):
+    """The host statements' arguments: contiguous arrays of the film's sizes (m2 / counts: None where
+    the statement takes none), the film info and the noise info."""
     a = np.ascontiguousarray(sums, dtype=np.uint64)
     m = None if m2 is None else np.ascontiguousarray(m2, dtype=np.uint64)
-    c = np.ascontiguousarray(counts, dtype=np.uint32)
-    info = spt_film_info(int(width), int(rows), int(spp_total), int(front) * int(batch))
-    noise = spt_film_noise_info(1, int(batch), int(front))
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    info = spt_film_info(int(width), int(rows), int(spp_total), int(samples_done))
+    noise = spt_film_noise_info(1, int(batch), int(batches_done))
     npix = max(info.rows, 0) * max(info.width, 0)
-    if a.size != 3 * npix or c.size != npix or (m is not None and m.size != 6 * npix):
-        raise SptError(1, "sums / m2 / counts do not have the film's elements")
+    if a.size != 3 * npix or (m is not None and m.size != 6 * npix) or \
+            (c is not None and c.size != npix):
+        raise SptError(1, "sums / m2 do not have rows * width * 3 elements / pairs" if c is None else
+                       "sums / m2 / counts do not have the film's elements")
     return a, m, c, info, noise
 
 
 def film_adaptive_resolve_host(sums, counts, width: int, rows: int, spp_total: int,
                                batch: int) -> np.ndarray:
     """spt_film_adaptive_resolve_host(): the resolve with every pixel's own count (no device)."""
-    a, _, c, info, noise = _adaptive_host_args(sums, None, counts, width, rows, spp_total, batch, 0)
+    a, _, c, info, noise = _film_host_args(sums, None, counts, width, rows, spp_total, 0, batch, 0)
     out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
     _check(load_library().spt_film_adaptive_resolve_host(a.ctypes.data, c.ctypes.data,
                                                          ctypes.byref(info), ctypes.byref(noise),
@@ -724,7 +718,7 @@ def film_adaptive_resolve_host(sums, counts, width: int, rows: int, spp_total: i
 def film_adaptive_noise_map_host(sums, m2, counts, width: int, rows: int, spp_total: int,
                                  batch: int) -> np.ndarray:
     """spt_film_adaptive_noise_map_host(): the error map with every pixel's own count."""
-    a, m, c, info, noise = _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, 0)
+    a, m, c, info, noise = _film_host_args(sums, m2, counts, width, rows, spp_total, 0, batch, 0)
     out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
     _check(load_library().spt_film_adaptive_noise_map_host(a.ctypes.data, m.ctypes.data, c.ctypes.data,
                                                            ctypes.byref(info), ctypes.byref(noise),
@@ -736,7 +730,8 @@ def film_adaptive_noise_summary_host(sums, m2, counts, width: int, rows: int, sp
                                      batch: int, front: int) -> dict:
     """spt_film_adaptive_noise_summary_host(): the image figures (the mean over all pixels), each
     pixel with its own count; batches_done reports `front`."""
-    a, m, c, info, noise = _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, front)
+    a, m, c, info, noise = _film_host_args(sums, m2, counts, width, rows, spp_total,
+                                           int(front) * int(batch), batch, front)
     out = spt_noise_summary()
     _check(load_library().spt_film_adaptive_noise_summary_host(a.ctypes.data, m.ctypes.data,
                                                                c.ctypes.data, ctypes.byref(info),
@@ -748,7 +743,8 @@ def film_adaptive_select_host(sums, m2, counts, width: int, rows: int, spp_total
                               front: int, threshold: float, keep=None):
     """spt_film_adaptive_select_host(): -> (the new counts plane (rows, width) uint32, the new active
     list ascending). keep: rows * width bytes or None."""
-    a, m, c, info, noise = _adaptive_host_args(sums, m2, counts, width, rows, spp_total, batch, front)
+    a, m, c, info, noise = _film_host_args(sums, m2, counts, width, rows, spp_total,
+                                           int(front) * int(batch), batch, front)
     k = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
     if k is not None and k.size != c.size:
         raise SptError(1, "keep does not have rows * width bytes")
@@ -860,22 +856,35 @@ class Film:
                                               int(count), ctypes.c_void_p(rgb_dev_ptr or None),
                                               ctypes.c_void_p(stream_ptr or None)))
 
+    def _float_plane(self, call, dev_ptr: int, stream_ptr: int):
+        """A "device float plane" call (rows * width * 3 floats). With dev_ptr: enqueued into that
+        buffer. Without: into a buffer of this call's own, returned on the host as (rows, width, 3)."""
+        if dev_ptr:
+            _check(call(self._f, ctypes.c_void_p(dev_ptr), ctypes.c_void_p(stream_ptr or None)))
+            return None
+        import torch
+        with torch.cuda.device(self.device):
+            buf = _film_buffer(self)
+            _check(call(self._f, ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(stream_ptr or None)))
+        return _film_image(self, buf)
+
+    def _download(self, call, per_pixel: tuple, dtype, stream_ptr: int) -> np.ndarray:
+        i = self.info()
+        out = np.zeros((i["rows"], i["width"]) + per_pixel, dtype=dtype)
+        _check(call(self._f, out.ctypes.data, ctypes.c_void_p(stream_ptr or None)))
+        return out
+
+    def _upload(self, call, plane, per_pixel: int, dtype, mismatch: str, stream_ptr: int, *state):
+        i = self.info()
+        a = np.ascontiguousarray(plane, dtype=dtype)
+        if a.size != i["rows"] * i["width"] * per_pixel:
+            raise SptError(1, mismatch)
+        _check(call(self._f, a.ctypes.data, *state, ctypes.c_void_p(stream_ptr or None)))
+
     def resolve(self, rgb_dev_ptr: int = 0, stream_ptr: int = 0):
         """Film -> float image. With rgb_dev_ptr: enqueued into that device buffer. Without: into a
         buffer of this call's own, returned on the host as (rows, width, 3) float32."""
-        if rgb_dev_ptr:
-            _check(self.lib.spt_film_resolve(self._f, ctypes.c_void_p(rgb_dev_ptr),
-                                             ctypes.c_void_p(stream_ptr or None)))
-            return None
-        import torch
-        i = self.info()
-        with torch.cuda.device(self.device):
-            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
-                              device=f"cuda:{self.device}")
-            _check(self.lib.spt_film_resolve(self._f, ctypes.c_void_p(buf.data_ptr()),
-                                             ctypes.c_void_p(stream_ptr or None)))
-            torch.cuda.synchronize(self.device)
-        return buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+        return self._float_plane(self.lib.spt_film_resolve, rgb_dev_ptr, stream_ptr)
 
     def merge(self, other: "Film", stream_ptr: int = 0):
         """self += other (equal width, rows, spp_total; one device)."""
@@ -883,20 +892,12 @@ class Film:
 
     def to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
         """The sums on the host: (rows, width, 3) uint64."""
-        i = self.info()
-        out = np.zeros((i["rows"], i["width"], 3), dtype=np.uint64)
-        _check(self.lib.spt_film_download(self._f, out.ctypes.data,
-                                          ctypes.c_void_p(stream_ptr or None)))
-        return out
+        return self._download(self.lib.spt_film_download, (3,), np.uint64, stream_ptr)
 
     def from_numpy(self, sums: np.ndarray, samples_done: int, stream_ptr: int = 0):
         """Replace the sums (rows * width * 3 uint64) and samples_done: resume from a checkpoint."""
-        i = self.info()
-        a = np.ascontiguousarray(sums, dtype=np.uint64)
-        if a.size != i["rows"] * i["width"] * 3:
-            raise SptError(1, "sums do not have rows * width * 3 elements")
-        _check(self.lib.spt_film_upload(self._f, a.ctypes.data, int(samples_done),
-                                        ctypes.c_void_p(stream_ptr or None)))
+        self._upload(self.lib.spt_film_upload, sums, 3, np.uint64,
+                     "sums do not have rows * width * 3 elements", stream_ptr, int(samples_done))
 
     def save(self, path: str):
         if self.adaptive_info()["enabled"]:
@@ -923,37 +924,17 @@ class Film:
 
     def noise_to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
         """The moment plane on the host: (rows, width, 3, 2) uint64, [..., 0] = lo, [..., 1] = hi."""
-        i = self.info()
-        out = np.zeros((i["rows"], i["width"], 3, 2), dtype=np.uint64)
-        _check(self.lib.spt_film_noise_download(self._f, out.ctypes.data,
-                                                ctypes.c_void_p(stream_ptr or None)))
-        return out
+        return self._download(self.lib.spt_film_noise_download, (3, 2), np.uint64, stream_ptr)
 
     def noise_from_numpy(self, m2: np.ndarray, batches_done: int, stream_ptr: int = 0):
         """Replace the moment plane and batches_done (beside from_numpy: a checkpoint's other half)."""
-        i = self.info()
-        a = np.ascontiguousarray(m2, dtype=np.uint64)
-        if a.size != i["rows"] * i["width"] * 6:
-            raise SptError(1, "m2 does not have rows * width * 3 pairs")
-        _check(self.lib.spt_film_noise_upload(self._f, a.ctypes.data, int(batches_done),
-                                              ctypes.c_void_p(stream_ptr or None)))
+        self._upload(self.lib.spt_film_noise_upload, m2, 6, np.uint64,
+                     "m2 does not have rows * width * 3 pairs", stream_ptr, int(batches_done))
 
     def noise_map(self, se_dev_ptr: int = 0, stream_ptr: int = 0):
         """The standard error of every resolved value. With se_dev_ptr: enqueued into that device
         buffer (rows * width * 3 floats). Without: returned on the host as (rows, width, 3) float32."""
-        if se_dev_ptr:
-            _check(self.lib.spt_film_noise_map(self._f, ctypes.c_void_p(se_dev_ptr),
-                                               ctypes.c_void_p(stream_ptr or None)))
-            return None
-        import torch
-        i = self.info()
-        with torch.cuda.device(self.device):
-            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
-                              device=f"cuda:{self.device}")
-            _check(self.lib.spt_film_noise_map(self._f, ctypes.c_void_p(buf.data_ptr()),
-                                               ctypes.c_void_p(stream_ptr or None)))
-            torch.cuda.synchronize(self.device)
-        return buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+        return self._float_plane(self.lib.spt_film_noise_map, se_dev_ptr, stream_ptr)
 
     def noise_summary(self, stream_ptr: int = 0) -> dict:
         """spt_film_noise_summary(): {"rmse": [r, g, b], "rmse_all", "se_max", "clamped",
@@ -962,7 +943,6 @@ class Film:
         _check(self.lib.spt_film_noise_summary(self._f, ctypes.byref(out),
                                                ctypes.c_void_p(stream_ptr or None)))
         return out.as_dict()
-
 
     # ---- the adaptive film (spt_film_adaptive_*) ----
     def enable_adaptive(self):
@@ -999,21 +979,47 @@ class Film:
 
     def counts_to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
         """The counts plane on the host: (rows, width) uint32 (COUNT_MASK, COUNT_RETIRED)."""
-        i = self.info()
-        out = np.zeros((i["rows"], i["width"]), dtype=np.uint32)
-        _check(self.lib.spt_film_adaptive_download(self._f, out.ctypes.data,
-                                                   ctypes.c_void_p(stream_ptr or None)))
-        return out
+        return self._download(self.lib.spt_film_adaptive_download, (), np.uint32, stream_ptr)
 
     def counts_from_numpy(self, counts: np.ndarray, stream_ptr: int = 0):
         """Replace the counts plane (the last of a checkpoint's three uploads): rebuilds the active
         list and sets the front."""
-        i = self.info()
-        a = np.ascontiguousarray(counts, dtype=np.uint32)
-        if a.size != i["rows"] * i["width"]:
-            raise SptError(1, "counts do not have rows * width elements")
-        _check(self.lib.spt_film_adaptive_upload(self._f, a.ctypes.data,
-                                                 ctypes.c_void_p(stream_ptr or None)))
+        self._upload(self.lib.spt_film_adaptive_upload, counts, 1, np.uint32,
+                     "counts do not have rows * width elements", stream_ptr)
+
+
+def _film_buffer(film: Film):
+    """A device float buffer for the film's resolved image (at least one element)."""
+    import torch
+    i = film.info()
+    return torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
+                       device=f"cuda:{film.device}")
+
+
+def _film_image(film: Film, buf) -> np.ndarray:
+    """Wait for the device and return the film's image in `buf` on the host: (rows, width, 3)."""
+    import torch
+    i = film.info()
+    torch.cuda.synchronize(film.device)
+    return buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+
+
+@_contextmanager
+def _film_session(params: spt_params, batch: int = 0, adaptive: bool = False):
+    """-> (renderer, film, image buffer, stream) on params.device, the film a noise film of `batch`
+    (and adaptive) when asked; the renderer and the film are closed on the way out."""
+    import torch
+    r, film = Renderer(params.device), Film(params, params.device)
+    try:
+        if batch:
+            film.enable_noise(batch)
+        if adaptive:
+            film.enable_adaptive()
+        with torch.cuda.device(params.device):
+            yield r, film, _film_buffer(film), torch.cuda.current_stream().cuda_stream
+    finally:
+        film.close()
+        r.close()
 
 
 def render_progressive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, passes,
@@ -1022,32 +1028,47 @@ def render_progressive(prims: Sequence[spt_prim], cam: Camera, params: spt_param
     near-equal windows (sample_windows) or a list of (base, count). Returns the host image, equal to
     render()'s bit for bit when the windows cover [0, spp) once; return_stats: also the integer
     spt_stats fields summed over the passes (kernel_ms summed too)."""
-    import torch
     windows = sample_windows(params.spp, passes) if isinstance(passes, int) else list(passes)
-    dev = params.device
-    r, film = Renderer(dev), Film(params, dev)
-    try:
-        i = film.info()
-        total = dict.fromkeys(STAT_KEYS + ["shadow_proven"], 0)
-        total["kernel_ms"] = 0.0
-        with torch.cuda.device(dev):
-            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
-                              device=f"cuda:{dev}")
-            stream = torch.cuda.current_stream().cuda_stream
-            for k, (base, count) in enumerate(windows):
-                last = k == len(windows) - 1
-                film.render(r, prims, cam, params, base, count, buf.data_ptr() if last else 0, stream)
-                st = r.stats()
-                for key in total:
-                    total[key] += st[key]
-            if not windows:
-                film.resolve(buf.data_ptr(), stream)
-            torch.cuda.synchronize(dev)
-        out = buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
-    finally:
-        film.close()
-        r.close()
+    total = dict.fromkeys(STAT_KEYS + ["shadow_proven"], 0)
+    total["kernel_ms"] = 0.0
+    with _film_session(params) as (r, film, buf, stream):
+        for k, (base, count) in enumerate(windows):
+            last = k == len(windows) - 1
+            film.render(r, prims, cam, params, base, count, buf.data_ptr() if last else 0, stream)
+            st = r.stats()
+            for key in total:
+                total[key] += st[key]
+        if not windows:
+            film.resolve(buf.data_ptr(), stream)
+        out = _film_image(film, buf)
     return (out, total) if return_stats else out
+
+
+def _render_to_target(who: str, prims, cam, params, target_rmse, batch, min_batches, select, info_of):
+    """render_until and render_adaptive: batches in index order until max(rmse) <= target_rmse.
+    select(film, stream) -> the pixels still active (None: every batch renders every pixel);
+    info_of(film, stream) -> the caller's info, to which "rmse" is added."""
+    spp = int(params.spp)
+    if batch is None:
+        if spp % 8:
+            raise ValueError(f"{who}: spp is no multiple of 8, give batch")
+        batch = spp // 8
+    need = max(2, int(min_batches))
+    rmse = None
+    with _film_session(params, batch, select is not None) as (r, film, buf, stream):
+        for k in range(spp // batch):
+            film.render(r, prims, cam, params, k * batch, batch, 0, stream)
+            r.stats()  # a pass that hit the runaway guard raises here
+            if k + 1 >= need:
+                rmse = film.noise_summary(stream)["rmse"]
+                if max(rmse) <= target_rmse:
+                    break
+                if select is not None and k + 1 < spp // batch and select(film, stream) == 0:
+                    break
+        film.resolve(buf.data_ptr(), stream)
+        out = _film_image(film, buf)
+        info = dict(info_of(film, stream), rmse=rmse)
+    return out, info
 
 
 def render_until(prims: Sequence[spt_prim], cam: Camera, params: spt_params, target_rmse: float,
@@ -1058,38 +1079,10 @@ def render_until(prims: Sequence[spt_prim], cam: Camera, params: spt_params, tar
     image (a preview when it stopped early; render()'s image bit for bit when every batch was
     rendered); return_info: also {"samples_done", "batches_done", "rmse"}.
     batch defaults to spp / 8 when 8 divides spp and must be given otherwise."""
-    import torch
-    spp = int(params.spp)
-    if batch is None:
-        if spp % 8:
-            raise ValueError("render_until: spp is no multiple of 8, give batch")
-        batch = spp // 8
-    dev = params.device
-    r, film = Renderer(dev), Film(params, dev)
-    try:
-        film.enable_noise(batch)
-        i = film.info()
-        need = max(2, int(min_batches))
-        rmse = None
-        with torch.cuda.device(dev):
-            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
-                              device=f"cuda:{dev}")
-            stream = torch.cuda.current_stream().cuda_stream
-            for k in range(spp // batch):
-                film.render(r, prims, cam, params, k * batch, batch, 0, stream)
-                r.stats()  # a pass that hit the runaway guard raises here
-                if k + 1 >= need:
-                    rmse = film.noise_summary(stream)["rmse"]
-                    if max(rmse) <= target_rmse:
-                        break
-            film.resolve(buf.data_ptr(), stream)
-            torch.cuda.synchronize(dev)
-        out = buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
-        info = {"samples_done": film.info()["samples_done"],
-                "batches_done": film.noise_info()["batches_done"], "rmse": rmse}
-    finally:
-        film.close()
-        r.close()
+    out, info = _render_to_target(
+        "render_until", prims, cam, params, target_rmse, batch, min_batches, None,
+        lambda film, stream: {"samples_done": film.info()["samples_done"],
+                              "batches_done": film.noise_info()["batches_done"]})
     return (out, info) if return_info else out
 
 
@@ -1103,43 +1096,14 @@ def render_adaptive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, 
     the rest, until nothing is active or every batch of params.spp is in. A pixel retired on its own
     estimate may look converged by luck: min_batches is the guard. Returns the
     resolved image; return_info: also {"front", "samples_total", "rmse", "counts"}."""
-    import torch
-    spp = int(params.spp)
-    if batch is None:
-        if spp % 8:
-            raise ValueError("render_adaptive: spp is no multiple of 8, give batch")
-        batch = spp // 8
-    dev = params.device
-    r, film = Renderer(dev), Film(params, dev)
-    try:
-        film.enable_noise(batch)
-        film.enable_adaptive()
-        i = film.info()
-        need = max(2, int(min_batches))
-        rmse = None
-        with torch.cuda.device(dev):
-            buf = torch.empty(max(1, i["rows"] * i["width"] * 3), dtype=torch.float32,
-                              device=f"cuda:{dev}")
-            stream = torch.cuda.current_stream().cuda_stream
-            for k in range(spp // batch):
-                film.render(r, prims, cam, params, k * batch, batch, 0, stream)
-                r.stats()  # a pass that hit the runaway guard raises here
-                if k + 1 >= need:
-                    rmse = film.noise_summary(stream)["rmse"]
-                    if max(rmse) <= target_rmse:
-                        break
-                    if k + 1 < spp // batch and \
-                            film.adaptive_select(threshold_scale * target_rmse, None, stream) == 0:
-                        break
-            film.resolve(buf.data_ptr(), stream)
-            torch.cuda.synchronize(dev)
-        out = buf[: i["rows"] * i["width"] * 3].cpu().numpy().reshape(i["rows"], i["width"], 3)
+    def info_of(film, stream):
         a = film.adaptive_info()
-        info = {"front": a["front"], "samples_total": a["samples_total"], "rmse": rmse,
+        return {"front": a["front"], "samples_total": a["samples_total"],
                 "counts": film.counts_to_numpy(stream)}
-    finally:
-        film.close()
-        r.close()
+
+    out, info = _render_to_target(
+        "render_adaptive", prims, cam, params, target_rmse, batch, min_batches,
+        lambda film, stream: film.adaptive_select(threshold_scale * target_rmse, None, stream), info_of)
     return (out, info) if return_info else out
 
 

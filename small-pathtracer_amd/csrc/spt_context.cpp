@@ -270,13 +270,9 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   SPT_HIP(hipGetLastError());
   SPT_HIP(hipEventRecord(c->ev1, stream));
   const uint32_t np = (uint32_t)K.n_local_pix;
-  if (film && list_dev) {  // scatter the list's sums into the film's pixels
-    st = spt_film_accumulate_listed(film, c, c->accum, c->slots, rgb_dev, np, plan.n_chunks, K.scr_k,
-                                    K.scr_q, c->stats, s_count, stream);
-    if (st != SPT_OK) return st;
-  } else if (film) {  // add the window's sums to the film (and resolve it into rgb_dev, if given)
-    st = spt_film_accumulate(film, c, c->accum, c->slots, rgb_dev, np, plan.n_chunks, K.scr_k,
-                             K.scr_q, c->stats, s_count, stream);
+  if (film) {  // add the window's sums to the film (and resolve it into rgb_dev, if given)
+    const spt_film_launch launch{c->accum, c->slots, np, plan.n_chunks, K.scr_k, K.scr_q, c->stats};
+    st = spt_film_accumulate(film, c, launch, rgb_dev, s_count, stream);
     if (st != SPT_OK) return st;
   } else {
     launch_finalize_slots(c->accum, c->slots, rgb_dev, np, plan.n_chunks, K.scr_k, K.scr_q, c->stats,

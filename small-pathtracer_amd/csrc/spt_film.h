@@ -31,12 +31,11 @@ struct spt_film {
   uint32_t* cnt = nullptr;             // [rows * width]: low 31 bits batches held, bit 31 retired
   // While nothing has retired every count is the front, so the unlisted passes do not touch the
   // plane; cnt_front is the front it was last written for (-1: never) and whoever reads the plane
-  // brings it up first (adaptive_sync_counts).
-  mutable int64_t cnt_front = -1;
+  // brings it up first (sync_counts).
+  int64_t cnt_front = -1;
   uint32_t* list = nullptr;            // [n_active] active pixels ascending (valid once any_retired)
   uint32_t* scan = nullptr;            // the compaction's per-block counts, then the total
-  void* table = nullptr;               // AdaptRow[b_max + 1], device; h_table the host's copy
-  void* h_table = nullptr;
+  void* table = nullptr;               // NoiseArgs[b_max + 1] (spt_film_math.h), device
   int32_t b_max = 0;                   // spp_total / batch
   int64_t n_active = 0, samples_total = 0;
   int64_t last_pass_samples = 0;       // what the last pass added to samples_total (rollback)
@@ -51,18 +50,21 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
                              const uint32_t* list_dev = nullptr, uint32_t n_list = 0);
 void spt_context_forget_film(spt_context* c, const spt_film* film);
 
-// spt_film.hip: enqueue the accumulate pass behind a render launch of `c` (the launch's stolen-range
-// sums, unit slots and statistics words) and count its s_count samples into the film.
-spt_status spt_film_accumulate(spt_film* film, spt_context* c, const unsigned long long* accum,
-                               const unsigned long long* slots, float* rgb_dev, uint32_t npix,
-                               uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
-                               const unsigned long long* stats, int32_t s_count, void* stream);
-// The same behind a launch over the film's active list (npix = the list's length): virtual pixel v
-// adds into pixel list[v], and that pixel's count goes up by one.
-spt_status spt_film_accumulate_listed(spt_film* film, spt_context* c, const unsigned long long* accum,
-                                      const unsigned long long* slots, float* rgb_dev, uint32_t npix,
-                                      uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
-                                      const unsigned long long* stats, int32_t s_count, void* stream);
+// What the film takes from a render launch: the stolen-range sums, the unit slots and their layout,
+// the statistics words (word 0: the runaway guard).
+struct spt_film_launch {
+  const unsigned long long* accum;
+  const unsigned long long* slots;
+  uint32_t npix, n_chunks, scr_k, scr_q;
+  const unsigned long long* stats;
+};
+
+// spt_film.hip: enqueue the accumulate pass behind a render launch of `c` and count its s_count
+// samples into the film. Once a pixel of an adaptive film has retired the launch is over the film's
+// active list (npix = its length): virtual pixel v adds into pixel list[v], and that pixel's count
+// goes up by one.
+spt_status spt_film_accumulate(spt_film* film, spt_context* c, const spt_film_launch& launch,
+                               float* rgb_dev, int32_t s_count, void* stream);
 // The pass of `c` hit the runaway guard and added nothing: samples_done goes back by s_count.
 void spt_film_rollback(spt_film* film, const spt_context* c, int32_t s_count);
 void spt_film_forget_context(spt_film* film, const spt_context* c);

@@ -19,29 +19,26 @@
 //
 // All three stream: one pass over the sums at 16 bytes per access (two sums, or four floats),
 // 256 threads per block, no reuse -- HBM-bound. -ffp-contract=off (the Makefile) keeps the preview two
-// separate multiplies, as spt_film_resolve_host and a numpy restatement compute it.
+// separate multiplies, as spt_film_resolve_host and a numpy restatement compute it. The per-element
+// arithmetic is spt_film_math.h's, shared with the CPU statements (spt_film_host.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
+#include <new>
 #include <string>
+#include <vector>
 
 #include "spt_film.h"
+#include "spt_film_math.h"
 
 int spt_shard_row_count(const spt_params* p);  // spt_host.cpp
 
 namespace {
 
-using u64 = unsigned long long;
+using namespace spt_film_math;
 constexpr int kBlock = 256;
 constexpr uint32_t kQuadLanes = 192;  // 3 * kBlock sums per block / 4 per lane
-
-__host__ __device__ __forceinline__ float film_resolve1(u64 v, float r, int full) {
-  float f = (float)v * 0x1p-31f;
-  if (!full) f = f * r;
-  return f > 1.0f ? 1.0f : f;
-}
 
 // Every 16-byte load of a thread has landed before any of its registers is used. Measured on
 // gfx950: the first form of the resolve kernel (tail loop and unaligned-store branch in the same
@@ -53,22 +50,6 @@ __host__ __device__ __forceinline__ float film_resolve1(u64 v, float r, int full
 // HBM-bound, the wait costs nothing measurable. tests/test_gpu_film.py checks them at that size.
 __device__ __forceinline__ void loads_landed(ulonglong2& a, ulonglong2& b) {
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y)::"memory");
-}
-
-// 64 x 64 -> high 64 bits.
-__host__ __device__ __forceinline__ u64 mulhi64(u64 a, u64 b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __umul64hi(a, b);
-#else
-  return (u64)(((unsigned __int128)a * b) >> 64);
-#endif
-}
-
-// m += p^2 in 128 bits, m = (lo, hi). Exact: p <= batch * 2^31 (the moment plane's bound, spt.h).
-__host__ __device__ __forceinline__ void m2_add_square(ulonglong2& m, u64 p) {
-  const u64 lo = p * p, nl = m.x + lo;
-  m.y += mulhi64(p, p) + (u64)(nl < lo);
-  m.x = nl;
 }
 
 // The same wait for one 16-byte load (an element of the moment plane).
@@ -283,45 +264,20 @@ film_merge_m2_kernel(ulonglong2* dst, const ulonglong2* src, size_t n) {
   }
 }
 
-// What the error map and the summary take from the host: B = batches_done, the factor k of spt.h
-// and its square (both rounded once, in double), the resolve's factor for the clamp rule.
-struct NoiseArgs {
-  u64 B;
-  double k, k2;
-  float r;
-  int full;
-};
-
-// One element: D = B * M2 - S^2 in 128 bits as a double, or 0 with *clamped set where the resolved
-// value is the clamp. se = (float)(sqrt(d) * k); the summary adds d * k2.
-__host__ __device__ __forceinline__ double noise_d(u64 S, ulonglong2 m, const NoiseArgs& A,
-                                                   bool* clamped) {
-  *clamped = film_resolve1(S, A.r, A.full) == 1.0f;
-  if (*clamped) return 0.0;
-  const u64 blo = A.B * m.x, bhi = A.B * m.y + mulhi64(A.B, m.x);
-  const u64 slo = S * S, shi = mulhi64(S, S);
-  const u64 lo = blo - slo, hi = bhi - shi - (u64)(blo < slo);
-  return (double)hi * 0x1p64 + (double)lo;
-}
-
+// The error map: one element per thread, its NoiseArgs from the count source (UniformCount: a noise
+// film's one, passed by value; PixelCount: the row of the pixel's own count, an adaptive film).
+template <class Counts>
 __global__ void __launch_bounds__(kBlock)
-film_noise_map_kernel(const u64* sums, const ulonglong2* m2, float* se, size_t n, NoiseArgs A) {
+film_noise_map_kernel(const u64* sums, const ulonglong2* m2, float* se, size_t n, Counts cs) {
   const size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x;
   if (e < n) {
     ulonglong2 m = m2[e];
     load_landed(m);
+    const NoiseArgs A = cs.at(e / 3);
     bool c;
-    se[e] = (float)(sqrt(noise_d(sums[e], m, A, &c)) * A.k);
+    se[e] = noise_se(noise_d(sums[e], m, A, &c), A);
   }
 }
-
-// The summary's partial sums: of a block (stage 1), of the image (stage 2).
-struct NoisePartial {
-  double s[3];  // per channel: sum of d * k2
-  float se_max;
-  uint32_t pad;
-  u64 clamped;
-};
 
 // p[0] = the block's 256 partials combined pairwise, in an order fixed by the thread index alone.
 __device__ __forceinline__ void noise_block_reduce(NoisePartial* p) {
@@ -342,9 +298,10 @@ __device__ __forceinline__ void noise_block_reduce(NoisePartial* p) {
 
 // Stage 1: one pixel per thread (three sums, three moments), one partial per block. The partials
 // are five planes of nb = gridDim.x 8-byte words (s[0], s[1], s[2], se_max as a double, clamped), so
-// that stage 2 reads them with 8-byte loads.
+// that stage 2 reads them with 8-byte loads. The pixel's NoiseArgs come from the count source.
+template <class Counts>
 __global__ void __launch_bounds__(kBlock)
-film_noise_partials_kernel(const u64* sums, const ulonglong2* m2, size_t npix, NoiseArgs A,
+film_noise_partials_kernel(const u64* sums, const ulonglong2* m2, size_t npix, Counts cs,
                            double* out) {
   __shared__ NoisePartial s_p[kBlock];
   const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
@@ -354,12 +311,13 @@ film_noise_partials_kernel(const u64* sums, const ulonglong2* m2, size_t npix, N
     loads_landed(m0, m1);
     load_landed(mm);
     const ulonglong2 m[3] = {m0, m1, mm};
+    const NoiseArgs A = cs.at(px);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       bool cl;
       const double d = noise_d(sums[3 * px + c], m[c], A, &cl);
       v.s[c] = d * A.k2;
-      v.se_max = fmaxf(v.se_max, (float)(sqrt(d) * A.k));
+      v.se_max = fmaxf(v.se_max, noise_se(d, A));
       v.clamped += cl ? 1u : 0u;
     }
   }
@@ -392,541 +350,16 @@ film_noise_total_kernel(const double* parts, uint32_t n, NoisePartial* total) {
   if (threadIdx.x == 0) *total = s_p[0];
 }
 
-spt_status fail(spt_status s, const std::string& msg) {
-  spt_set_last_error(msg);
-  return s;
-}
-#define FILM_HIP(call)                                                                  \
-  do {                                                                                  \
-    hipError_t e_ = (call);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                   \
-  } while (0)
-
-int tile_rows_of(const spt_params* p) { return p->tile_rows > 0 ? p->tile_rows : 8; }
-
-// The preview factor spp_total / samples_done, rounded once; *full = no factor at all.
-float resolve_factor(int32_t spp_total, int64_t done, int* full) {
-  *full = done == (int64_t)spp_total;
-  return done > 0 ? (float)((double)spp_total / (double)done) : 0.0f;
-}
-
-// The adaptive film's forms of the calls above them (defined in the last section).
-void adaptive_sync_counts(const spt_film* f, hipStream_t stream);
-spt_status adaptive_resolve(const spt_film* f, float* rgb_dev, const u64* stats, hipStream_t stream);
-spt_status adaptive_noise_map(const spt_film* f, float* se_dev, hipStream_t stream);
-spt_status adaptive_noise_summary(spt_film* f, spt_noise_summary* out, hipStream_t stream);
-
-unsigned quad_blocks(size_t n) { return (unsigned)(((n + 3) / 4 + kBlock - 1) / kBlock); }
-unsigned tail_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-}  // namespace
-
-extern "C" spt_status spt_film_create(int32_t device, const spt_params* p, spt_film** out) {
-  if (!p || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  if (p->width <= 0 || p->height <= 0 || p->spp <= 0)
-    return fail(SPT_ERR_INVALID_ARG, "width/height/spp must be positive");
-  if ((uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull)
-    return fail(SPT_ERR_INVALID_ARG, "image too large for 32-bit pixel counters");
-  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count || p->tile_rows < 0)
-    return fail(SPT_ERR_INVALID_ARG, "bad shard_index/shard_count/tile_rows");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail(SPT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= count) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
-  FILM_HIP(hipSetDevice(device));
-  spt_film* f = new spt_film();
-  f->device = device;
-  f->width = p->width;
-  f->height = p->height;
-  f->spp_total = p->spp;
-  f->tile_rows = tile_rows_of(p);
-  f->shard_index = p->shard_index;
-  f->shard_count = p->shard_count;
-  f->rows = spt_shard_row_count(p);
-  f->n = 3ull * (size_t)f->rows * (size_t)f->width;
-  if (f->n) {
-    hipError_t e = hipMalloc(&f->sums, f->n * sizeof(u64));
-    if (e == hipSuccess) e = hipMemset(f->sums, 0, f->n * sizeof(u64));
-    if (e != hipSuccess) {
-      if (f->sums) (void)hipFree(f->sums);
-      delete f;
-      return fail(SPT_ERR_OOM, std::string("film alloc: ") + hipGetErrorString(e));
-    }
-  }
-  *out = f;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_destroy(spt_film* f) {
-  if (!f) return SPT_OK;
-  if (f->last_ctx) spt_context_forget_film(f->last_ctx, f);
-  if (f->sums || f->m2 || f->partials) (void)hipSetDevice(f->device);
-  if (f->sums) (void)hipFree(f->sums);
-  if (f->m2) (void)hipFree(f->m2);
-  if (f->partials) (void)hipFree(f->partials);
-  if (f->cnt) (void)hipFree(f->cnt);
-  if (f->list) (void)hipFree(f->list);
-  if (f->scan) (void)hipFree(f->scan);
-  if (f->table) (void)hipFree(f->table);
-  std::free(f->h_table);
-  delete f;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_info_get(const spt_film* f, spt_film_info* out) {
-  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  out->width = f->width;
-  out->rows = f->rows;
-  out->spp_total = f->spp_total;
-  out->samples_done = f->samples_done;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_clear(spt_film* f, void* stream) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (f->n) {
-    FILM_HIP(hipSetDevice(f->device));
-    FILM_HIP(hipMemsetAsync(f->sums, 0, f->n * sizeof(u64), (hipStream_t)stream));
-    if (f->m2) FILM_HIP(hipMemsetAsync(f->m2, 0, f->n * sizeof(ulonglong2), (hipStream_t)stream));
-    if (f->cnt) FILM_HIP(hipMemsetAsync(f->cnt, 0, f->n / 3 * sizeof(uint32_t), (hipStream_t)stream));
-  }
-  if (f->adaptive) {  // every pixel active again at count 0; the list is rebuilt by the next select
-    f->any_retired = false;
-    f->cnt_front = 0;
-    f->n_active = (int64_t)(f->n / 3);
-    f->samples_total = 0;
-    f->last_pass_samples = 0;
-  }
-  f->samples_done = 0;
-  f->batches_done = 0;
-  return SPT_OK;
-}
-
-spt_status spt_film_accumulate(spt_film* f, spt_context* c, const unsigned long long* accum,
-                               const unsigned long long* slots, float* rgb_dev, uint32_t npix,
-                               uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
-                               const unsigned long long* stats, int32_t s_count, void* stream) {
-  if (f->n != 3ull * npix) return fail(SPT_ERR_INVALID_ARG, "the film does not have the launch's pixels");
-  int full = 0;
-  const float r = resolve_factor(f->spp_total, f->samples_done + s_count, &full);
-  if (f->batch)  // a noise film: the same pass also squares its sums into the moment plane
-    hipLaunchKernelGGL(film_accumulate_kernel<true>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock),
-                       0, (hipStream_t)stream, accum, slots, f->sums, rgb_dev, npix, n_chunks, scr_k,
-                       scr_q, stats, r, full, (int)aligned16(rgb_dev), (ulonglong2*)f->m2);
-  else
-    hipLaunchKernelGGL(film_accumulate_kernel<false>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock),
-                       0, (hipStream_t)stream, accum, slots, f->sums, rgb_dev, npix, n_chunks, scr_k,
-                       scr_q, stats, r, full, (int)aligned16(rgb_dev), (ulonglong2*)nullptr);
-  FILM_HIP(hipGetLastError());
-  f->samples_done += s_count;
-  if (f->batch) f->batches_done += 1;
-  if (f->adaptive) {  // nothing has retired: every pixel took the batch, the counts stay implied
-    f->last_pass_samples = (int64_t)npix * s_count;
-    f->samples_total += f->last_pass_samples;
-  }
-  if (f->last_ctx && f->last_ctx != c) spt_context_forget_film(f->last_ctx, f);
-  f->last_ctx = c;
-  return SPT_OK;
-}
-
-void spt_film_rollback(spt_film* f, const spt_context* c, int32_t s_count) {
-  if (f->last_ctx == c && f->samples_done >= s_count) {
-    f->samples_done -= s_count;
-    if (f->batch && f->batches_done > 0) f->batches_done -= 1;  // a pass of a noise film is one batch
-    if (f->adaptive) {  // the front goes back; the guarded pass incremented no count
-      f->samples_total -= f->last_pass_samples;
-      f->last_pass_samples = 0;
-      if (!f->any_retired && f->cnt_front > f->batches_done) f->cnt_front = -1;
-    }
-  }
-}
-
-void spt_film_forget_context(spt_film* f, const spt_context* c) {
-  if (f->last_ctx == c) f->last_ctx = nullptr;
-}
-
-extern "C" spt_status spt_film_render_async(spt_context* ctx, spt_film* f, const spt_prim* prims,
-                                            int32_t n_prims, const spt_camera* cam,
-                                            const spt_params* p, int32_t sample_base,
-                                            int32_t sample_count, float* rgb_dev, void* stream) {
-  if (!ctx || !f || !p) return fail(SPT_ERR_INVALID_ARG, "null context/film/params");
-  if (p->width != f->width || p->height != f->height || p->spp != f->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "width/height/spp differ from the film's");
-  if (p->tile_rows < 0 || tile_rows_of(p) != f->tile_rows || p->shard_index != f->shard_index ||
-      p->shard_count != f->shard_count)
-    return fail(SPT_ERR_INVALID_ARG, "the shard fields differ from the film's");
-  if (sample_base < 0 || sample_count < 1 || (int64_t)sample_base + sample_count > f->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
-  if (f->samples_done + sample_count > f->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "the film would hold more than spp samples");
-  if (f->batch && (sample_count != f->batch || sample_base % f->batch != 0))
-    return fail(SPT_ERR_INVALID_ARG, "a noise film takes whole batches: sample_count == batch, sample_base % batch == 0");
-  if (f->adaptive) {
-    if ((int64_t)sample_base != f->batches_done * f->batch)
-      return fail(SPT_ERR_INVALID_ARG, "an adaptive film takes the next window only: sample_base == front * batch");
-    if (f->n && f->n_active == 0)
-      return fail(SPT_ERR_INVALID_ARG, "the adaptive film has no active pixel");
-  }
-  // once a pixel has retired the pass runs over the active list; until then it is a noise film's
-  const bool listed = f->adaptive && f->any_retired;
-  const spt_status st = spt_render_window(ctx, prims, n_prims, cam, p, sample_base, sample_count,
-                                          rgb_dev, f, stream, listed ? f->list : nullptr,
-                                          listed ? (uint32_t)f->n_active : 0u);
-  if (st != SPT_OK) return st;
-  if (f->rows == 0) {  // a shard without rows: nothing to add, still counted
-    f->samples_done += sample_count;
-    if (f->batch) f->batches_done += 1;
-  }
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_resolve(const spt_film* f, float* rgb_dev, void* stream) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (f->n == 0) return SPT_OK;
-  if (!rgb_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
-  FILM_HIP(hipSetDevice(f->device));
-  if (f->adaptive) return adaptive_resolve(f, rgb_dev, nullptr, (hipStream_t)stream);
-  int full = 0;
-  const float r = resolve_factor(f->spp_total, f->samples_done, &full);
-  const size_t body = aligned16(rgb_dev) ? f->n & ~(size_t)3 : 0;  // sums the 16-byte kernel takes
-  if (body) {
-    hipLaunchKernelGGL(film_resolve_kernel, dim3(quad_blocks(body)), dim3(kBlock), 0,
-                       (hipStream_t)stream, (const u64*)f->sums, rgb_dev, body, r, full);
-    FILM_HIP(hipGetLastError());
-  }
-  if (body < f->n) {
-    hipLaunchKernelGGL(film_resolve_tail_kernel, dim3(tail_blocks(f->n - body)), dim3(kBlock), 0,
-                       (hipStream_t)stream, (const u64*)f->sums, rgb_dev, body, f->n, r, full);
-    FILM_HIP(hipGetLastError());
-  }
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_merge(spt_film* dst, const spt_film* src, void* stream) {
-  if (!dst || !src || dst == src) return fail(SPT_ERR_INVALID_ARG, "merge needs two films");
-  if (dst->width != src->width || dst->rows != src->rows || dst->spp_total != src->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "films of unequal width/rows/spp");
-  if (dst->device != src->device)
-    return fail(SPT_ERR_INVALID_ARG, "films on different devices: download one and upload it beside the other");
-  if (dst->samples_done + src->samples_done > dst->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "the merged film would hold more than spp samples");
-  if (dst->adaptive || src->adaptive)
-    return fail(SPT_ERR_INVALID_ARG, "an adaptive film cannot be merged: its pixels hold different sample ranges");
-  if (dst->batch != src->batch)
-    return fail(SPT_ERR_INVALID_ARG, "merge needs two plain films or two noise films of equal batch");
-  if (dst->n) {
-    FILM_HIP(hipSetDevice(dst->device));
-    const size_t body = dst->n & ~(size_t)3;
-    if (body) {
-      hipLaunchKernelGGL(film_merge_kernel, dim3(quad_blocks(body)), dim3(kBlock), 0,
-                         (hipStream_t)stream, dst->sums, (const u64*)src->sums, body);
-      FILM_HIP(hipGetLastError());
-    }
-    if (body < dst->n) {
-      hipLaunchKernelGGL(film_merge_tail_kernel, dim3(tail_blocks(dst->n - body)), dim3(kBlock), 0,
-                         (hipStream_t)stream, dst->sums, (const u64*)src->sums, body, dst->n);
-      FILM_HIP(hipGetLastError());
-    }
-    if (dst->batch) {
-      hipLaunchKernelGGL(film_merge_m2_kernel, dim3(tail_blocks(dst->n)), dim3(kBlock), 0,
-                         (hipStream_t)stream, (ulonglong2*)dst->m2, (const ulonglong2*)src->m2, dst->n);
-      FILM_HIP(hipGetLastError());
-    }
-  }
-  dst->batches_done += src->batches_done;
-  dst->samples_done += src->samples_done;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_download(const spt_film* f, uint64_t* host_sums, void* stream) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (f->n == 0) return SPT_OK;
-  if (!host_sums) return fail(SPT_ERR_INVALID_ARG, "null output");
-  FILM_HIP(hipSetDevice(f->device));
-  FILM_HIP(hipMemcpyAsync(host_sums, f->sums, f->n * sizeof(u64), hipMemcpyDeviceToHost,
-                          (hipStream_t)stream));
-  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_upload(spt_film* f, const uint64_t* host_sums, int64_t samples_done,
-                                      void* stream) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (samples_done < 0 || samples_done > f->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "samples_done outside [0, spp]");
-  if (f->batch && samples_done % f->batch != 0)
-    return fail(SPT_ERR_INVALID_ARG, "a noise film holds whole batches: samples_done % batch != 0");
-  if (f->n) {
-    if (!host_sums) return fail(SPT_ERR_INVALID_ARG, "null input");
-    FILM_HIP(hipSetDevice(f->device));
-    FILM_HIP(hipMemcpyAsync(f->sums, host_sums, f->n * sizeof(u64), hipMemcpyHostToDevice,
-                            (hipStream_t)stream));
-    FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
-  }
-  f->samples_done = samples_done;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_resolve_host(const uint64_t* sums, const spt_film_info* info,
-                                            float* rgb_out) {
-  if (!info) return fail(SPT_ERR_INVALID_ARG, "null info");
-  if (info->width <= 0 || info->rows < 0 || info->spp_total <= 0 || info->samples_done < 0 ||
-      info->samples_done > info->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "bad film info");
-  const size_t n = 3ull * (size_t)info->rows * (size_t)info->width;
-  if (n == 0) return SPT_OK;
-  if (!sums || !rgb_out) return fail(SPT_ERR_INVALID_ARG, "null sums/output");
-  int full = 0;
-  const float r = resolve_factor(info->spp_total, info->samples_done, &full);
-  for (size_t k = 0; k < n; ++k) rgb_out[k] = film_resolve1((u64)sums[k], r, full);
-  return SPT_OK;
-}
-
-// ---- the noise film: moment plane, error map, image figures (include/spt.h SPT_HAS_FILM_NOISE) ----
-namespace {
-
-// The factor of the error map in double, rounded once: se = sqrt(d) * k. B >= 2.
-NoiseArgs noise_args(int32_t spp_total, int64_t samples_done, int32_t batch, int64_t B) {
-  NoiseArgs A;
-  A.B = (u64)B;
-  A.k = (double)spp_total / ((double)batch * 0x1p31 * (double)B * std::sqrt((double)(B - 1)));
-  A.k2 = A.k * A.k;
-  A.r = resolve_factor(spp_total, samples_done, &A.full);
-  return A;
-}
-
-void noise_finish(const NoisePartial& t, size_t npix, int64_t B, spt_noise_summary* out) {
-  const double n = npix ? (double)npix : 1.0;
-  for (int c = 0; c < 3; ++c) out->rmse[c] = std::sqrt(t.s[c] / n);
-  out->rmse_all = std::sqrt((t.s[0] + t.s[1] + t.s[2]) / (3.0 * n));
-  out->se_max = t.se_max;
-  out->clamped = t.clamped;
-  out->batches_done = B;
-}
-
-spt_status noise_host_args(const spt_film_info* info, const spt_film_noise_info* noise, size_t* n) {
-  if (!info || !noise) return fail(SPT_ERR_INVALID_ARG, "null info");
-  if (info->width <= 0 || info->rows < 0 || info->spp_total <= 0 || info->samples_done < 0 ||
-      info->samples_done > info->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "bad film info");
-  if (!noise->enabled || noise->batch < 1)
-    return fail(SPT_ERR_INVALID_ARG, "not a noise film");
-  if (noise->batches_done < 2)
-    return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
-  *n = 3ull * (size_t)info->rows * (size_t)info->width;
-  return SPT_OK;
-}
-
-}  // namespace
-
-extern "C" spt_status spt_film_noise_enable(spt_film* f, int32_t batch) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (f->batch) return fail(SPT_ERR_INVALID_ARG, "the film is a noise film already");
-  if (f->samples_done != 0) return fail(SPT_ERR_INVALID_ARG, "noise is enabled on an empty film only");
-  if (batch < 1 || f->spp_total % batch != 0 || f->spp_total / batch < 2)
-    return fail(SPT_ERR_INVALID_ARG, "batch must divide spp into at least two batches");
-  if (f->n) {
-    FILM_HIP(hipSetDevice(f->device));
-    const unsigned blocks = tail_blocks(f->n / 3);
-    unsigned long long* m2 = nullptr;
-    void* parts = nullptr;
-    hipError_t e = hipMalloc(&m2, f->n * sizeof(ulonglong2));
-    if (e == hipSuccess)  // five planes of 8-byte words, then the total
-      e = hipMalloc(&parts, 5 * (size_t)blocks * sizeof(double) + sizeof(NoisePartial));
-    if (e == hipSuccess) e = hipMemset(m2, 0, f->n * sizeof(ulonglong2));
-    if (e != hipSuccess) {
-      if (m2) (void)hipFree(m2);
-      if (parts) (void)hipFree(parts);
-      return fail(SPT_ERR_OOM, std::string("moment plane alloc: ") + hipGetErrorString(e));
-    }
-    f->m2 = m2;
-    f->partials = parts;
-    f->n_partials = blocks;
-  }
-  f->batch = batch;
-  f->batches_done = 0;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_noise_info_get(const spt_film* f, spt_film_noise_info* out) {
-  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  out->enabled = f->batch != 0;
-  out->batch = f->batch;
-  out->batches_done = f->batches_done;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_noise_download(const spt_film* f, uint64_t* host_m2, void* stream) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
-  if (f->n == 0) return SPT_OK;
-  if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null output");
-  FILM_HIP(hipSetDevice(f->device));
-  FILM_HIP(hipMemcpyAsync(host_m2, f->m2, f->n * sizeof(ulonglong2), hipMemcpyDeviceToHost,
-                          (hipStream_t)stream));
-  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_noise_upload(spt_film* f, const uint64_t* host_m2, int64_t batches_done,
-                                            void* stream) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
-  if (batches_done < 0 || batches_done > f->spp_total / f->batch)
-    return fail(SPT_ERR_INVALID_ARG, "batches_done outside [0, spp / batch]");
-  if (f->n) {
-    if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null input");
-    FILM_HIP(hipSetDevice(f->device));
-    FILM_HIP(hipMemcpyAsync(f->m2, host_m2, f->n * sizeof(ulonglong2), hipMemcpyHostToDevice,
-                            (hipStream_t)stream));
-    FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
-  }
-  f->batches_done = batches_done;
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_noise_map(const spt_film* f, float* se_dev, void* stream) {
-  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
-  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
-  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
-  if (f->n == 0) return SPT_OK;
-  if (!se_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
-  FILM_HIP(hipSetDevice(f->device));
-  if (f->adaptive) return adaptive_noise_map(f, se_dev, (hipStream_t)stream);
-  const NoiseArgs A = noise_args(f->spp_total, f->samples_done, f->batch, f->batches_done);
-  hipLaunchKernelGGL(film_noise_map_kernel, dim3(tail_blocks(f->n)), dim3(kBlock), 0,
-                     (hipStream_t)stream, (const u64*)f->sums, (const ulonglong2*)f->m2, se_dev, f->n, A);
-  FILM_HIP(hipGetLastError());
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_noise_summary(spt_film* f, spt_noise_summary* out, void* stream) {
-  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
-  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
-  if (f->adaptive) return adaptive_noise_summary(f, out, (hipStream_t)stream);
-  NoisePartial total{};
-  if (f->n) {
-    FILM_HIP(hipSetDevice(f->device));
-    const NoiseArgs A = noise_args(f->spp_total, f->samples_done, f->batch, f->batches_done);
-    double* parts = (double*)f->partials;
-    NoisePartial* total_dev = (NoisePartial*)(parts + 5 * (size_t)f->n_partials);
-    hipLaunchKernelGGL(film_noise_partials_kernel, dim3(f->n_partials), dim3(kBlock), 0,
-                       (hipStream_t)stream, (const u64*)f->sums, (const ulonglong2*)f->m2, f->n / 3, A,
-                       parts);
-    FILM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(film_noise_total_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream,
-                       (const double*)parts, (uint32_t)f->n_partials, total_dev);
-    FILM_HIP(hipGetLastError());
-    FILM_HIP(hipMemcpyAsync(&total, total_dev, sizeof total, hipMemcpyDeviceToHost,
-                            (hipStream_t)stream));
-  }
-  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
-  noise_finish(total, f->n / 3, f->batches_done, out);
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_noise_map_host(const uint64_t* sums, const uint64_t* m2,
-                                              const spt_film_info* info,
-                                              const spt_film_noise_info* noise, float* se_out) {
-  size_t n = 0;
-  const spt_status st = noise_host_args(info, noise, &n);
-  if (st != SPT_OK) return st;
-  if (n == 0) return SPT_OK;
-  if (!sums || !m2 || !se_out) return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const NoiseArgs A = noise_args(info->spp_total, info->samples_done, noise->batch, noise->batches_done);
-  for (size_t e = 0; e < n; ++e) {
-    ulonglong2 m;
-    m.x = m2[2 * e];
-    m.y = m2[2 * e + 1];
-    bool c;
-    se_out[e] = (float)(std::sqrt(noise_d((u64)sums[e], m, A, &c)) * A.k);
-  }
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_noise_summary_host(const uint64_t* sums, const uint64_t* m2,
-                                                  const spt_film_info* info,
-                                                  const spt_film_noise_info* noise,
-                                                  spt_noise_summary* out) {
-  size_t n = 0;
-  const spt_status st = noise_host_args(info, noise, &n);
-  if (st != SPT_OK) return st;
-  if (!out || (n && (!sums || !m2))) return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const NoiseArgs A = noise_args(info->spp_total, info->samples_done, noise->batch, noise->batches_done);
-  NoisePartial t{};
-  for (size_t e = 0; e < n; ++e) {
-    ulonglong2 m;
-    m.x = m2[2 * e];
-    m.y = m2[2 * e + 1];
-    bool c;
-    const double d = noise_d((u64)sums[e], m, A, &c);
-    t.s[e % 3] += d * A.k2;
-    t.se_max = std::fmax(t.se_max, (float)(std::sqrt(d) * A.k));
-    t.clamped += c ? 1u : 0u;
-  }
-  noise_finish(t, n / 3, noise->batches_done, out);
-  return SPT_OK;
-}
-
-// ---- the adaptive film: counts plane, listed accumulate, selection (spt.h SPT_HAS_FILM_ADAPTIVE) ----
-// New kernels throughout: the kernels above are launched by plain and noise films exactly as before.
-namespace {
-
-constexpr uint32_t kRetired = 0x80000000u, kCntMask = 0x7FFFFFFFu;
-constexpr int32_t kAdaptMaxBatches = 4096;
-
-// One row of the table, for a pixel that holds B batches: the resolve's factor and the error's.
-struct AdaptRow {
-  double k, k2;
-  float r;
-  int full;
-};
-
-// Computed once on the host in double; kernels and host statements read the same values.
-AdaptRow adapt_row(int32_t spp_total, int32_t batch, int64_t B) {
-  AdaptRow t{};
-  t.r = resolve_factor(spp_total, B * (int64_t)batch, &t.full);
-  if (B >= 2) {
-    const NoiseArgs A = noise_args(spp_total, B * (int64_t)batch, batch, B);
-    t.k = A.k;
-    t.k2 = A.k2;
-  }
-  return t;
-}
-
-__host__ __device__ __forceinline__ NoiseArgs adapt_args(const AdaptRow& t, uint32_t B) {
-  NoiseArgs A;
-  A.B = B;
-  A.k = t.k;
-  A.k2 = t.k2;
-  A.r = t.r;
-  A.full = t.full;
-  return A;
-}
-
-// Is some channel of the pixel above the threshold? d * k2 > thr2, no square root: the same IEEE
-// operations on the host and on the device (-ffp-contract=off).
-__host__ __device__ __forceinline__ bool adapt_noisy(const u64* S, const ulonglong2* m, const NoiseArgs& A,
-                                                     double thr2) {
-  bool noisy = false;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    bool cl;
-    const double d = noise_d(S[c], m[c], A, &cl);
-    noisy = noisy || d * A.k2 > thr2;
-  }
-  return noisy;
-}
+// ---- the adaptive film's kernels: listed accumulate, per-pixel resolve, selection ----
 
 // The pass over the active list: thread t sums the slots of unit-order virtual pixel t (as the
 // unlisted kernel's phase 1), v = its spread virtual pixel (the accumulator's index), g = list[v]
 // the film's pixel. A scatter: 8-byte accesses of the sums, one 16-byte load and store per moment
 // (straight-line, the full wait before any register is used), the pixel's count + 1. No two threads
 // share a g (the list holds every pixel once). A guarded launch adds nothing.
+// The slot sum is written out in both accumulate kernels: called as a shared inline function the loop
+// is rotated before it is inlined, and film_accumulate_kernel comes out with its blocks in another
+// order and other registers (HISTORY.md, round 15); its instructions are to stay the parent's.
 __global__ void __launch_bounds__(kBlock)
 film_accumulate_listed_kernel(const u64* __restrict__ accum, const u64* __restrict__ slots,
                               u64* __restrict__ film, ulonglong2* __restrict__ m2,
@@ -966,7 +399,7 @@ film_accumulate_listed_kernel(const u64* __restrict__ accum, const u64* __restri
 // the pass this resolve follows; a guarded pass leaves rgb all NaN, as the unlisted pass does.
 __global__ void __launch_bounds__(kBlock)
 film_adapt_resolve_kernel(const u64* __restrict__ sums, const uint32_t* __restrict__ cnt,
-                          const AdaptRow* __restrict__ tab, float* __restrict__ rgb, size_t npix,
+                          const NoiseArgs* __restrict__ tab, float* __restrict__ rgb, size_t npix,
                           const u64* __restrict__ stats) {
   const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
   if (p >= npix) return;
@@ -974,69 +407,17 @@ film_adapt_resolve_kernel(const u64* __restrict__ sums, const uint32_t* __restri
     rgb[3 * p] = rgb[3 * p + 1] = rgb[3 * p + 2] = __builtin_nanf("");
     return;
   }
-  const uint32_t B = cnt[p] & kCntMask;
-  const float r = tab[B].r;
-  const int full = tab[B].full;
-  rgb[3 * p] = film_resolve1(sums[3 * p], r, full);
-  rgb[3 * p + 1] = film_resolve1(sums[3 * p + 1], r, full);
-  rgb[3 * p + 2] = film_resolve1(sums[3 * p + 2], r, full);
-}
-
-// The error map with the pixel's own B: one element per thread, as film_noise_map_kernel.
-__global__ void __launch_bounds__(kBlock)
-film_adapt_map_kernel(const u64* sums, const ulonglong2* m2, const uint32_t* cnt, const AdaptRow* tab,
-                      float* se, size_t n) {
-  const size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e < n) {
-    ulonglong2 m = m2[e];
-    load_landed(m);
-    const uint32_t B = cnt[e / 3] & kCntMask;
-    const NoiseArgs A = adapt_args(tab[B], B);
-    bool c;
-    se[e] = (float)(sqrt(noise_d(sums[e], m, A, &c)) * A.k);
-  }
-}
-
-// The summary's stage 1 with the pixel's own B (stage 2 is film_noise_total_kernel).
-__global__ void __launch_bounds__(kBlock)
-film_adapt_partials_kernel(const u64* sums, const ulonglong2* m2, const uint32_t* cnt,
-                           const AdaptRow* tab, size_t npix, double* out) {
-  __shared__ NoisePartial s_p[kBlock];
-  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
-  NoisePartial v{};
-  if (px < npix) {
-    ulonglong2 m0 = m2[3 * px], m1 = m2[3 * px + 1], mm = m2[3 * px + 2];
-    loads_landed(m0, m1);
-    load_landed(mm);
-    const ulonglong2 m[3] = {m0, m1, mm};
-    const uint32_t B = cnt[px] & kCntMask;
-    const NoiseArgs A = adapt_args(tab[B], B);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      bool cl;
-      const double d = noise_d(sums[3 * px + c], m[c], A, &cl);
-      v.s[c] = d * A.k2;
-      v.se_max = fmaxf(v.se_max, (float)(sqrt(d) * A.k));
-      v.clamped += cl ? 1u : 0u;
-    }
-  }
-  s_p[threadIdx.x] = v;
-  noise_block_reduce(s_p);
-  if (threadIdx.x == 0) {
-    const size_t nb = gridDim.x;
-    out[blockIdx.x] = s_p[0].s[0];
-    out[nb + blockIdx.x] = s_p[0].s[1];
-    out[2 * nb + blockIdx.x] = s_p[0].s[2];
-    out[3 * nb + blockIdx.x] = (double)s_p[0].se_max;
-    ((u64*)out)[4 * nb + blockIdx.x] = s_p[0].clamped;
-  }
+  const NoiseArgs A = PixelCount{cnt, tab}.at(p);
+  rgb[3 * p] = film_resolve1(sums[3 * p], A.r, A.full);
+  rgb[3 * p + 1] = film_resolve1(sums[3 * p + 1], A.r, A.full);
+  rgb[3 * p + 2] = film_resolve1(sums[3 * p + 2], A.r, A.full);
 }
 
 // The selection's first step: an active pixel that the mask drops, or none of whose channels is above
 // the threshold, gets bit 31. One pixel per thread; the moments are loaded by every thread in range
 // (straight-line), used or not.
 __global__ void __launch_bounds__(kBlock)
-film_adapt_mark_kernel(const u64* sums, const ulonglong2* m2, uint32_t* cnt, const AdaptRow* tab,
+film_adapt_mark_kernel(const u64* sums, const ulonglong2* m2, uint32_t* cnt, const NoiseArgs* tab,
                        const uint8_t* keep, size_t npix, double thr2, int all) {
   const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
   if (px >= npix) return;
@@ -1049,7 +430,7 @@ film_adapt_mark_kernel(const u64* sums, const ulonglong2* m2, uint32_t* cnt, con
   if (stay && !all) {
     const ulonglong2 m[3] = {m0, m1, mm};
     const u64 S[3] = {sums[3 * px], sums[3 * px + 1], sums[3 * px + 2]};
-    stay = adapt_noisy(S, m, adapt_args(tab[c], c), thr2);
+    stay = adapt_noisy(S, m, PixelCount{cnt, tab}.row(c), thr2);
   }
   if (!stay) cnt[px] = c | kRetired;
 }
@@ -1114,8 +495,138 @@ film_adapt_scatter_kernel(const uint32_t* cnt, size_t npix, const uint32_t* offs
   if (active) list[at + ballot_rank(b)] = (uint32_t)px;  // at + rank < the total <= npix
 }
 
-// f->list = the active pixels ascending, *n_out their number. Waits on the stream.
-spt_status adaptive_rebuild_list(spt_film* f, hipStream_t stream, int64_t* n_out) {
+spt_status fail(spt_status s, const std::string& msg) {
+  spt_set_last_error(msg);
+  return s;
+}
+#define FILM_HIP(call)                                                                  \
+  do {                                                                                  \
+    hipError_t e_ = (call);                                                             \
+    if (e_ != hipSuccess)                                                               \
+      return fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                \
+                  std::string(#call) + ": " + hipGetErrorString(e_));                   \
+  } while (0)
+
+int tile_rows_of(const spt_params* p) { return p->tile_rows > 0 ? p->tile_rows : 8; }
+
+unsigned quad_blocks(size_t n) { return (unsigned)(((n + 3) / 4 + kBlock - 1) / kBlock); }
+unsigned tail_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// A device plane of `bytes` bytes, zeroed on request. *p stays null when the allocation fails.
+template <class T>
+hipError_t plane_alloc(T** p, size_t bytes, bool zero) {
+  hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess && zero) e = hipMemset(*p, 0, bytes);
+  return e;
+}
+
+// Free the planes of the film's layers named in `layers` (and forget them).
+enum : unsigned { kSumsPlane = 1, kNoisePlanes = 2, kAdaptPlanes = 4, kAllPlanes = 7 };
+void free_planes(spt_film* f, unsigned layers) {
+  auto drop = [](auto*& p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  };
+  if (layers & kSumsPlane) drop(f->sums);
+  if (layers & kNoisePlanes) drop(f->m2), drop(f->partials);
+  if (layers & kAdaptPlanes) drop(f->cnt), drop(f->list), drop(f->scan), drop(f->table);
+}
+
+// Copy a plane to or from the host and wait.
+spt_status plane_copy(const spt_film* f, void* dst, const void* src, size_t bytes, hipMemcpyKind kind,
+                      void* stream) {
+  FILM_HIP(hipSetDevice(f->device));
+  FILM_HIP(hipMemcpyAsync(dst, src, bytes, kind, (hipStream_t)stream));
+  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return SPT_OK;
+}
+
+// The 16-byte kernel over the `body` whole quads it may take, the one-sum kernel over [body, n).
+// quad(blocks) / tail(blocks) enqueue them.
+template <class Quad, class Tail>
+spt_status launch_quads_and_tail(size_t body, size_t n, Quad quad, Tail tail) {
+  if (body) {
+    quad(quad_blocks(body));
+    FILM_HIP(hipGetLastError());
+  }
+  if (body < n) {
+    tail(tail_blocks(n - body));
+    FILM_HIP(hipGetLastError());
+  }
+  return SPT_OK;
+}
+
+// Count a pass of s_count samples over npix pixels into the film (spt_film_rollback is the inverse).
+// c: the context that rendered it and may take it back; nullptr when nothing was launched.
+void count_pass(spt_film* f, spt_context* c, uint32_t npix, int32_t s_count) {
+  f->samples_done += s_count;
+  if (f->batch) f->batches_done += 1;  // a pass of a noise film is one batch
+  if (f->adaptive) {
+    f->last_pass_samples = (int64_t)npix * s_count;
+    f->samples_total += f->last_pass_samples;
+  }
+  if (!c) return;
+  if (f->last_ctx && f->last_ctx != c) spt_context_forget_film(f->last_ctx, f);
+  f->last_ctx = c;
+}
+
+// The adaptive film's count source. The public calls that only read a film take it const; bringing
+// the counts plane up to date writes the film's cnt_front, so those calls cast here, once.
+spt_film* counts_owner(const spt_film* f) { return const_cast<spt_film*>(f); }
+
+// While nothing has retired the passes leave the counts plane alone (every count is the front):
+// write it before anything reads it.
+void sync_counts(spt_film* f, hipStream_t stream) {
+  if (!f->adaptive || f->any_retired || f->n == 0 || f->cnt_front == f->batches_done) return;
+  (void)hipMemsetD32Async((hipDeviceptr_t)f->cnt, (int)f->batches_done, f->n / 3, stream);
+  f->cnt_front = f->batches_done;
+}
+
+PixelCount pixel_counts(spt_film* f, hipStream_t stream) {
+  sync_counts(f, stream);
+  return PixelCount{f->cnt, (const NoiseArgs*)f->table};
+}
+
+UniformCount uniform_count(const spt_film* f) {
+  return UniformCount{noise_args(f->spp_total, f->samples_done, f->batch, f->batches_done)};
+}
+
+// film -> float with every pixel's own factor. stats: the words of the pass it follows, or null.
+spt_status adaptive_resolve(spt_film* f, float* rgb_dev, const u64* stats, hipStream_t stream) {
+  const PixelCount cs = pixel_counts(f, stream);
+  hipLaunchKernelGGL(film_adapt_resolve_kernel, dim3(tail_blocks(f->n / 3)), dim3(kBlock), 0, stream,
+                     (const u64*)f->sums, cs.cnt, cs.tab, rgb_dev, f->n / 3, stats);
+  FILM_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+template <class Counts>
+spt_status noise_map_launch(const spt_film* f, const Counts& cs, float* se_dev, hipStream_t stream) {
+  hipLaunchKernelGGL(film_noise_map_kernel<Counts>, dim3(tail_blocks(f->n)), dim3(kBlock), 0, stream,
+                     (const u64*)f->sums, (const ulonglong2*)f->m2, se_dev, f->n, cs);
+  FILM_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+// The summary's two stages and the copy of the image's partial into *total (not waited for).
+template <class Counts>
+spt_status noise_summary_launch(const spt_film* f, const Counts& cs, NoisePartial* total,
+                                hipStream_t stream) {
+  double* parts = (double*)f->partials;
+  NoisePartial* total_dev = (NoisePartial*)(parts + 5 * (size_t)f->n_partials);
+  hipLaunchKernelGGL(film_noise_partials_kernel<Counts>, dim3(f->n_partials), dim3(kBlock), 0, stream,
+                     (const u64*)f->sums, (const ulonglong2*)f->m2, f->n / 3, cs, parts);
+  FILM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(film_noise_total_kernel, dim3(1), dim3(kBlock), 0, stream, (const double*)parts,
+                     (uint32_t)f->n_partials, total_dev);
+  FILM_HIP(hipGetLastError());
+  FILM_HIP(hipMemcpyAsync(total, total_dev, sizeof *total, hipMemcpyDeviceToHost, stream));
+  return SPT_OK;
+}
+
+// f->list = the active pixels ascending, f->n_active their number. Waits on the stream.
+spt_status rebuild_list(spt_film* f, hipStream_t stream) {
   const size_t npix = f->n / 3;
   const unsigned nblk = tail_blocks(npix);
   hipLaunchKernelGGL(film_adapt_count_kernel, dim3(nblk), dim3(kBlock), 0, stream,
@@ -1129,99 +640,340 @@ spt_status adaptive_rebuild_list(spt_film* f, hipStream_t stream, int64_t* n_out
   uint32_t total = 0;
   FILM_HIP(hipMemcpyAsync(&total, f->scan + nblk, sizeof total, hipMemcpyDeviceToHost, stream));
   FILM_HIP(hipStreamSynchronize(stream));
-  *n_out = (int64_t)total;
+  f->n_active = (int64_t)total;
   return SPT_OK;
 }
 
-// While nothing has retired the passes leave the counts plane alone (every count is the front):
-// write it before anything reads it.
-void adaptive_sync_counts(const spt_film* f, hipStream_t stream) {
-  if (!f->adaptive || f->any_retired || f->n == 0 || f->cnt_front == f->batches_done) return;
-  (void)hipMemsetD32Async((hipDeviceptr_t)f->cnt, (int)f->batches_done, f->n / 3, stream);
-  f->cnt_front = f->batches_done;
+// An adaptive film with every pixel active at count 0.
+void adaptive_reset(spt_film* f) {
+  f->any_retired = false;
+  f->cnt_front = 0;
+  f->n_active = (int64_t)(f->n / 3);
+  f->samples_total = 0;
+  f->last_pass_samples = 0;
 }
 
-spt_status adaptive_resolve(const spt_film* f, float* rgb_dev, const u64* stats, hipStream_t stream) {
-  adaptive_sync_counts(f, stream);
-  hipLaunchKernelGGL(film_adapt_resolve_kernel, dim3(tail_blocks(f->n / 3)), dim3(kBlock), 0, stream,
-                     (const u64*)f->sums, (const uint32_t*)f->cnt, (const AdaptRow*)f->table, rgb_dev,
-                     f->n / 3, stats);
+}  // namespace
+
+extern "C" spt_status spt_film_create(int32_t device, const spt_params* p, spt_film** out) {
+  if (!p || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (p->width <= 0 || p->height <= 0 || p->spp <= 0)
+    return fail(SPT_ERR_INVALID_ARG, "width/height/spp must be positive");
+  if ((uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull)
+    return fail(SPT_ERR_INVALID_ARG, "image too large for 32-bit pixel counters");
+  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count || p->tile_rows < 0)
+    return fail(SPT_ERR_INVALID_ARG, "bad shard_index/shard_count/tile_rows");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
+    return fail(SPT_ERR_NO_DEVICE, "no HIP device");
+  if (device < 0 || device >= count) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
+  FILM_HIP(hipSetDevice(device));
+  spt_film* f = new spt_film();
+  f->device = device;
+  f->width = p->width;
+  f->height = p->height;
+  f->spp_total = p->spp;
+  f->tile_rows = tile_rows_of(p);
+  f->shard_index = p->shard_index;
+  f->shard_count = p->shard_count;
+  f->rows = spt_shard_row_count(p);
+  f->n = 3ull * (size_t)f->rows * (size_t)f->width;
+  if (f->n) {
+    const hipError_t e = plane_alloc(&f->sums, f->n * sizeof(u64), true);
+    if (e != hipSuccess) {
+      free_planes(f, kAllPlanes);
+      delete f;
+      return fail(SPT_ERR_OOM, std::string("film alloc: ") + hipGetErrorString(e));
+    }
+  }
+  *out = f;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_destroy(spt_film* f) {
+  if (!f) return SPT_OK;
+  if (f->last_ctx) spt_context_forget_film(f->last_ctx, f);
+  if (f->n) (void)hipSetDevice(f->device);
+  free_planes(f, kAllPlanes);
+  delete f;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_info_get(const spt_film* f, spt_film_info* out) {
+  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  out->width = f->width;
+  out->rows = f->rows;
+  out->spp_total = f->spp_total;
+  out->samples_done = f->samples_done;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_clear(spt_film* f, void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (f->n) {
+    FILM_HIP(hipSetDevice(f->device));
+    FILM_HIP(hipMemsetAsync(f->sums, 0, f->n * sizeof(u64), (hipStream_t)stream));
+    if (f->m2) FILM_HIP(hipMemsetAsync(f->m2, 0, f->n * sizeof(ulonglong2), (hipStream_t)stream));
+    if (f->cnt) FILM_HIP(hipMemsetAsync(f->cnt, 0, f->n / 3 * sizeof(uint32_t), (hipStream_t)stream));
+  }
+  if (f->adaptive) adaptive_reset(f);  // the list is rebuilt by the next select
+  f->samples_done = 0;
+  f->batches_done = 0;
+  return SPT_OK;
+}
+
+spt_status spt_film_accumulate(spt_film* f, spt_context* c, const spt_film_launch& L, float* rgb_dev,
+                               int32_t s_count, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  const dim3 grid((L.npix + kBlock - 1) / kBlock), block(kBlock);
+  // once a pixel has retired the pass is over the active list; until then it is a noise film's
+  const bool listed = f->adaptive && f->any_retired;
+  if (listed) {
+    if ((int64_t)L.npix != f->n_active)
+      return fail(SPT_ERR_INVALID_ARG, "the launch is not over the film's active list");
+    hipLaunchKernelGGL(film_accumulate_listed_kernel, grid, block, 0, stream, L.accum, L.slots, f->sums,
+                       (ulonglong2*)f->m2, f->cnt, (const uint32_t*)f->list, L.npix, L.n_chunks,
+                       L.scr_k, L.scr_q, L.stats);
+  } else {
+    if (f->n != 3ull * L.npix)
+      return fail(SPT_ERR_INVALID_ARG, "the film does not have the launch's pixels");
+    int full = 0;
+    const float r = resolve_factor(f->spp_total, f->samples_done + s_count, &full);
+    if (f->batch)  // a noise film: the same pass also squares its sums into the moment plane
+      hipLaunchKernelGGL(film_accumulate_kernel<true>, grid, block, 0, stream, L.accum, L.slots, f->sums,
+                         rgb_dev, L.npix, L.n_chunks, L.scr_k, L.scr_q, L.stats, r, full,
+                         (int)aligned16(rgb_dev), (ulonglong2*)f->m2);
+    else
+      hipLaunchKernelGGL(film_accumulate_kernel<false>, grid, block, 0, stream, L.accum, L.slots,
+                         f->sums, rgb_dev, L.npix, L.n_chunks, L.scr_k, L.scr_q, L.stats, r, full,
+                         (int)aligned16(rgb_dev), (ulonglong2*)nullptr);
+  }
   FILM_HIP(hipGetLastError());
+  count_pass(f, c, L.npix, s_count);
+  if (listed && rgb_dev) return adaptive_resolve(f, rgb_dev, L.stats, stream);
   return SPT_OK;
 }
 
-spt_status adaptive_noise_map(const spt_film* f, float* se_dev, hipStream_t stream) {
-  adaptive_sync_counts(f, stream);
-  hipLaunchKernelGGL(film_adapt_map_kernel, dim3(tail_blocks(f->n)), dim3(kBlock), 0, stream,
-                     (const u64*)f->sums, (const ulonglong2*)f->m2, (const uint32_t*)f->cnt,
-                     (const AdaptRow*)f->table, se_dev, f->n);
-  FILM_HIP(hipGetLastError());
+void spt_film_rollback(spt_film* f, const spt_context* c, int32_t s_count) {
+  if (f->last_ctx == c && f->samples_done >= s_count) {  // count_pass, taken back
+    f->samples_done -= s_count;
+    if (f->batch && f->batches_done > 0) f->batches_done -= 1;
+    if (f->adaptive) {  // the front goes back; the guarded pass incremented no count
+      f->samples_total -= f->last_pass_samples;
+      f->last_pass_samples = 0;
+      if (!f->any_retired && f->cnt_front > f->batches_done) f->cnt_front = -1;
+    }
+  }
+}
+
+void spt_film_forget_context(spt_film* f, const spt_context* c) {
+  if (f->last_ctx == c) f->last_ctx = nullptr;
+}
+
+extern "C" spt_status spt_film_render_async(spt_context* ctx, spt_film* f, const spt_prim* prims,
+                                            int32_t n_prims, const spt_camera* cam,
+                                            const spt_params* p, int32_t sample_base,
+                                            int32_t sample_count, float* rgb_dev, void* stream) {
+  if (!ctx || !f || !p) return fail(SPT_ERR_INVALID_ARG, "null context/film/params");
+  if (p->width != f->width || p->height != f->height || p->spp != f->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "width/height/spp differ from the film's");
+  if (p->tile_rows < 0 || tile_rows_of(p) != f->tile_rows || p->shard_index != f->shard_index ||
+      p->shard_count != f->shard_count)
+    return fail(SPT_ERR_INVALID_ARG, "the shard fields differ from the film's");
+  if (sample_base < 0 || sample_count < 1 || (int64_t)sample_base + sample_count > f->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
+  if (f->samples_done + sample_count > f->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "the film would hold more than spp samples");
+  if (f->batch && (sample_count != f->batch || sample_base % f->batch != 0))
+    return fail(SPT_ERR_INVALID_ARG, "a noise film takes whole batches: sample_count == batch, sample_base % batch == 0");
+  if (f->adaptive) {
+    if ((int64_t)sample_base != f->batches_done * f->batch)
+      return fail(SPT_ERR_INVALID_ARG, "an adaptive film takes the next window only: sample_base == front * batch");
+    if (f->n && f->n_active == 0)
+      return fail(SPT_ERR_INVALID_ARG, "the adaptive film has no active pixel");
+  }
+  // once a pixel has retired the pass runs over the active list (spt_film_accumulate)
+  const bool listed = f->adaptive && f->any_retired;
+  const spt_status st = spt_render_window(ctx, prims, n_prims, cam, p, sample_base, sample_count,
+                                          rgb_dev, f, stream, listed ? f->list : nullptr,
+                                          listed ? (uint32_t)f->n_active : 0u);
+  if (st != SPT_OK) return st;
+  if (f->rows == 0) count_pass(f, nullptr, 0, sample_count);  // a shard without rows: still counted
   return SPT_OK;
 }
 
-spt_status adaptive_noise_summary(spt_film* f, spt_noise_summary* out, hipStream_t stream) {
+extern "C" spt_status spt_film_resolve(const spt_film* f, float* rgb_dev, void* stream_v) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (f->n == 0) return SPT_OK;
+  if (!rgb_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
+  hipStream_t stream = (hipStream_t)stream_v;
+  FILM_HIP(hipSetDevice(f->device));
+  if (f->adaptive) return adaptive_resolve(counts_owner(f), rgb_dev, nullptr, stream);
+  int full = 0;
+  const float r = resolve_factor(f->spp_total, f->samples_done, &full);
+  const u64* sums = f->sums;
+  const size_t n = f->n, body = aligned16(rgb_dev) ? n & ~(size_t)3 : 0;  // sums the 16-byte kernel takes
+  return launch_quads_and_tail(
+      body, n,
+      [&](unsigned blocks) {
+        hipLaunchKernelGGL(film_resolve_kernel, dim3(blocks), dim3(kBlock), 0, stream, sums, rgb_dev,
+                           body, r, full);
+      },
+      [&](unsigned blocks) {
+        hipLaunchKernelGGL(film_resolve_tail_kernel, dim3(blocks), dim3(kBlock), 0, stream, sums,
+                           rgb_dev, body, n, r, full);
+      });
+}
+
+extern "C" spt_status spt_film_merge(spt_film* dst, const spt_film* src, void* stream_v) {
+  if (!dst || !src || dst == src) return fail(SPT_ERR_INVALID_ARG, "merge needs two films");
+  if (dst->width != src->width || dst->rows != src->rows || dst->spp_total != src->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "films of unequal width/rows/spp");
+  if (dst->device != src->device)
+    return fail(SPT_ERR_INVALID_ARG, "films on different devices: download one and upload it beside the other");
+  if (dst->samples_done + src->samples_done > dst->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "the merged film would hold more than spp samples");
+  if (dst->adaptive || src->adaptive)
+    return fail(SPT_ERR_INVALID_ARG, "an adaptive film cannot be merged: its pixels hold different sample ranges");
+  if (dst->batch != src->batch)
+    return fail(SPT_ERR_INVALID_ARG, "merge needs two plain films or two noise films of equal batch");
+  if (dst->n) {
+    hipStream_t stream = (hipStream_t)stream_v;
+    FILM_HIP(hipSetDevice(dst->device));
+    u64* d = dst->sums;
+    const u64* s = src->sums;
+    const size_t n = dst->n, body = n & ~(size_t)3;
+    const spt_status st = launch_quads_and_tail(
+        body, n,
+        [&](unsigned blocks) {
+          hipLaunchKernelGGL(film_merge_kernel, dim3(blocks), dim3(kBlock), 0, stream, d, s, body);
+        },
+        [&](unsigned blocks) {
+          hipLaunchKernelGGL(film_merge_tail_kernel, dim3(blocks), dim3(kBlock), 0, stream, d, s, body, n);
+        });
+    if (st != SPT_OK) return st;
+    if (dst->batch) {
+      hipLaunchKernelGGL(film_merge_m2_kernel, dim3(tail_blocks(n)), dim3(kBlock), 0, stream,
+                         (ulonglong2*)dst->m2, (const ulonglong2*)src->m2, n);
+      FILM_HIP(hipGetLastError());
+    }
+  }
+  dst->batches_done += src->batches_done;
+  dst->samples_done += src->samples_done;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_download(const spt_film* f, uint64_t* host_sums, void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (f->n == 0) return SPT_OK;
+  if (!host_sums) return fail(SPT_ERR_INVALID_ARG, "null output");
+  return plane_copy(f, host_sums, f->sums, f->n * sizeof(u64), hipMemcpyDeviceToHost, stream);
+}
+
+extern "C" spt_status spt_film_upload(spt_film* f, const uint64_t* host_sums, int64_t samples_done,
+                                      void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (samples_done < 0 || samples_done > f->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "samples_done outside [0, spp]");
+  if (f->batch && samples_done % f->batch != 0)
+    return fail(SPT_ERR_INVALID_ARG, "a noise film holds whole batches: samples_done % batch != 0");
+  if (f->n) {
+    if (!host_sums) return fail(SPT_ERR_INVALID_ARG, "null input");
+    const spt_status st =
+        plane_copy(f, f->sums, host_sums, f->n * sizeof(u64), hipMemcpyHostToDevice, stream);
+    if (st != SPT_OK) return st;
+  }
+  f->samples_done = samples_done;
+  return SPT_OK;
+}
+
+// ---- the noise film: moment plane, error map, image figures (include/spt.h SPT_HAS_FILM_NOISE) ----
+
+extern "C" spt_status spt_film_noise_enable(spt_film* f, int32_t batch) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (f->batch) return fail(SPT_ERR_INVALID_ARG, "the film is a noise film already");
+  if (f->samples_done != 0) return fail(SPT_ERR_INVALID_ARG, "noise is enabled on an empty film only");
+  if (batch < 1 || f->spp_total % batch != 0 || f->spp_total / batch < 2)
+    return fail(SPT_ERR_INVALID_ARG, "batch must divide spp into at least two batches");
+  if (f->n) {
+    FILM_HIP(hipSetDevice(f->device));
+    const unsigned blocks = tail_blocks(f->n / 3);
+    hipError_t e = plane_alloc(&f->m2, f->n * sizeof(ulonglong2), true);
+    if (e == hipSuccess)  // five planes of 8-byte words, then the total
+      e = plane_alloc(&f->partials, 5 * (size_t)blocks * sizeof(double) + sizeof(NoisePartial), false);
+    if (e != hipSuccess) {
+      free_planes(f, kNoisePlanes);
+      return fail(SPT_ERR_OOM, std::string("moment plane alloc: ") + hipGetErrorString(e));
+    }
+    f->n_partials = blocks;
+  }
+  f->batch = batch;
+  f->batches_done = 0;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_info_get(const spt_film* f, spt_film_noise_info* out) {
+  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  out->enabled = f->batch != 0;
+  out->batch = f->batch;
+  out->batches_done = f->batches_done;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_download(const spt_film* f, uint64_t* host_m2, void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (f->n == 0) return SPT_OK;
+  if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null output");
+  return plane_copy(f, host_m2, f->m2, f->n * sizeof(ulonglong2), hipMemcpyDeviceToHost, stream);
+}
+
+extern "C" spt_status spt_film_noise_upload(spt_film* f, const uint64_t* host_m2, int64_t batches_done,
+                                            void* stream) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (batches_done < 0 || batches_done > f->spp_total / f->batch)
+    return fail(SPT_ERR_INVALID_ARG, "batches_done outside [0, spp / batch]");
+  if (f->n) {
+    if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null input");
+    const spt_status st =
+        plane_copy(f, f->m2, host_m2, f->n * sizeof(ulonglong2), hipMemcpyHostToDevice, stream);
+    if (st != SPT_OK) return st;
+  }
+  f->batches_done = batches_done;
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_film_noise_map(const spt_film* f, float* se_dev, void* stream_v) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
+  if (f->n == 0) return SPT_OK;
+  if (!se_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
+  hipStream_t stream = (hipStream_t)stream_v;
+  FILM_HIP(hipSetDevice(f->device));
+  if (f->adaptive) return noise_map_launch(f, pixel_counts(counts_owner(f), stream), se_dev, stream);
+  return noise_map_launch(f, uniform_count(f), se_dev, stream);
+}
+
+extern "C" spt_status spt_film_noise_summary(spt_film* f, spt_noise_summary* out, void* stream_v) {
+  if (!f || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
+  hipStream_t stream = (hipStream_t)stream_v;
   NoisePartial total{};
   if (f->n) {
     FILM_HIP(hipSetDevice(f->device));
-    adaptive_sync_counts(f, stream);
-    double* parts = (double*)f->partials;
-    NoisePartial* total_dev = (NoisePartial*)(parts + 5 * (size_t)f->n_partials);
-    hipLaunchKernelGGL(film_adapt_partials_kernel, dim3(f->n_partials), dim3(kBlock), 0, stream,
-                       (const u64*)f->sums, (const ulonglong2*)f->m2, (const uint32_t*)f->cnt,
-                       (const AdaptRow*)f->table, f->n / 3, parts);
-    FILM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(film_noise_total_kernel, dim3(1), dim3(kBlock), 0, stream, (const double*)parts,
-                       (uint32_t)f->n_partials, total_dev);
-    FILM_HIP(hipGetLastError());
-    FILM_HIP(hipMemcpyAsync(&total, total_dev, sizeof total, hipMemcpyDeviceToHost, stream));
+    const spt_status st = f->adaptive ? noise_summary_launch(f, pixel_counts(f, stream), &total, stream)
+                                      : noise_summary_launch(f, uniform_count(f), &total, stream);
+    if (st != SPT_OK) return st;
   }
   FILM_HIP(hipStreamSynchronize(stream));
   noise_finish(total, f->n / 3, f->batches_done, out);
   return SPT_OK;
 }
 
-// The host statements' arguments: *n = the film's elements, tab = the table for noise->batch.
-spt_status adaptive_host_args(const uint32_t* counts, const spt_film_info* info,
-                              const spt_film_noise_info* noise, size_t* n, AdaptRow** tab) {
-  if (!info || !noise) return fail(SPT_ERR_INVALID_ARG, "null info");
-  if (info->width <= 0 || info->rows < 0 || info->spp_total <= 0)
-    return fail(SPT_ERR_INVALID_ARG, "bad film info");
-  if (!noise->enabled || noise->batch < 1 || info->spp_total % noise->batch != 0 ||
-      info->spp_total / noise->batch > kAdaptMaxBatches)
-    return fail(SPT_ERR_INVALID_ARG, "not an adaptive film's batch");
-  *n = 3ull * (size_t)info->rows * (size_t)info->width;
-  if (*n && !counts) return fail(SPT_ERR_INVALID_ARG, "null counts");
-  const int32_t b_max = info->spp_total / noise->batch;
-  for (size_t p = 0; p < *n / 3; ++p)
-    if ((counts[p] & kCntMask) > (uint32_t)b_max)
-      return fail(SPT_ERR_INVALID_ARG, "a count above spp_total / batch");
-  *tab = (AdaptRow*)std::malloc(sizeof(AdaptRow) * (size_t)(b_max + 1));
-  if (!*tab) return fail(SPT_ERR_OOM, "table alloc");
-  for (int32_t B = 0; B <= b_max; ++B) (*tab)[B] = adapt_row(info->spp_total, noise->batch, B);
-  return SPT_OK;
-}
-
-}  // namespace
-
-spt_status spt_film_accumulate_listed(spt_film* f, spt_context* c, const unsigned long long* accum,
-                                      const unsigned long long* slots, float* rgb_dev, uint32_t npix,
-                                      uint32_t n_chunks, uint32_t scr_k, uint32_t scr_q,
-                                      const unsigned long long* stats, int32_t s_count, void* stream) {
-  if (!f->adaptive || !f->any_retired || (int64_t)npix != f->n_active)
-    return fail(SPT_ERR_INVALID_ARG, "the launch is not over the film's active list");
-  hipLaunchKernelGGL(film_accumulate_listed_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0,
-                     (hipStream_t)stream, accum, slots, f->sums, (ulonglong2*)f->m2, f->cnt,
-                     (const uint32_t*)f->list, npix, n_chunks, scr_k, scr_q, stats);
-  FILM_HIP(hipGetLastError());
-  f->samples_done += s_count;
-  f->batches_done += 1;
-  f->last_pass_samples = (int64_t)npix * s_count;
-  f->samples_total += f->last_pass_samples;
-  if (f->last_ctx && f->last_ctx != c) spt_context_forget_film(f->last_ctx, f);
-  f->last_ctx = c;
-  if (rgb_dev) return adaptive_resolve(f, rgb_dev, stats, (hipStream_t)stream);
-  return SPT_OK;
-}
+// ---- the adaptive film: counts plane, listed accumulate, selection (spt.h SPT_HAS_FILM_ADAPTIVE) ----
 
 extern "C" spt_status spt_film_adaptive_enable(spt_film* f) {
   if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
@@ -1232,42 +984,30 @@ extern "C" spt_status spt_film_adaptive_enable(spt_film* f) {
   const int32_t b_max = f->spp_total / f->batch;
   if (b_max > kAdaptMaxBatches)
     return fail(SPT_ERR_INVALID_ARG, "adaptive sampling takes at most 4096 batches: raise batch");
-  AdaptRow* h = (AdaptRow*)std::malloc(sizeof(AdaptRow) * (size_t)(b_max + 1));
-  if (!h) return fail(SPT_ERR_OOM, "table alloc");
-  for (int32_t B = 0; B <= b_max; ++B) h[B] = adapt_row(f->spp_total, f->batch, B);
+  std::vector<NoiseArgs> tab;
+  try {
+    tab = noise_table(f->spp_total, f->batch);
+  } catch (const std::bad_alloc&) {
+    return fail(SPT_ERR_OOM, "table alloc");
+  }
   if (f->n) {
     const size_t npix = f->n / 3;
-    const size_t tab_bytes = sizeof(AdaptRow) * (size_t)(b_max + 1);
-    uint32_t *cnt = nullptr, *list = nullptr, *scan = nullptr;
-    void* tab = nullptr;
+    const size_t tab_bytes = tab.size() * sizeof(NoiseArgs);
     hipError_t e = hipSetDevice(f->device);
-    if (e == hipSuccess) e = hipMalloc(&cnt, npix * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&list, npix * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&scan, ((size_t)tail_blocks(npix) + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&tab, tab_bytes);
-    if (e == hipSuccess) e = hipMemset(cnt, 0, npix * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(tab, h, tab_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = plane_alloc(&f->cnt, npix * sizeof(uint32_t), true);
+    if (e == hipSuccess) e = plane_alloc(&f->list, npix * sizeof(uint32_t), false);
+    if (e == hipSuccess)
+      e = plane_alloc(&f->scan, ((size_t)tail_blocks(npix) + 1) * sizeof(uint32_t), false);
+    if (e == hipSuccess) e = plane_alloc(&f->table, tab_bytes, false);
+    if (e == hipSuccess) e = hipMemcpy(f->table, tab.data(), tab_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-      if (cnt) (void)hipFree(cnt);
-      if (list) (void)hipFree(list);
-      if (scan) (void)hipFree(scan);
-      if (tab) (void)hipFree(tab);
-      std::free(h);
+      free_planes(f, kAdaptPlanes);
       return fail(SPT_ERR_OOM, std::string("adaptive planes alloc: ") + hipGetErrorString(e));
     }
-    f->cnt = cnt;
-    f->list = list;
-    f->scan = scan;
-    f->table = tab;
   }
-  f->h_table = h;
   f->b_max = b_max;
   f->adaptive = true;
-  f->any_retired = false;
-  f->cnt_front = 0;
-  f->n_active = (int64_t)(f->n / 3);
-  f->samples_total = 0;
-  f->last_pass_samples = 0;
+  adaptive_reset(f);
   return SPT_OK;
 }
 
@@ -1294,22 +1034,20 @@ extern "C" spt_status spt_film_adaptive_select(spt_film* f, double se_threshold,
     return SPT_OK;
   }
   FILM_HIP(hipSetDevice(f->device));
-  adaptive_sync_counts(f, stream);
+  sync_counts(f, stream);
   const size_t npix = f->n / 3;
   const int all = se_threshold < 0.0;
   const double thr2 = se_threshold * se_threshold;  // once, in double
   if (keep_dev || !all) {
     hipLaunchKernelGGL(film_adapt_mark_kernel, dim3(tail_blocks(npix)), dim3(kBlock), 0, stream,
                        (const u64*)f->sums, (const ulonglong2*)f->m2, f->cnt,
-                       (const AdaptRow*)f->table, keep_dev, npix, thr2, all);
+                       (const NoiseArgs*)f->table, keep_dev, npix, thr2, all);
     FILM_HIP(hipGetLastError());
   }
-  int64_t n = 0;
-  const spt_status st = adaptive_rebuild_list(f, stream, &n);
+  const spt_status st = rebuild_list(f, stream);
   if (st != SPT_OK) return st;
-  f->n_active = n;
-  if ((size_t)n != npix) f->any_retired = true;
-  *n_active = n;
+  if ((size_t)f->n_active != npix) f->any_retired = true;
+  *n_active = f->n_active;
   return SPT_OK;
 }
 
@@ -1320,11 +1058,8 @@ extern "C" spt_status spt_film_adaptive_download(const spt_film* f, uint32_t* ho
   if (f->n == 0) return SPT_OK;
   if (!host_counts) return fail(SPT_ERR_INVALID_ARG, "null output");
   FILM_HIP(hipSetDevice(f->device));
-  adaptive_sync_counts(f, (hipStream_t)stream);
-  FILM_HIP(hipMemcpyAsync(host_counts, f->cnt, f->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          (hipStream_t)stream));
-  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
-  return SPT_OK;
+  sync_counts(counts_owner(f), (hipStream_t)stream);
+  return plane_copy(f, host_counts, f->cnt, f->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
 }
 
 extern "C" spt_status spt_film_adaptive_upload(spt_film* f, const uint32_t* host_counts,
@@ -1352,10 +1087,9 @@ extern "C" spt_status spt_film_adaptive_upload(spt_film* f, const uint32_t* host
   }
   if (front < 0) front = top;
   if (top > front) return fail(SPT_ERR_INVALID_ARG, "a retired pixel holds more batches than the front");
-  FILM_HIP(hipSetDevice(f->device));
-  FILM_HIP(hipMemcpyAsync(f->cnt, host_counts, npix * sizeof(uint32_t), hipMemcpyHostToDevice,
-                          (hipStream_t)stream));
-  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  const spt_status st =
+      plane_copy(f, f->cnt, host_counts, npix * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+  if (st != SPT_OK) return st;
   f->batches_done = front;
   f->samples_done = front * (int64_t)f->batch;
   f->cnt_front = front;
@@ -1363,126 +1097,6 @@ extern "C" spt_status spt_film_adaptive_upload(spt_film* f, const uint32_t* host
   f->n_active = (int64_t)(npix - retired);
   f->samples_total = total * (int64_t)f->batch;  // what the counts imply
   f->last_pass_samples = 0;
-  if (f->any_retired) {
-    int64_t n = 0;
-    const spt_status st = adaptive_rebuild_list(f, (hipStream_t)stream, &n);
-    if (st != SPT_OK) return st;
-    f->n_active = n;
-  }
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_adaptive_resolve_host(const uint64_t* sums, const uint32_t* counts,
-                                                     const spt_film_info* info,
-                                                     const spt_film_noise_info* noise, float* rgb_out) {
-  size_t n = 0;
-  AdaptRow* tab = nullptr;
-  if (info && info->rows > 0 && info->width > 0 && (!sums || !rgb_out))
-    return fail(SPT_ERR_INVALID_ARG, "null sums/output");
-  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
-  if (st != SPT_OK) return st;
-  for (size_t e = 0; e < n; ++e) {
-    const AdaptRow& t = tab[counts[e / 3] & kCntMask];
-    rgb_out[e] = film_resolve1((u64)sums[e], t.r, t.full);
-  }
-  std::free(tab);
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_adaptive_noise_map_host(const uint64_t* sums, const uint64_t* m2,
-                                                       const uint32_t* counts,
-                                                       const spt_film_info* info,
-                                                       const spt_film_noise_info* noise,
-                                                       float* se_out) {
-  size_t n = 0;
-  AdaptRow* tab = nullptr;
-  if (info && info->rows > 0 && info->width > 0 && (!sums || !m2 || !se_out))
-    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
-  if (st != SPT_OK) return st;
-  for (size_t e = 0; e < n; ++e) {
-    const uint32_t B = counts[e / 3] & kCntMask;
-    const NoiseArgs A = adapt_args(tab[B], B);
-    ulonglong2 m;
-    m.x = m2[2 * e];
-    m.y = m2[2 * e + 1];
-    bool c;
-    se_out[e] = (float)(std::sqrt(noise_d((u64)sums[e], m, A, &c)) * A.k);
-  }
-  std::free(tab);
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_adaptive_noise_summary_host(const uint64_t* sums, const uint64_t* m2,
-                                                           const uint32_t* counts,
-                                                           const spt_film_info* info,
-                                                           const spt_film_noise_info* noise,
-                                                           spt_noise_summary* out) {
-  size_t n = 0;
-  AdaptRow* tab = nullptr;
-  if (!out || (info && info->rows > 0 && info->width > 0 && (!sums || !m2)))
-    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
-  if (st != SPT_OK) return st;
-  NoisePartial t{};
-  for (size_t e = 0; e < n; ++e) {
-    const uint32_t B = counts[e / 3] & kCntMask;
-    const NoiseArgs A = adapt_args(tab[B], B);
-    ulonglong2 m;
-    m.x = m2[2 * e];
-    m.y = m2[2 * e + 1];
-    bool c;
-    const double d = noise_d((u64)sums[e], m, A, &c);
-    t.s[e % 3] += d * A.k2;
-    t.se_max = std::fmax(t.se_max, (float)(std::sqrt(d) * A.k));
-    t.clamped += c ? 1u : 0u;
-  }
-  std::free(tab);
-  noise_finish(t, n / 3, noise->batches_done, out);
-  return SPT_OK;
-}
-
-extern "C" spt_status spt_film_adaptive_select_host(const uint64_t* sums, const uint64_t* m2,
-                                                    const uint32_t* counts, const spt_film_info* info,
-                                                    const spt_film_noise_info* noise,
-                                                    double se_threshold, const uint8_t* keep,
-                                                    uint32_t* counts_out, uint32_t* list_out,
-                                                    int64_t* n_active) {
-  size_t n = 0;
-  AdaptRow* tab = nullptr;
-  if (!n_active) return fail(SPT_ERR_INVALID_ARG, "null n_active");
-  if (se_threshold != se_threshold) return fail(SPT_ERR_INVALID_ARG, "the threshold is NaN");
-  if (noise && noise->batches_done < 2)
-    return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
-  if (info && info->rows > 0 && info->width > 0 && (!sums || !m2 || !counts_out || !list_out))
-    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const spt_status st = adaptive_host_args(counts, info, noise, &n, &tab);
-  if (st != SPT_OK) return st;
-  const bool all = se_threshold < 0.0;
-  const double thr2 = se_threshold * se_threshold;
-  int64_t na = 0;
-  for (size_t px = 0; px < n / 3; ++px) {
-    uint32_t c = counts[px];
-    if (!(c & kRetired)) {
-      bool stay = keep ? keep[px] != 0 : true;
-      if (stay && !all) {
-        ulonglong2 m[3];
-        u64 S[3];
-        for (int ch = 0; ch < 3; ++ch) {
-          S[ch] = (u64)sums[3 * px + ch];
-          m[ch].x = m2[2 * (3 * px + ch)];
-          m[ch].y = m2[2 * (3 * px + ch) + 1];
-        }
-        stay = adapt_noisy(S, m, adapt_args(tab[c], c), thr2);
-      }
-      if (stay)
-        list_out[na++] = (uint32_t)px;
-      else
-        c |= kRetired;
-    }
-    counts_out[px] = c;
-  }
-  std::free(tab);
-  *n_active = na;
+  if (f->any_retired) return rebuild_list(f, (hipStream_t)stream);
   return SPT_OK;
 }

@@ -139,6 +139,25 @@ def test_summary_host_against_python_integers(spt):
     assert got["se_max"] == float(m.max())
 
 
+def test_equal_counts_give_the_uniform_statements_bit_for_bit(spt):
+    """With every count equal to B >= 2 each adaptive statement is the uniform one for batches_done =
+    B, samples_done = B * batch: the resolve, the map and every field of the summary."""
+    sums, m2, _, _, _, _ = synthetic()
+    for B in (2, 5, B_MAX):
+        counts = np.full((ROWS, W), B, dtype=np.uint32)
+        counts.reshape(-1)[::3] |= np.uint32(RETIRED)  # the retired bit changes nothing
+        done = B * BATCH
+        assert spt.film_adaptive_resolve_host(sums, counts, W, ROWS, SPP, BATCH).tobytes() == \
+            spt.film_resolve_host(sums, W, ROWS, SPP, done).tobytes()
+        assert spt.film_adaptive_noise_map_host(sums, m2, counts, W, ROWS, SPP, BATCH).tobytes() == \
+            spt.film_noise_map_host(sums, m2, W, ROWS, SPP, done, BATCH, B).tobytes()
+        a = spt.film_adaptive_noise_summary_host(sums, m2, counts, W, ROWS, SPP, BATCH, B)
+        u = spt.film_noise_summary_host(sums, m2, W, ROWS, SPP, done, BATCH, B)
+        assert a == u and a["batches_done"] == B
+        assert [x.hex() for x in a["rmse"] + [a["rmse_all"], a["se_max"]]] == \
+            [x.hex() for x in u["rmse"] + [u["rmse_all"], u["se_max"]]]
+
+
 def py_select(S, M, B, counts, threshold, keep):
     _, dk2, _ = statement(S, M, B)
     thr2 = threshold * threshold

@@ -12,7 +12,9 @@ wall time around them (the summary synchronises, so the wall time is its real pr
 
 The accumulate kernel alone cannot be bracketed by events (it is enqueued inside the pass): run this
 script under `rocprofv3 --kernel-trace --stats -- python tools/film_noise_bench.py` for the times of
-film_accumulate_kernel<false> (plain) and <true> (with the moment plane).
+film_accumulate_kernel<false> (plain) and <true> (with the moment plane), and of the summary's
+film_noise_partials_kernel<UniformCount> and film_noise_total_kernel (an adaptive film launches the
+<PixelCount> instantiations of the partials and the error-map kernel instead).
 
 usage: python tools/film_noise_bench.py [--width W --height H --spp S --passes K --reps N --out F.json]
 """
