@@ -32,10 +32,12 @@ extern "C" {
                              spt_context_kernel. Added since, with no change to an existing struct or
                              entry point (so the version stays): SPT_HAS_FILM, the spt_film_* calls;
                              SPT_HAS_FILM_NOISE, the spt_film_noise_* calls; SPT_HAS_FILM_ADAPTIVE,
-                             the spt_film_adaptive_* calls */
+                             the spt_film_adaptive_* calls; SPT_HAS_FILM_POOL, spt_film_noise_pool_map,
+                             spt_film_adaptive_select_pooled and their *_host statements */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
+#define SPT_HAS_FILM_POOL 1 /* the error pooled over a pixel's neighbourhood: map and selection (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -425,6 +427,59 @@ spt_status spt_film_adaptive_select_host(const uint64_t* sums, const uint64_t* m
                                          const spt_film_noise_info* noise, double se_threshold,
                                          const uint8_t* keep_or_null, uint32_t* counts_out,
                                          uint32_t* list_out, int64_t* n_active);
+
+/* ---- the pooled error: a pixel's neighbourhood decides, not its own estimate (SPT_HAS_FILM_POOL) ----
+ * A pixel's own estimate after B batches has B - 1 degrees of freedom; a selection on it retires the
+ * pixels whose estimate is low by luck. These calls pool the per-batch variance over a window of
+ * (2 radius + 1)^2 pixels. For pixel q with B_q = cnt[q] & 0x7FFFFFFF (a uniform noise film:
+ * batches_done) and channel c
+ *   u(q,c) = (d(q,c) * k2(B_q)) * (double)B_q      d of the error map (0 for a clamped channel)
+ * the estimated variance of a ONE-batch estimate in resolved units, comparable between pixels at
+ * different counts. A pixel with B_q < 2 has u = 0 and is not counted (uploaded counts only).
+ * The window of pixel (y, x): columns max(0, x - R) .. min(w - 1, x + R); rows y - R .. y + R clipped
+ * to the film's rows and, with band_rows > 0, to the pixel's band [b, b + band_rows), b = y - y %
+ * band_rows: no window crosses a row that is a multiple of band_rows. The device passes band_rows = 0
+ * for an unsharded film and the effective tile_rows for a film with shard_count > 1 (a shard's compact
+ * rows are image neighbours only inside one tile). The sums, in this order and no other (both sides
+ * are built without contraction, so host and device run the same IEEE double operations):
+ *   h(y,x,c) = 0.0 + u(y,x0,c) + ... + u(y,x1,c)    columns ascending
+ *   g(y,x,c) = 0.0 + h(y0,x,c) + ... + h(y1,x,c)    rows ascending
+ *   n(y,x)   = the window's pixels with B_q >= 2
+ *   SPT_POOL_EXCLUDE_CENTER: g = g - u(y,x,c), one subtraction per channel, and n = n - 1 if B_p >= 2;
+ *   the decision about a pixel then does not depend on that pixel's own samples.
+ * The pooled error map: se_pool(p,c) = (float)sqrt(g / ((double)n * (double)B_p)), 0 where n == 0 or
+ * B_p < 2. The pooled selection is spt_film_adaptive_select with one clause changed: an active pixel
+ * stays iff keep allows it and (se_threshold < 0 or some channel has
+ * g > (thr2 * (double)n) * (double)B_p), thr2 = se_threshold^2 once on the host: no division, no square
+ * root. Where n == 0 the pixel's own rule (spt_film_adaptive_select's) decides. Every decision is taken
+ * from the planes as they were before this selection marked anything. */
+#define SPT_POOL_MAX_RADIUS 16
+#define SPT_POOL_EXCLUDE_CENTER 1u /* other flag bits must be 0 */
+/* The pooled map, rows*w*3 floats (DEVICE), enqueued on `stream`: any noise film with batches_done >=
+ * 2 (an adaptive one: every pixel's own count). Rejected, nothing queued: a plain film, fewer than
+ * two batches, radius outside [1, SPT_POOL_MAX_RADIUS], unknown flag bits. The film's pooling scratch
+ * (52 bytes per pixel) is allocated at its first pooled call and freed by spt_film_destroy. */
+spt_status spt_film_noise_pool_map(const spt_film* film, int32_t radius, uint32_t flags,
+                                   float* se_dev, void* stream);
+/* The pooled selection: marks, list, count and the wait on `stream` as spt_film_adaptive_select.
+ * Rejected, nothing queued, film untouched: what spt_film_adaptive_select rejects (a NaN threshold, a
+ * plain or non-adaptive film, front < 2), a radius outside [1, SPT_POOL_MAX_RADIUS], unknown flag
+ * bits. A shard without rows returns SPT_OK and *n_active = 0. */
+spt_status spt_film_adaptive_select_pooled(spt_film* film, double se_threshold, int32_t radius,
+                                           uint32_t flags, const uint8_t* keep_dev_or_null,
+                                           int64_t* n_active, void* stream);
+/* Both as pure host functions (no device). counts_or_null: NULL = a uniform noise film (info's
+ * samples_done, noise's batches_done >= 2), else an adaptive film's plane. band_rows >= 0 as above. */
+spt_status spt_film_noise_pool_map_host(const uint64_t* sums, const uint64_t* m2,
+                                        const uint32_t* counts_or_null, const spt_film_info* info,
+                                        const spt_film_noise_info* noise, int32_t band_rows,
+                                        int32_t radius, uint32_t flags, float* se_out);
+spt_status spt_film_adaptive_select_pooled_host(const uint64_t* sums, const uint64_t* m2,
+                                                const uint32_t* counts, const spt_film_info* info,
+                                                const spt_film_noise_info* noise, int32_t band_rows,
+                                                double se_threshold, int32_t radius, uint32_t flags,
+                                                const uint8_t* keep_or_null, uint32_t* counts_out,
+                                                uint32_t* list_out, int64_t* n_active);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

@@ -149,9 +149,13 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_film_adaptive_enable", "spt_film_adaptive_info_get", "spt_film_adaptive_select",
            "spt_film_adaptive_download", "spt_film_adaptive_upload",
            "spt_film_adaptive_resolve_host", "spt_film_adaptive_noise_map_host",
-           "spt_film_adaptive_noise_summary_host", "spt_film_adaptive_select_host"]
+           "spt_film_adaptive_noise_summary_host", "spt_film_adaptive_select_host",
+           "spt_film_noise_pool_map", "spt_film_adaptive_select_pooled",
+           "spt_film_noise_pool_map_host", "spt_film_adaptive_select_pooled_host"]
 COUNT_RETIRED = 0x80000000  # bit 31 of an adaptive film's counts: the pixel takes no more batches
 COUNT_MASK = 0x7FFFFFFF     # ... and the batches it holds
+POOL_MAX_RADIUS = 16        # SPT_POOL_MAX_RADIUS: the pooled calls take a radius in [1, 16]
+POOL_EXCLUDE_CENTER = 1     # SPT_POOL_EXCLUDE_CENTER: a pixel's window without the pixel itself
 IMAGE_FORMATS = {"p3": 0, "p6": 1, "pfm": 2}
 FLAG_UNIFORM_SCATTER = 1  # spt_params.flags: random_scattering from the uniform code of :352-359
 # spt_params.flags: leaked paths go on from the miss vertex as the reference's (:371-377) instead of
@@ -278,6 +282,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                          P(spt_film_noise_info), P(spt_noise_summary)]
     lib.spt_film_adaptive_select_host.argtypes = [VP, VP, VP, P(spt_film_info), P(spt_film_noise_info),
                                                   ctypes.c_double, VP, VP, VP, P(I64)]
+    lib.spt_film_noise_pool_map.argtypes = [VP, I32, U32, VP, VP]
+    lib.spt_film_adaptive_select_pooled.argtypes = [VP, ctypes.c_double, I32, U32, VP, P(I64), VP]
+    lib.spt_film_noise_pool_map_host.argtypes = [VP, VP, VP, P(spt_film_info), P(spt_film_noise_info),
+                                                 I32, I32, U32, VP]
+    lib.spt_film_adaptive_select_pooled_host.argtypes = [VP, VP, VP, P(spt_film_info),
+                                                         P(spt_film_noise_info), I32, ctypes.c_double,
+                                                         I32, U32, VP, VP, VP, P(I64)]
     for name in EXPORTS:
         if name.startswith("spt_film_"):
             getattr(lib, name).restype = I32
@@ -758,6 +769,42 @@ def film_adaptive_select_host(sums, m2, counts, width: int, rows: int, spp_total
     return out, lst[: n.value].copy()
 
 
+def film_noise_pool_map_host(sums, m2, counts, width: int, rows: int, spp_total: int, batch: int,
+                             batches_done: int, radius: int, exclude_center: bool = False,
+                             band_rows: int = 0) -> np.ndarray:
+    """spt_film_noise_pool_map_host(): the error pooled over every pixel's (2 radius + 1)^2 window.
+    counts: None for a uniform noise film (batches_done batches everywhere), else an adaptive film's
+    plane. band_rows: 0, or the tile_rows of a sharded film (no window crosses a band)."""
+    a, m, c, info, noise = _film_host_args(sums, m2, counts, width, rows, spp_total,
+                                           int(batches_done) * int(batch), batch, batches_done)
+    out = np.empty((max(info.rows, 0), max(info.width, 0), 3), dtype=np.float32)
+    _check(load_library().spt_film_noise_pool_map_host(
+        a.ctypes.data, m.ctypes.data, None if c is None else c.ctypes.data, ctypes.byref(info),
+        ctypes.byref(noise), int(band_rows), int(radius),
+        POOL_EXCLUDE_CENTER if exclude_center else 0, out.ctypes.data))
+    return out
+
+
+def film_adaptive_select_pooled_host(sums, m2, counts, width: int, rows: int, spp_total: int,
+                                     batch: int, front: int, threshold: float, radius: int,
+                                     exclude_center: bool = False, keep=None, band_rows: int = 0):
+    """spt_film_adaptive_select_pooled_host(): film_adaptive_select_host with the pooled clause ->
+    (the new counts plane (rows, width) uint32, the new active list ascending)."""
+    a, m, c, info, noise = _film_host_args(sums, m2, counts, width, rows, spp_total,
+                                           int(front) * int(batch), batch, front)
+    k = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    if k is not None and k.size != c.size:
+        raise SptError(1, "keep does not have rows * width bytes")
+    out = np.zeros((max(info.rows, 0), max(info.width, 0)), dtype=np.uint32)
+    lst = np.zeros(max(1, c.size), dtype=np.uint32)
+    n = ctypes.c_int64(0)
+    _check(load_library().spt_film_adaptive_select_pooled_host(
+        a.ctypes.data, m.ctypes.data, c.ctypes.data, ctypes.byref(info), ctypes.byref(noise),
+        int(band_rows), float(threshold), int(radius), POOL_EXCLUDE_CENTER if exclude_center else 0,
+        None if k is None else k.ctypes.data, out.ctypes.data, lst.ctypes.data, ctypes.byref(n)))
+    return out, lst[: n.value].copy()
+
+
 def write_film_file(path: str, sums: np.ndarray, width: int, rows: int, spp_total: int,
                     samples_done: int, m2: np.ndarray | None = None, batch: int = 0,
                     batches_done: int = 0) -> None:
@@ -936,6 +983,15 @@ class Film:
         buffer (rows * width * 3 floats). Without: returned on the host as (rows, width, 3) float32."""
         return self._float_plane(self.lib.spt_film_noise_map, se_dev_ptr, stream_ptr)
 
+    def noise_pool_map(self, radius: int, exclude_center: bool = False, se_dev_ptr: int = 0,
+                       stream_ptr: int = 0):
+        """noise_map with every value's error pooled over the pixel's (2 radius + 1)^2 window (clipped
+        to the film, and to the tile of a sharded film); exclude_center: without the pixel itself."""
+        flags = POOL_EXCLUDE_CENTER if exclude_center else 0
+        return self._float_plane(
+            lambda f, dev, stream: self.lib.spt_film_noise_pool_map(f, int(radius), flags, dev, stream),
+            se_dev_ptr, stream_ptr)
+
     def noise_summary(self, stream_ptr: int = 0) -> dict:
         """spt_film_noise_summary(): {"rmse": [r, g, b], "rmse_all", "se_max", "clamped",
         "batches_done"} of the clamped image; waits for the stream."""
@@ -955,10 +1011,13 @@ class Film:
         _check(self.lib.spt_film_adaptive_info_get(self._f, ctypes.byref(i)))
         return {k: int(getattr(i, k)) for k in ("enabled", "front", "n_active", "samples_total")}
 
-    def adaptive_select(self, threshold: float, keep=None, stream_ptr: int = 0) -> int:
+    def adaptive_select(self, threshold: float, keep=None, stream_ptr: int = 0, pool_radius: int = 0,
+                        exclude_center: bool = False) -> int:
         """Retire the active pixels whose every channel has se <= threshold (threshold < 0: none by
         the error) or whose keep entry is 0; -> the pixels still active. keep: None, a device pointer
-        (rows * width bytes), or an array (uploaded for this call)."""
+        (rows * width bytes), or an array (uploaded for this call). pool_radius > 0: se is the error
+        pooled over the pixel's (2 pool_radius + 1)^2 window (spt_film_adaptive_select_pooled),
+        exclude_center: without the pixel itself."""
         n = ctypes.c_int64(0)
         ptr, hold = None, None
         if keep is not None and not isinstance(keep, int):
@@ -972,8 +1031,13 @@ class Film:
             ptr = hold.data_ptr()
         elif keep:
             ptr = int(keep)
-        _check(self.lib.spt_film_adaptive_select(self._f, float(threshold), ctypes.c_void_p(ptr),
-                                                 ctypes.byref(n), ctypes.c_void_p(stream_ptr or None)))
+        if pool_radius:
+            _check(self.lib.spt_film_adaptive_select_pooled(
+                self._f, float(threshold), int(pool_radius), POOL_EXCLUDE_CENTER if exclude_center else 0,
+                ctypes.c_void_p(ptr), ctypes.byref(n), ctypes.c_void_p(stream_ptr or None)))
+        else:
+            _check(self.lib.spt_film_adaptive_select(self._f, float(threshold), ctypes.c_void_p(ptr),
+                                                     ctypes.byref(n), ctypes.c_void_p(stream_ptr or None)))
         del hold
         return int(n.value)
 
@@ -1088,22 +1152,29 @@ def render_until(prims: Sequence[spt_prim], cam: Camera, params: spt_params, tar
 
 def render_adaptive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, target_rmse: float,
                     batch: int | None = None, min_batches: int = 4, threshold_scale: float = 1.0,
-                    return_info=False):
+                    return_info=False, pool_radius: int = 0, pool_exclude_center: bool = False):
     """render_until with the samples going where the error is. Full batches until min_batches (at
     least 2; pass a small value to retire earlier). After every pass from then on the film's summary
     is read and the render stops once max(rmse) <= target_rmse; otherwise the pixels whose every
     channel has se <= threshold_scale * target_rmse retire (adaptive_select) and the next pass renders
     the rest, until nothing is active or every batch of params.spp is in. A pixel retired on its own
-    estimate may look converged by luck: min_batches is the guard. Returns the
-    resolved image; return_info: also {"front", "samples_total", "rmse", "counts"}."""
+    estimate may look converged by luck: min_batches is the guard.
+    pool_radius > 0 retires on the error pooled over the pixel's (2 pool_radius + 1)^2 window
+    instead, pool_exclude_center without the pixel itself (the decision then does not depend on the
+    pixel's own samples). Measured at C3: pool_radius=2 with
+    pool_exclude_center=True keeps the true error at the estimate, which the default does not.
+    Returns the resolved image; return_info: also {"front", "samples_total",
+    "rmse", "counts", "pool_radius", "pool_exclude_center"}."""
     def info_of(film, stream):
         a = film.adaptive_info()
         return {"front": a["front"], "samples_total": a["samples_total"],
-                "counts": film.counts_to_numpy(stream)}
+                "counts": film.counts_to_numpy(stream), "pool_radius": int(pool_radius),
+                "pool_exclude_center": bool(pool_exclude_center)}
 
     out, info = _render_to_target(
         "render_adaptive", prims, cam, params, target_rmse, batch, min_batches,
-        lambda film, stream: film.adaptive_select(threshold_scale * target_rmse, None, stream), info_of)
+        lambda film, stream: film.adaptive_select(threshold_scale * target_rmse, None, stream,
+                                                  pool_radius, pool_exclude_center), info_of)
     return (out, info) if return_info else out
 
 

@@ -2,7 +2,7 @@
 //   smallpt_amd [W H SPP [SEED [OUT.ppm]]] [--cos] [--uniform] [--reference-leaks] [--q Q]
 //               [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]
 //               [--device N | --devices N] [--p6 | --pfm]
-//               [--noise T [--batch B] [--adaptive [--min-batches M]]]
+//               [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]
 //   --uniform: random_scattering from the commented-out uniform hemisphere code (:352-359)
 //   --reference-leaks: leaked paths go on from the miss vertex as the reference's (:371-377)
 //                      instead of ending at their first miss (SPT_FLAG_REFERENCE_LEAKS)
@@ -36,6 +36,10 @@
 //               channel has a standard error <= T retire and the next pass renders the rest, until
 //               none is left or every batch is in. Prints "SAMPLES_TOTAL : N" (the pixel-samples
 //               spent) beside DURATION. Not with --film: the counts plane has no file format.
+//   --pool R [--pool-loo] (with --adaptive): a pixel retires on the error pooled over its (2R + 1)^2
+//               neighbourhood (spt_film_adaptive_select_pooled, R in 1..16) instead of its own
+//               estimate; --pool-loo leaves the pixel itself out of its window
+//               (SPT_POOL_EXCLUDE_CENTER), so that the decision does not depend on its own samples.
 // Same scene, camera (:521), clamp/toInt and P3 output; the pixel loop is one spt_render() call.
 #include <algorithm>
 #include <chrono>
@@ -72,6 +76,8 @@ struct NoiseOpts {
   int batch = 0;  // 0: SPP / 8
   bool adaptive = false;
   int min_batches = 4;
+  int pool_radius = 0;  // 0: a pixel retires on its own estimate
+  bool pool_loo = false;
   int64_t samples_total = -1;  // out: the pixel-samples an adaptive run spent
 };
 
@@ -160,7 +166,12 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
       if (std::max(sm.rmse[0], std::max(sm.rmse[1], sm.rmse[2])) <= noise.target) break;
       if (noise.adaptive && k + 1 < todo / batch) {  // retire what is below the target, render the rest
         int64_t n_active = 0;
-        check(spt_film_adaptive_select(film, noise.target, nullptr, &n_active, nullptr));
+        if (noise.pool_radius)
+          check(spt_film_adaptive_select_pooled(film, noise.target, noise.pool_radius,
+                                                noise.pool_loo ? SPT_POOL_EXCLUDE_CENTER : 0u, nullptr,
+                                                &n_active, nullptr));
+        else
+          check(spt_film_adaptive_select(film, noise.target, nullptr, &n_active, nullptr));
         if (n_active == 0) break;
       }
     }
@@ -245,6 +256,8 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) noise.batch = std::max(1, std::atoi(argv[++i]));
     else if (!std::strcmp(argv[i], "--adaptive")) noise.adaptive = true;
     else if (!std::strcmp(argv[i], "--min-batches") && i + 1 < argc) noise.min_batches = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--pool") && i + 1 < argc) noise.pool_radius = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--pool-loo")) noise.pool_loo = true;
     else if (!std::strcmp(argv[i], "--p6")) format = SPT_IMAGE_P6;
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
     else if (npos < 4) pos[npos++] = std::atoi(argv[i]);
@@ -270,10 +283,15 @@ int main(int argc, char* argv[]) {
                                         : specular ? cornell_specular_scene()
                                         : spheres ? spheres32_scene()
                                                   : cornell_scene();
-    if (passes > 0 || film_path || noise.on || noise.adaptive) {
+    if (passes > 0 || film_path || noise.on || noise.adaptive || noise.pool_radius || noise.pool_loo) {
       if (devices > 0 || repeat > 1)
         throw std::runtime_error("--passes / --film / --noise go with one device and no --repeat");
       if (noise.adaptive && !noise.on) throw std::runtime_error("--adaptive goes with --noise T");
+      if ((noise.pool_radius || noise.pool_loo) && !noise.adaptive)
+        throw std::runtime_error("--pool goes with --noise T --adaptive");
+      if (noise.pool_loo && !noise.pool_radius) throw std::runtime_error("--pool-loo goes with --pool R");
+      if (noise.pool_radius < 0 || noise.pool_radius > SPT_POOL_MAX_RADIUS)
+        throw std::runtime_error("--pool: the radius is 1..16");
       if (noise.adaptive && film_path)
         throw std::runtime_error("--adaptive does not go with --film: the counts plane has no file format");
       image = render_film(scene, cam, p, passes, film_path, add, noise, &st);

@@ -39,6 +39,9 @@ struct spt_film {
   int32_t b_max = 0;                   // spp_total / batch
   int64_t n_active = 0, samples_total = 0;
   int64_t last_pass_samples = 0;       // what the last pass added to samples_total (rollback)
+  // the pooled error's scratch (spt.h SPT_HAS_FILM_POOL), allocated at the first pooled call:
+  // planes u[3][npix] and h[3][npix] of doubles, then hn[npix] of uint32 (the row sums' counts)
+  double* pool = nullptr;
 };
 
 // spt_context.cpp: one render launch over a sample window (film == nullptr: the one-shot finalize).

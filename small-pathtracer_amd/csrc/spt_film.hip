@@ -16,6 +16,8 @@
 //   adaptive    an adaptive film's counts plane: passes over the active list scatter their sums, the
 //               selection retires pixels and compacts the rest, and the resolve, the map and the
 //               summary take every pixel's own batch count (the last section of this file)
+//   pool        the error pooled over a pixel's neighbourhood: its map, and the selection that retires
+//               on it (two streaming passes through a scratch plane of row sums)
 //
 // All three stream: one pass over the sums at 16 bytes per access (two sums, or four floats),
 // 256 threads per block, no reuse -- HBM-bound. -ffp-contract=off (the Makefile) keeps the preview two
@@ -495,6 +497,141 @@ film_adapt_scatter_kernel(const uint32_t* cnt, size_t npix, const uint32_t* offs
   if (active) list[at + ballot_rank(b)] = (uint32_t)px;  // at + rank < the total <= npix
 }
 
+// ---- the pooled error's kernels (spt.h SPT_HAS_FILM_POOL) ----
+//
+// Two streaming passes. (1) film_pool_rows_kernel reads what the error map reads (24 B of sums, 48 B of
+// moments, the count), evaluates u once per place of its tile and forms the row sums h over the
+// window's columns through LDS. (2) film_pool_mark_kernel / film_pool_map_kernel add h over the
+// window's rows and decide. Pass 2 reads only the scratch planes pass 1 wrote and its own pixel's
+// count, so the selection marks in place and still decides every pixel from the planes as they were
+// before it marked anything. The additions run in the stated order (spt.h): no atomics, no sliding sums.
+
+// A block covers kBlock consecutive columns of one row, the R-column halo on either side included:
+// thread t evaluates column tile * (kBlock - 2R) - R + t (0.0 and uncounted outside the row: u is
+// never -0.0, so adding 0.0 for a clipped column changes no bit) and the kBlock - 2R threads in the
+// middle add their 2R + 1 columns, ascending. LDS: three planes of doubles, one per channel, so that a
+// wave's 8-byte reads are consecutive, and one of counts: 7 KB.
+template <class Counts>
+__global__ void __launch_bounds__(kBlock)
+film_pool_rows_kernel(const u64* __restrict__ sums, const ulonglong2* __restrict__ m2, Counts cs,
+                      uint32_t w, uint32_t tiles, uint32_t R, size_t npix, double* __restrict__ u_out,
+                      double* __restrict__ h_out, uint32_t* __restrict__ hn_out) {
+  __shared__ double s_u[3][kBlock];
+  __shared__ uint32_t s_n[kBlock];
+  const uint32_t t = threadIdx.x;
+  const uint32_t row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+  const int64_t x = (int64_t)tile * (int64_t)(kBlock - 2u * R) - (int64_t)R + (int64_t)t;
+  const bool in = x >= 0 && x < (int64_t)w;
+  const size_t px = (size_t)row * w + (size_t)(in ? x : 0);
+  double u0 = 0.0, u1 = 0.0, u2 = 0.0;
+  uint32_t counted = 0;
+  if (in) {
+    ulonglong2 m0 = m2[3 * px], m1 = m2[3 * px + 1], mm = m2[3 * px + 2];
+    loads_landed(m0, m1);
+    load_landed(mm);
+    const NoiseArgs A = cs.at(px);
+    u0 = pool_u(sums[3 * px], m0, A);
+    u1 = pool_u(sums[3 * px + 1], m1, A);
+    u2 = pool_u(sums[3 * px + 2], mm, A);
+    counted = A.B >= 2 ? 1u : 0u;
+  }
+  s_u[0][t] = u0;
+  s_u[1][t] = u1;
+  s_u[2][t] = u2;
+  s_n[t] = counted;
+  __syncthreads();
+  if (!in || t < R || t >= kBlock - R) return;
+  double h0 = 0.0, h1 = 0.0, h2 = 0.0;
+  uint32_t n = 0;
+  for (uint32_t j = t - R; j <= t + R; ++j) {  // inside [0, kBlock): R <= t < kBlock - R
+    h0 = h0 + s_u[0][j];
+    h1 = h1 + s_u[1][j];
+    h2 = h2 + s_u[2][j];
+    n += s_n[j];
+  }
+  u_out[px] = u0;
+  u_out[npix + px] = u1;
+  u_out[2 * npix + px] = u2;
+  h_out[px] = h0;
+  h_out[npix + px] = h1;
+  h_out[2 * npix + px] = h2;
+  hn_out[px] = n;
+}
+
+// g and n of pixel px: the row sums of its column over the window's rows, ascending; the centre out
+// on request. u and h are the planes of film_pool_rows_kernel.
+__device__ __forceinline__ void pool_gather(const double* __restrict__ u, const double* __restrict__ h,
+                                            const uint32_t* __restrict__ hn, size_t npix, uint32_t w,
+                                            uint32_t rows, int32_t band_rows, int32_t R, uint32_t flags,
+                                            size_t px, bool counted, double g[3], uint32_t* n) {
+  const int32_t y = (int32_t)((uint32_t)px / w);  // a film has at most 2^32 - 1 pixels
+  int32_t y0, y1;
+  pool_row_window(y, (int32_t)rows, band_rows, R, &y0, &y1);
+  g[0] = g[1] = g[2] = 0.0;
+  *n = 0;
+  size_t q = px - (size_t)(y - y0) * w;
+  for (int32_t yy = y0; yy <= y1; ++yy, q += w) {
+    g[0] = g[0] + h[q];
+    g[1] = g[1] + h[npix + q];
+    g[2] = g[2] + h[2 * npix + q];
+    *n += hn[q];
+  }
+  if (flags & SPT_POOL_EXCLUDE_CENTER) {
+    const double uc[3] = {u[px], u[npix + px], u[2 * npix + px]};
+    pool_exclude_center(g, n, uc, counted);
+  }
+}
+
+// The pooled selection's mark: film_adapt_mark_kernel with the pooled clause. One pixel per thread.
+// Where the window counts nothing the pixel's own rule decides (rare: the moments are loaded there,
+// straight-line behind the full wait).
+__global__ void __launch_bounds__(kBlock)
+film_pool_mark_kernel(const u64* __restrict__ sums, const ulonglong2* __restrict__ m2,
+                      uint32_t* __restrict__ cnt, const NoiseArgs* __restrict__ tab,
+                      const uint8_t* __restrict__ keep, const double* __restrict__ u,
+                      const double* __restrict__ h, const uint32_t* __restrict__ hn, size_t npix,
+                      uint32_t w, uint32_t rows, int32_t band_rows, int32_t R, uint32_t flags,
+                      double thr2) {
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (px >= npix) return;
+  const uint32_t c = cnt[px];
+  if (c & kRetired) return;
+  bool stay = keep ? keep[px] != 0 : true;
+  if (stay) {
+    double g[3];
+    uint32_t n;
+    pool_gather(u, h, hn, npix, w, rows, band_rows, R, flags, px, c >= 2u, g, &n);
+    if (n) {
+      stay = pool_noisy(g, n, (u64)c, thr2);
+    } else {
+      ulonglong2 m0 = m2[3 * px], m1 = m2[3 * px + 1], mm = m2[3 * px + 2];
+      loads_landed(m0, m1);
+      load_landed(mm);
+      const ulonglong2 m[3] = {m0, m1, mm};
+      const u64 S[3] = {sums[3 * px], sums[3 * px + 1], sums[3 * px + 2]};
+      stay = adapt_noisy(S, m, PixelCount{cnt, tab}.row(c), thr2);
+    }
+  }
+  if (!stay) cnt[px] = c | kRetired;
+}
+
+// The pooled error map: one pixel per thread, three floats.
+template <class Counts>
+__global__ void __launch_bounds__(kBlock)
+film_pool_map_kernel(Counts cs, const double* __restrict__ u, const double* __restrict__ h,
+                     const uint32_t* __restrict__ hn, size_t npix, uint32_t w, uint32_t rows,
+                     int32_t band_rows, int32_t R, uint32_t flags, float* __restrict__ se) {
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (px >= npix) return;
+  const u64 B = cs.at(px).B;
+  double g[3];
+  uint32_t n;
+  pool_gather(u, h, hn, npix, w, rows, band_rows, R, flags, px, B >= 2, g, &n);
+  se[3 * px] = pool_se(g[0], n, B);
+  se[3 * px + 1] = pool_se(g[1], n, B);
+  se[3 * px + 2] = pool_se(g[2], n, B);
+}
+
 spt_status fail(spt_status s, const std::string& msg) {
   spt_set_last_error(msg);
   return s;
@@ -522,7 +659,7 @@ hipError_t plane_alloc(T** p, size_t bytes, bool zero) {
 }
 
 // Free the planes of the film's layers named in `layers` (and forget them).
-enum : unsigned { kSumsPlane = 1, kNoisePlanes = 2, kAdaptPlanes = 4, kAllPlanes = 7 };
+enum : unsigned { kSumsPlane = 1, kNoisePlanes = 2, kAdaptPlanes = 4, kPoolPlanes = 8, kAllPlanes = 15 };
 void free_planes(spt_film* f, unsigned layers) {
   auto drop = [](auto*& p) {
     if (p) (void)hipFree(p);
@@ -531,6 +668,7 @@ void free_planes(spt_film* f, unsigned layers) {
   if (layers & kSumsPlane) drop(f->sums);
   if (layers & kNoisePlanes) drop(f->m2), drop(f->partials);
   if (layers & kAdaptPlanes) drop(f->cnt), drop(f->list), drop(f->scan), drop(f->table);
+  if (layers & kPoolPlanes) drop(f->pool);
 }
 
 // Copy a plane to or from the host and wait.
@@ -641,6 +779,57 @@ spt_status rebuild_list(spt_film* f, hipStream_t stream) {
   FILM_HIP(hipMemcpyAsync(&total, f->scan + nblk, sizeof total, hipMemcpyDeviceToHost, stream));
   FILM_HIP(hipStreamSynchronize(stream));
   f->n_active = (int64_t)total;
+  return SPT_OK;
+}
+
+// The pooled calls' arguments, and the scratch: allocated once, at the film's first pooled call.
+spt_status pool_args(int32_t radius, uint32_t flags) {
+  if (radius < 1 || radius > SPT_POOL_MAX_RADIUS)
+    return fail(SPT_ERR_INVALID_ARG, "radius outside [1, SPT_POOL_MAX_RADIUS]");
+  if (flags & ~SPT_POOL_EXCLUDE_CENTER) return fail(SPT_ERR_INVALID_ARG, "unknown pool flag bits");
+  return SPT_OK;
+}
+
+spt_status pool_scratch(spt_film* f) {
+  if (f->pool) return SPT_OK;
+  const size_t npix = f->n / 3;
+  const hipError_t e = plane_alloc(&f->pool, npix * (6 * sizeof(double) + sizeof(uint32_t)), false);
+  if (e != hipSuccess) {
+    free_planes(f, kPoolPlanes);
+    return fail(SPT_ERR_OOM, std::string("pool scratch alloc: ") + hipGetErrorString(e));
+  }
+  return SPT_OK;
+}
+
+// A window never crosses a tile of a sharded film: its compact rows are image neighbours inside one.
+int32_t pool_band_rows(const spt_film* f) { return f->shard_count > 1 ? f->tile_rows : 0; }
+
+// Pass 1 of a pooled call: u, h and hn of every pixel into the scratch.
+template <class Counts>
+spt_status pool_rows_launch(const spt_film* f, const Counts& cs, int32_t R, hipStream_t stream) {
+  const size_t npix = f->n / 3;
+  const uint32_t w = (uint32_t)f->width, out_w = (uint32_t)kBlock - 2u * (uint32_t)R;
+  const uint32_t tiles = (w + out_w - 1) / out_w;
+  const uint64_t blocks = (uint64_t)f->rows * tiles;
+  if (blocks > 0x7FFFFFFFull) return fail(SPT_ERR_INVALID_ARG, "film too large for a pooled pass");
+  hipLaunchKernelGGL(film_pool_rows_kernel<Counts>, dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+                     (const u64*)f->sums, (const ulonglong2*)f->m2, cs, w, tiles, (uint32_t)R, npix,
+                     f->pool, f->pool + 3 * npix, (uint32_t*)(f->pool + 6 * npix));
+  FILM_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+template <class Counts>
+spt_status pool_map_launch(const spt_film* f, const Counts& cs, int32_t R, uint32_t flags, float* se_dev,
+                           hipStream_t stream) {
+  const spt_status st = pool_rows_launch(f, cs, R, stream);
+  if (st != SPT_OK) return st;
+  const size_t npix = f->n / 3;
+  hipLaunchKernelGGL(film_pool_map_kernel<Counts>, dim3(tail_blocks(npix)), dim3(kBlock), 0, stream, cs,
+                     (const double*)f->pool, (const double*)(f->pool + 3 * npix),
+                     (const uint32_t*)(f->pool + 6 * npix), npix, (uint32_t)f->width, (uint32_t)f->rows,
+                     pool_band_rows(f), R, flags, se_dev);
+  FILM_HIP(hipGetLastError());
   return SPT_OK;
 }
 
@@ -1098,5 +1287,59 @@ extern "C" spt_status spt_film_adaptive_upload(spt_film* f, const uint32_t* host
   f->samples_total = total * (int64_t)f->batch;  // what the counts imply
   f->last_pass_samples = 0;
   if (f->any_retired) return rebuild_list(f, (hipStream_t)stream);
+  return SPT_OK;
+}
+
+// ---- the pooled error: map and selection over a pixel's neighbourhood (spt.h SPT_HAS_FILM_POOL) ----
+
+extern "C" spt_status spt_film_noise_pool_map(const spt_film* f, int32_t radius, uint32_t flags,
+                                              float* se_dev, void* stream_v) {
+  if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
+  if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
+  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
+  spt_status st = pool_args(radius, flags);
+  if (st != SPT_OK) return st;
+  if (f->n == 0) return SPT_OK;
+  if (!se_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
+  hipStream_t stream = (hipStream_t)stream_v;
+  FILM_HIP(hipSetDevice(f->device));
+  st = pool_scratch(counts_owner(f));
+  if (st != SPT_OK) return st;
+  if (f->adaptive)
+    return pool_map_launch(f, pixel_counts(counts_owner(f), stream), radius, flags, se_dev, stream);
+  return pool_map_launch(f, uniform_count(f), radius, flags, se_dev, stream);
+}
+
+extern "C" spt_status spt_film_adaptive_select_pooled(spt_film* f, double se_threshold, int32_t radius,
+                                                      uint32_t flags, const uint8_t* keep_dev,
+                                                      int64_t* n_active, void* stream_v) {
+  if (!f || !n_active) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (!f->adaptive) return fail(SPT_ERR_INVALID_ARG, "not an adaptive film");
+  if (se_threshold != se_threshold) return fail(SPT_ERR_INVALID_ARG, "the threshold is NaN");
+  if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
+  spt_status st = pool_args(radius, flags);
+  if (st != SPT_OK) return st;
+  // without a threshold no error is looked at: the selection by the mask alone
+  if (se_threshold < 0.0 || f->n == 0)
+    return spt_film_adaptive_select(f, se_threshold, keep_dev, n_active, stream_v);
+  hipStream_t stream = (hipStream_t)stream_v;
+  FILM_HIP(hipSetDevice(f->device));
+  st = pool_scratch(f);
+  if (st != SPT_OK) return st;
+  const PixelCount cs = pixel_counts(f, stream);
+  st = pool_rows_launch(f, cs, radius, stream);
+  if (st != SPT_OK) return st;
+  const size_t npix = f->n / 3;
+  const double thr2 = se_threshold * se_threshold;  // once, in double
+  hipLaunchKernelGGL(film_pool_mark_kernel, dim3(tail_blocks(npix)), dim3(kBlock), 0, stream,
+                     (const u64*)f->sums, (const ulonglong2*)f->m2, f->cnt, cs.tab, keep_dev,
+                     (const double*)f->pool, (const double*)(f->pool + 3 * npix),
+                     (const uint32_t*)(f->pool + 6 * npix), npix, (uint32_t)f->width, (uint32_t)f->rows,
+                     pool_band_rows(f), radius, flags, thr2);
+  FILM_HIP(hipGetLastError());
+  st = rebuild_list(f, stream);
+  if (st != SPT_OK) return st;
+  if ((size_t)f->n_active != npix) f->any_retired = true;
+  *n_active = f->n_active;
   return SPT_OK;
 }

@@ -212,3 +212,170 @@ extern "C" spt_status spt_film_adaptive_select_host(const uint64_t* sums, const 
   *n_active = na;
   return SPT_OK;
 }
+
+// ---- the pooled error (spt.h SPT_HAS_FILM_POOL): u, its row sums h, the window sums g and n ----
+
+namespace {
+
+spt_status pool_args(int32_t band_rows, int32_t radius, uint32_t flags) {
+  if (radius < 1 || radius > SPT_POOL_MAX_RADIUS)
+    return fail(SPT_ERR_INVALID_ARG, "radius outside [1, SPT_POOL_MAX_RADIUS]");
+  if (flags & ~SPT_POOL_EXCLUDE_CENTER) return fail(SPT_ERR_INVALID_ARG, "unknown pool flag bits");
+  if (band_rows < 0) return fail(SPT_ERR_INVALID_ARG, "band_rows < 0");
+  return SPT_OK;
+}
+
+// The planes every pooled statement starts from: u per element, counted per pixel (B >= 2), and the
+// row sums over the columns of the window, ascending.
+struct PoolPlanes {
+  std::vector<double> u, h;
+  std::vector<uint32_t> counted, hn;
+};
+
+template <class Counts>
+void pool_planes(const uint64_t* sums, const uint64_t* m2, int64_t w, int64_t rows, const Counts& cs,
+                 int32_t R, PoolPlanes* P) {
+  const size_t npix = (size_t)(w * rows);
+  P->u.assign(3 * npix, 0.0);
+  P->h.assign(3 * npix, 0.0);
+  P->counted.assign(npix, 0u);
+  P->hn.assign(npix, 0u);
+  for (size_t px = 0; px < npix; ++px) {
+    const NoiseArgs& A = cs.at(px);
+    P->counted[px] = A.B >= 2 ? 1u : 0u;
+    for (size_t c = 0; c < 3; ++c)
+      P->u[3 * px + c] = pool_u((u64)sums[3 * px + c], m2_at(m2, 3 * px + c), A);
+  }
+  for (int64_t y = 0; y < rows; ++y)
+    for (int64_t x = 0; x < w; ++x) {
+      const int64_t x0 = x - R > 0 ? x - R : 0, x1 = x + R < w - 1 ? x + R : w - 1;
+      double h[3] = {0.0, 0.0, 0.0};
+      uint32_t n = 0;
+      for (int64_t xx = x0; xx <= x1; ++xx) {
+        const size_t q = (size_t)(y * w + xx);
+        for (int c = 0; c < 3; ++c) h[c] = h[c] + P->u[3 * q + c];
+        n += P->counted[q];
+      }
+      const size_t px = (size_t)(y * w + x);
+      for (int c = 0; c < 3; ++c) P->h[3 * px + c] = h[c];
+      P->hn[px] = n;
+    }
+}
+
+// g and n of pixel (y, x): the row sums over the window's rows, ascending; the centre out on request.
+void pool_window(const PoolPlanes& P, int64_t w, int64_t rows, int32_t band_rows, int32_t R,
+                 uint32_t flags, int64_t y, int64_t x, double g[3], uint32_t* n) {
+  int32_t y0, y1;
+  pool_row_window((int32_t)y, (int32_t)rows, band_rows, R, &y0, &y1);
+  g[0] = g[1] = g[2] = 0.0;
+  *n = 0;
+  for (int64_t yy = y0; yy <= y1; ++yy) {
+    const size_t q = (size_t)(yy * w + x);
+    for (int c = 0; c < 3; ++c) g[c] = g[c] + P.h[3 * q + c];
+    *n += P.hn[q];
+  }
+  const size_t px = (size_t)(y * w + x);
+  if (flags & SPT_POOL_EXCLUDE_CENTER) pool_exclude_center(g, n, &P.u[3 * px], P.counted[px] != 0);
+}
+
+template <class Counts>
+spt_status pool_map_loop(const uint64_t* sums, const uint64_t* m2, const spt_film_info* info,
+                         const Counts& cs, int32_t band_rows, int32_t R, uint32_t flags,
+                         float* se_out) {
+  PoolPlanes P;
+  try {
+    pool_planes(sums, m2, info->width, info->rows, cs, R, &P);
+  } catch (const std::bad_alloc&) {
+    return fail(SPT_ERR_OOM, "pool planes alloc");
+  }
+  for (int64_t y = 0; y < info->rows; ++y)
+    for (int64_t x = 0; x < info->width; ++x) {
+      double g[3];
+      uint32_t n;
+      pool_window(P, info->width, info->rows, band_rows, R, flags, y, x, g, &n);
+      const size_t px = (size_t)(y * info->width + x);
+      const u64 B = cs.at(px).B;
+      for (int c = 0; c < 3; ++c) se_out[3 * px + c] = pool_se(g[c], n, B);
+    }
+  return SPT_OK;
+}
+
+}  // namespace
+
+extern "C" spt_status spt_film_noise_pool_map_host(const uint64_t* sums, const uint64_t* m2,
+                                                   const uint32_t* counts,
+                                                   const spt_film_info* info,
+                                                   const spt_film_noise_info* noise,
+                                                   int32_t band_rows, int32_t radius, uint32_t flags,
+                                                   float* se_out) {
+  size_t n = 0;
+  std::vector<NoiseArgs> tab;
+  spt_status st = pool_args(band_rows, radius, flags);
+  if (st != SPT_OK) return st;
+  if (has_pixels(info) && (!sums || !m2 || !se_out))
+    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
+  st = counts ? host_args(kAdaptive, info, noise, counts, &n, &tab)
+              : host_args(kNoise, info, noise, nullptr, &n, nullptr);
+  if (st != SPT_OK) return st;
+  if (n == 0) return SPT_OK;
+  if (counts)
+    return pool_map_loop(sums, m2, info, PixelCount{counts, tab.data()}, band_rows, radius, flags,
+                         se_out);
+  return pool_map_loop(sums, m2, info, uniform(info, noise), band_rows, radius, flags, se_out);
+}
+
+extern "C" spt_status spt_film_adaptive_select_pooled_host(
+    const uint64_t* sums, const uint64_t* m2, const uint32_t* counts, const spt_film_info* info,
+    const spt_film_noise_info* noise, int32_t band_rows, double se_threshold, int32_t radius,
+    uint32_t flags, const uint8_t* keep, uint32_t* counts_out, uint32_t* list_out,
+    int64_t* n_active) {
+  size_t n = 0;
+  std::vector<NoiseArgs> tab;
+  if (!n_active) return fail(SPT_ERR_INVALID_ARG, "null n_active");
+  spt_status st = pool_args(band_rows, radius, flags);
+  if (st != SPT_OK) return st;
+  if (se_threshold != se_threshold) return fail(SPT_ERR_INVALID_ARG, "the threshold is NaN");
+  if (noise && noise->batches_done < 2)
+    return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
+  if (has_pixels(info) && (!sums || !m2 || !counts_out || !list_out))
+    return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
+  st = host_args(kAdaptive, info, noise, counts, &n, &tab);
+  if (st != SPT_OK) return st;
+  const bool all = se_threshold < 0.0;
+  const double thr2 = se_threshold * se_threshold;  // once, in double
+  PoolPlanes P;
+  if (n && !all) {  // every decision below reads these planes, made before anything is marked
+    try {
+      pool_planes(sums, m2, info->width, info->rows, PixelCount{counts, tab.data()}, radius, &P);
+    } catch (const std::bad_alloc&) {
+      return fail(SPT_ERR_OOM, "pool planes alloc");
+    }
+  }
+  int64_t na = 0;
+  for (size_t px = 0; px < n / 3; ++px) {
+    uint32_t c = counts[px];
+    if (!(c & kRetired)) {
+      bool stay = keep ? keep[px] != 0 : true;
+      if (stay && !all) {
+        double g[3];
+        uint32_t cnt_n;
+        pool_window(P, info->width, info->rows, band_rows, radius, flags,
+                    (int64_t)(px / (size_t)info->width), (int64_t)(px % (size_t)info->width), g, &cnt_n);
+        if (cnt_n) {
+          stay = pool_noisy(g, cnt_n, (u64)c, thr2);
+        } else {  // nothing to pool: the pixel's own rule
+          const m2_t m[3] = {m2_at(m2, 3 * px), m2_at(m2, 3 * px + 1), m2_at(m2, 3 * px + 2)};
+          const u64 S[3] = {(u64)sums[3 * px], (u64)sums[3 * px + 1], (u64)sums[3 * px + 2]};
+          stay = adapt_noisy(S, m, tab[c], thr2);
+        }
+      }
+      if (stay)
+        list_out[na++] = (uint32_t)px;
+      else
+        c |= kRetired;
+    }
+    counts_out[px] = c;
+  }
+  *n_active = na;
+  return SPT_OK;
+}

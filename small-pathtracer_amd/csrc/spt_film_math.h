@@ -142,6 +142,49 @@ SPT_FILM_FN bool adapt_noisy(const u64* S, const m2_t* m, const NoiseArgs& A, do
   return noisy;
 }
 
+// ---- the pooled error (spt.h SPT_HAS_FILM_POOL) ----
+
+// u: the estimated variance of a one-batch estimate of this element, in resolved units. 0 for a
+// clamped channel (noise_d) and for a pixel with fewer than two batches. Never negative and never
+// -0.0 (d >= +0), so a window sum may take 0.0 for a place outside the film: x + 0.0 is x.
+SPT_FILM_FN double pool_u(u64 S, m2_t m, const NoiseArgs& A) {
+  if (A.B < 2) return 0.0;
+  bool cl;
+  return (noise_d(S, m, A, &cl) * A.k2) * (double)A.B;
+}
+
+// The rows of pixel row y's window: y - R .. y + R clipped to the film and to the row's band (written
+// so that nothing overflows 32 bits).
+SPT_FILM_FN void pool_row_window(int32_t y, int32_t rows, int32_t band_rows, int32_t R, int32_t* y0,
+                                 int32_t* y1) {
+  int32_t b0 = 0, b1 = rows;
+  if (band_rows > 0) {
+    b0 = y - y % band_rows;
+    b1 = rows - b0 > band_rows ? b0 + band_rows : rows;
+  }
+  *y0 = y - b0 > R ? y - R : b0;
+  *y1 = b1 - 1 - y > R ? y + R : b1 - 1;
+}
+
+// The centre taken out of its own window: one subtraction per channel; counted = B_p >= 2.
+SPT_FILM_FN void pool_exclude_center(double g[3], uint32_t* n, const double u[3], bool counted) {
+  g[0] = g[0] - u[0];
+  g[1] = g[1] - u[1];
+  g[2] = g[2] - u[2];
+  if (counted) *n -= 1u;
+}
+
+// Is some channel's pooled error above the threshold? g / (n B) > thr2 without the division. n >= 1.
+SPT_FILM_FN bool pool_noisy(const double g[3], uint32_t n, u64 B, double thr2) {
+  const double t = (thr2 * (double)n) * (double)B;
+  return g[0] > t || g[1] > t || g[2] > t;
+}
+
+SPT_FILM_FN float pool_se(double g, uint32_t n, u64 B) {
+  if (n == 0 || B < 2) return 0.0f;
+  return (float)sqrt(g / ((double)n * (double)B));
+}
+
 // The summary's partial sums: of a block (stage 1), of the image (stage 2).
 struct NoisePartial {
   double s[3];  // per channel: sum of d * k2
