@@ -209,7 +209,11 @@ spt_status spt_context_destroy(spt_context* ctx);
 /* Enqueue a render on `stream` (a hipStream_t, NULL = default stream). rgb_dev: DEVICE buffer of
  * shard_rows*w*3 floats. No allocation once the context is large enough (spt_context_reserve) and
  * no host synchronisation, except that a second call before spt_context_stats() first waits for
- * the previous call's scene upload (the pinned staging buffers are reused). */
+ * the previous call's scene upload (the pinned staging buffers are reused). prims, cam and p are
+ * consumed before the call returns: the caller may change or free them at once. A context's frames
+ * share its device buffers, so its calls must be serialised by the caller and enqueued on one stream
+ * (or ordered by the caller, e.g. by an event recorded after one call that the next call's stream
+ * waits for); frames of different contexts need no ordering. */
 spt_status spt_context_reserve(spt_context* ctx, int32_t n_prims, const spt_params* p);
 spt_status spt_render_async(spt_context* ctx, const spt_prim* prims, int32_t n_prims,
                             const spt_camera* cam, const spt_params* p, float* rgb_dev,
