@@ -33,11 +33,13 @@ extern "C" {
                              entry point (so the version stays): SPT_HAS_FILM, the spt_film_* calls;
                              SPT_HAS_FILM_NOISE, the spt_film_noise_* calls; SPT_HAS_FILM_ADAPTIVE,
                              the spt_film_adaptive_* calls; SPT_HAS_FILM_POOL, spt_film_noise_pool_map,
-                             spt_film_adaptive_select_pooled and their *_host statements */
+                             spt_film_adaptive_select_pooled and their *_host statements;
+                             SPT_HAS_GUIDE, the spt_guide_* calls */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
 #define SPT_HAS_FILM_POOL 1 /* the error pooled over a pixel's neighbourhood: map and selection (below) */
+#define SPT_HAS_GUIDE 1 /* guide planes: first-hit albedo, normal, depth and coverage (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -484,6 +486,73 @@ spt_status spt_film_adaptive_select_pooled_host(const uint64_t* sums, const uint
                                                 double se_threshold, int32_t radius, uint32_t flags,
                                                 const uint8_t* keep_or_null, uint32_t* counts_out,
                                                 uint32_t* list_out, int64_t* n_active);
+
+/* ---- guide planes: first-hit albedo, normal, depth and coverage (SPT_HAS_GUIDE) ----
+ * The noise-free per-pixel features of the first hit, for a denoiser's edge-stopping terms, an
+ * adaptive pass's keep mask or a compositor. For pixel p, sample index s in [0, spp) and the seed, a
+ * guide takes THE RENDER'S OWN first ray: Philox counter (p, s, 1, seed), the jitter from the low
+ * bytes, the camera's fma chain of contract v5 in its general form, the direction normalised by the
+ * scene's direction contract (rsq_nr with a sphere or a REFR primitive in the scene, else rsq_nr1) --
+ * and its nearest hit (hit, t, id) of the contract, t the winner's exact t. Each sample that hits adds
+ * one record to the pixel's 64-byte record int64[8]; a miss adds nothing (no "primitive 0 on a miss"):
+ *   slots 0-2 albedo  fix(c_k), the hit primitive's colour (fp32 as uploaded), fix = the render's own
+ *                     1.31 conversion: fminf(c * inv_spp, 1) * 2^31 truncated, inv_spp = 1 / spp
+ *   slots 3-5 normal  sgn(nl_k) * fix(fabsf(nl_k)), nl the normal oriented against the ray: a
+ *                     rectangle's +-axis, signed by the ray's component on that axis; a sphere's
+ *                     gn = (x - centre) * (1 / r), x = o + d * t (a multiply, then an add), negated when
+ *                     dot(gn, d) >= 0
+ *   slot 6 depth      (uint64)(fminf(t, 2^20) * 65536.0f): a power-of-two scale, then truncation
+ *   slot 7 hits       1
+ * spp is at most 2^24 (slot 6 cannot overflow; SPT_ERR_INVALID_ARG at creation). All slots are
+ * integers, so the sums depend on no lane mapping, window split, window order, shard or GPU: a guide
+ * filled with every index of [0, spp) exactly once is one well-defined object. Records are in image
+ * pixel order, a shard's guide holds its compact rows (spt_shard_rows), as a film does.
+ * Depth is the ray parameter along the contract's direction: the distance where directions are unit,
+ * and within the free-scale contract's 1.8e-3 of it in rect-only DIFF scenes. Albedo is the first
+ * hit's own colour: a mirror or a glass ball reads as its .999.
+ * The resolve, n = samples_done, r = (float)((double)spp_total / n) (device kernel and host statement
+ * run the same IEEE operations):
+ *   albedo_k = min(((float)S_k * 2^-31) [* r when n < spp_total], 1)     spt_film_resolve's rule
+ *   normal_k = sgn(S_k) * (((float)|S_k| * 2^-31) [* r])     not clamped, not renormalised: a length
+ *                                                             below 1 at an edge is information
+ *   depth    = hits ? (float)((double)S_6 / ((double)hits * 65536.0)) : 0    the mean over the hits
+ *   coverage = (float)((double)hits / (double)n)
+ *   n == 0: zeros everywhere. */
+typedef struct spt_guide spt_guide;
+typedef struct spt_guide_info {
+  int32_t width, rows, spp_total; /* rows = the shard's row count */
+  int64_t samples_done;           /* samples per pixel added so far, 0 .. spp_total */
+  int32_t lanes_per_pixel;        /* lanes of a wave that shared a pixel in the last launch (a power of
+                                     two, 1..64: the launch's sizing, never a result); 0 before any */
+  int32_t reserved;
+} spt_guide_info;
+int32_t spt_guide_info_size(void); /* sizeof(spt_guide_info) as the library was built */
+/* A zeroed guide on `device` for passes with p's width, height, spp (= spp_total) and shard fields. */
+spt_status spt_guide_create(int32_t device, const spt_params* p, spt_guide** out);
+spt_status spt_guide_destroy(spt_guide* guide);
+spt_status spt_guide_clear(spt_guide* guide, void* stream); /* records and samples_done back to 0 */
+spt_status spt_guide_info_get(const spt_guide* guide, spt_guide_info* out);
+/* Enqueue the guide pass of the window on `stream`. The rules are a film pass's: p's width, height,
+ * spp and shard fields must equal the guide's, the window must lie in [0, spp) with sample_count >= 1,
+ * samples_done + sample_count must not exceed spp -- SPT_ERR_INVALID_ARG otherwise, nothing queued, the
+ * guide untouched. ctx and guide must be on one device. Keeping windows disjoint is the caller's duty.
+ * The pass goes through ctx's scene upload and pinned staging (so spt_render_async's reuse rule
+ * holds: a call first waits for the previous call's upload) and must be ordered with ctx's other calls
+ * on one stream, but it is no render: spt_context_stats and spt_context_kernel still describe the
+ * context's last render. A shard without rows only counts. */
+spt_status spt_guide_render_async(spt_context* ctx, spt_guide* guide, const spt_prim* prims,
+                                  int32_t n_prims, const spt_camera* cam, const spt_params* p,
+                                  int32_t sample_base, int32_t sample_count, void* stream);
+/* Guide -> float planes (DEVICE; any of them may be NULL): albedo and normal rows*w*3 floats, depth and
+ * coverage rows*w floats. */
+spt_status spt_guide_resolve(const spt_guide* guide, float* albedo_dev, float* normal_dev,
+                             float* depth_dev, float* coverage_dev, void* stream);
+/* The records to HOST memory (rows*w*8 int64, pixel order); waits for its copy on `stream`. */
+spt_status spt_guide_download(const spt_guide* guide, int64_t* host_records, void* stream);
+/* The resolve as a pure host function (no device); planes may be NULL. Uses info's width, rows,
+ * spp_total and samples_done. */
+spt_status spt_guide_resolve_host(const int64_t* records, const spt_guide_info* info, float* albedo,
+                                  float* normal, float* depth, float* coverage);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

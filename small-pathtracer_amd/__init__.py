@@ -119,6 +119,12 @@ class spt_film_adaptive_info(ctypes.Structure):
                 ("n_active", ctypes.c_int64), ("samples_total", ctypes.c_int64)]
 
 
+class spt_guide_info(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("rows", ctypes.c_int32), ("spp_total", ctypes.c_int32),
+                ("samples_done", ctypes.c_int64), ("lanes_per_pixel", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -151,7 +157,13 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_film_adaptive_resolve_host", "spt_film_adaptive_noise_map_host",
            "spt_film_adaptive_noise_summary_host", "spt_film_adaptive_select_host",
            "spt_film_noise_pool_map", "spt_film_adaptive_select_pooled",
-           "spt_film_noise_pool_map_host", "spt_film_adaptive_select_pooled_host"]
+           "spt_film_noise_pool_map_host", "spt_film_adaptive_select_pooled_host",
+           "spt_guide_info_size", "spt_guide_create", "spt_guide_destroy", "spt_guide_clear",
+           "spt_guide_info_get", "spt_guide_render_async", "spt_guide_resolve", "spt_guide_download",
+           "spt_guide_resolve_host"]
+SPT_HAS_GUIDE = 1           # include/spt.h: the spt_guide_* calls (Guide, render_guides)
+GUIDE_SLOTS = 8             # a guide record: albedo 0-2, normal 3-5, depth 6 (48.16), hits 7
+GUIDE_MAX_SPP = 1 << 24
 COUNT_RETIRED = 0x80000000  # bit 31 of an adaptive film's counts: the pixel takes no more batches
 COUNT_MASK = 0x7FFFFFFF     # ... and the batches it holds
 POOL_MAX_RADIUS = 16        # SPT_POOL_MAX_RADIUS: the pooled calls take a radius in [1, 16]
@@ -289,8 +301,18 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_film_adaptive_select_pooled_host.argtypes = [VP, VP, VP, P(spt_film_info),
                                                          P(spt_film_noise_info), I32, ctypes.c_double,
                                                          I32, U32, VP, VP, VP, P(I64)]
+    lib.spt_guide_info_size.argtypes = []
+    lib.spt_guide_create.argtypes = [I32, P(spt_params), P(VP)]
+    lib.spt_guide_destroy.argtypes = [VP]
+    lib.spt_guide_clear.argtypes = [VP, VP]
+    lib.spt_guide_info_get.argtypes = [VP, P(spt_guide_info)]
+    lib.spt_guide_render_async.argtypes = [VP, VP, P(spt_prim), I32, P(spt_camera), P(spt_params),
+                                           I32, I32, VP]
+    lib.spt_guide_resolve.argtypes = [VP, VP, VP, VP, VP, VP]
+    lib.spt_guide_download.argtypes = [VP, VP, VP]
+    lib.spt_guide_resolve_host.argtypes = [VP, P(spt_guide_info), VP, VP, VP, VP]
     for name in EXPORTS:
-        if name.startswith("spt_film_"):
+        if name.startswith("spt_film_") or name.startswith("spt_guide_"):
             getattr(lib, name).restype = I32
     for name in ("spt_comm_unique_id", "spt_comm_create", "spt_comm_destroy", "spt_comm_reserve",
                  "spt_gather_framebuffer", "spt_deinterleave_rows", "spt_render_multi",
@@ -317,7 +339,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
 KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_variants.h", "csrc/spt_kparams.h", "csrc/spt_launch.h",
                   "csrc/spt_dispatch.cpp", "csrc/spt_context.cpp",
                   "csrc/spt_device.h", "csrc/spt_cornell.h", "csrc/spt_diag.h", "csrc/Makefile", "../include/spt.h", "../include/spt_flops.h", "csrc/spt_film.hip",
-                  "csrc/spt_film.h", "csrc/spt_film_math.h", "csrc/spt_film_host.cpp")
+                  "csrc/spt_film.h", "csrc/spt_film_math.h", "csrc/spt_film_host.cpp",
+                  "csrc/spt_guide.hip", "csrc/spt_guide_host.cpp", "csrc/spt_guide.h")
 
 
 def kernel_sources_sha16() -> str:
@@ -1050,6 +1073,111 @@ class Film:
         list and sets the front."""
         self._upload(self.lib.spt_film_adaptive_upload, counts, 1, np.uint32,
                      "counts do not have rows * width elements", stream_ptr)
+
+
+# ---------------------------------------------------------------------------------------------
+# Guide planes: first-hit albedo, normal, depth and coverage (spt_guide_*)
+# ---------------------------------------------------------------------------------------------
+GUIDE_PLANES = ("albedo", "normal", "depth", "coverage")
+
+
+def guide_resolve_host(records: np.ndarray, width: int, rows: int, spp_total: int,
+                       samples_done: int) -> dict:
+    """spt_guide_resolve_host(): the CPU statement of the guide's resolve (no device). records:
+    rows * width * 8 int64. -> {"albedo", "normal": (rows, width, 3), "depth", "coverage": (rows,
+    width)} float32."""
+    a = np.ascontiguousarray(records, dtype=np.int64)
+    info = spt_guide_info(int(width), int(rows), int(spp_total), int(samples_done), 0, 0)
+    rr, ww = max(info.rows, 0), max(info.width, 0)
+    if a.size != GUIDE_SLOTS * rr * ww:
+        raise SptError(1, "records do not have rows * width * 8 elements")
+    out = {"albedo": np.empty((rr, ww, 3), np.float32), "normal": np.empty((rr, ww, 3), np.float32),
+           "depth": np.empty((rr, ww), np.float32), "coverage": np.empty((rr, ww), np.float32)}
+    _check(load_library().spt_guide_resolve_host(a.ctypes.data, ctypes.byref(info),
+                                                 *[out[k].ctypes.data for k in GUIDE_PLANES]))
+    return out
+
+
+class Guide:
+    """spt_guide: per pixel the integer sums of the first hit's colour, oriented normal, ray parameter
+    and hit count over the samples added so far, on the device. The rays are the render's own camera
+    rays, so passes over disjoint sample windows add up to one object whatever the split."""
+
+    def __init__(self, params: spt_params, device: int = 0):
+        self.lib = load_library()
+        self._g = ctypes.c_void_p()
+        _check(self.lib.spt_guide_create(int(device), ctypes.byref(params), ctypes.byref(self._g)))
+        self.device = device
+
+    def close(self):
+        if self._g:
+            self.lib.spt_guide_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def info(self) -> dict:
+        i = spt_guide_info()
+        _check(self.lib.spt_guide_info_get(self._g, ctypes.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in i._fields_ if k != "reserved"}
+
+    def clear(self, stream_ptr: int = 0):
+        _check(self.lib.spt_guide_clear(self._g, ctypes.c_void_p(stream_ptr or None)))
+
+    def render(self, renderer: "Renderer", prims, cam: Camera, params: spt_params, base: int,
+               count: int, stream_ptr: int = 0):
+        """Enqueue the first hits of samples [base, base + count) of the params.spp-sample image and
+        add them. The renderer's statistics and kernel() still describe its last render."""
+        renderer._prims = _scene_array(prims)
+        _check(self.lib.spt_guide_render_async(renderer._ctx, self._g, renderer._prims, len(prims),
+                                               ctypes.byref(cam._c), ctypes.byref(params), int(base),
+                                               int(count), ctypes.c_void_p(stream_ptr or None)))
+
+    def to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
+        """The records on the host: (rows, width, 8) int64."""
+        i = self.info()
+        out = np.zeros((i["rows"], i["width"], GUIDE_SLOTS), dtype=np.int64)
+        _check(self.lib.spt_guide_download(self._g, out.ctypes.data, ctypes.c_void_p(stream_ptr or None)))
+        return out
+
+    def resolve(self, planes=GUIDE_PLANES, stream_ptr: int = 0) -> dict:
+        """The device resolve of the planes asked for -> {"albedo", "normal": (rows, width, 3),
+        "depth", "coverage": (rows, width)} float32 on the host."""
+        import torch
+        i = self.info()
+        n = i["rows"] * i["width"]
+        with torch.cuda.device(self.device):
+            bufs = {k: torch.empty(max(1, n * (3 if k in ("albedo", "normal") else 1)),
+                                   dtype=torch.float32, device=f"cuda:{self.device}")
+                    for k in GUIDE_PLANES if k in planes}
+            _check(self.lib.spt_guide_resolve(
+                self._g, *[ctypes.c_void_p(bufs[k].data_ptr() if k in bufs else None)
+                           for k in GUIDE_PLANES], ctypes.c_void_p(stream_ptr or None)))
+            torch.cuda.synchronize(self.device)
+        out = {}
+        for k, b in bufs.items():
+            c = 3 if k in ("albedo", "normal") else 1
+            a = b[: n * c].cpu().numpy()
+            out[k] = a.reshape(i["rows"], i["width"], 3) if c == 3 else a.reshape(i["rows"], i["width"])
+        return out
+
+
+def render_guides(prims: Sequence[spt_prim], cam: Camera, params: spt_params) -> dict:
+    """The guide planes of the full window [0, params.spp): {"albedo", "normal", "depth",
+    "coverage"} as float32 arrays on the host (Guide.resolve)."""
+    import torch
+    r, g = Renderer(params.device), Guide(params, params.device)
+    try:
+        with torch.cuda.device(params.device):
+            g.render(r, prims, cam, params, 0, params.spp, torch.cuda.current_stream().cuda_stream)
+            return g.resolve(stream_ptr=torch.cuda.current_stream().cuda_stream)
+    finally:
+        g.close()
+        r.close()
 
 
 def _film_buffer(film: Film):

@@ -3,6 +3,13 @@
 //               [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]
 //               [--device N | --devices N] [--p6 | --pfm]
 //               [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]
+//               [--guides PREFIX] [--help]
+//   --guides PREFIX: beside the image, the guide planes of the same scene, camera, W H SPP and SEED
+//               (spt_guide_*: the first hit of every sample's own camera ray) as PREFIX_albedo.pfm,
+//               PREFIX_normal.pfm and PREFIX_depth.pfm. The PFM encoder writes the floats as they
+//               are, so the normal is stored signed (components in [-1, 1], not 0.5 + 0.5 n) and the
+//               depth (the mean ray parameter of the samples that hit) is replicated to the three
+//               channels. The image file is the same bytes as without the flag.
 //   --uniform: random_scattering from the commented-out uniform hemisphere code (:352-359)
 //   --reference-leaks: leaked paths go on from the miss vertex as the reference's (:371-377)
 //                      instead of ending at their first miss (SPT_FLAG_REFERENCE_LEAKS)
@@ -224,6 +231,50 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
   return dev;
 }
 
+// --guides: the guide planes of the full window, resolved on the device and written as three PFMs.
+void write_guides(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
+                  const std::string& prefix) {
+  spt_context* ctx = nullptr;
+  spt_guide* guide = nullptr;
+  check(spt_context_create(p.device, &ctx));
+  check(spt_guide_create(p.device, &p, &guide));
+  spt_guide_info info{};
+  check(spt_guide_info_get(guide, &info));
+  const size_t npix = (size_t)info.rows * (size_t)info.width;
+  float* dev = nullptr;  // albedo, normal (3 floats each), depth (1)
+  if (hipMalloc(&dev, std::max<size_t>(npix, 1) * 7 * sizeof(float)) != hipSuccess)
+    throw std::runtime_error("device allocation failed");
+  check(spt_guide_render_async(ctx, guide, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
+                               p.spp, nullptr));
+  check(spt_guide_resolve(guide, dev, dev + 3 * npix, dev + 6 * npix, nullptr, nullptr));
+  std::vector<float> host(7 * npix), depth3(3 * npix);
+  if (hipMemcpy(host.data(), dev, host.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+    throw std::runtime_error("guide download failed");
+  for (size_t i = 0; i < npix; ++i) depth3[3 * i] = depth3[3 * i + 1] = depth3[3 * i + 2] = host[6 * npix + i];
+  const struct { const char* name; const float* data; } planes[3] = {
+      {"_albedo.pfm", host.data()}, {"_normal.pfm", host.data() + 3 * npix}, {"_depth.pfm", depth3.data()}};
+  for (const auto& pl : planes) {
+    const std::string path = prefix + pl.name;
+    if (write_ppm(path.c_str(), info.width, info.rows, pl.data, p.device, SPT_IMAGE_PFM))
+      throw std::runtime_error("cannot write " + path + ": " + spt_last_error());
+  }
+  (void)hipFree(dev);
+  check(spt_guide_destroy(guide));
+  check(spt_context_destroy(ctx));
+}
+
+const char kUsage[] =
+    "smallpt_amd [W H SPP [SEED [OUT.ppm]]] [--cos] [--uniform] [--reference-leaks] [--q Q]\n"
+    "            [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]\n"
+    "            [--device N | --devices N] [--p6 | --pfm] [--repeat N] [--passes K]\n"
+    "            [--film PATH [--add N]]\n"
+    "            [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]\n"
+    "            [--guides PREFIX]\n"
+    "  --guides PREFIX  also write the first-hit guide planes PREFIX_albedo.pfm, PREFIX_normal.pfm\n"
+    "                   and PREFIX_depth.pfm (linear PFM). The normal is stored signed, components\n"
+    "                   in [-1, 1] (not 0.5 + 0.5 n); the depth is the mean ray parameter of the\n"
+    "                   samples that hit, replicated to three channels. One device (no --devices).\n";
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -234,6 +285,7 @@ int main(int argc, char* argv[]) {
   int device = 0, devices = 0, max_depth = 0, npos = 0, format = SPT_IMAGE_P3, repeat = 1;
   int passes = 0, add = 0;
   const char* film_path = nullptr;
+  const char* guides = nullptr;
   NoiseOpts noise;
   float q = -1.0f;
   for (int i = 1; i < argc; ++i) {
@@ -258,6 +310,8 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--min-batches") && i + 1 < argc) noise.min_batches = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--pool") && i + 1 < argc) noise.pool_radius = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--pool-loo")) noise.pool_loo = true;
+    else if (!std::strcmp(argv[i], "--guides") && i + 1 < argc) guides = argv[++i];
+    else if (!std::strcmp(argv[i], "--help")) { std::cout << kUsage; return 0; }
     else if (!std::strcmp(argv[i], "--p6")) format = SPT_IMAGE_P6;
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
     else if (npos < 4) pos[npos++] = std::atoi(argv[i]);
@@ -277,12 +331,15 @@ int main(int argc, char* argv[]) {
   spt_stats st{};
   std::vector<float> c;
   const float* image = nullptr;  // what the writer reads: c's data, or the film's device image
+  std::vector<spt_prim> guide_scene;
   try {
+    if (guides && devices > 0) throw std::runtime_error("--guides goes with one device");
     const std::vector<spt_prim> scene = classic ? smallpt_classic_scene()
                                         : mirror_glass ? smallpt_mirror_glass_scene()
                                         : specular ? cornell_specular_scene()
                                         : spheres ? spheres32_scene()
                                                   : cornell_scene();
+    if (guides) guide_scene = scene;
     if (passes > 0 || film_path || noise.on || noise.adaptive || noise.pool_radius || noise.pool_loo) {
       if (devices > 0 || repeat > 1)
         throw std::runtime_error("--passes / --film / --noise go with one device and no --repeat");
@@ -320,6 +377,14 @@ int main(int argc, char* argv[]) {
   if (write_ppm(out, p.width, p.height, image, device, format)) {
     std::cerr << "cannot write " << out << ": " << spt_last_error() << std::endl;
     return 1;
+  }
+  if (guides) {  // after the image: its bytes are those of a run without the flag
+    try {
+      write_guides(guide_scene, cam, p, guides);
+    } catch (const std::exception& e) {
+      std::cerr << "guides failed: " << e.what() << std::endl;
+      return 1;
+    }
   }
   const auto t2 = std::chrono::high_resolution_clock::now();
   std::cout << "WRITE_MS : " << std::chrono::duration<double, std::milli>(t2 - w0).count() << std::endl;

@@ -14,6 +14,7 @@
 #include "../../include/spt_flops.h"
 #include "spt_diag.h"
 #include "spt_film.h"
+#include "spt_guide.h"
 #include "spt_launch.h"
 
 using namespace spt;
@@ -58,6 +59,11 @@ struct spt_context {
   double scene_flop = 0;     // FLOP-model cost of one ray against the scene
   spt_film* last_film = nullptr;  // the film of the last launch (nullptr: a plain render)
   int32_t last_film_count = 0;    // ... and the samples that pass added to its samples_done
+  // A guide pass (spt_guide_window) goes through the same scene upload and staging but is no render:
+  // it has its own upload event, and leaves everything above alone (stats, last_kv, the film).
+  hipEvent_t ev_guide = nullptr;
+  bool guide_pending = false;     // the staging may still be read by a guide pass's upload
+  int guide_bpc[2] = {0, 0};      // resident blocks per CU of the guide kernels (generic, wide); 0: not asked yet
 };
 
 extern "C" int32_t spt_shard_rows(const spt_params* p, int32_t* rows_out, int32_t cap);
@@ -130,6 +136,7 @@ extern "C" spt_status spt_context_destroy(spt_context* c) {
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
+  if (c->ev_guide) (void)hipEventDestroy(c->ev_guide);
   if (c->h_stats) (void)hipHostFree(c->h_stats);
   if (c->last_film) spt_film_forget_context(c->last_film, c);
   delete c;
@@ -185,6 +192,10 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
 
   KParams K{};
   if (c->pending) SPT_HIP(hipEventSynchronize(c->ev0));  // staging still read by a prior upload
+  if (c->guide_pending) {  // ... or by a guide pass's
+    SPT_HIP(hipEventSynchronize(c->ev_guide));
+    c->guide_pending = false;
+  }
   to_dev(prims, n_prims, c->h_prims);
   int light_pos = -1;
   build_geo(prims, n_prims, c->h_geo, p->light_id, &light_pos);
@@ -288,6 +299,79 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   c->last_kv = kv;
   return SPT_OK;
 }
+
+// One guide launch over the sample window (spt_guide.h): the context's scene upload and staging, the
+// guide kernel, the records of `rec_dev` (int64[rows * w][8]) updated in place. The context's render
+// state -- statistics, last kernel, last film, the events spt_context_stats reads -- is not touched.
+// force_k > 0 (a measurement's override, never the ABI's): that many lanes per pixel.
+spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
+                            const spt_camera* cam, const spt_params* p, int32_t s_base,
+                            int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
+                            void* stream_v) {
+  if (!c || !rec_dev) return fail(SPT_ERR_INVALID_ARG, "null context/guide");
+  spt_status st = validate(prims, n_prims, cam, p);
+  if (st != SPT_OK) return st;
+  if (s_base < 0 || s_count < 1 || (int64_t)s_base + s_count > p->spp)
+    return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
+  const int rows = spt_shard_row_count(p);
+  if (rows == 0) return SPT_OK;
+  SPT_HIP(hipSetDevice(c->device));
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (!c->ev_guide) SPT_HIP(hipEventCreate(&c->ev_guide));
+
+  KParams K{};
+  if (c->pending) SPT_HIP(hipEventSynchronize(c->ev0));  // staging still read by a prior upload
+  if (c->guide_pending) SPT_HIP(hipEventSynchronize(c->ev_guide));
+  c->guide_pending = false;
+  to_dev(prims, n_prims, c->h_prims);
+  int light_pos = -1;
+  build_geo(prims, n_prims, c->h_geo, p->light_id, &light_pos);
+  const bool wide = c->h_geo->n_sph_wide > 0;
+  if (c->guide_bpc[wide] == 0) {
+    const int bpc = guide_kernel_occupancy(wide);
+    c->guide_bpc[wide] = bpc > 0 ? bpc : 4;
+  }
+  // the fp32 camera and the launch's terms (shard, magic divisors, fixed-point scale, camera chain)
+  // as a render of the scene's run-time kernel would set them; the unit and queue sizes are unused
+  (void)select_variant(prims, n_prims, cam, p, *c->h_geo, light_pos, &K);
+  LaunchPlan plan;
+  spt_params q = *p;
+  q.chunk = s_count;  // one unit per pixel: never "too many work units"
+  st = plan_launch(c->n_cu, c->guide_bpc[wide], wide ? KV_WIDE : KV_GENERIC, &q, s_count,
+                   rows * p->width, &K, &plan);
+  if (st != SPT_OK) return st;
+  int k = force_k > 0 ? force_k : guide_lanes_per_pixel(c->n_cu, c->guide_bpc[wide], K.n_local_pix, s_count);
+  uint32_t ksh = 0;
+  while ((1 << (ksh + 1)) <= k && ksh < 6) ++ksh;
+  k = 1 << ksh;
+  const uint64_t lanes = (uint64_t)K.n_local_pix << ksh;
+  const uint64_t grid = (lanes + kBlock - 1) / kBlock;
+  if (grid >= 0x7FFFFFFFull) return fail(SPT_ERR_INVALID_ARG, "the guide launch is too large");
+  SPT_HIP(hipMemcpyAsync(c->prims, c->h_prims, sizeof(DevPrim) * n_prims, hipMemcpyHostToDevice,
+                         stream));
+  SPT_HIP(hipMemcpyAsync(c->geo, c->h_geo, sizeof(SceneGeo), hipMemcpyHostToDevice, stream));
+  K.prims = c->prims;
+  K.geo = c->geo;
+  K.n_prims = n_prims;
+  K.width = p->width; K.height = p->height; K.spp = p->spp;
+  K.s_base = (uint32_t)s_base; K.s_count = (uint32_t)s_count; K.s_lim = (uint32_t)(s_base + s_count);
+  K.seed = p->seed;
+  K.unit_dirs = 0;  // the ray-direction contract, as spt_render_window states it
+  for (int i = 0; i < n_prims; ++i)
+    if (prims[i].kind == SPT_SPHERE || prims[i].refl == SPT_REFR) K.unit_dirs = 1;
+  K.guide_rec = rec_dev;
+  K.guide_kshift = ksh;
+  *c->h_kp = K;
+  SPT_HIP(hipMemcpyAsync(c->d_kp, c->h_kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
+  SPT_HIP(hipEventRecord(c->ev_guide, stream));
+  c->guide_pending = true;
+  launch_guide_kernel(wide, (int)grid, c->d_kp, stream);
+  SPT_HIP(hipGetLastError());
+  if (lanes_out) *lanes_out = k;
+  return SPT_OK;
+}
+
+int spt_context_device(const spt_context* c) { return c ? c->device : -1; }
 
 extern "C" spt_status spt_render_async(spt_context* c, const spt_prim* prims, int32_t n_prims,
                                        const spt_camera* cam, const spt_params* p, float* rgb_dev,

@@ -707,6 +707,15 @@ spt_status plan_launch(int n_cu, int variant_bpc, int kv, const spt_params* p, i
   return SPT_OK;
 }
 
+int guide_lanes_per_pixel(int n_cu, int bpc, int n_local_pix, int32_t s_count) {
+  const uint64_t lanes = (uint64_t)std::max(1, n_cu) * (uint64_t)std::max(1, bpc) * kBlock;
+  int cap = 1;  // the window's sample count rounded up to a power of two
+  while (cap < 64 && cap < s_count) cap <<= 1;
+  int k = 1;
+  while (k < cap && (uint64_t)std::max(1, n_local_pix) * (uint64_t)k < lanes) k <<= 1;
+  return k;
+}
+
 }  // namespace spt
 
 using namespace spt;

@@ -1596,4 +1596,140 @@ void launch_finalize_slots(const unsigned long long* accum, const unsigned long 
                      (hipStream_t)stream, accum, slots, rgb, npix, n_chunks, scr_k, scr_q, stats);
 }
 
+// ---- The guide planes (include/spt.h, SPT_HAS_GUIDE): the render's own first ray of every sample
+// of the window, stopped at its first vertex. Per hit sample the pixel's record int64[8] takes the
+// hit primitive's colour in the render's 1.31 fixed point (fix31), the oriented normal as
+// sgn * fix31(|n|), the ray parameter in 48.16 and a hit count; a miss adds nothing.
+// Every (pixel, sample) costs the same -- one Philox call, one trace -- so there is no queue and no
+// stealing: K = 2^guide_kshift lanes of one wave share local pixel lp = global lane >> kshift, lane l
+// of the group takes samples s_base + l, + K, ..., the eight partial sums are reduced over the group
+// with an xor butterfly of cross-lane moves (no LDS memory), and the group's first lane does the
+// read-add-write of the record. Within a launch a pixel belongs to one group and launches on one guide
+// are ordered by the caller's stream, so no atomics. The integers make the sums independent of K,
+// the window split and the shard.
+// The camera ray is the general form of contract v5 with P_c per pixel (render_kernel's CAMAX 2
+// arithmetic: the same bits as the inline general form, oracle c_path).
+__device__ __forceinline__ long long shfl_xor64(long long v, int m) {
+  const int lo = __shfl_xor((int)(uint32_t)(unsigned long long)v, m, 64);
+  const int hi = __shfl_xor((int)(uint32_t)((unsigned long long)v >> 32), m, 64);
+  return (long long)(((unsigned long long)(uint32_t)hi << 32) | (unsigned long long)(uint32_t)lo);
+}
+template <class TP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SPT_NUM_SGPR)))
+guide_kernel(const KParams* __restrict__ Pg) {
+  static_assert(!TP::CONSTGEO && TP::MAT && TP::SPH, "the guide kernel runs the run-time topologies");
+  __shared__ DevPrim s_prims[kMaxPrims];
+  __shared__ int s_pos2idx[kMaxPrims];  // grouped position -> primitive index
+  __shared__ GeoTest s_test[TP::WIDE ? 1 : kMaxPrims];
+  {  // the block's staging, as render_kernel's
+    const SPT_CONST KParams* P = cptr(Pg);
+    const SPT_CONST SceneGeo* G = cptr(P->geo);
+    const int nrect = G->n_xy + G->n_xz + G->n_yz;
+    for (int i = threadIdx.x; i < P->n_prims; i += kBlock) {
+      s_prims[i] = P->prims[i];
+      s_pos2idx[i] = i < nrect ? G->rect[i].idx : G->sph[i - nrect].idx;
+      if (!TP::WIDE && i < G->n_txy + G->n_txz + G->n_tyz + 3 * G->has_room + 3 * G->n_box) {
+        const SPT_CONST GeoTest& q = G->test[i];
+        s_test[i] = GeoTest{q.k0, q.k1, q.ma, q.ha, q.mb, q.hb, q.pos0, q.pos1};
+      }
+    }
+  }
+  __syncthreads();
+
+  const SPT_CONST KParams* P = cptr(Pg);
+  const uint32_t ksh = P->guide_kshift, K = 1u << ksh;
+  const uint32_t gl = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  const uint32_t lp = gl >> ksh, l = gl & (K - 1u);
+  const bool live = lp < (uint32_t)P->n_local_pix;  // (a group is live or not as a whole)
+  long long a0 = 0, a1 = 0, a2 = 0, n0 = 0, n1 = 0, n2 = 0, dsum = 0, hits = 0;
+  if (live) {
+    PxKey pk;
+    float fx, fy;
+    pixel_terms<false>(P, lp, pk, fx, fy);
+    const f3 o = mk(P->cam[0], P->cam[1], P->cam[2]);
+    const float px = fmaf(P->cam_au[0], fx, fmaf(P->cam_av[0], fy, P->cam_l[0]));
+    const float py = fmaf(P->cam_au[1], fx, fmaf(P->cam_av[1], fy, P->cam_l[1]));
+    const float pz = fmaf(P->cam_au[2], fx, fmaf(P->cam_av[2], fy, P->cam_l[2]));
+    const bool unit = unit_dirs_of<TP>(Pg);
+    const float scale = P->fix_scale;
+    const uint32_t s_lim = P->s_lim;
+    for (uint32_t s = P->s_base + l; s < s_lim; s += K) {
+      const SPT_CONST KParams* C = cptr(Pg);  // re-issued scalar loads, not long-lived SGPRs
+      const SPT_CONST SceneGeo* G = cptr(C->geo);
+      const u4 r = philox_px(pk, s, 1u);
+      const float Fu = jitter_f(r.x, r.y), Fv = jitter_f(r.z, r.w);
+      const f3 v = mk(fmaf(Fv, C->cam_cv[0], fmaf(Fu, C->cam_cu[0], px)),
+                      fmaf(Fv, C->cam_cv[1], fmaf(Fu, C->cam_cu[1], py)),
+                      fmaf(Fv, C->cam_cv[2], fmaf(Fu, C->cam_cu[2], pz)));
+      const f3 d = normalize_dir(v, unit);
+      int id = 0, hpos;
+      float ia_hit = 0.0f;
+      uint32_t n_miss = 0;
+      f3 inv;
+      const bool hit = intersect_scene<TP, false>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph,
+                                                  s_pos2idx, o, d, id, ia_hit, hpos, n_miss, inv);
+      if (hit) {
+        const DevPrim& H = s_prims[id];
+        const float t = hit_t<TP>(H, hpos, o, d, ia_hit, G);  // the winner's exact t
+        f3 nl;
+        if (H.kind == SPT_RECT_XY) {
+          nl = d.z < 0.0f ? mk(0, 0, 1) : mk(0, 0, -1);
+        } else if (H.kind == SPT_RECT_XZ) {
+          nl = d.y < 0.0f ? mk(0, 1, 0) : mk(0, -1, 0);
+        } else if (H.kind == SPT_RECT_YZ) {
+          nl = d.x < 0.0f ? mk(1, 0, 0) : mk(-1, 0, 0);
+        } else {  // Sphere::normal as (x - p) * (1/r), x = o + d * t (render_kernel, oracle c_path)
+          const f3 x = mk(o.x + d.x * t, o.y + d.y * t, o.z + d.z * t);
+          const f3 n = mk((x.x - H.w1) * H.w5, (x.y - H.w2) * H.w5, (x.z - H.w3) * H.w5);
+          nl = dot3(n, d) < 0.0f ? n : mk(-n.x, -n.y, -n.z);
+        }
+        a0 += (long long)fix31(H.cx, scale);
+        a1 += (long long)fix31(H.cy, scale);
+        a2 += (long long)fix31(H.cz, scale);
+        const long long m0 = (long long)fix31(fabsf(nl.x), scale), m1 = (long long)fix31(fabsf(nl.y), scale);
+        const long long m2 = (long long)fix31(fabsf(nl.z), scale);
+        n0 += nl.x < 0.0f ? -m0 : m0;
+        n1 += nl.y < 0.0f ? -m1 : m1;
+        n2 += nl.z < 0.0f ? -m2 : m2;
+        dsum += (long long)(unsigned long long)(fminf(t, 0x1p20f) * 65536.0f);
+        hits += 1;
+      }
+    }
+  }
+  // the group's sums: every lane of the wave takes part (a dead group's lanes hold zeros)
+  for (uint32_t m = 1; m < K; m <<= 1) {
+    a0 += shfl_xor64(a0, (int)m);
+    a1 += shfl_xor64(a1, (int)m);
+    a2 += shfl_xor64(a2, (int)m);
+    n0 += shfl_xor64(n0, (int)m);
+    n1 += shfl_xor64(n1, (int)m);
+    n2 += shfl_xor64(n2, (int)m);
+    dsum += shfl_xor64(dsum, (int)m);
+    hits += shfl_xor64(hits, (int)m);
+  }
+  if (live && l == 0) {
+    long long* rec = cptr(Pg)->guide_rec + 8ull * lp;
+    rec[0] += a0;
+    rec[1] += a1;
+    rec[2] += a2;
+    rec[3] += n0;
+    rec[4] += n1;
+    rec[5] += n2;
+    rec[6] += dsum;
+    rec[7] += hits;
+  }
+}
+
+int guide_kernel_occupancy(bool wide) {
+  int bpc = 0;
+  const auto fn = wide ? guide_kernel<TopoGenericWide> : guide_kernel<TopoGeneric>;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kBlock, 0) != hipSuccess) return 0;
+  return bpc;
+}
+
+void launch_guide_kernel(bool wide, int grid, const KParams* kp_dev, void* stream) {
+  hipLaunchKernelGGL(wide ? guide_kernel<TopoGenericWide> : guide_kernel<TopoGeneric>, dim3(grid),
+                     dim3(kBlock), 0, (hipStream_t)stream, kp_dev);
+}
+
 }  // namespace spt

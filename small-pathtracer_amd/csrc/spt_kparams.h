@@ -210,6 +210,10 @@ struct KParams {  // in device memory, read through a laundered constant-space p
   // is the real local pixel pix_list[lp] (ascending, row-tile shard order), n_local_pix = the list's
   // length. nullptr: the launch's pixels are the shard's, as ever. Read in pixel_terms() only.
   const uint32_t* pix_list;
+  // A guide launch (guide_kernel; appended, so no offset the render kernels read moves): the guide's
+  // records int64[n_local_pix][8] and log2 of the lanes that share a pixel.
+  long long* guide_rec;
+  uint32_t guide_kshift;
 };
 
 }  // namespace spt

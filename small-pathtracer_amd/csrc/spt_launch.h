@@ -47,5 +47,14 @@ void launch_render_kernel(int kv, int grid, const KParams* kp_dev, void* stream,
 void launch_finalize_slots(const unsigned long long* accum, const unsigned long long* slots,
                            float* rgb, uint32_t npix, uint32_t n_chunks, uint32_t scr_k,
                            uint32_t scr_q, const unsigned long long* stats, void* stream);
+// The guide kernel (SPT_HAS_GUIDE): guide_kernel<TopoGenericWide> for a scene with wide spheres, else
+// guide_kernel<TopoGeneric>. grid * kBlock lanes >= n_local_pix << guide_kshift.
+int guide_kernel_occupancy(bool wide);  // resident blocks per CU; <= 0: query failed
+void launch_guide_kernel(bool wide, int grid, const KParams* kp_dev, void* stream);
+
+// ---- spt_dispatch.cpp: lanes per pixel of a guide launch (a power of two, 1..64): the smallest K
+// with n_local_pix * K >= the device's resident lanes (n_cu * bpc * kBlock), at most the window's
+// sample count rounded up to a power of two.
+int guide_lanes_per_pixel(int n_cu, int bpc, int n_local_pix, int32_t s_count);
 
 }  // namespace spt
