@@ -34,12 +34,14 @@ extern "C" {
                              SPT_HAS_FILM_NOISE, the spt_film_noise_* calls; SPT_HAS_FILM_ADAPTIVE,
                              the spt_film_adaptive_* calls; SPT_HAS_FILM_POOL, spt_film_noise_pool_map,
                              spt_film_adaptive_select_pooled and their *_host statements;
-                             SPT_HAS_GUIDE, the spt_guide_* calls */
+                             SPT_HAS_GUIDE, the spt_guide_* calls; SPT_HAS_DENOISE, the
+                             spt_denoise_* and spt_denoiser_* calls and spt_film_denoise */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
 #define SPT_HAS_FILM_POOL 1 /* the error pooled over a pixel's neighbourhood: map and selection (below) */
 #define SPT_HAS_GUIDE 1 /* guide planes: first-hit albedo, normal, depth and coverage (below) */
+#define SPT_HAS_DENOISE 1 /* the edge-stopping a-trous filter over a film and its guides (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -553,6 +555,95 @@ spt_status spt_guide_download(const spt_guide* guide, int64_t* host_records, voi
  * spp_total and samples_done. */
 spt_status spt_guide_resolve_host(const int64_t* records, const spt_guide_info* info, float* albedo,
                                   float* normal, float* depth, float* coverage);
+
+/* ---- denoising: a variance-guided, feature-guided a-trous wavelet filter (SPT_HAS_DENOISE) ----
+ * The consumer of a noise film's error map and of the guide planes, in the style of Dammertz et al.
+ * 2010 and SVGF: a 5x5 B3-spline filter applied `iterations` times with the tap spacing doubling,
+ * every tap weighted down where the normal, the depth, the albedo or the (variance-normalised) colour
+ * says that it lies across an edge. Exact fp32 arithmetic: IEEE + - * /, fmaxf, fminf, fabsf and sqrtf
+ * only (no exp, no pow), no contraction, every sum in the order given here, so the device kernels and
+ * the host statement run the same operations and agree bit for bit.
+ * Inputs, for a w x h image in pixel order: rgb (h*w*3, the resolved, clamped image), se (h*w*3, the
+ * error map), albedo and normal (h*w*3 each) and depth (h*w) of the guide's resolve. Coverage is no
+ * input: a missed or partly covered pixel already has a short normal.
+ * Prepare, per pixel: a_k = fmaxf(albedo_k, albedo_floor), or a_k = 1 with SPT_DENOISE_NO_DEMODULATE;
+ *   c_k = rgb_k / a_k;  e_k = se_k / a_k;  v = ((e_0*e_0 + e_1*e_1) + e_2*e_2) * (1.0f/3.0f).
+ *   The depth gradient gx (along x; gy alike along y): 0.5f * (z(x+1) - z(x-1)) inside, the one-sided
+ *   difference z(1) - z(0) or z(w-1) - z(w-2) at a border, 0 on an axis of length 1.
+ * Iteration i = 0 .. iterations-1 has step s = 2^i and maps the planes (c, v) to (c', v'); every pixel
+ * reads the previous iteration's values. For pixel p = (x, y):
+ *   vt(p) = (sum of k*v(q)) / (sum of k) over the 3x3 window at spacing 1, k = (2-|dy|)*(2-|dx|)/16,
+ *           rows ascending, then columns; a tap outside the image is skipped; both sums start at 0.0f.
+ *   The 25 taps q = (x + i*s, y + j*s), j, i in -2..2, rows (j) ascending, then columns (i). A tap
+ *   outside the image is skipped, not added with weight 0 (the two differ when an input is not
+ *   finite). h = (1, 4, 6, 4, 1)/16. The centre tap has w = h_2*h_2 by rule. Every other tap has
+ *     w = ((((h_j*h_i) * w_n) * w_z) * w_a) * w_c
+ *     w_n = fmaxf(0, (nx_p*nx_q + ny_p*ny_q) + nz_p*nz_q), then squared normal_squarings times
+ *     w_z = phi(fabsf(z_p - z_q) / ((sigma_depth * fabsf(gx_p*dx + gy_p*dy) + 1e-3f*z_p) + 1e-6f)),
+ *           dx = (float)(i*s), dy = (float)(j*s)
+ *     w_a = phi(((d_0*d_0 + d_1*d_1) + d_2*d_2) / sigma_albedo^2), d = albedo_p - albedo_q (the planes as
+ *           given, not floored)
+ *     w_c = phi(((d_0*d_0 + d_1*d_1) + d_2*d_2) / (sigma_color^2 * (vt_p + vt_q) + 1e-10f)), d = c_p - c_q
+ *     phi(x) = t^4 as two squarings, t = fmaxf(0, 1 - 0.25f*x)
+ *   The squares of the sigmas are taken once on the host in fp32. With W, C_k, V starting at 0.0f, each
+ *   tap in order does W += w, C_k += w*c_q,k, V += (w*w)*v_q; then c'_k = C_k / W and v' = V / (W*W).
+ *   W >= h_2*h_2 > 0: nothing divides by zero.
+ * Finish: out_k = fminf(c_k * a_k, 1), se_out_k = sqrtf(v) * a_k (optional plane). iterations == 0: out
+ * is rgb and se_out is se, copied bit for bit (no divide-and-multiply round trip).
+ * What it is not. The denoised image is BIASED, unlike a film: it trades variance for blur wherever no
+ * guide separates the signal (soft shadow edges, the rim of the light). se_out ignores the correlation
+ * that earlier iterations introduce between neighbours: an optimistic estimate, not a bound. Inputs
+ * that are not finite give unspecified values, never a fault. */
+#define SPT_DENOISE_NO_DEMODULATE 1u /* filter rgb itself, not rgb / albedo; other flag bits must be 0 */
+typedef struct spt_denoise_params {
+  int32_t iterations;       /* 0..6; iteration i uses step 2^i. Default 5 */
+  float sigma_color;        /* finite, > 0. Default 4 */
+  float sigma_depth;        /* finite, > 0. Default 1 */
+  float sigma_albedo;       /* finite, > 0. Default 0.1 */
+  int32_t normal_squarings; /* 0..8: the normal weight is the clamped dot product ^ (2^this). Default 7 */
+  float albedo_floor;       /* finite, > 0. Default 0.01 */
+  uint32_t flags;           /* SPT_DENOISE_NO_DEMODULATE */
+  uint32_t reserved;        /* 0 */
+} spt_denoise_params;
+void spt_denoise_default_params(spt_denoise_params* p);
+/* A denoiser for width x height images on `device`. It owns all its scratch (124 bytes per pixel: two
+ * ping-pong planes of (c, v), the packed guides, and five float planes for the film path below),
+ * allocated here; no later call allocates. Rejected: width or height not positive, more than 2^31 - 1
+ * pixels (the guide's limit), or a shape so narrow or so flat that its tiles do not fit one launch: the
+ * kernels cover the image with tiles of 64 x 4 and of 32 x 8 pixels and a launch holds at most 2^24 - 1
+ * tiles of either kind (a 1-pixel-wide image may have 2^24 - 1 tiles of 4 rows: 67108860 rows). Calls on
+ * one denoiser are serialised by the caller on one stream. */
+typedef struct spt_denoiser spt_denoiser;
+spt_status spt_denoiser_create(int32_t device, int32_t width, int32_t height, spt_denoiser** out);
+spt_status spt_denoiser_destroy(spt_denoiser* dn);
+/* Enqueue the filter of five DEVICE planes on `stream`: out_dev (h*w*3) and, if given, se_out_dev
+ * (h*w*3). Rejected with SPT_ERR_INVALID_ARG, nothing queued, out untouched: a null plane, a parameter
+ * out of range or not finite, unknown flag bits, out_dev or se_out_dev equal to an input pointer or to
+ * each other. No host synchronisation. */
+spt_status spt_denoise_async(spt_denoiser* dn, const float* rgb_dev, const float* se_dev,
+                             const float* albedo_dev, const float* normal_dev, const float* depth_dev,
+                             const spt_denoise_params* params, float* out_dev,
+                             float* se_out_dev_or_null, void* stream);
+/* The same as a pure host function (no device), HOST pointers: the CPU statement of the filter. Also
+ * rejects a width or height that is not positive or more than 2^31 - 1 pixels. */
+spt_status spt_denoise_host(const float* rgb, const float* se, const float* albedo, const float* normal,
+                            const float* depth, int32_t width, int32_t height,
+                            const spt_denoise_params* params, float* out, float* se_out_or_null);
+/* Film and guide in one call: the film's resolve, its error map and the guide's resolve go into the
+ * denoiser's scratch and the filter runs on them, all enqueued on `stream` with no host
+ * synchronisation; the result equals spt_denoise_async on the separately resolved planes bit for bit.
+ * An adaptive film works unchanged (its resolve and error map take every pixel's own count).
+ * Rejected, nothing queued, out untouched: what spt_denoise_async rejects; a plain film; a film with
+ * batches_done < 2; a guide with samples_done == 0; a film or guide whose width or rows differ from the
+ * denoiser's width and height; a film on another device; a film of a sharded render (shard_count > 1:
+ * a shard's compact rows are not image neighbours -- a multi-GPU user gathers the five planes and
+ * calls spt_denoise_async on the full image). A sharded guide is refused only through its row count,
+ * which is below the image's height whenever another shard holds rows. THE GUIDE'S DEVICE IS NOT
+ * CHECKED (a guide's public info does not name it): a guide on the denoiser's device is the caller's
+ * duty, and one on another device is undefined behaviour, as a foreign device pointer is. */
+spt_status spt_film_denoise(const spt_film* film, const spt_guide* guide, spt_denoiser* dn,
+                            const spt_denoise_params* params, float* out_dev, float* se_out_dev_or_null,
+                            void* stream);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

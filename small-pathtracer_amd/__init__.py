@@ -125,6 +125,13 @@ class spt_guide_info(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class spt_denoise_params(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int32), ("sigma_color", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float), ("sigma_albedo", ctypes.c_float),
+                ("normal_squarings", ctypes.c_int32), ("albedo_floor", ctypes.c_float),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -160,7 +167,11 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_film_noise_pool_map_host", "spt_film_adaptive_select_pooled_host",
            "spt_guide_info_size", "spt_guide_create", "spt_guide_destroy", "spt_guide_clear",
            "spt_guide_info_get", "spt_guide_render_async", "spt_guide_resolve", "spt_guide_download",
-           "spt_guide_resolve_host"]
+           "spt_guide_resolve_host",
+           "spt_denoise_default_params", "spt_denoiser_create", "spt_denoiser_destroy",
+           "spt_denoise_async", "spt_denoise_host", "spt_film_denoise"]
+SPT_HAS_DENOISE = 1         # include/spt.h: the a-trous filter (Denoiser, denoise_host, render_denoised)
+DENOISE_NO_DEMODULATE = 1   # SPT_DENOISE_NO_DEMODULATE: filter rgb itself, not rgb / albedo
 SPT_HAS_GUIDE = 1           # include/spt.h: the spt_guide_* calls (Guide, render_guides)
 GUIDE_SLOTS = 8             # a guide record: albedo 0-2, normal 3-5, depth 6 (48.16), hits 7
 GUIDE_MAX_SPP = 1 << 24
@@ -311,6 +322,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_guide_resolve.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.spt_guide_download.argtypes = [VP, VP, VP]
     lib.spt_guide_resolve_host.argtypes = [VP, P(spt_guide_info), VP, VP, VP, VP]
+    lib.spt_denoise_default_params.argtypes = [P(spt_denoise_params)]
+    lib.spt_denoise_default_params.restype = None
+    lib.spt_denoiser_create.argtypes = [I32, I32, I32, P(VP)]
+    lib.spt_denoiser_destroy.argtypes = [VP]
+    lib.spt_denoise_async.argtypes = [VP, VP, VP, VP, VP, VP, P(spt_denoise_params), VP, VP, VP]
+    lib.spt_denoise_host.argtypes = [VP, VP, VP, VP, VP, I32, I32, P(spt_denoise_params), VP, VP]
+    lib.spt_film_denoise.argtypes = [VP, VP, VP, P(spt_denoise_params), VP, VP, VP]
+    for name in ("spt_denoiser_create", "spt_denoiser_destroy", "spt_denoise_async", "spt_denoise_host"):
+        getattr(lib, name).restype = I32
     for name in EXPORTS:
         if name.startswith("spt_film_") or name.startswith("spt_guide_"):
             getattr(lib, name).restype = I32
@@ -340,7 +360,8 @@ KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_variants.h", "csrc/spt_kparam
                   "csrc/spt_dispatch.cpp", "csrc/spt_context.cpp",
                   "csrc/spt_device.h", "csrc/spt_cornell.h", "csrc/spt_diag.h", "csrc/Makefile", "../include/spt.h", "../include/spt_flops.h", "csrc/spt_film.hip",
                   "csrc/spt_film.h", "csrc/spt_film_math.h", "csrc/spt_film_host.cpp",
-                  "csrc/spt_guide.hip", "csrc/spt_guide_host.cpp", "csrc/spt_guide.h")
+                  "csrc/spt_guide.hip", "csrc/spt_guide_host.cpp", "csrc/spt_guide.h",
+                  "csrc/spt_denoise.hip", "csrc/spt_denoise_host.cpp", "csrc/spt_denoise.h")
 
 
 def kernel_sources_sha16() -> str:
@@ -1304,6 +1325,170 @@ def render_adaptive(prims: Sequence[spt_prim], cam: Camera, params: spt_params, 
         lambda film, stream: film.adaptive_select(threshold_scale * target_rmse, None, stream,
                                                   pool_radius, pool_exclude_center), info_of)
     return (out, info) if return_info else out
+
+
+# ---------------------------------------------------------------------------------------------
+# Denoising: the edge-stopping a-trous filter over a film's image, its error map and the guide planes
+# (spt_denoise_*, spt_film_denoise)
+# ---------------------------------------------------------------------------------------------
+DenoiseParams = spt_denoise_params
+
+
+def default_denoise_params(**kw) -> spt_denoise_params:
+    """spt_denoise_default_params() with the given fields replaced."""
+    p = spt_denoise_params()
+    load_library().spt_denoise_default_params(ctypes.byref(p))
+    for k, v in kw.items():
+        if k not in dict(spt_denoise_params._fields_):
+            raise TypeError(f"spt_denoise_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _denoise_planes(rgb, se, albedo, normal, depth):
+    """The five planes as contiguous float32 arrays, and (height, width) taken from rgb."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise SptError(1, "rgb is not (height, width, 3)")
+    h, w = rgb.shape[:2]
+    planes = [rgb] + [np.ascontiguousarray(a, dtype=np.float32) for a in (se, albedo, normal, depth)]
+    for a, c, name in zip(planes, (3, 3, 3, 3, 1), ("rgb", "se", "albedo", "normal", "depth")):
+        if a.size != h * w * c:
+            raise SptError(1, f"{name} does not have height * width * {c} elements")
+    return planes, h, w
+
+
+def denoise_host(rgb, se, albedo, normal, depth, params: spt_denoise_params | None = None,
+                 return_se=False):
+    """spt_denoise_host(): the CPU statement of the filter (no device). Planes as (h, w, 3) float32,
+    depth (h, w). -> the denoised image (h, w, 3), with return_se also se_out."""
+    planes, h, w = _denoise_planes(rgb, se, albedo, normal, depth)
+    p = params if params is not None else default_denoise_params()
+    out = np.empty((h, w, 3), np.float32)
+    se_out = np.empty((h, w, 3), np.float32) if return_se else None
+    _check(load_library().spt_denoise_host(*[a.ctypes.data for a in planes], w, h, ctypes.byref(p),
+                                           out.ctypes.data, se_out.ctypes.data if return_se else None))
+    return (out, se_out) if return_se else out
+
+
+class Denoiser:
+    """spt_denoiser: the filter's scratch for width x height images on one device. Calls on one
+    denoiser go on one stream."""
+
+    def __init__(self, width: int, height: int, device: int = 0):
+        self.lib = load_library()
+        self._d = ctypes.c_void_p()
+        _check(self.lib.spt_denoiser_create(int(device), int(width), int(height), ctypes.byref(self._d)))
+        self.width, self.height, self.device = int(width), int(height), int(device)
+
+    def close(self):
+        if self._d:
+            self.lib.spt_denoiser_destroy(self._d)
+            self._d = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _outputs(self, return_se: bool):
+        import torch
+        n = self.width * self.height * 3
+        dev = f"cuda:{self.device}"
+        return (torch.empty(n, dtype=torch.float32, device=dev),
+                torch.empty(n, dtype=torch.float32, device=dev) if return_se else None)
+
+    def _host(self, out, se_out):
+        import torch
+        torch.cuda.synchronize(self.device)
+        shape = (self.height, self.width, 3)
+        img = out.cpu().numpy().reshape(shape)
+        return (img, se_out.cpu().numpy().reshape(shape)) if se_out is not None else img
+
+    def denoise_async(self, rgb_ptr: int, se_ptr: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int,
+                      params: spt_denoise_params, out_ptr: int, se_out_ptr: int = 0, stream_ptr: int = 0):
+        """spt_denoise_async() on device pointers."""
+        V = ctypes.c_void_p
+        _check(self.lib.spt_denoise_async(self._d, V(rgb_ptr or None), V(se_ptr or None),
+                                          V(albedo_ptr or None), V(normal_ptr or None),
+                                          V(depth_ptr or None), ctypes.byref(params), V(out_ptr or None),
+                                          V(se_out_ptr or None), V(stream_ptr or None)))
+
+    def denoise(self, rgb, se, albedo, normal, depth, params: spt_denoise_params | None = None,
+                return_se=False):
+        """Host arrays in (uploaded through torch), the denoised image out: (h, w, 3) float32, with
+        return_se also se_out."""
+        import torch
+        planes, h, w = _denoise_planes(rgb, se, albedo, normal, depth)
+        if (h, w) != (self.height, self.width):
+            raise SptError(1, "the planes are not the denoiser's height x width")
+        p = params if params is not None else default_denoise_params()
+        with torch.cuda.device(self.device):
+            dev = [torch.from_numpy(a.reshape(-1)).to(f"cuda:{self.device}") for a in planes]
+            out, se_out = self._outputs(return_se)
+            self.denoise_async(*[t.data_ptr() for t in dev], p, out.data_ptr(),
+                               se_out.data_ptr() if return_se else 0,
+                               torch.cuda.current_stream().cuda_stream)
+            return self._host(out, se_out)
+
+    def denoise_film_async(self, film: "Film", guide: "Guide", params: spt_denoise_params, out_ptr: int,
+                           se_out_ptr: int = 0, stream_ptr: int = 0):
+        """spt_film_denoise() into device pointers."""
+        V = ctypes.c_void_p
+        _check(self.lib.spt_film_denoise(film._f, guide._g, self._d, ctypes.byref(params),
+                                         V(out_ptr or None), V(se_out_ptr or None), V(stream_ptr or None)))
+
+    def denoise_film(self, film: "Film", guide: "Guide", params: spt_denoise_params | None = None,
+                     return_se=False):
+        """The film's image, its error map and the guide's planes resolved and filtered on the device
+        in one call -> the denoised image on the host, with return_se also se_out."""
+        import torch
+        p = params if params is not None else default_denoise_params()
+        with torch.cuda.device(self.device):
+            out, se_out = self._outputs(return_se)
+            self.denoise_film_async(film, guide, p, out.data_ptr(), se_out.data_ptr() if return_se else 0,
+                                    torch.cuda.current_stream().cuda_stream)
+            return self._host(out, se_out)
+
+
+def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, batch: int | None = None,
+                    guide_spp: int | None = None, denoise: spt_denoise_params | None = None,
+                    return_info=False):
+    """Render all params.spp samples into a noise film (batches of `batch`, default spp / 8 as in
+    render_until), fill a guide with the sample window [0, min(spp, guide_spp or 64)), and return the
+    film's image denoised (Denoiser.denoise_film). One device. return_info: also {"noisy": the film's
+    own image, "noise": the film's noise_summary, "guides": the guide planes, "se": se_out}."""
+    spp = int(params.spp)
+    if params.shard_count > 1:
+        raise SptError(1, "render_denoised: a shard's rows are not image neighbours; gather the planes")
+    if batch is None:
+        if spp % 8:
+            raise SptError(1, "render_denoised: spp is no multiple of 8, give batch")
+        batch = spp // 8
+    if batch < 1 or spp % batch:
+        raise SptError(1, "render_denoised: batch must divide spp (every sample is rendered)")
+    n_guide = min(spp, int(guide_spp or 64))
+    guide = Guide(params, params.device)
+    dn = None
+    try:
+        dn = Denoiser(params.width, params.height, params.device)
+        with _film_session(params, batch) as (r, film, buf, stream):
+            for k in range(spp // batch):
+                film.render(r, prims, cam, params, k * batch, batch, 0, stream)
+                r.stats()  # a pass that hit the runaway guard raises here
+            guide.render(r, prims, cam, params, 0, n_guide, stream)
+            out = dn.denoise_film(film, guide, denoise, return_se=return_info)
+            if not return_info:
+                return out
+            film.resolve(buf.data_ptr(), stream)
+            info = {"noisy": _film_image(film, buf), "noise": film.noise_summary(stream),
+                    "guides": guide.resolve(stream_ptr=stream), "se": out[1]}
+            return out[0], info
+    finally:
+        if dn is not None:
+            dn.close()
+        guide.close()
 
 
 def render_multi(prims: Sequence[spt_prim], cam: Camera, params: spt_params, devices,

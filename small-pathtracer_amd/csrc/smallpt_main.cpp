@@ -3,7 +3,13 @@
 //               [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]
 //               [--device N | --devices N] [--p6 | --pfm]
 //               [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]
-//               [--guides PREFIX] [--help]
+//               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]] [--help]
+//   --denoise: the output file becomes the image denoised by the edge-stopping a-trous filter
+//               (spt_film_denoise: the film's image and error map, and guide planes of the first
+//               min(SPP, 64) samples' camera rays). The render goes through a noise film: --noise T
+//               and --batch B as given (with --adaptive if wanted), else every sample in 8 batches (or
+//               --batch B). --denoise-iters N (0..6, default 5) and --denoise-sigma S (the colour
+//               sigma, default 4) replace those two defaults. One device (no --devices above 1).
 //   --guides PREFIX: beside the image, the guide planes of the same scene, camera, W H SPP and SEED
 //               (spt_guide_*: the first hit of every sample's own camera ray) as PREFIX_albedo.pfm,
 //               PREFIX_normal.pfm and PREFIX_depth.pfm. The PFM encoder writes the floats as they
@@ -50,6 +56,7 @@
 // Same scene, camera (:521), clamp/toInt and P3 output; the pixel loop is one spt_render() call.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -88,6 +95,13 @@ struct NoiseOpts {
   int64_t samples_total = -1;  // out: the pixel-samples an adaptive run spent
 };
 
+struct DenoiseOpts {
+  bool on = false;
+  bool iters_given = false, sigma_given = false;  // not given: the library's default
+  int iters = 0;
+  double sigma = 0.0;
+};
+
 void check(spt_status s) {
   if (s != SPT_OK) throw std::runtime_error(std::string(spt_status_string(s)) + ": " + spt_last_error());
 }
@@ -98,7 +112,7 @@ void check(spt_status s) {
 // estimated RMSE is at most noise.target. Returns the DEVICE image.
 float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
                    int passes, const char* film_path, int add, NoiseOpts& noise,
-                   spt_stats* total) {
+                   const DenoiseOpts& denoise, spt_stats* total) {
   spt_context* ctx = nullptr;
   spt_film* film = nullptr;
   check(spt_context_create(p.device, &ctx));
@@ -226,6 +240,22 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
     if (!o) throw std::runtime_error(std::string("cannot write ") + film_path);
     std::cout << "FILM : " << info.samples_done << " / " << info.spp_total << " samples" << std::endl;
   }
+  if (denoise.on) {  // the image in dev becomes the filtered one; the film file above is the film's own
+    spt_denoise_params dp;
+    spt_denoise_default_params(&dp);
+    if (denoise.iters_given) dp.iterations = denoise.iters;
+    if (denoise.sigma_given) dp.sigma_color = (float)denoise.sigma;
+    spt_guide* guide = nullptr;
+    spt_denoiser* dn = nullptr;
+    check(spt_guide_create(p.device, &p, &guide));
+    check(spt_denoiser_create(p.device, p.width, p.height, &dn));
+    check(spt_guide_render_async(ctx, guide, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
+                                 std::min(p.spp, 64), nullptr));
+    check(spt_film_denoise(film, guide, dn, &dp, dev, nullptr, nullptr));
+    if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("denoise failed on the device");
+    check(spt_denoiser_destroy(dn));
+    check(spt_guide_destroy(guide));
+  }
   check(spt_film_destroy(film));
   check(spt_context_destroy(ctx));
   return dev;
@@ -269,11 +299,16 @@ const char kUsage[] =
     "            [--device N | --devices N] [--p6 | --pfm] [--repeat N] [--passes K]\n"
     "            [--film PATH [--add N]]\n"
     "            [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]\n"
-    "            [--guides PREFIX]\n"
+    "            [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]]\n"
     "  --guides PREFIX  also write the first-hit guide planes PREFIX_albedo.pfm, PREFIX_normal.pfm\n"
     "                   and PREFIX_depth.pfm (linear PFM). The normal is stored signed, components\n"
     "                   in [-1, 1] (not 0.5 + 0.5 n); the depth is the mean ray parameter of the\n"
-    "                   samples that hit, replicated to three channels. One device (no --devices).\n";
+    "                   samples that hit, replicated to three channels. One device (no --devices).\n"
+    "  --denoise        write the image denoised by the edge-stopping a-trous filter over the noise\n"
+    "                   film's image, its error map and the guide planes (--noise/--batch as given,\n"
+    "                   else 8 batches; goes with --adaptive; one device)\n"
+    "  --denoise-iters N  filter iterations, 0..6 (default 5)\n"
+    "  --denoise-sigma S  the colour sigma (default 4)\n";
 
 }  // namespace
 
@@ -287,6 +322,7 @@ int main(int argc, char* argv[]) {
   const char* film_path = nullptr;
   const char* guides = nullptr;
   NoiseOpts noise;
+  DenoiseOpts denoise;
   float q = -1.0f;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--cos")) cosine = true;
@@ -311,6 +347,9 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--pool") && i + 1 < argc) noise.pool_radius = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--pool-loo")) noise.pool_loo = true;
     else if (!std::strcmp(argv[i], "--guides") && i + 1 < argc) guides = argv[++i];
+    else if (!std::strcmp(argv[i], "--denoise")) denoise.on = true;
+    else if (!std::strcmp(argv[i], "--denoise-iters") && i + 1 < argc) { denoise.iters_given = true; denoise.iters = std::atoi(argv[++i]); }
+    else if (!std::strcmp(argv[i], "--denoise-sigma") && i + 1 < argc) { denoise.sigma_given = true; denoise.sigma = std::atof(argv[++i]); }
     else if (!std::strcmp(argv[i], "--help")) { std::cout << kUsage; return 0; }
     else if (!std::strcmp(argv[i], "--p6")) format = SPT_IMAGE_P6;
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
@@ -340,6 +379,16 @@ int main(int argc, char* argv[]) {
                                         : spheres ? spheres32_scene()
                                                   : cornell_scene();
     if (guides) guide_scene = scene;
+    if ((denoise.iters_given || denoise.sigma_given) && !denoise.on)
+      throw std::runtime_error("--denoise-iters / --denoise-sigma go with --denoise");
+    if (denoise.on) {
+      if (devices > 1) throw std::runtime_error("--denoise goes with one device: a shard's rows are not image neighbours");
+      if (denoise.iters_given && (denoise.iters < 0 || denoise.iters > 6))
+        throw std::runtime_error("--denoise-iters: 0..6");
+      if (denoise.sigma_given && !(denoise.sigma > 0.0 && std::isfinite((float)denoise.sigma)))
+        throw std::runtime_error("--denoise-sigma: a positive, finite number");
+      if (!noise.on) { noise.on = true; noise.target = 0.0; }  // every sample, in batches
+    }
     if (passes > 0 || film_path || noise.on || noise.adaptive || noise.pool_radius || noise.pool_loo) {
       if (devices > 0 || repeat > 1)
         throw std::runtime_error("--passes / --film / --noise go with one device and no --repeat");
@@ -351,7 +400,7 @@ int main(int argc, char* argv[]) {
         throw std::runtime_error("--pool: the radius is 1..16");
       if (noise.adaptive && film_path)
         throw std::runtime_error("--adaptive does not go with --film: the counts plane has no file format");
-      image = render_film(scene, cam, p, passes, film_path, add, noise, &st);
+      image = render_film(scene, cam, p, passes, film_path, add, noise, denoise, &st);
       repeat = 0;
     }
     for (int k = 0; k < repeat; ++k) {

@@ -1,0 +1,185 @@
+// spt_denoise.h — the edge-stopping a-trous filter's arithmetic, stated once for the kernels
+// (spt_denoise.hip) and for the CPU statement (spt_denoise_host.cpp, plain C++: it runs under the host
+// sanitizers). Internal: the public statement is include/spt.h (SPT_HAS_DENOISE). Needs
+// -ffp-contract=off on both sides. IEEE fp32 + - * /, fmaxf, fminf, fabsf and sqrtf only.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/spt.h"
+#include "spt_film_math.h"  // SPT_FILM_FN
+
+namespace spt_denoise_math {
+
+constexpr int32_t kMaxIterations = 6, kMaxSquarings = 8;
+constexpr int64_t kMaxPixels = 0x7FFFFFFF;  // the guide's limit: 32-bit pixel counters
+
+// A pixel's packed state: cv = (c_r, c_g, c_b, v), nz = (n_x, n_y, n_z, z), av = (albedo_r, albedo_g,
+// albedo_b, vt) with vt the 3x3 binomial filter of the current v (written before every iteration).
+struct alignas(16) f4 {  // one 16-byte load on the device
+  float x, y, z, w;
+};
+
+// The parameters as the filter reads them: the squares taken once on the host.
+struct Args {
+  float sc2, sa2, sd, floor_;
+  int32_t squarings, demodulate;
+};
+
+inline Args make_args(const spt_denoise_params* p) {
+  Args a;
+  a.sc2 = p->sigma_color * p->sigma_color;
+  a.sa2 = p->sigma_albedo * p->sigma_albedo;
+  a.sd = p->sigma_depth;
+  a.floor_ = p->albedo_floor;
+  a.squarings = p->normal_squarings;
+  a.demodulate = (p->flags & SPT_DENOISE_NO_DEMODULATE) ? 0 : 1;
+  return a;
+}
+
+// NULL when the parameters are in range, else what is wrong with them.
+inline const char* params_error(const spt_denoise_params* p) {
+  if (!p) return "null params";
+  if (p->iterations < 0 || p->iterations > kMaxIterations) return "iterations outside 0..6";
+  if (p->normal_squarings < 0 || p->normal_squarings > kMaxSquarings) return "normal_squarings outside 0..8";
+  const float s[4] = {p->sigma_color, p->sigma_depth, p->sigma_albedo, p->albedo_floor};
+  for (float v : s)
+    if (!(v > 0.0f) || !std::isfinite(v)) return "sigma_color, sigma_depth, sigma_albedo and albedo_floor must be finite and > 0";
+  if (p->flags & ~SPT_DENOISE_NO_DEMODULATE) return "unknown flag bits";
+  if (p->reserved != 0) return "reserved must be 0";
+  return nullptr;
+}
+
+SPT_FILM_FN float phi(float x) {
+  float t = fmaxf(0.0f, 1.0f - 0.25f * x);
+  t = t * t;
+  return t * t;
+}
+
+SPT_FILM_FN float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
+
+SPT_FILM_FN float divisor(float albedo, const Args& A) { return A.demodulate ? fmaxf(albedo, A.floor_) : 1.0f; }
+
+// Prepare: the demodulated colour and the variance of one pixel.
+SPT_FILM_FN f4 prepare(const float* rgb, const float* se, const float* albedo, const Args& A) {
+  const float a0 = divisor(albedo[0], A), a1 = divisor(albedo[1], A), a2 = divisor(albedo[2], A);
+  const float e0 = se[0] / a0, e1 = se[1] / a1, e2 = se[2] / a2;
+  f4 o;
+  o.x = rgb[0] / a0;
+  o.y = rgb[1] / a1;
+  o.z = rgb[2] / a2;
+  o.w = ((e0 * e0 + e1 * e1) + e2 * e2) * (1.0f / 3.0f);
+  return o;
+}
+
+// The depth gradient along one axis of length n at position i: zm, z0, zp = z(i - 1), z(i), z(i + 1)
+// (a value outside the axis is not read by the rule that applies there).
+SPT_FILM_FN float gradient(int32_t i, int32_t n, float zm, float z0, float zp) {
+  if (n == 1) return 0.0f;
+  if (i == 0) return zp - z0;
+  if (i == n - 1) return z0 - zm;
+  return 0.5f * (zp - zm);
+}
+
+SPT_FILM_FN float h5(int k) { return k == 0 ? 0.375f : (k == 1 || k == -1) ? 0.25f : 0.0625f; }
+
+// vt: the 3x3 binomial filter of v at spacing 1, taps outside the image skipped. Plane: any accessor
+// with float v(int32_t x, int32_t y).
+template <class Plane>
+SPT_FILM_FN float variance_filter(const Plane& P, int32_t x, int32_t y, int32_t w, int32_t h) {
+  float s = 0.0f, ws = 0.0f;
+  for (int dy = -1; dy <= 1; ++dy) {
+    const int32_t yy = y + dy;
+    if (yy < 0 || yy >= h) continue;
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int32_t xx = x + dx;
+      if (xx < 0 || xx >= w) continue;
+      const float k = (float)((2 - (dy < 0 ? -dy : dy)) * (2 - (dx < 0 ? -dx : dx))) * 0.0625f;
+      s = s + k * P.v(xx, yy);
+      ws = ws + k;
+    }
+  }
+  return s / ws;
+}
+
+// The running sums of one pixel's iteration.
+struct Acc {
+  float c0, c1, c2, v, w;
+};
+
+SPT_FILM_FN void acc_centre(Acc& a, const f4& cv) {
+  const float w = 0.375f * 0.375f;
+  a.w = a.w + w;
+  a.c0 = a.c0 + w * cv.x;
+  a.c1 = a.c1 + w * cv.y;
+  a.c2 = a.c2 + w * cv.z;
+  a.v = a.v + (w * w) * cv.w;
+}
+
+// One tap that is not the centre: offset (i, j) * step, i the column's, j the row's index in -2..2.
+SPT_FILM_FN void acc_tap(Acc& a, int i, int j, int32_t step, const f4& cvp, const f4& nzp, const f4& avp,
+                         float gx, float gy, const f4& cvq, const f4& nzq, const f4& avq, const Args& A) {
+  float wn = fmaxf(0.0f, dot3(nzp.x, nzp.y, nzp.z, nzq.x, nzq.y, nzq.z));
+  for (int k = 0; k < A.squarings; ++k) wn = wn * wn;
+  const float dx = (float)(i * step), dy = (float)(j * step);
+  const float wz = phi(fabsf(nzp.w - nzq.w) / ((A.sd * fabsf(gx * dx + gy * dy) + 1e-3f * nzp.w) + 1e-6f));
+  const float a0 = avp.x - avq.x, a1 = avp.y - avq.y, a2 = avp.z - avq.z;
+  const float wa = phi(dot3(a0, a1, a2, a0, a1, a2) / A.sa2);
+  const float d0 = cvp.x - cvq.x, d1 = cvp.y - cvq.y, d2 = cvp.z - cvq.z;
+  const float wc = phi(dot3(d0, d1, d2, d0, d1, d2) / (A.sc2 * (avp.w + avq.w) + 1e-10f));
+  const float w = ((((h5(j) * h5(i)) * wn) * wz) * wa) * wc;
+  a.w = a.w + w;
+  a.c0 = a.c0 + w * cvq.x;
+  a.c1 = a.c1 + w * cvq.y;
+  a.c2 = a.c2 + w * cvq.z;
+  a.v = a.v + (w * w) * cvq.w;
+}
+
+SPT_FILM_FN f4 acc_result(const Acc& a) {
+  f4 o;
+  o.x = a.c0 / a.w;
+  o.y = a.c1 / a.w;
+  o.z = a.c2 / a.w;
+  o.w = a.v / (a.w * a.w);
+  return o;
+}
+
+// One pixel of one iteration. Planes: any accessor with f4 cv(x, y), nz(x, y), av(x, y).
+template <class Planes>
+SPT_FILM_FN f4 iterate(const Planes& P, int32_t x, int32_t y, int32_t w, int32_t h, int32_t step,
+                       float gx, float gy, const Args& A) {
+  const f4 cvp = P.cv(x, y), nzp = P.nz(x, y), avp = P.av(x, y);
+  Acc a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  for (int j = -2; j <= 2; ++j) {
+    const int64_t yy = (int64_t)y + (int64_t)j * step;
+    if (yy < 0 || yy >= h) continue;
+    for (int i = -2; i <= 2; ++i) {
+      const int64_t xx = (int64_t)x + (int64_t)i * step;
+      if (xx < 0 || xx >= w) continue;
+      if (i == 0 && j == 0)
+        acc_centre(a, cvp);
+      else
+        acc_tap(a, i, j, step, cvp, nzp, avp, gx, gy, P.cv((int32_t)xx, (int32_t)yy),
+                P.nz((int32_t)xx, (int32_t)yy), P.av((int32_t)xx, (int32_t)yy), A);
+    }
+  }
+  return acc_result(a);
+}
+
+// Finish: remodulate, clamp; the standard error that is left.
+SPT_FILM_FN void finish(const f4& cv, const f4& av, const Args& A, float* out, float* se_out) {
+  const float a0 = divisor(av.x, A), a1 = divisor(av.y, A), a2 = divisor(av.z, A);
+  out[0] = fminf(cv.x * a0, 1.0f);
+  out[1] = fminf(cv.y * a1, 1.0f);
+  out[2] = fminf(cv.z * a2, 1.0f);
+  if (se_out) {
+    const float s = sqrtf(cv.w);
+    se_out[0] = s * a0;
+    se_out[1] = s * a1;
+    se_out[2] = s * a2;
+  }
+}
+
+}  // namespace spt_denoise_math

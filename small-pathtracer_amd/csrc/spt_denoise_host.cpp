@@ -1,0 +1,93 @@
+// spt_denoise_host.cpp — the a-trous filter as a pure host function (include/spt.h, SPT_HAS_DENOISE):
+// the CPU statement every GPU denoise test compares the device kernels against. Plain C++, no HIP: it
+// is also built into tests/probe/spt_denoise_check under the host sanitizers.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/spt.h"
+#include "spt_denoise.h"
+
+void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp
+
+static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params layout (the Python mirror's)");
+
+extern "C" void spt_denoise_default_params(spt_denoise_params* p) {
+  if (!p) return;
+  p->iterations = 5;
+  p->sigma_color = 4.0f;
+  p->sigma_depth = 1.0f;
+  p->sigma_albedo = 0.1f;
+  p->normal_squarings = 7;
+  p->albedo_floor = 0.01f;
+  p->flags = 0;
+  p->reserved = 0;
+}
+
+namespace {
+
+using namespace spt_denoise_math;
+
+struct HostPlanes {
+  const f4 *cv_, *nz_, *av_;
+  int32_t w;
+  f4 cv(int32_t x, int32_t y) const { return cv_[(size_t)y * w + x]; }
+  f4 nz(int32_t x, int32_t y) const { return nz_[(size_t)y * w + x]; }
+  f4 av(int32_t x, int32_t y) const { return av_[(size_t)y * w + x]; }
+  float v(int32_t x, int32_t y) const { return cv_[(size_t)y * w + x].w; }
+};
+
+spt_status fail(const char* msg) {
+  spt_set_last_error(std::string("spt_denoise_host: ") + msg);
+  return SPT_ERR_INVALID_ARG;
+}
+
+}  // namespace
+
+extern "C" spt_status spt_denoise_host(const float* rgb, const float* se, const float* albedo,
+                                       const float* normal, const float* depth, int32_t width,
+                                       int32_t height, const spt_denoise_params* params, float* out,
+                                       float* se_out) {
+  if (!rgb || !se || !albedo || !normal || !depth || !out) return fail("null plane");
+  if (const char* e = params_error(params)) return fail(e);
+  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
+    return fail("width/height must be positive and hold at most 2^31 - 1 pixels");
+  for (const float* in : {rgb, se, albedo, normal, depth})
+    if (out == in || (se_out && se_out == in)) return fail("an output plane is an input plane");
+  if (se_out == out) return fail("out and se_out are one plane");
+  const size_t npix = (size_t)width * (size_t)height;
+  if (params->iterations == 0) {
+    std::memcpy(out, rgb, npix * 3 * sizeof(float));
+    if (se_out) std::memcpy(se_out, se, npix * 3 * sizeof(float));
+    return SPT_OK;
+  }
+  const Args A = make_args(params);
+  std::vector<f4> cv0(npix), cv1(npix), nz(npix), av(npix);
+  std::vector<float> gx(npix), gy(npix);
+  for (int32_t y = 0; y < height; ++y)
+    for (int32_t x = 0; x < width; ++x) {
+      const size_t i = (size_t)y * width + x;
+      cv0[i] = prepare(rgb + 3 * i, se + 3 * i, albedo + 3 * i, A);
+      nz[i] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]};
+      av[i] = {albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f};
+      gx[i] = gradient(x, width, x > 0 ? depth[i - 1] : 0.0f, depth[i], x < width - 1 ? depth[i + 1] : 0.0f);
+      gy[i] = gradient(y, height, y > 0 ? depth[i - width] : 0.0f, depth[i],
+                       y < height - 1 ? depth[i + width] : 0.0f);
+    }
+  f4 *cur = cv0.data(), *nxt = cv1.data();
+  for (int32_t it = 0; it < params->iterations; ++it) {
+    const HostPlanes P{cur, nz.data(), av.data(), width};
+    for (int32_t y = 0; y < height; ++y)
+      for (int32_t x = 0; x < width; ++x) av[(size_t)y * width + x].w = variance_filter(P, x, y, width, height);
+    for (int32_t y = 0; y < height; ++y)
+      for (int32_t x = 0; x < width; ++x) {
+        const size_t i = (size_t)y * width + x;
+        nxt[i] = iterate(P, x, y, width, height, (int32_t)1 << it, gx[i], gy[i], A);
+      }
+    f4* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  for (size_t i = 0; i < npix; ++i) finish(cur[i], av[i], A, out + 3 * i, se_out ? se_out + 3 * i : nullptr);
+  return SPT_OK;
+}

@@ -1,0 +1,252 @@
+"""Time and quality of the a-trous denoiser on the GPU (profiles/r19_denoise.json).
+
+usage (on an MI355X, from the repo root):  python tools/denoise_bench.py [OUT.json]
+(OUT.json defaults to build/r19_denoise.json)
+
+Time: spt_denoise_async on synthetic planes at 1024x768 and 4096x4096, by device events, 20 timed
+runs after 5 warm-up runs, for iterations = 0..6. T(k) - T(k-1) is iteration k's variance pass and
+a-trous pass (step 2^(k-1)); T(1) also holds the pack kernel, and the last iteration of every call
+is the variant with the finish fused in. Beside it the render kernel's time of one 64-spp frame at
+1024x768 from the same session, and the bytes one iteration requests per pixel.
+Single kernels (only with the bench library: `make -C small-pathtracer_amd/csrc denoise_bench`, then
+SPT_LIB=build/libspt_denoise_bench.so): pack, the variance pass, and the a-trous pass at every step with
+and without the fused finish, each as 50 launches between one pair of device events, 7 rounds, the
+forms of one step alternating round by round (the plain-load form against the LDS-tiled form where the
+build has one).
+Quality: the HEAD scene at 256x192, 16 seeds at 64, 256 and 1024 spp in 8 batches with a guide of 64
+samples, against the library's own 65536-spp render merged from 16 seeds of 4096.
+"""
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+# per pixel and iteration: 25 taps x three 16-byte loads, the centre's gradient, the 3x3 variance
+# reads (nine 4-byte components of 16-byte elements) and its 4-byte write, 16 bytes out
+BYTES_PER_PIXEL_ITERATION = 25 * 48 + 8 + 9 * 4 + 4 + 16
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
+
+
+def time_denoise(spt, torch, w, h, runs=20, warmup=5):
+    import denoise_truth as dt
+    tile = dt.synthetic(256, 192)
+    reps = (-(-h // 192), -(-w // 256))
+    planes = [np.tile(tile[k], reps + ((1,) if tile[k].ndim == 3 else ()))[:h, :w] for k in dt.PLANES]
+    dev = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).cuda() for a in planes]
+    out = torch.empty(w * h * 3, dtype=torch.float32, device="cuda")
+    se_out = torch.empty(w * h * 3, dtype=torch.float32, device="cuda")
+    dn = spt.Denoiser(w, h, 0)
+    res = {}
+    try:
+        for it in range(7):
+            p = spt.default_denoise_params(iterations=it)
+            ms = []
+            for k in range(warmup + runs):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                dn.denoise_async(*[t.data_ptr() for t in dev], p, out.data_ptr(), se_out.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+                b.record()
+                torch.cuda.synchronize()
+                if k >= warmup:
+                    ms.append(a.elapsed_time(b))
+            res[str(it)] = {"median_ms": float(np.median(ms)), "min_ms": float(np.min(ms)),
+                            "max_ms": float(np.max(ms))}
+    finally:
+        dn.close()
+    med = [res[str(k)]["median_ms"] for k in range(7)]
+    per_iter = [med[k] - med[k - 1] for k in range(2, 7)]
+    res["iteration_ms_steps_2_to_32"] = per_iter
+    res["bytes_per_pixel_iteration"] = BYTES_PER_PIXEL_ITERATION
+    res["requested_TB_per_s_steps_2_to_32"] = [BYTES_PER_PIXEL_ITERATION * w * h / (t * 1e-3) / 1e12
+                                               for t in per_iter]
+    return res
+
+
+def kernel_times(spt, torch, w, h, launches=50, rounds=7):
+    """Per-launch milliseconds of every denoise kernel alone (the bench library's entry point)."""
+    import ctypes
+    import denoise_truth as dt
+    lib = spt.load_library()
+    if not hasattr(lib, "spt_denoise_bench_kernel"):
+        return {"skipped": "the loaded library has no bench entry points (make denoise_bench)"}
+    V, I32 = ctypes.c_void_p, ctypes.c_int32
+    lib.spt_denoise_bench_kernel.argtypes = [V, I32, I32, I32, V, V, V, V, V,
+                                             ctypes.POINTER(spt.spt_denoise_params), V, V, V]
+    lib.spt_denoise_bench_kernel.restype = I32
+    tile = dt.synthetic(256, 192)
+    reps = (-(-h // 192), -(-w // 256))
+    planes = [np.tile(tile[k], reps + ((1,) if tile[k].ndim == 3 else ()))[:h, :w] for k in dt.PLANES]
+    dev = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).cuda() for a in planes]
+    out = torch.empty(w * h * 3, dtype=torch.float32, device="cuda")
+    se_out = torch.empty(w * h * 3, dtype=torch.float32, device="cuda")
+    p = spt.default_denoise_params()
+    dn = spt.Denoiser(w, h, 0)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def launch(which, step, form):
+        return lib.spt_denoise_bench_kernel(dn._d, which, step, form, *[V(t.data_ptr()) for t in dev],
+                                            ctypes.byref(p), V(out.data_ptr()), V(se_out.data_ptr()), V(stream))
+
+    def once(which, step, form):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(launches):
+            launch(which, step, form)
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / launches
+
+    def stat(ms):
+        return {"median_ms": float(np.median(ms)), "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms))}
+
+    res = {"launches_per_round": launches, "rounds": rounds}
+    try:
+        assert launch(0, 1, 1) == 0 and launch(1, 1, 1) == 0  # the scratch holds a packed image from here on
+        has_tiled = launch(2, 1, 2) == 0
+        torch.cuda.synchronize()
+        res["tiled_form_in_this_build"] = bool(has_tiled)
+        for name, which in (("pack", 0), ("variance", 1)):
+            once(which, 1, 1)
+            res[name] = stat([once(which, 1, 1) for _ in range(rounds)])
+        for step in (1, 2, 4, 8, 16, 32):
+            forms = [("plain", 1)] + ([("tiled", 2)] if has_tiled and step <= 2 else [])
+            for name, which in (("atrous", 2), ("atrous_finish", 3)):
+                ms = {f: [] for f, _ in forms}
+                for f, form in forms:
+                    once(which, step, form)
+                for _ in range(rounds):
+                    for f, form in forms:
+                        ms[f].append(once(which, step, form))
+                for f, _ in forms:
+                    res[f"{name}_step{step}_{f}"] = stat(ms[f])
+    finally:
+        dn.close()
+    return res
+
+
+def test_quality(spt):
+    """The configuration tests/test_gpu_denoise.py pins: HEAD 64x48, 64 spp in batches of 8, a guide of
+    16 samples, seeds 1..4, the truth 8192 spp with seed 77; the default parameters."""
+    w, h = 64, 48
+    prims = spt.cornell_scene()
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = spt.render(prims, cam, spt.default_params(width=w, height=h, spp=8192, seed=77))
+    seeds = {}
+    for seed in (1, 2, 3, 4):
+        p = spt.default_params(width=w, height=h, spp=64, seed=seed)
+        r, film, guide, dn = spt.Renderer(0), spt.Film(p, 0), spt.Guide(p, 0), spt.Denoiser(w, h, 0)
+        try:
+            film.enable_noise(8)
+            for k in range(8):
+                film.render(r, prims, cam, p, k * 8, 8)
+                r.stats()
+            guide.render(r, prims, cam, p, 0, 16)
+            noisy, den = film.resolve(), dn.denoise_film(film, guide)
+        finally:
+            for o in (dn, guide, film, r):
+                o.close()
+        seeds[str(seed)] = {"rmse_noisy": rmse(noisy, truth), "rmse_denoised": rmse(den, truth),
+                            "ratio": rmse(den, truth) / rmse(noisy, truth),
+                            "mean_shift": abs(float(den.mean(dtype=np.float64) / noisy.mean(dtype=np.float64)) - 1.0)}
+    return {"what": "tests/test_gpu_denoise.py::test_denoised_is_closer_to_the_truth", "seeds": seeds}
+
+
+def quality(spt, w=256, h=192, seeds=16, spps=(64, 256, 1024)):
+    prims = spt.cornell_scene()
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = np.zeros((h, w, 3), np.float64)
+    for s in range(16):
+        truth += spt.render(prims, cam, spt.default_params(width=w, height=h, spp=4096, seed=1000 + s))
+    truth = (truth / 16).astype(np.float32)
+    variants = {"default": {}, "no_demodulate": {"flags": spt.DENOISE_NO_DEMODULATE},
+                "sigma_color_2": {"sigma_color": 2.0}, "sigma_color_8": {"sigma_color": 8.0}}
+    acc = {v: {spp: [] for spp in spps} for v in variants}
+    noisy_rmse = {spp: [] for spp in spps}
+    for spp in spps:
+        for seed in range(1, seeds + 1):
+            p = spt.default_params(width=w, height=h, spp=spp, seed=seed)
+            r, film, guide, dn = spt.Renderer(0), spt.Film(p, 0), spt.Guide(p, 0), spt.Denoiser(w, h, 0)
+            try:
+                film.enable_noise(spp // 8)
+                for k in range(8):
+                    film.render(r, prims, cam, p, k * (spp // 8), spp // 8)
+                    r.stats()
+                guide.render(r, prims, cam, p, 0, 64)
+                noisy = film.resolve()
+                noisy_rmse[spp].append(rmse(noisy, truth))
+                for v, kw in variants.items():
+                    den, se = dn.denoise_film(film, guide, spt.default_denoise_params(**kw), return_se=True)
+                    acc[v][spp].append({
+                        "rmse": rmse(den, truth),
+                        "mean_change": float(den.mean(dtype=np.float64) / noisy.mean(dtype=np.float64) - 1.0),
+                        "se2_over_err2": float(np.mean(se.astype(np.float64) ** 2) /
+                                               np.mean((den.astype(np.float64) - truth) ** 2))})
+            finally:
+                for o in (dn, guide, film, r):
+                    o.close()
+    res = {"scene": "HEAD", "width": w, "height": h, "seeds": seeds, "truth": "16 seeds x 4096 spp",
+           "noisy_rmse": {str(s): float(np.mean(noisy_rmse[s])) for s in spps}, "variants": {}}
+    inv = np.array([1.0 / np.sqrt(s) for s in spps])
+    base = np.array([np.mean(noisy_rmse[s]) for s in spps])
+    for v in variants:
+        res["variants"][v] = {}
+        for spp in spps:
+            rows = acc[v][spp]
+            d = float(np.mean([x["rmse"] for x in rows]))
+            n = float(np.mean(noisy_rmse[spp]))
+            # the sample count at which the plain film reaches d: the noisy RMSE is linear in 1/sqrt(spp)
+            # (a least-squares line through the three measured counts), solved for the count
+            slope, icpt = np.polyfit(inv, base, 1)
+            x = (d - icpt) / slope
+            equal_spp = float(1.0 / (x * x)) if x > 0 else float("inf")
+            res["variants"][v][str(spp)] = {
+                "rmse_noisy": n, "rmse_denoised": d, "ratio": d / n,
+                "ratio_min_max": [float(min(x["rmse"] / m for x, m in zip(rows, noisy_rmse[spp]))),
+                                  float(max(x["rmse"] / m for x, m in zip(rows, noisy_rmse[spp])))],
+                "mean_change": float(np.mean([x["mean_change"] for x in rows])),
+                "plain_spp_for_equal_rmse": equal_spp, "times_fewer_samples": equal_spp / spp,
+                "mean_se_out2_over_true_err2": float(np.mean([x["se2_over_err2"] for x in rows]))}
+    return res
+
+
+def main():
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "r19_denoise.json")
+    import torch
+    spt = importlib.import_module("small-pathtracer_amd")
+    spt.load_library()
+    assert torch.cuda.is_available(), "denoise_bench needs the GPU"
+    rec = {"kernel_sources_sha16": spt.build_sources_sha16(), "device": torch.cuda.get_device_name(0),
+           "utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()), "time": {}}
+    rec["kernels"] = {}
+    for w, h in ((1024, 768), (4096, 4096)):
+        rec["time"][f"{w}x{h}"] = time_denoise(spt, torch, w, h)
+        rec["kernels"][f"{w}x{h}"] = kernel_times(spt, torch, w, h)
+    rec["test_quality"] = test_quality(spt)
+    p = spt.default_params(width=1024, height=768, spp=64, seed=1)
+    cam = spt.Camera(aspect=float(np.float32(1024) / np.float32(768)))
+    ms = []
+    for _ in range(4):
+        _, st = spt.render(spt.cornell_scene(), cam, p, return_stats=True)
+        ms.append(st["kernel_ms"])
+    rec["render_kernel_ms_1024x768_64spp"] = float(np.median(ms[1:]))
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump(rec, open(out, "w"), indent=1)  # the timings survive a failure below
+    rec["quality"] = quality(spt)
+    json.dump(rec, open(out, "w"), indent=1)
+    print(json.dumps({"time_1024x768": rec["time"]["1024x768"]["iteration_ms_steps_2_to_32"],
+                      "default": rec["quality"]["variants"]["default"]}))
+
+
+if __name__ == "__main__":
+    main()
