@@ -1568,10 +1568,16 @@ static fv c_path(const c_ctx* C, uint32_t pix, uint32_t s, int px, int py, const
     }
     if (H->refl != SPT_DIFF) {
       /* SPEC :481-482 and REFR :484-495 (smallpt's commented-out code, fp32): no NEE; the RR of
-         :448 above already ran. reflRay direction r.d - n*2*n.dot(r.d), not renormalised. */
+         :448 above already ran. reflRay direction r.d - n*2*n.dot(r.d). Contract v8: renormalised
+         in the unit-direction contract. A sphere's gn = (x - p) / r is unit only as far as x lies
+         on the sphere (the root's rsq_nr2: |gn| - 1 ~ 3e-6), the mirror formula then changes |d| by
+         4 (gn.d)^2 (|gn| - 1) per bounce, and the sphere test assumes |d| = 1: inside the glass ball
+         the error compounds until a ray that leaves the ball finds its far root again beyond the
+         2e-3 epsilon. Rect-only SPEC scenes (free-scale) flip one component's sign: exact. */
       const fv Tf = fv3(T.x * f.x, T.y * f.y, T.z * f.z);
       const float k2 = 2.0f * fdot(gn, d);
-      const fv refl = fv3(d.x - gn.x * k2, d.y - gn.y * k2, d.z - gn.z * k2);
+      fv refl = fv3(d.x - gn.x * k2, d.y - gn.y * k2, d.z - gn.z * k2);
+      if (C->unit) refl = fnormalize(refl);
       L = fv3(fmaf(T.x, e.x, L.x), fmaf(T.y, e.y, L.y), fmaf(T.z, e.z, L.z));
       o = x;
       T = Tf;

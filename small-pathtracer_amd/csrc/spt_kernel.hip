@@ -1238,10 +1238,12 @@ render_kernel(const KParams* __restrict__ Pg) {
         uint32_t nxt = kStCos;  // the state after this vertex unless the path ends here
         if (TP::MAT && !term && H.refl != SPT_DIFF) {
           // SPEC :481-482 and REFR :484-495 (smallpt's commented-out code; oracle c_path): no NEE.
-          // reflRay direction r.d - n*2*n.dot(r.d), not renormalised.
+          // reflRay direction r.d - n*2*n.dot(r.d), renormalised in the unit-direction contract
+          // (contract v8: a sphere's gn is unit only to ~3e-6 and the sphere test assumes |d| = 1).
           const f3 Tf = T;
           const float k2 = 2.0f * dot3(gn, d);
-          const f3 refl = mk(d.x - gn.x * k2, d.y - gn.y * k2, d.z - gn.z * k2);
+          f3 refl = mk(d.x - gn.x * k2, d.y - gn.y * k2, d.z - gn.z * k2);
+          if (unit_dirs_of<TP>(Pg)) refl = normalize3(refl);
           bool use_refl = true;
           if (H.refl == SPT_REFR) {
             const bool into = dot3(gn, nl) > 0.0f;                 // :485

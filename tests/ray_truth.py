@@ -76,6 +76,32 @@ class Truth:
         return ids, t0, gap, m[rows, order[:, 0]]
 
 
+def t_bound(T, prims, o, d, ids, t64):
+    """The issue's bound on |t32 - t64| for equal ids. Rectangles: 4 (2^-24 max(|k|, |o_a|) / |d_a| +
+    2^-22 t): the rounding of k - o_a, then rcp_nr, the fma and the float store. Narrow spheres, the
+    analogue for t = b - sqrt(b^2 - op.op + r^2) in fp32 with |d| = 1 assumed: b carries 3 roundings
+    of size 2^-24 |op|, the discriminant 2^-23 (b^2 + op.op + r^2) which the root divides by 2 sd, the
+    root itself rsq_nr2's 5e-6. Wide spheres are fp64 stored as a float: 2^-22 t."""
+    o, d = o.astype(np.float64), d.astype(np.float64)
+    b = np.full(len(o), np.nan)
+    for i, ax, *_rest in T.rects:
+        k = _rest[2]
+        s = ids == i
+        b[s] = 4 * (2.0 ** -24 * np.maximum(abs(k), np.abs(o[s, ax])) / np.abs(d[s, ax]) + 2.0 ** -22 * t64[s])
+    for i, r, c in T.spheres:
+        s = ids == i
+        if r >= WIDE_RADIUS:
+            b[s] = 2.0 ** -22 * t64[s]
+            continue
+        op = c[None, :] - o[s]
+        op2 = (op * op).sum(axis=1)
+        bb = (op * d[s]).sum(axis=1)
+        sd = np.abs(bb - t64[s])
+        b[s] = 4 * (2.0 ** -24 * (3 * np.sqrt(op2) + (bb * bb + op2 + r * r) / np.maximum(sd, 1e-6))
+                    + 5e-6 * sd + 2.0 ** -22 * t64[s])
+    return b
+
+
 def unit(v):
     v = np.asarray(v, dtype=np.float64)
     return v / np.sqrt((v * v).sum(axis=-1, keepdims=True))

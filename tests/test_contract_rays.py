@@ -28,32 +28,6 @@ def random_dirs(rng, n, min_comp=1e-3):
     return d[(np.abs(d) >= min_comp).all(axis=1)][:n].astype(np.float32)
 
 
-def t_bound(T, prims, o, d, ids, t64):
-    """The issue's bound on |t32 - t64| for equal ids. Rectangles: 4 (2^-24 max(|k|, |o_a|) / |d_a| +
-    2^-22 t): the rounding of k - o_a, then rcp_nr, the fma and the float store. Narrow spheres, the
-    analogue for t = b - sqrt(b^2 - op.op + r^2) in fp32 with |d| = 1 assumed: b carries 3 roundings
-    of size 2^-24 |op|, the discriminant 2^-23 (b^2 + op.op + r^2) which the root divides by 2 sd, the
-    root itself rsq_nr2's 5e-6. Wide spheres are fp64 stored as a float: 2^-22 t."""
-    o, d = o.astype(np.float64), d.astype(np.float64)
-    b = np.full(len(o), np.nan)
-    for i, ax, *_rest in T.rects:
-        k = _rest[2]
-        s = ids == i
-        b[s] = 4 * (2.0 ** -24 * np.maximum(abs(k), np.abs(o[s, ax])) / np.abs(d[s, ax]) + 2.0 ** -22 * t64[s])
-    for i, r, c in T.spheres:
-        s = ids == i
-        if r >= rt.WIDE_RADIUS:
-            b[s] = 2.0 ** -22 * t64[s]
-            continue
-        op = c[None, :] - o[s]
-        op2 = (op * op).sum(axis=1)
-        bb = (op * d[s]).sum(axis=1)
-        sd = np.abs(bb - t64[s])
-        b[s] = 4 * (2.0 ** -24 * (3 * np.sqrt(op2) + (bb * bb + op2 + r * r) / np.maximum(sd, 1e-6))
-                    + 5e-6 * sd + 2.0 ** -22 * t64[s])
-    return b
-
-
 @pytest.mark.parametrize("name", GENERIC_SCENES)
 def test_f1_generic_rays(spt, oracle, name):
     """Origins uniform in the room, random unit directions with every |d_a| >= 1e-3. Measured: no id
@@ -73,7 +47,7 @@ def test_f1_generic_rays(spt, oracle, name):
     assert np.array_equal(id32[keep], ids[keep])
     same = (ids == id32) & (ids >= 0)
     err = np.abs(t32.astype(np.float64) - t64)[same]
-    bound = t_bound(T, prims, o, d, ids, t64)[same]
+    bound = rt.t_bound(T, prims, o, d, ids, t64)[same]
     print(f"{name}: max |t32 - t64| {err.max():.3e}, max err / bound {np.max(err / bound):.3f}")
     assert np.all(err <= bound)
 
@@ -182,7 +156,7 @@ def test_f3_origin_on_a_plane(spt, oracle, name, origin, own):
     assert np.array_equal(id32[keep], ids[keep])
     same = (ids == id32) & (ids >= 0)
     err = np.abs(t32.astype(np.float64) - t64)[same]
-    assert np.all(err <= t_bound(T, prims, o, d, ids, t64)[same])
+    assert np.all(err <= rt.t_bound(T, prims, o, d, ids, t64)[same])
 
 
 def _fan_check(spt, oracle, name, origin, target):
@@ -227,7 +201,7 @@ def test_f4_grazes(spt, oracle, name):
         leaks_total += int(leaks.sum())
         same = (ids == id32) & (ids >= 0)
         err = np.abs(t32.astype(np.float64) - t64)[same]
-        assert np.all(err <= t_bound(T, prims, o, d, ids, t64)[same]), label
+        assert np.all(err <= rt.t_bound(T, prims, o, d, ids, t64)[same]), label
     print(f"{name}: {leaks_total} leaks of {total} grazing rays")
     assert leaks_total == 0
 
@@ -289,7 +263,7 @@ def test_f6_wide_spheres(spt, oracle):
         assert np.all(allowed | (near_tie & (id32 >= 0))) and not leaks.any(), label
         same = (ids == id32) & (ids >= 0)
         err = np.abs(t32.astype(np.float64) - t64)[same]
-        assert np.all(err <= t_bound(T, prims, o, d, ids, t64)[same]), label
+        assert np.all(err <= rt.t_bound(T, prims, o, d, ids, t64)[same]), label
     T = rt.Truth(oracle, prims)
     rng = np.random.default_rng(9)
     for origin in [(27 + 4, 16.5 + 3, 47 - 2), (1, 40, 80), (50, 81.33, 81.6)]:
@@ -302,7 +276,7 @@ def test_f6_wide_spheres(spt, oracle):
         assert np.array_equal(id32[keep], ids[keep]), origin
         same = (ids == id32) & (ids >= 0)
         err = np.abs(t32.astype(np.float64) - t64)[same]
-        assert np.all(err <= t_bound(T, prims, o, d, ids, t64)[same]), origin
+        assert np.all(err <= rt.t_bound(T, prims, o, d, ids, t64)[same]), origin
 
 
 @pytest.mark.parametrize("seed", [1, 2])
