@@ -131,11 +131,14 @@ constexpr uint32_t kKeyNone = __builtin_bit_cast(uint32_t, 1e20f) | 63u;  // tmi
 constexpr float kNegTiny = -0x1p-149f;
 __device__ __forceinline__ float plane_t(float n, float inv) { return fmaf(n, inv, kNegTiny); }
 __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-// c += b for a per-lane event counter as ONE v_addc_co_u32 with b's lane mask as its carry-in
-// (LLVM spells c + (b ? 1 : 0) as a v_cndmask and a v_add)
-__device__ __forceinline__ void count_if(uint32_t& c, bool b) {
-  const uint64_t m = __builtin_amdgcn_ballot_w64(b);
-  asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(c) : "s"(m) : "vcc");
+// An event counter takes the lanes of mask m, at a convergent point of the render loop. Wave-uniform
+// (c in an SGPR): the mask's population. Per lane (KernelTraits::kLaneEvents; c in a VGPR, summed over
+// the wave at the end): ONE v_addc_co_u32 with the mask as its carry-in (LLVM spells c + (b ? 1 : 0)
+// as a v_cndmask and a v_add).
+template <bool LANE>
+__device__ __forceinline__ void count_lanes(uint32_t& c, uint64_t m) {
+  if constexpr (LANE) asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(c) : "s"(m) : "vcc");
+  else c += (uint32_t)__popcll(m);
 }
 // (bits(t) | 63) ^ (63 - pos) as ONE v_bitop3 (0x36 = (S0 | S2) ^ S1)
 template <int POS>
@@ -377,11 +380,10 @@ __device__ __forceinline__ auto tests_of(const SPT_CONST SceneGeo* G, const GeoT
 }
 // The scene's room of contract v5 in uploaded geometry: SceneGeo.room_test[] (three GeoTests kept
 // out of the per-kind test lists) and the box (host build_geo, oracle c_find_room).
-template <class TP, bool COUNT_MISS = false, class GP, class GT, class SP>
+template <class TP, class GP, class GT, class SP>
 __device__ __forceinline__ bool intersect_scene(const SPT_CONST SceneGeo* G, GP rect, GT tests,
                                                 SP sphs, const int* pos2idx, f3 o, f3 d, int& id,
-                                                float& ia_hit, int& pos_out, uint32_t& n_miss,
-                                                f3& inv) {
+                                                float& ia_hit, int& pos_out, f3& inv) {
   const float ix = rcp_nr(d.x), iy = rcp_nr(d.y), iz = rcp_nr(d.z);
   inv = mk(ix, iy, iz);
   uint32_t tmin = kKeyNone;
@@ -438,9 +440,6 @@ __device__ __forceinline__ bool intersect_scene(const SPT_CONST SceneGeo* G, GP 
     }
   }
   const bool hit = tmin < kKeyNone;
-  // COUNT_MISS: every lane's miss is a path ray's (a traced shadow ray always meets the light, whose
-  // test in the trace is the pre-test's, bit for bit): counted here, where the compare is fresh
-  if constexpr (COUNT_MISS) count_if(n_miss, tmin >= kKeyNone);
   int pos = (int)(tmin & 63u);  // (63 on a miss: a valid LDS index, the id is kept)
   // HEAD kernels: a miss reports the position of prim 0, whose id a missed path ray keeps (:373-374),
   // so the shading takes the hit's plane axis from the same two position compares as ia_hit
@@ -728,11 +727,10 @@ render_kernel(const KParams* __restrict__ Pg) {
   // Sphere vertices shaded, per wave (SPH only). They are counted inside the divergent shading
   // block, where a wave-uniform register would turn per-lane (a ballot there sees only the active
   // lanes); one LDS add per wave (the atomic optimizer folds the lanes) keeps it out of the VGPRs.
+  // (The shaded primitive's kind is told apart there by three rectangle compares; a sphere is what
+  // is left, so there is no compare of its own to take to a convergent ballot.)
   __shared__ uint32_t s_nsph[TP::SPH ? kBlock / 64 : 1];
   if (TP::SPH && threadIdx.x < kBlock / 64) s_nsph[threadIdx.x] = 0;
-  // Shadow rays resolved early, per wave, in the sphere kernels (same reason: no VGPR counter)
-  __shared__ uint32_t s_nearly[TP::SPH ? kBlock / 64 : 1];
-  if (TP::SPH && threadIdx.x < kBlock / 64) s_nearly[threadIdx.x] = 0;
   // The set-up of the units of each wave's pool (spt_kparams.h, SPT_POOL_LDS): 64 entries per wave,
   // written and read by that wave alone. The generic kernels keep the per-lane set-up: the REFR
   // stack fills their LDS (5 blocks per CU), and 8 KB more would cost them a block.
@@ -838,18 +836,26 @@ render_kernel(const KParams* __restrict__ Pg) {
   // is a sample's camera ray or a cosine continuation, so the cosine rays are n_gen less the launch's
   // samples, taken off once at the end. The generic kernel counts n_path and n_cos themselves.
   uint32_t n_path = 0, n_cos = 0, n_gen = 0;
-  // Per-lane counts of events that happen inside divergent blocks, incremented in place and
-  // summed once at the end (a boolean per event carried to a convergent ballot cost 3 VALU each).
+  // The events from the trace to the path end are counted the same way. That region runs under a
+  // wave-uniform guard (some lane traces), not a divergent one, so its top level is convergent and a
+  // counter updated there stays in an SGPR: each event's lane mask is a compare the region needs
+  // anyway, taken by a ballot where it is final (s_and / s_bcnt1 / s_add, no VALU, no VGPR).
+  //   n_miss:   path rays that hit nothing        n_hit:   traced shadow rays that reach the light
+  //   n_shadow: shadow rays resolved (traced, and in the early-resolve kernels proven)
+  //   n_early:  shadow rays proven to reach the light without a trace (stats[kStatShadowProven])
+  // (Per lane in the kLaneEvents variants, spt_variants.h: the same masks at the same points, each
+  // added to the lanes it holds, and the wave's lanes summed at the end.)
+  uint32_t n_miss = 0, n_hit = 0, n_shadow = 0, n_early = 0;
   // What the variant's types imply (spt_variants.h, where the host reads the same values).
   using KT = KernelTraits<TP, CF>;
+  static_assert(!TP::MAT || TP::SPH, "the generic kernels count their misses in the sphere shading branch");
   constexpr bool kNeeByIdentity = KT::kNeeByIdentity, kEarlyNee = KT::kEarlyNee,
-                 kEarlySph = KT::kEarlySph, kEarlyGeo = KT::kEarlyGeo, kEarly = KT::kEarly;
-  uint32_t l_early = 0;  // shadow rays resolved early (stats[kStatShadowProven])
-  uint32_t l_miss = 0, l_nee = 0, l_hit = 0;
-  // Shadow rays traced (NEE samples that passed light_accepts()): per lane in the rect kernels,
-  // wave-uniform in the sphere kernels (a ballot of the kStShadow lanes at the convergent point
-  // before the trace), whose VGPR budget is the tighter one.
-  uint32_t l_shadow = 0;
+                 kEarlySph = KT::kEarlySph, kEarlyGeo = KT::kEarlyGeo, kEarly = KT::kEarly,
+                 kLaneEvents = KT::kLaneEvents;
+  // NEE samples taken (the run-time estimator's kernels): per lane, incremented in place inside the
+  // nested shading branches and summed once at the end. Its predicate (a DIFF vertex, the sample
+  // drawn, the path alive) exists only there; carried to a convergent ballot it cost 3 VALU.
+  uint32_t l_nee = 0;
 #ifdef SPT_REGION_STATS
   uint32_t reg_exec[kRegions] = {}, reg_lanes[kRegions] = {};
   uint32_t reg_flags = 0;
@@ -1079,10 +1085,21 @@ render_kernel(const KParams* __restrict__ Pg) {
 
     // Path rays: counted here by the generic kernel only (the others: n_gen, above).
     if constexpr (TP::MAT) n_path += (uint32_t)__popcll(__ballot(ls == kStPath));
-    if constexpr (TP::SPH) l_shadow += (uint32_t)__popcll(__ballot(ls == kStShadow));
-    if (ls >= kStPath) {  // kStPath or kStShadow
+    // (The generic kernels, kLaneEvents and at 78+ VGPRs, keep the forms they had: this ballot for the
+    // shadow rays, and below the light hits and misses added per lane inside the divergent blocks.
+    // With their counts at the region's top level they took 1 to 14 more VGPRs.)
+    if constexpr (TP::MAT) n_shadow += (uint32_t)__popcll(__ballot(ls == kStShadow));
+    // Everything from the trace to the path end runs when some lane holds a ray (kStPath or
+    // kStShadow): a wave-uniform guard. Only idle lanes hold none here, and under the guard they run
+    // the trace too, on their stale finite o and d: a VALU instruction costs the wave the same
+    // whatever its lane mask. What they compute lands in locals (id, hit, hpos, inv); every block
+    // below keeps its own state guard, which an idle lane fails, so it writes no loop-carried state;
+    // and every event mask is and-ed with a state compare, so nothing of theirs is counted. In the
+    // last, empty iteration no lane traces and the region is skipped as before.
+    // (The kLaneEvents variants keep the divergent guard: the lanes that hold a ray.)
+    if (kLaneEvents ? ls >= kStPath : __ballot(ls >= kStPath) != 0) {
       // 4) trace the lane's ray (path ray: hittingPoint :371-377; shadow ray: :466).
-      SPT_REGION(4);
+      if (ls >= kStPath) SPT_REGION(4);
 #ifdef SPT_PROBE_SALU  // diagnostic build SPT_DIAG=3: N extra SALU per wave-iteration (issue cost)
       { uint32_t z_ = iter; asm volatile(".rept " SPT_XSTR(SPT_PROBE_SALU) "\n s_add_u32 %0, %0, 1\n .endr" : "+s"(z_)); }
 #endif
@@ -1098,8 +1115,8 @@ render_kernel(const KParams* __restrict__ Pg) {
       int hpos;
       f3 inv;  // 1/d per axis (rcp_nr), the trace's
       // (the early-resolve kernels trace a shadow ray only when the light accepts it: it never misses)
-      bool hit = intersect_scene<TP, kEarly>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph, s_pos2idx,
-                                             o, d, id, ia_hit, hpos, l_miss, inv);
+      bool hit = intersect_scene<TP>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph, s_pos2idx, o, d,
+                                     id, ia_hit, hpos, inv);
       if constexpr (TP::CONSTGEO)
         ia_hit = hpos < kCornellNXY ? inv.z : (hpos < kCornellNXY + kCornellNXZ ? inv.y : inv.x);
 
@@ -1109,20 +1126,35 @@ render_kernel(const KParams* __restrict__ Pg) {
       //    and applied as T*1 (exact) where the light is not reached: no branch. (The HEAD NEE
       //    kernel resolves in 5') below instead, after the shading block.)
       bool traced_shadow = ls == kStShadow;
+      uint64_t tsm = __ballot(ls == kStShadow);  // the same as a lane mask
       if constexpr (kEarly) {
         // as a lane mask taken here: compared where 5') reads it, the state word of before the
         // shading stays live beside the new one (two v_mov per iteration)
-        uint64_t tsm = __ballot(ls == kStShadow);
         asm volatile("" : "+s"(tsm));
         traced_shadow = __builtin_amdgcn_inverse_ballot_w64(tsm);
       }
-      if (!kEarly && ls == kStShadow) {
+      // (a cosine-only kernel, CF::NEE == 0, never sets a shadow ray: no resolve block at all)
+      if constexpr (!kEarly && CF::NEE != 0) {
+      // Skipped as a whole, on the scalar mask, when no lane resolves: the light's slot is a scalar
+      // load in the run-time estimator's kernels. (The kLaneEvents variants' guard is the block's own.)
+      if (kLaneEvents || tsm != 0) {
+      const SPT_CONST KParams* D = cptr_at<2>(Pg, left);
+      bool lh = false;
+      if constexpr (!TP::MAT) {
+        // the light compare at the top level, where its mask and the shadow lanes' can be counted
+        // (each mask the ballot of one compare, combined on the scalar unit: the ballot of a combined
+        // boolean is built through a VGPR, a v_cndmask and a v_cmp each)
+        lh = id == light_slot_of<TP, CF>(D);
+        count_lanes<kLaneEvents>(n_shadow, tsm);
+        count_lanes<kLaneEvents>(n_hit, tsm & __ballot(lh));
+      }
+      if (traced_shadow) {
         SPT_REGION(6);
-        const SPT_CONST KParams* D = cptr_at<2>(Pg, left);
-        const bool lh = id == light_slot_of<TP, CF>(D);
+        if constexpr (TP::MAT) {  // (in place, as they were: see above)
+          lh = id == light_slot_of<TP, CF>(D);
+          count_lanes<true>(n_hit, __ballot(lh));
+        }
         if (lh) SPT_REGION(7);
-        count_if(l_hit, lh);
-        if constexpr (!TP::SPH) ++l_shadow;
         const float larea = CF::LREF == 1 ? kRefLarea : D->larea;
         const float nee_c = CF::LREF == 1 ? kRefNeeC : D->nee_c;
         t = hit_t<TP>(s_prims[id], hpos, o, d, ia_hit, G);  // the light's t (the winner's)
@@ -1134,9 +1166,17 @@ render_kernel(const KParams* __restrict__ Pg) {
           r = philox_px(pk, s, (uint32_t)dp1 | (TP::MAT ? branch << 24 : 0u));
         ls = lh ? kStPath : kStCos;
       }
+      }
+      }
 
       // 6) shade a vertex (:422, :444-480).
-      if (ls == kStPath) {
+      const bool shade = ls == kStPath;
+      // A vertex with no hit is a miss: a path ray's, or in the kernels that resolve above the shadow
+      // ray's of a vertex on the light, which keeps its id. (In the early-resolve kernels a traced
+      // shadow ray always meets the light, whose test in the trace is the pre-test's, bit for bit.)
+      // The block's own guard and the trace's compare.
+      if constexpr (!TP::MAT) count_lanes<kLaneEvents>(n_miss, __ballot(shade) & ~__ballot(hit));
+      if (shade) {
         SPT_REGION(5);
         const DevPrim& H = s_prims[id];
         const int kind = H.kind;
@@ -1168,14 +1208,13 @@ render_kernel(const KParams* __restrict__ Pg) {
           // a miss vertex is the origin (:373-374); a leaked path ending at its miss (the LEAK == 1
           // kernels, see below) never reads it
           if constexpr (CF::LEAK != 1) x = hit ? x : mk(0, 0, 0);
-          if constexpr (!kEarly) l_miss += hit ? 0u : 1u;
           const float sg = da < 0.0f ? 1.0f : -1.0f;
           nl = mk(kyz ? sg : 0.0f, kxz ? sg : 0.0f, kxy ? sg : 0.0f);
           if (TP::MAT) gn = mk(kyz ? 1.0f : 0.0f, kxz ? 1.0f : 0.0f, kxy ? 1.0f : 0.0f);
         } else {
         if (!hit) {
           x = mk(0, 0, 0);
-          if constexpr (!kEarly) ++l_miss;
+          if constexpr (TP::MAT) ++n_miss;
         } else {
           // plane distance as the reference derives it (:103); spheres: the root
           float tr = hit_t<TP>(H, hpos, o, d, ia_hit, G);
@@ -1371,21 +1410,22 @@ render_kernel(const KParams* __restrict__ Pg) {
       //    that reaches it shades the light vertex as L += (T*w)*e and ends the path (RR with
       //    p == 0, :448), which is all the common vertex block would do there.
       if constexpr (kEarly) {
-        if (traced_shadow || ls == kStEarly) {
+        // The block's masks are taken at the top level, where they are counted: the proven lanes,
+        // the resolving ones (the block's guard), and the light compare on the trace's final id.
+        // (As lane masks, see 5.)
+        const uint64_t eam = __ballot(ls == kStEarly);
+        // a traced shadow ray that reached the light; never a proven lane (its path ray hit what
+        // it shaded, not the black light, which would have ended the path)
+        const uint64_t thm = __ballot(id == light_slot_of<TP, CF>(cptr_at<5>(Pg, left)));
+        const uint64_t resm = tsm | eam;
+        count_lanes<kLaneEvents>(n_early, eam);
+        count_lanes<kLaneEvents>(n_shadow, resm);
+        count_lanes<kLaneEvents>(n_hit, resm & thm);  // (+ the proven ones, n_early, at the end)
+        if (__builtin_amdgcn_inverse_ballot_w64(resm)) {
           SPT_REGION(6);
-          const bool ea = ls == kStEarly;
-          // a traced shadow ray that reached the light; never a proven lane (its path ray hit what
-          // it shaded, not the black light, which would have ended the path)
-          const bool th = id == light_slot_of<TP, CF>(cptr_at<5>(Pg, left));
-          const bool lh = ea | th;
+          const bool ea = __builtin_amdgcn_inverse_ballot_w64(eam);
+          const bool lh = __builtin_amdgcn_inverse_ballot_w64(eam | thm);
           if (lh) SPT_REGION(7);
-          count_if(l_hit, th);  // (+ the proven ones, l_early / s_nearly, at the end)
-          if constexpr (TP::SPH) {  // (sphere kernels ballot-count the traced ones)
-            if (ea) atomicAdd(&s_nearly[threadIdx.x / 64], 1u);
-          } else {
-            l_early += ea ? 1u : 0u;
-            ++l_shadow;
-          }
           float wl;
           if constexpr (kEarlyNee) {
             wl = w_nee;  // (from the vertex, above)
@@ -1499,44 +1539,37 @@ render_kernel(const KParams* __restrict__ Pg) {
       }
     }
 #endif
+    // The event counts: wave-uniform, lane 0 adds them; in the kLaneEvents variants every lane adds
+    // its own (the atomic optimizer reduces each over the wave).
+    const unsigned long long np = TP::MAT ? n_path : n_gen;
+    auto add_events = [&](bool mine) {
+      if (!mine) return;
+      // light hits: the traced ones and the proven ones (a proven shadow ray reaches the light)
+      const unsigned long long nh = (unsigned long long)n_hit + (kEarly ? n_early : 0u);
+      atomicAdd(st + 3, nh + (kLaneEvents ? 0ull : np));  // vertices = path rays + light hits
+      atomicAdd(st + 5, nh);
+      atomicAdd(st + 7, (unsigned long long)n_miss);
+      if constexpr (!TP::MAT) atomicAdd(st + kStatShadowTraced, (unsigned long long)n_shadow);
+      if constexpr (kEarly) atomicAdd(st + kStatShadowProven, (unsigned long long)n_early);
+    };
+    if constexpr (kLaneEvents) add_events(true);
     if (lane == 0) {  // wave-uniform counters: one lane adds them
       if (capped) atomicAdd(st + 0, 1ull);  // the host reports an error
-      const unsigned long long np = TP::MAT ? n_path : n_gen;
       atomicAdd(st + 1, np);
-      atomicAdd(st + 3, np);  // + the light hits, added per lane below
+      if constexpr (kLaneEvents) atomicAdd(st + 3, np);
       atomicAdd(st + 6, (unsigned long long)(TP::MAT ? n_cos : n_gen));
+      add_events(!kLaneEvents);
+      if constexpr (TP::MAT) atomicAdd(st + kStatShadowTraced, (unsigned long long)n_shadow);  // (wave-uniform)
+      if constexpr (TP::SPH) atomicAdd(st + kStatSphereVertices, (unsigned long long)s_nsph[threadIdx.x / 64]);
     }
     if (!TP::MAT && blockIdx.x == 0 && threadIdx.x == 0) {  // one camera ray per sample: not cosine rays
       const SPT_CONST KParams* C = cptr(Pg);
       const unsigned long long samples = (unsigned long long)C->n_local_pix * (unsigned long long)C->s_count;
       atomicAdd(st + 6, 0ull - samples);  // (the word is whole again once every wave has added its n_gen)
     }
-    {  // per-lane event counts (the atomic optimizer reduces each over the wave)
-      if constexpr (!kNeeByIdentity) {
-        atomicAdd(st + 2, (unsigned long long)l_nee);
-        atomicAdd(st + 4, (unsigned long long)l_nee);
-      }
-      if constexpr (kEarlyNee || kEarlyGeo) l_hit += l_early;  // proven shadow rays reach the light
-      atomicAdd(st + 3, (unsigned long long)l_hit);
-      atomicAdd(st + 5, (unsigned long long)l_hit);
-      atomicAdd(st + 7, (unsigned long long)l_miss);
-      if constexpr (TP::SPH) {
-        if (lane == 0) atomicAdd(st + kStatShadowTraced, (unsigned long long)l_shadow);
-      } else {
-        atomicAdd(st + kStatShadowTraced, (unsigned long long)l_shadow);
-      }
-      if constexpr (TP::SPH)
-        if (lane == 0) atomicAdd(st + kStatSphereVertices, (unsigned long long)s_nsph[threadIdx.x / 64]);
-      if constexpr (kEarlyNee || kEarlyGeo) atomicAdd(st + kStatShadowProven, (unsigned long long)l_early);
-      if constexpr (kEarlySph) {
-        if (lane == 0) {
-          const unsigned long long ne = s_nearly[threadIdx.x / 64];
-          atomicAdd(st + kStatShadowProven, ne);
-          atomicAdd(st + kStatShadowTraced, ne);
-          atomicAdd(st + 3, ne);  // proven shadow rays reach the light (vertices, light hits)
-          atomicAdd(st + 5, ne);
-        }
-      }
+    if constexpr (!kNeeByIdentity) {  // the per-lane count (the atomic optimizer reduces it over the wave)
+      atomicAdd(st + 2, (unsigned long long)l_nee);
+      atomicAdd(st + 4, (unsigned long long)l_nee);
     }
   }
 }
@@ -1666,10 +1699,9 @@ guide_kernel(const KParams* __restrict__ Pg) {
       const f3 d = normalize_dir(v, unit);
       int id = 0, hpos;
       float ia_hit = 0.0f;
-      uint32_t n_miss = 0;
       f3 inv;
-      const bool hit = intersect_scene<TP, false>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph,
-                                                  s_pos2idx, o, d, id, ia_hit, hpos, n_miss, inv);
+      const bool hit = intersect_scene<TP>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph, s_pos2idx, o,
+                                           d, id, ia_hit, hpos, inv);
       if (hit) {
         const DevPrim& H = s_prims[id];
         const float t = hit_t<TP>(H, hpos, o, d, ia_hit, G);  // the winner's exact t

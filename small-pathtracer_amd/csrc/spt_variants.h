@@ -129,6 +129,14 @@ struct KernelTraits {
   static constexpr bool kEarlyGeo = !kEarlyNee && !TP::SPH && !TP::MAT && TP::NBOX == 2 && CF::NEE == 1 &&
                                     CF::BLACK == 1 && CF::LREF == 1 && CF::MAXD0 == 1;
   static constexpr bool kEarly = kEarlyNee || kEarlySph || kEarlyGeo;
+  // The loop's event counters (misses, shadow rays, light hits) are wave-uniform, in SGPRs. Three
+  // NEE variants sit at the SGPR cap and paid four more with SGPR spills into VGPR lanes and a VGPR
+  // (the run-time-geometry rect kernels cornell_nee and rectdiff_nee, and uplight_nee_cam): theirs
+  // stay per lane, in VGPRs. So do the generic kernels' (SPEC/REFR materials), which are not at the
+  // cap (78 VGPRs, 5-6 waves per SIMD) and ran 1.7 % slower with the scalar form. A measured choice
+  // (profiles/r21_vgprs.txt, profiles/r21_event_counts_ab.txt), like the young cut.
+  static constexpr bool kLaneEvents =
+      TP::MAT || (!TP::SPH && CF::NEE == 1 && (!TP::CONSTGEO || (TP::UPLIGHT && CF::CAMAX == 2)));
   // For the host. The UPBOX / UPLIGHT kernels are CONSTGEO (kEarlyNee) and take their box clauses
   // from KParams (early_geo_proven inside early_nee_proven's place): clauses, not literals.
   static constexpr EarlyKind early = kEarlyNee ? (TP::UPBOX ? kEarlyClauses : kEarlyLiteral)

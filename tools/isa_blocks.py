@@ -5,7 +5,7 @@
 
 --bb splits at LLVM's '; %bb.N' comments too (fall-through blocks), --min hides blocks with fewer
 VALU. `slots` weights each VALU by its issue cost on gfx950 (tools/valu_rates.hip,
-profiles/r01_valu_rates.txt): full-rate 1, half-rate 2, transcendental 4.
+profiles/r01_valu_rates.txt, profiles/r21_valu_rates.txt): full-rate 1, half-rate 2, transcendental 4.
 """
 import re
 import sys
@@ -13,10 +13,16 @@ from collections import Counter
 
 # Issue cost in VALU slots (one slot = a full-rate wave64 instruction, 2 cycles on a SIMD-32),
 # measured by tools/valu_rates.hip (profiles/r01_valu_rates.txt): half-rate ops 2, transcendental 4.
+# Round 21 (profiles/r21_valu_rates.txt) timed what the hot blocks are full of and found at half rate:
+# the three-operand and the two-operand min / max (integer, and v_min_f32), the VOP3 select (an SGPR-pair mask), every
+# compare, the carry add and mbcnt; v_lshl_add_u64 stays at half; v_fmaak / v_fmamk are full rate.
 HALF = ("v_mad_u64_u32", "v_mad_i64_i32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mul_u32_u24",
         "v_mul_hi_u32_u24", "v_mad_u32_u24", "v_cvt_", "v_perm_b32", "v_bfe_", "v_bfi_b32",
         "v_add3_u32", "v_lshl_add_u32", "v_lshl_or_b32", "v_and_or_b32", "v_or3_b32", "v_med3_",
-        "v_xad_u32", "v_pk_", "v_fma_f64", "v_add_f64", "v_mul_f64", "v_lshl_add_u64")
+        "v_xad_u32", "v_pk_", "v_fma_f64", "v_add_f64", "v_mul_f64", "v_lshl_add_u64",
+        "v_min3_", "v_max3_", "v_min_u32", "v_max_u32", "v_min_i32", "v_max_i32", "v_min_f32",
+        "v_cndmask_b32_e64", "v_cmp_",
+        "v_addc_co_u32", "v_mbcnt_")
 QUARTER = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_sin_", "v_cos_", "v_exp_", "v_log_", "v_div_")
 
 

@@ -13,6 +13,10 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed) {
   uint32_t a0 = threadIdx.x ^ seed, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5,
            a6 = a0 + 6, a7 = a0 + 7;
   const uint32_t b = seed | 1;
+  // a wave-uniform lane mask for the forms that read one from an SGPR pair, and where the SGPR pairs
+  // a compare writes end up (so the compares stay)
+  const uint64_t sm = 0x5555555555555555ull * (seed | 1);
+  uint64_t sink = 0;
   for (int i = 0; i < N_ITER; ++i) {
 #define DO(INS) asm volatile(INS " %0, %0, %1" : "+v"(a0) : "v"(b)); asm volatile(INS " %0, %0, %1" : "+v"(a1) : "v"(b)); \
   asm volatile(INS " %0, %0, %1" : "+v"(a2) : "v"(b)); asm volatile(INS " %0, %0, %1" : "+v"(a3) : "v"(b)); \
@@ -59,8 +63,65 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed) {
     if constexpr (K == 26) { DO3("v_bfe_u32") }
     if constexpr (K == 27) { DO("v_lshrrev_b32") }
     if constexpr (K == 28) { DO("v_mul_u32_u24") }
+    // what the render loop's hot blocks are full of (tools/isa_blocks.py charged these one slot
+    // unmeasured): three-operand min / max, selects in both encodings, compares into an SGPR pair,
+    // fma with a literal, the carry add, mbcnt
+    if constexpr (K == 29) { DO3("v_min3_u32") }
+    if constexpr (K == 30) { DO3("v_min3_i32") }
+    if constexpr (K == 31) { DO3("v_max3_i32") }
+#define EACH(M) M(a0) M(a1) M(a2) M(a3) M(a4) M(a5) M(a6) M(a7)
+    if constexpr (K == 42) { DO("v_min_i32") }
+    if constexpr (K == 43) { DO("v_max_i32") }
+    if constexpr (K == 44) { DO("v_min_f32") }
+    if constexpr (K == 45) { DO("v_max_u32") }
+    if constexpr (K == 32) {  // VOP2: the mask is vcc (whatever it holds)
+#define M(X) asm volatile("v_cndmask_b32_e32 %0, %0, %1, vcc" : "+v"(X) : "v"(b));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 33) {  // VOP3: the mask is an SGPR pair
+#define M(X) asm volatile("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(X) : "v"(b), "s"(sm));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 34) {  // a compare that writes an SGPR pair (eight independent ones)
+#define M(X) { uint64_t m_; asm volatile("v_cmp_lt_u32_e64 %0, %1, %2" : "=s"(m_) : "v"(X), "v"(b)); sink ^= m_; }
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 35) {
+#define M(X) asm volatile("v_fmaak_f32 %0, %0, %1, 0x3fc00000" : "+v"(X) : "v"(b));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 36) {
+#define M(X) asm volatile("v_fmamk_f32 %0, %0, 0x3fc00000, %1" : "+v"(X) : "v"(b));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 37) {  // the carry add with an SGPR pair as carry-in (the per-lane event count)
+#define M(X) asm volatile("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(X) : "s"(sm) : "vcc");
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 38) { DO("v_min_u32") }
+    if constexpr (K == 39) {
+#define M(X) asm volatile("v_mbcnt_lo_u32_b32 %0, %1, %0" : "+v"(X) : "v"(b));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 40) {
+#define M(X) asm volatile("v_mbcnt_hi_u32_b32 %0, %1, %0" : "+v"(X) : "v"(b));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 41) {  // the VOPC form of the same compare (writes vcc)
+#define M(X) asm volatile("v_cmp_lt_u32_e32 vcc, %0, %1" : : "v"(X), "v"(b) : "vcc");
+      EACH(M)
+#undef M
+    }
   }
-  out[blockIdx.x * 256 + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;
+  out[blockIdx.x * 256 + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7 ^ (uint32_t)sink;
 }
 
 // 64-bit / packed forms need register pairs
@@ -93,6 +154,11 @@ __global__ void __launch_bounds__(256) k_rate64(uint64_t* out, uint32_t seed) {
     }
     if constexpr (K == 4) {
 #define M(X) asm volatile("v_fma_f64 %0, %0, %1, %0" : "+v"(X) : "v"(b));
+      M(a0) M(a1) M(a2) M(a3) M(a4) M(a5) M(a6) M(a7)
+#undef M
+    }
+    if constexpr (K == 5) {  // the 64-bit accumulator add of the path end
+#define M(X) asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(X) : "v"(b));
       M(a0) M(a1) M(a2) M(a3) M(a4) M(a5) M(a6) M(a7)
 #undef M
     }
@@ -136,7 +202,12 @@ int main() {
   R32(20, "v_cvt_f32_ubyte0") R32(21, "v_cvt_f32_ubyte1") R32(22, "v_bfi_b32") R32(23, "v_and_or_b32")
   R32(24, "v_lshl_or_b32") R32(25, "v_cvt_f32_i32") R32(26, "v_bfe_u32") R32(27, "v_lshrrev_b32")
   R64(0, "v_pk_fma_f32") R64(1, "v_pk_mul_f32") R64(2, "v_pk_add_f32") R64(3, "v_mad_u64_u32")
-  R64(4, "v_fma_f64")
+  R64(4, "v_fma_f64") R64(5, "v_lshl_add_u64")
+  R32(29, "v_min3_u32") R32(30, "v_min3_i32") R32(31, "v_max3_i32") R32(38, "v_min_u32")
+  R32(42, "v_min_i32") R32(43, "v_max_i32") R32(45, "v_max_u32") R32(44, "v_min_f32")
+  R32(32, "v_cndmask_b32_e32") R32(33, "v_cndmask_b32_e64") R32(34, "v_cmp_lt_u32_e64 sgpr")
+  R32(41, "v_cmp_lt_u32_e32 vcc") R32(35, "v_fmaak_f32") R32(36, "v_fmamk_f32")
+  R32(37, "v_addc_co_u32_e64") R32(39, "v_mbcnt_lo_u32_b32") R32(40, "v_mbcnt_hi_u32_b32")
   printf("CUs %d clock %d kHz\n", ncu, p.clockRate);
   return 0;
 }
