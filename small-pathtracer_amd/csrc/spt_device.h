@@ -64,6 +64,40 @@ __device__ __forceinline__ uint32_t xor3k(uint32_t a, uint32_t b, uint32_t k) {
   asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "s"(k));
   return r;
 }
+// The same with all three words in VGPRs. LLVM spells a ^ b ^ c as two v_xor.
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+// Selects as full-rate bit operations (profiles/r21_valu_rates.txt: a VOP3 v_cndmask, every v_cmp and
+// the integer min / max issue at half rate, v_bitop3 / v_and / v_xor / v_add_u32 and the shifts at
+// full rate). A lane mask here is a VGPR word of all ones or all zeros; with such a mask a bit select
+// is the select, bit for bit, whatever a and b hold (NaN payloads and signed zeros included).
+//   mask_lt(v, K): all ones iff v < K, for 0 <= v < 2^31 and a literal 0 < K < 2^31: the sign of
+//   v - K, spread by an arithmetic shift. Opaque, or LLVM turns it back into a compare and a select.
+template <int K>
+__device__ __forceinline__ uint32_t mask_lt(int v) {
+  static_assert(K > 0, "mask_lt: v - K must not wrap");
+  uint32_t m;
+  asm("v_ashrrev_i32 %0, 31, %1" : "=v"(m) : "v"((uint32_t)v + (uint32_t)(-K)));
+  return m;
+}
+//   bsel(m, a, b) = m ? a : b per bit, ONE v_bitop3 (0xe4 = S2 ? S0 : S1)
+__device__ __forceinline__ uint32_t bsel(uint32_t m, uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xe4" : "=v"(r) : "v"(a), "v"(b), "v"(m));
+  return r;
+}
+__device__ __forceinline__ float bself(uint32_t m, float a, float b) {
+  return __uint_as_float(bsel(m, __float_as_uint(a), __float_as_uint(b)));
+}
+//   a & m & ~n, ONE v_bitop3 (0x40 = S0 & S1 & ~S2)
+__device__ __forceinline__ uint32_t band_andn(uint32_t a, uint32_t m, uint32_t n) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x40" : "=v"(r) : "v"(a), "v"(m), "v"(n));
+  return r;
+}
 __device__ __forceinline__ u4 philox_px(PxKey pk, uint32_t c1, uint32_t c2) {
   uint32_t k0 = SPT_PHILOX_KEY0, k1 = SPT_PHILOX_KEY1;
   // round 1: the pixel word's product is per unit (philox_pixel_key)
@@ -232,8 +266,9 @@ __device__ __forceinline__ void disk_dir(uint32_t ra, float& c_out, float& s_out
   const float sn = r * ps;
   pc = fmaf(r2, pc, -1.2336976528167725f);
   const float cs = fmaf(r2, pc, 1.0f);
-  const bool sw = (ra & 0x20000000u) != 0u;
-  const float c = sw ? sn : cs, s = sw ? cs : sn;
+  // the swap as two bit selects on bit 29 spread over the word (bsel: the select, bit for bit)
+  const uint32_t sw = (uint32_t)((int32_t)(ra << 2) >> 31);
+  const float c = bself(sw, sn, cs), s = bself(sw, cs, sn);
   c_out = __uint_as_float(__float_as_uint(c) ^ (ra & 0x80000000u));
   s_out = __uint_as_float(__float_as_uint(s) ^ ((ra << 1) & 0x80000000u));
 }

@@ -112,6 +112,18 @@ __device__ __forceinline__ Ray6 ray6(f3 o, f3 d, float ix, float iy, float iz) {
   return Ray6{o.x, ix, d.y, o.y, d.z, o.z};
 }
 
+// The plane axis of the hit at grouped position pos (0 <= pos <= 63) in the literal HEAD kernels, as
+// two lane masks (spt_device.h, mask_lt): xy = pos is an XY rect, xyxz = an XY or an XZ one. What the
+// axis picks -- o_a, d_a, 1/d_a, the NEE weight's |dl_a| -- is then two full-rate bit selects, and the
+// normal three ands, where the compares' SGPR-pair masks fed half-rate VOP3 selects.
+struct AxisMasks { uint32_t xy, xyxz; };
+__device__ __forceinline__ AxisMasks axis_masks(int pos) {
+  return AxisMasks{mask_lt<kCornellNXY>(pos), mask_lt<kCornellNXY + kCornellNXZ>(pos)};
+}
+__device__ __forceinline__ float axis_pick(AxisMasks m, float z, float y, float x) {
+  return bself(m.xy, z, bself(m.xyxz, y, x));
+}
+
 // ---- Nearest hit, contract v5 (round 4; oracle c_intersect / c_key). A candidate at t on the plane
 // or sphere with grouped position pos is ranked by its KEY: the float bits of t with the low 6 bits
 // replaced by pos (negatives, inf and NaN rank last; a plane's zero distance is -2^-149, plane_t,
@@ -205,14 +217,22 @@ __device__ __forceinline__ void cornell_test(const Ray6* rays, uint32_t& tmin) {
 // negative t is a negative integer -- give the slab interval [min, max]; entry = the largest start,
 // exit = the smallest end, crossed iff entry <= exit. The candidate is the entry, or for an origin
 // inside the box (negative entry) the exit face, as the per-face tests find it: as unsigned keys
-// min(entry, exit). Per box 6 plane keys, 8 integer min/max, one compare: the 4 faces' and the top's
-// in-plane compares and lane-mask selects are gone (trace 153 -> 131 VALU per wave-iteration).
+// min(entry, exit). Per box 6 plane keys, 5 integer min/max, 3 xors (imax_of), one compare: the 4
+// faces' and the top's in-plane compares and lane-mask selects are gone (trace 153 -> 131 VALU per
+// wave-iteration).
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+// A slab's end is a ^ b ^ min(a, b): max(a, b) for every pair of 32-bit integers (the min is one of
+// the two, and the xor leaves the other), so a NaN key goes through as it did. One full-rate v_bitop3
+// where v_max_i32 issues at half rate (spt_device.h, xor3): three slots fewer per box.
+__device__ __forceinline__ int imax_of(int a, int b, int mn) {
+  return (int)xor3((uint32_t)a, (uint32_t)b, (uint32_t)mn);
+}
 __device__ __forceinline__ void box_keys(int kx0, int kx1, int kz0, int kz1, int ky0, int ky1,
                                          uint32_t& tmin) {
-  const int en = imax(imax(imin(kx0, kx1), imin(kz0, kz1)), imin(ky0, ky1));
-  const int ex = imin(imin(imax(kx0, kx1), imax(kz0, kz1)), imax(ky0, ky1));
+  const int nx = imin(kx0, kx1), nz = imin(kz0, kz1), ny = imin(ky0, ky1);
+  const int en = imax(imax(nx, nz), ny);
+  const int ex = imin(imin(imax_of(kx0, kx1, nx), imax_of(kz0, kz1, nz)), imax_of(ky0, ky1, ny));
   tmin = umin(tmin, en <= ex ? umin((uint32_t)en, (uint32_t)ex) : 0xFFFFFFFFu);
 }
 // The room of contract v6 as the same slab (from inside: the exit face, the nearest positive wall)
@@ -220,9 +240,15 @@ __device__ __forceinline__ void cornell_room(const Ray6* rays, uint32_t& tmin) {
   constexpr CTest Z = kCornellTests.t[kCornellRoom[0]], Y = kCornellTests.t[kCornellRoom[1]];
   constexpr CTest X = kCornellTests.t[kCornellRoom[2]];
   const Ray6 &rz = rays[2], &ry = rays[1], &rx = rays[0];
+  // The two planes at k = +0 (Front, Bottom): (0 - o) * inv - 2^-149 as ONE fma with a negated source
+  // where the subtract and a v_fmaak stood. 0 - o is -o for every o but +0, where it is +0 and -o is
+  // -0; fma(+-0, inv, -2^-149) is -2^-149 for either zero (NaN for an infinite or NaN inv, either
+  // way), so the distance is the same bits.
+  static_assert(__builtin_bit_cast(uint32_t, Z.k0) == 0u && __builtin_bit_cast(uint32_t, Y.k0) == 0u,
+                "HEAD room: Front z = +0, Bottom y = +0");
   box_keys((int)key_c<X.pos0>(plane_t(X.k0 - rx.oa, rx.ia)), (int)key_c<X.pos1>(plane_t(X.k1 - rx.oa, rx.ia)),
-           (int)key_c<Z.pos0>(plane_t(Z.k0 - rz.oa, rz.ia)), (int)key_c<Z.pos1>(plane_t(Z.k1 - rz.oa, rz.ia)),
-           (int)key_c<Y.pos0>(plane_t(Y.k0 - ry.oa, ry.ia)), (int)key_c<Y.pos1>(plane_t(Y.k1 - ry.oa, ry.ia)),
+           (int)key_c<Z.pos0>(plane_t(-rz.oa, rz.ia)), (int)key_c<Z.pos1>(plane_t(Z.k1 - rz.oa, rz.ia)),
+           (int)key_c<Y.pos0>(plane_t(-ry.oa, ry.ia)), (int)key_c<Y.pos1>(plane_t(Y.k1 - ry.oa, ry.ia)),
            tmin);
 }
 template <int B>
@@ -232,7 +258,8 @@ __device__ __forceinline__ void cornell_box(const Ray6* rays, uint32_t& tmin) {
   const Ray6 &rz = rays[2], &ry = rays[1], &rx = rays[0];
   box_keys((int)key_c<X.pos0>(plane_t(X.k0 - rx.oa, rx.ia)), (int)key_c<X.pos1>(plane_t(X.k1 - rx.oa, rx.ia)),
            (int)key_c<Z.pos0>(plane_t(Z.k0 - rz.oa, rz.ia)), (int)key_c<Z.pos1>(plane_t(Z.k1 - rz.oa, rz.ia)),
-           (int)key_c<F.pos0>(plane_t(F.k0 - ry.oa, ry.ia)), (int)key_c<T.pos0>(plane_t(T.k0 - ry.oa, ry.ia)),
+           // (the floor's key as cornell_room spells it: the same value, CSE'd)
+           (int)key_c<F.pos0>(plane_t(-ry.oa, ry.ia)), (int)key_c<T.pos0>(plane_t(T.k0 - ry.oa, ry.ia)),
            tmin);
 }
 template <int... B>
@@ -1068,6 +1095,8 @@ render_kernel(const KParams* __restrict__ Pg) {
           }
           vc = mk(vv[0], vv[1], vv[2]);
         }
+        // (Selects on a compare, not on a mask of ls - 2 as the shading's axis picks are: the listing
+        // loses no slot with it, 108 either way, and C3 read the same, profiles/r22_bit_selects_ab.txt.)
         v = mk(cam ? vc.x : v.x, cam ? vc.y : v.y, cam ? vc.z : v.z);  // o: set at the path end
       }
       const f3 dn = normalize_dir(v, unit);  // rsq_nr1 in the free-scale contract (v7)
@@ -1117,8 +1146,9 @@ render_kernel(const KParams* __restrict__ Pg) {
       // (the early-resolve kernels trace a shadow ray only when the light accepts it: it never misses)
       bool hit = intersect_scene<TP>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph, s_pos2idx, o, d,
                                      id, ia_hit, hpos, inv);
-      if constexpr (TP::CONSTGEO)
-        ia_hit = hpos < kCornellNXY ? inv.z : (hpos < kCornellNXY + kCornellNXZ ? inv.y : inv.x);
+      // the hit's plane axis (the literal rect-only kernels), made once here for the shading too
+      [[maybe_unused]] const AxisMasks am = axis_masks(TP::CONSTGEO ? hpos : 0);
+      if constexpr (TP::CONSTGEO) ia_hit = axis_pick(am, inv.z, inv.y, inv.x);
 
       // 5) resolve a shadow ray: the light is reached iff the nearest hit is the light (:467). Then
       //    the light is the next vertex (shaded in the common block below, T = T*f*weight); else the
@@ -1182,35 +1212,37 @@ render_kernel(const KParams* __restrict__ Pg) {
         const int kind = H.kind;
         f3 x;
         f3 gn = mk(0, 0, 0);
-        bool ax_xy = false, ax_xz = false;  // the normal's axis (rect-only kernels)
         if constexpr (!TP::SPH) {
           // Rect-only scenes, branch-free: the plane axis of the hit kind selects (o_a, d_a); the
           // hit point re-derives t = (k - o_a) / d_a as the reference does (:103) and
           // the normal is the axis, oriented against the ray (:123,:166,:209).
-          bool kxy, kxz;
-          if constexpr (TP::CONSTGEO) {  // the axis from the position (intersect_scene)
-            kxy = hpos < kCornellNXY;
-            kxz = !kxy && hpos < kCornellNXY + kCornellNXZ;
+          float oa, da, ia = ia_hit;
+          if constexpr (TP::CONSTGEO) {  // the axis from the position: bit selects (axis_masks)
+            oa = axis_pick(am, o.z, o.y, o.x);
+            da = axis_pick(am, d.z, d.y, d.x);
           } else {
-            kxy = kind == SPT_RECT_XY;
-            kxz = kind == SPT_RECT_XZ;
+            const bool kxy = kind == SPT_RECT_XY, kxz = kind == SPT_RECT_XZ;
+            oa = kxy ? o.z : (kxz ? o.y : o.x);
+            da = kxy ? d.z : (kxz ? d.y : d.x);
           }
-          ax_xy = kxy;
-          ax_xz = kxz;
-          const bool kyz = !kxy && !kxz;
-          const float oa = kxy ? o.z : (kxz ? o.y : o.x);
-          const float da = kxy ? d.z : (kxz ? d.y : d.x);
           const float n_ = H.w1 - oa;
-          float ia = ia_hit;
-          if constexpr (TP::CONSTGEO) ia = kxy ? inv.z : (kxz ? inv.y : inv.x);  // (= ia_hit)
           const float tr = hit_plane_t(n_, da, ia, plane_t(n_, ia));  // the winner's t, corrected
           x = mk(keep(o.x + d.x * tr), keep(o.y + d.y * tr), keep(o.z + d.z * tr));
           // a miss vertex is the origin (:373-374); a leaked path ending at its miss (the LEAK == 1
           // kernels, see below) never reads it
           if constexpr (CF::LEAK != 1) x = hit ? x : mk(0, 0, 0);
           const float sg = da < 0.0f ? 1.0f : -1.0f;
-          nl = mk(kyz ? sg : 0.0f, kxz ? sg : 0.0f, kxy ? sg : 0.0f);
-          if (TP::MAT) gn = mk(kyz ? 1.0f : 0.0f, kxz ? 1.0f : 0.0f, kxy ? 1.0f : 0.0f);
+          if constexpr (TP::CONSTGEO) {
+            // sg on the hit's axis, +0 on the other two, as the selects gave: sg & ~(xy | xz),
+            // sg & (xy | xz) & ~xy, sg & xy
+            const uint32_t sb = __float_as_uint(sg);
+            nl = mk(__uint_as_float(band_andn(sb, sb, am.xyxz)), __uint_as_float(band_andn(sb, am.xyxz, am.xy)),
+                    __uint_as_float(sb & am.xy));
+          } else {
+            const bool kxy = kind == SPT_RECT_XY, kxz = kind == SPT_RECT_XZ, kyz = !kxy && !kxz;
+            nl = mk(kyz ? sg : 0.0f, kxz ? sg : 0.0f, kxy ? sg : 0.0f);
+            if (TP::MAT) gn = mk(kyz ? 1.0f : 0.0f, kxz ? 1.0f : 0.0f, kxy ? 1.0f : 0.0f);
+          }
         } else {
         if (!hit) {
           x = mk(0, 0, 0);
@@ -1382,7 +1414,7 @@ render_kernel(const KParams* __restrict__ Pg) {
               // arithmetic with |dl . nl| = |dl_a| on the normal's axis a (the dot's zero terms are
               // exact) and t = the light's own t, the bits the trace returns for it. The resolve
               // then needs neither the light's t nor the weight (round 4: -5 VALU per iteration).
-              const float adot = fabsf(ax_xy ? dl.z : (ax_xz ? dl.y : dl.x));
+              const float adot = fabsf(axis_pick(am, dl.z, dl.y, dl.x));
               const float num = fabsf(dl.y) * adot;
               const float vv = dot3(dl, dl);
               w_nee = (num * kRefNeeC) * rcp_nr((h.tt * h.tt) * (vv * vv));

@@ -5,7 +5,8 @@
 
 --bb splits at LLVM's '; %bb.N' comments too (fall-through blocks), --min hides blocks with fewer
 VALU. `slots` weights each VALU by its issue cost on gfx950 (tools/valu_rates.hip,
-profiles/r01_valu_rates.txt, profiles/r21_valu_rates.txt): full-rate 1, half-rate 2, transcendental 4.
+profiles/r01_valu_rates.txt, profiles/r21_valu_rates.txt, profiles/r22_valu_rates.txt): full-rate 1,
+half-rate 2, transcendental 4. `far_sel` counts the VOP2 selects that do not directly follow their compare.
 """
 import re
 import sys
@@ -24,12 +25,22 @@ HALF = ("v_mad_u64_u32", "v_mad_i64_i32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mul
         "v_cndmask_b32_e64", "v_cmp_",
         "v_addc_co_u32", "v_mbcnt_")
 QUARTER = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_sin_", "v_cos_", "v_exp_", "v_log_", "v_div_")
+# Round 22 (profiles/r22_valu_rates.txt): v_ashrrev_i32, v_and_b32, v_sub_u32 and v_bitop3_b32 on three
+# VGPRs are full rate; v_bitop3_b32 with an SGPR source is half rate (Philox's round keys), and so is
+# v_subrev_co_u32 with the borrow in vcc or an SGPR pair. A VOP2 v_cndmask_b32 right behind the v_cmp
+# that writes its vcc costs one slot (the pair reads 6.6 cycles, the compare alone 4.5). One that is not
+# read 18 cycles in the probe, where all eight waves of a SIMD do the same: a wait of the wave, not an
+# issue slot, so it stays at one slot here and is counted apart (`far_sel`).
+HALF += ("v_subrev_co_u32",)
+SGPR_SRC = re.compile(r"\bs(\d+|\[\d+:\d+\])")
 
 
-def slots(op):
+def slots(op, args=""):
     if op.startswith(QUARTER):
         return 4
     if op.startswith(HALF):
+        return 2
+    if op == "v_bitop3_b32" and SGPR_SRC.search(args.split(",", 1)[-1]):
         return 2
     return 1
 
@@ -67,7 +78,7 @@ def blocks_of(path, key, bb=False):
         m2 = re.match(r"^; (%bb\.\d+):", s) if bb else None
         if m or m2:
             cur = {"name": (m or m2).group(1)[:24], "valu": 0, "slots": 0, "salu": 0, "smem": 0,
-                   "lds": 0, "vmem": 0, "wait": 0, "ops": [], "vops": Counter()}
+                   "lds": 0, "vmem": 0, "wait": 0, "far_sel": 0, "ops": [], "vops": Counter()}
             blocks.append(cur)
             continue
         if not s or s.startswith((";", ".")) or cur is None:
@@ -76,10 +87,14 @@ def blocks_of(path, key, bb=False):
         c = classify(op)
         if c:
             cur[c] += 1
-            cur["ops"].append(op)
             if c == "valu":
-                cur["slots"] += slots(op)
+                cur["slots"] += slots(op, s[len(op):].split(";")[0])
                 cur["vops"][op] += 1
+                # a VOP2 select whose vcc is not the instruction before's (see the rates above)
+                prev = cur["ops"][-1] if cur["ops"] else ""
+                if op == "v_cndmask_b32_e32" and not (prev.startswith("v_cmp") and prev.endswith("_e32")):
+                    cur["far_sel"] += 1
+            cur["ops"].append(op)
     return blocks
 
 
@@ -89,7 +104,7 @@ def main():
     bb = "--bb" in sys.argv
     mn = int(sys.argv[sys.argv.index("--min") + 1]) if "--min" in sys.argv else 0
     blocks = blocks_of(path, key, bb)
-    tot = {k: sum(b[k] for b in blocks) for k in ("valu", "slots", "salu", "smem", "lds", "vmem")}
+    tot = {k: sum(b[k] for b in blocks) for k in ("valu", "slots", "salu", "smem", "lds", "vmem", "far_sel")}
     print("total", tot, "blocks", len(blocks))
     for b in blocks:
         if b["valu"] < mn:
@@ -97,7 +112,7 @@ def main():
         br = [o for o in b["ops"] if o.startswith("s_cbranch") or o == "s_branch"]
         top = ", ".join(f"{k}:{v}" for k, v in b["vops"].most_common(4))
         print(f"{b['name']:24s} valu {b['valu']:4d} slots {b['slots']:4d} salu {b['salu']:3d} "
-              f"smem {b['smem']:3d} lds {b['lds']:2d} vmem {b['vmem']:2d}  {' '.join(br)}  [{top}]")
+              f"smem {b['smem']:3d} lds {b['lds']:2d} vmem {b['vmem']:2d} far_sel {b['far_sel']:2d}  {' '.join(br)}  [{top}]")
 
 
 if __name__ == "__main__":

@@ -120,6 +120,44 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed) {
       EACH(M)
 #undef M
     }
+    // round 22: what selects restated as bit operations are made of, and the VOP2 select again
+    if constexpr (K == 46) { DO("v_ashrrev_i32") }
+    if constexpr (K == 47) { DO("v_and_b32") }
+    if constexpr (K == 48) {  // the bit operation with one source in an SGPR (xor3k's form)
+#define M(X) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(X) : "v"(b), "s"(seed));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 49) { DO("v_sub_u32") }
+    if constexpr (K == 50) {  // the subtract LLVM picks when it folds a compare into it (borrow to vcc)
+#define M(X) asm volatile("v_subrev_co_u32_e64 %0, vcc, %0, %1" : "+v"(X) : "v"(b) : "vcc");
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 51) {  // ... with the borrow in an SGPR pair
+#define M(X) { uint64_t m_; asm volatile("v_subrev_co_u32_e64 %0, %1, %0, %2" : "+v"(X), "=s"(m_) : "v"(b)); }
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 52) {  // the VOP2 select right behind the compare that writes its vcc: 8 pairs
+#define M(X) asm volatile("v_cmp_lt_u32_e32 vcc, %0, %1\n v_cndmask_b32_e32 %0, %0, %1, vcc" : "+v"(X) : "v"(b) : "vcc");
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 53) {  // one compare into vcc, then 8 VOP2 selects on it: 9 instructions
+      asm volatile("v_cmp_lt_u32_e32 vcc, %0, %8\n v_cndmask_b32_e32 %0, %0, %8, vcc\n"
+                   "v_cndmask_b32_e32 %1, %1, %8, vcc\n v_cndmask_b32_e32 %2, %2, %8, vcc\n"
+                   "v_cndmask_b32_e32 %3, %3, %8, vcc\n v_cndmask_b32_e32 %4, %4, %8, vcc\n"
+                   "v_cndmask_b32_e32 %5, %5, %8, vcc\n v_cndmask_b32_e32 %6, %6, %8, vcc\n"
+                   "v_cndmask_b32_e32 %7, %7, %8, vcc"
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
+                   : "v"(b) : "vcc");
+    }
+    if constexpr (K == 54) {  // the bit select of a VGPR mask (S2 ? S0 : S1)
+#define M(X) asm volatile("v_bitop3_b32 %0, %0, %1, %0 bitop3:0xe4" : "+v"(X) : "v"(b));
+      EACH(M)
+#undef M
+    }
   }
   out[blockIdx.x * 256 + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7 ^ (uint32_t)sink;
 }
@@ -208,6 +246,12 @@ int main() {
   R32(32, "v_cndmask_b32_e32") R32(33, "v_cndmask_b32_e64") R32(34, "v_cmp_lt_u32_e64 sgpr")
   R32(41, "v_cmp_lt_u32_e32 vcc") R32(35, "v_fmaak_f32") R32(36, "v_fmamk_f32")
   R32(37, "v_addc_co_u32_e64") R32(39, "v_mbcnt_lo_u32_b32") R32(40, "v_mbcnt_hi_u32_b32")
+  R32(46, "v_ashrrev_i32") R32(47, "v_and_b32") R32(48, "v_bitop3_b32 sgpr") R32(54, "v_bitop3_b32 0xe4")
+  R32(49, "v_sub_u32") R32(50, "v_subrev_co_u32 vcc") R32(51, "v_subrev_co_u32 sgpr")
+  // per compare + select pair, and per instruction of one compare and eight selects (9 per 8 counted)
+  R32(52, "v_cmp vcc + cndmask_e32")
+  report("cmp vcc, 8 cndmask_e32",
+         8.0 / 9.0 * time_it([&] { hipLaunchKernelGGL(k_rate<53>, dim3(blocks), dim3(256), 0, 0, (uint32_t*)buf, 7u); }));
   printf("CUs %d clock %d kHz\n", ncu, p.clockRate);
   return 0;
 }
