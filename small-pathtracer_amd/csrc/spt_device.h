@@ -89,6 +89,12 @@ __device__ __forceinline__ uint32_t bsel(uint32_t m, uint32_t a, uint32_t b) {
   asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xe4" : "=v"(r) : "v"(a), "v"(b), "v"(m));
   return r;
 }
+//   the same with a wave-uniform a, read from the SGPR that holds it (no copy into a VGPR)
+__device__ __forceinline__ uint32_t bsel_s(uint32_t m, uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xe4" : "=v"(r) : "s"(a), "v"(b), "v"(m));
+  return r;
+}
 __device__ __forceinline__ float bself(uint32_t m, float a, float b) {
   return __uint_as_float(bsel(m, __float_as_uint(a), __float_as_uint(b)));
 }
@@ -96,6 +102,13 @@ __device__ __forceinline__ float bself(uint32_t m, float a, float b) {
 __device__ __forceinline__ uint32_t band_andn(uint32_t a, uint32_t m, uint32_t n) {
   uint32_t r;
   asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x40" : "=v"(r) : "v"(a), "v"(m), "v"(n));
+  return r;
+}
+//   the bits of 1.0f with the inverse of a's sign bit, 1.0 | (~a & 2^31): +1 for a negative a, -1
+//   for a positive one. ONE v_bitop3 (0xae = (~S0 & S1) | S2) with the inline constant 1.0.
+__device__ __forceinline__ uint32_t sign_against(uint32_t a) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, 1.0 bitop3:0xae" : "=v"(r) : "v"(a), "s"(0x80000000u));
   return r;
 }
 __device__ __forceinline__ u4 philox_px(PxKey pk, uint32_t c1, uint32_t c2) {

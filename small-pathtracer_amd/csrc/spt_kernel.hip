@@ -38,15 +38,28 @@
 
 namespace spt {
 
-// Lane states of the render loop (render_kernel).
-constexpr uint32_t kStIdle = 0;    // no work unit
-constexpr uint32_t kStCam = 1;     // next: a camera ray (a new sample; retire the unit at s_end)
-constexpr uint32_t kStCos = 2;     // next: the cosine continuation of the last vertex
-constexpr uint32_t kStSpec = 3;    // next: a path ray whose direction is already set (SPEC/REFR)
-constexpr uint32_t kStPath = 4;    // a path ray is set: trace it, shade its vertex
-constexpr uint32_t kStShadow = 5;  // a NEE shadow ray toward the light is set: trace, resolve
-constexpr uint32_t kStTerm = 6;    // the path ended at this vertex (within an iteration)
-constexpr uint32_t kStEarly = 7;   // a NEE shadow ray proven to reach the light (early_nee_proven)
+// Lane states of the render loop (render_kernel). The generating states are Cam, Cos, Spec in this
+// order, and the states that hold a ray are ls >= kPath, in both numberings:
+//   GEN_FIRST: Cam 0, Cos 1, Spec 2, Idle 3, so that the generate guard is ONE compare with an inline
+//   constant, ls < kIdle, and the camera lanes' mask one subtract (ls - 1);
+//   else Idle 0, Cam 1, Cos 2, Spec 3 (guard: ls - kCam < 3u, an add and a compare), the numbering of
+//   the variants that the other one costs registers (KernelTraits::kGenStatesFirst).
+template <bool GEN_FIRST>
+struct LaneStates {
+  static constexpr uint32_t kCam = GEN_FIRST ? 0 : 1;   // next: a camera ray (a new sample; retire the unit at s_end)
+  static constexpr uint32_t kCos = kCam + 1;            // next: the cosine continuation of the last vertex
+  static constexpr uint32_t kSpec = kCam + 2;           // next: a path ray whose direction is already set (SPEC/REFR)
+  static constexpr uint32_t kIdle = GEN_FIRST ? 3 : 0;  // no work unit
+  static constexpr uint32_t kPath = 4;    // a path ray is set: trace it, shade its vertex
+  static constexpr uint32_t kShadow = 5;  // a NEE shadow ray toward the light is set: trace, resolve
+  static constexpr uint32_t kTerm = 6;    // the path ended at this vertex (within an iteration)
+  static constexpr uint32_t kEarly = 7;   // a NEE shadow ray proven to reach the light (early_nee_proven)
+  // the lanes that generate a ray (kCam, kCos, kSpec)
+  static __device__ __forceinline__ bool generates(uint32_t ls) {
+    if constexpr (GEN_FIRST) return ls < kIdle;
+    else return ls - kCam < 3u;
+  }
+};
 // Exit condition every wave reaches even if a path never terminated: a C3 wave runs ~4e3
 // iterations and a 1-GPU C5 wave ~3e6; stats[0] counts waves that hit the cap.
 constexpr uint32_t kMaxWaveIters = 1u << 26;
@@ -781,6 +794,9 @@ render_kernel(const KParams* __restrict__ Pg) {
   __syncthreads();
 
   const uint32_t lane = __lane_id();
+  using St = LaneStates<KernelTraits<TP, CF>::kGenStatesFirst>;
+  constexpr uint32_t kStIdle = St::kIdle, kStCam = St::kCam, kStCos = St::kCos, kStSpec = St::kSpec,
+                     kStPath = St::kPath, kStShadow = St::kShadow, kStTerm = St::kTerm, kStEarly = St::kEarly;
   // ---- per-lane state
   // The lane's state is ONE integer in a VGPR (kSt*), not a set of booleans: LLVM keeps loop-carried
   // booleans as 64-bit lane masks and merges each one at every join of the divergent blocks with an
@@ -1059,7 +1075,7 @@ render_kernel(const KParams* __restrict__ Pg) {
     // The generating lanes (the compare is the generate block's own), or in the generic kernel, whose
     // SPEC/REFR rays generate too, the cosine ones (a v_cmp of their own).
     if constexpr (TP::MAT) n_cos += (uint32_t)__popcll(__ballot(ls == kStCos));
-    else n_gen += (uint32_t)__popcll(__ballot(ls - kStCam < 3u));
+    else n_gen += (uint32_t)__popcll(__ballot(St::generates(ls)));
 
     // 3) generate the path ray (kStCam, kStCos, kStSpec): the cosine continuation from the last
     //    vertex (random_scattering :337-347, its xi from that vertex's Philox words) or the camera
@@ -1067,8 +1083,8 @@ render_kernel(const KParams* __restrict__ Pg) {
     //    call for the vertex the ray leads to, one normalize for both. Both directions are computed
     //    for every generating lane and selected: a wave nearly always holds lanes of both kinds, so
     //    branches would save no VALU and cost their exec-mask SALU.
-    if (ls - kStCam < 3u) {
-      const bool cam = ls == kStCam;
+    if (St::generates(ls)) {
+      [[maybe_unused]] const bool cam = ls == kStCam;
       if (ls != kStSpec) SPT_REGION(cam ? 3 : 8);
       const bool unit = unit_dirs_of<TP>(Pg);
       f3 v = cosine_vec<!TP::SPH>(nl, r.z, r.w, TP::MAT && cptr(Pg)->scatter_uniform != 0, unit);
@@ -1095,9 +1111,24 @@ render_kernel(const KParams* __restrict__ Pg) {
           }
           vc = mk(vv[0], vv[1], vv[2]);
         }
-        // (Selects on a compare, not on a mask of ls - 2 as the shading's axis picks are: the listing
-        // loses no slot with it, 108 either way, and C3 read the same, profiles/r22_bit_selects_ab.txt.)
-        v = mk(cam ? vc.x : v.x, cam ? vc.y : v.y, cam ? vc.z : v.z);  // o: set at the path end
+        // (Round 22 priced the mask form at the compare form's 108 slots. With the camera lanes' state
+        // 0 the mask is one subtract, and a VOP2 select takes an SGPR only as its first source, so the
+        // compare form copied the axis-aligned camera's z into a VGPR in every iteration: the mask
+        // form is one VALU fewer. The generic kernels, whose generating lanes may be kStSpec, and
+        // the variants the mask costs a register keep the compare: KernelTraits::kCamMask.)
+        if constexpr (KT::kCamMask) {
+          // Without SPEC/REFR a generating lane is kStCam (0) or kStCos (1): ls - 1 is the camera
+          // lanes' mask, and the select three bit selects (bsel: the select, bit for bit). The
+          // axis-aligned camera's z is wave-uniform and goes in as the SGPR it is held in.
+          static_assert(kStCam == 0 && kStCos == 1, "the camera lanes' mask is ls - 1");
+          const uint32_t cm = keep(ls - 1u);
+          float vz;
+          if constexpr (CF::CAMAX == 1) vz = __uint_as_float(bsel_s(cm, __float_as_uint(ck.lz), __float_as_uint(v.z)));
+          else vz = bself(cm, vc.z, v.z);
+          v = mk(bself(cm, vc.x, v.x), bself(cm, vc.y, v.y), vz);  // o: set at the path end
+        } else {
+          v = mk(cam ? vc.x : v.x, cam ? vc.y : v.y, cam ? vc.z : v.z);
+        }
       }
       const f3 dn = normalize_dir(v, unit);  // rsq_nr1 in the free-scale contract (v7)
       if constexpr (TP::MAT) {  // a SPEC/REFR direction is set already
@@ -1126,7 +1157,8 @@ render_kernel(const KParams* __restrict__ Pg) {
     // and every event mask is and-ed with a state compare, so nothing of theirs is counted. In the
     // last, empty iteration no lane traces and the region is skipped as before.
     // (The kLaneEvents variants keep the divergent guard: the lanes that hold a ray.)
-    if (kLaneEvents ? ls >= kStPath : __ballot(ls >= kStPath) != 0) {
+    const uint64_t raym = kLaneEvents ? 0 : __ballot(ls >= kStPath);  // the lanes that hold a ray
+    if (kLaneEvents ? ls >= kStPath : raym != 0) {
       // 4) trace the lane's ray (path ray: hittingPoint :371-377; shadow ray: :466).
       if (ls >= kStPath) SPT_REGION(4);
 #ifdef SPT_PROBE_SALU  // diagnostic build SPT_DIAG=3: N extra SALU per wave-iteration (issue cost)
@@ -1156,7 +1188,14 @@ render_kernel(const KParams* __restrict__ Pg) {
       //    and applied as T*1 (exact) where the light is not reached: no branch. (The HEAD NEE
       //    kernel resolves in 5') below instead, after the shading block.)
       bool traced_shadow = ls == kStShadow;
-      uint64_t tsm = __ballot(ls == kStShadow);  // the same as a lane mask
+      uint64_t tsm;  // the same as a lane mask
+      // A lane is idle, kStPath or kStShadow here and, where nothing resolves before the shading, up
+      // to the shade guard: the shadow lanes are the trace guard's lanes less the shade guard's, an
+      // s_andn2 of two ballots the loop takes anyway (KernelTraits::kStateMasks). (With the shade
+      // guard taken from the generate guard's ballot as well, whose lanes are the kStPath ones, the
+      // listing gained an instruction: the mask came back to the lanes through a VGPR.)
+      if constexpr (KT::kStateMasks) tsm = raym & ~__ballot(ls == kStPath);
+      else tsm = __ballot(ls == kStShadow);
       if constexpr (kEarly) {
         // as a lane mask taken here: compared where 5') reads it, the state word of before the
         // shading stays live beside the new one (two v_mov per iteration)
@@ -1199,6 +1238,11 @@ render_kernel(const KParams* __restrict__ Pg) {
       }
       }
 
+      // The light compare on the trace's final id, once for the whole iteration (kStateMasks): the
+      // shading's NEE candidates and the resolve's light hits read the same mask.
+      [[maybe_unused]] uint64_t idlm = 0;
+      if constexpr (KT::kStateMasks) idlm = __ballot(id == light_slot_of<TP, CF>(cptr_at<5>(Pg, left)));
+
       // 6) shade a vertex (:422, :444-480).
       const bool shade = ls == kStPath;
       // A vertex with no hit is a miss: a path ray's, or in the kernels that resolve above the shadow
@@ -1231,7 +1275,16 @@ render_kernel(const KParams* __restrict__ Pg) {
           // a miss vertex is the origin (:373-374); a leaked path ending at its miss (the LEAK == 1
           // kernels, see below) never reads it
           if constexpr (CF::LEAK != 1) x = hit ? x : mk(0, 0, 0);
-          const float sg = da < 0.0f ? 1.0f : -1.0f;
+          // The normal's sign: 1 against a ray that runs down the axis, else -1. In the literal
+          // leak-end kernels as ONE bit operation, 1.0 with the inverse of da's sign bit. The two forms
+          // differ only at da = -0.0 (the compare says -1, the bits +1), and no vertex whose nl is read
+          // has a zero da: a plane the ray runs parallel to has rcp_nr(+-0) = NaN for its distance and
+          // is not hit (spt_device.h), and a miss ends a leaked path here (term, LEAK == 1), after
+          // which the lane's next ray is a camera ray, whose select drops the cosine direction made
+          // from nl, or none at all. A NaN da is the same: no hit on that axis.
+          float sg;
+          if constexpr (TP::CONSTGEO && CF::LEAK == 1) sg = __uint_as_float(sign_against(__float_as_uint(da)));
+          else sg = da < 0.0f ? 1.0f : -1.0f;
           if constexpr (TP::CONSTGEO) {
             // sg on the hit's axis, +0 on the other two, as the selects gave: sg & ~(xy | xz),
             // sg & (xy | xz) & ~xy, sg & xy
@@ -1428,8 +1481,11 @@ render_kernel(const KParams* __restrict__ Pg) {
             } else {
               la = light_accepts<TP>(D, G2, rects_of<TP>(G2), x, dl);
             }
-            const bool cand = (id == light_slot_of<TP, CF>(D)) | la;
             d = dl;  // a rejected lane generates its cosine direction next iteration anyway
+            bool onl;  // the vertex lies on the light
+            if constexpr (KT::kStateMasks) onl = __builtin_amdgcn_inverse_ballot_w64(idlm);
+            else onl = id == light_slot_of<TP, CF>(D);
+            const bool cand = onl | la;
             nxt = early ? kStEarly : (cand ? kStShadow : kStCos);
           }
         }
@@ -1448,7 +1504,9 @@ render_kernel(const KParams* __restrict__ Pg) {
         const uint64_t eam = __ballot(ls == kStEarly);
         // a traced shadow ray that reached the light; never a proven lane (its path ray hit what
         // it shaded, not the black light, which would have ended the path)
-        const uint64_t thm = __ballot(id == light_slot_of<TP, CF>(cptr_at<5>(Pg, left)));
+        uint64_t thm;
+        if constexpr (KT::kStateMasks) thm = idlm;
+        else thm = __ballot(id == light_slot_of<TP, CF>(cptr_at<5>(Pg, left)));
         const uint64_t resm = tsm | eam;
         count_lanes<kLaneEvents>(n_early, eam);
         count_lanes<kLaneEvents>(n_shadow, resm);

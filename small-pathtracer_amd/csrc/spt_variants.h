@@ -137,6 +137,23 @@ struct KernelTraits {
   // (profiles/r21_vgprs.txt, profiles/r21_event_counts_ab.txt), like the young cut.
   static constexpr bool kLaneEvents =
       TP::MAT || (!TP::SPH && CF::NEE == 1 && (!TP::CONSTGEO || (TP::UPLIGHT && CF::CAMAX == 2)));
+  // The lane states' numbering (spt_kernel.hip, LaneStates): the generating states first, which makes
+  // the generate guard one compare. The generic kernels (SPEC/REFR) keep the idle state at 0: with the
+  // other numbering the wide-sphere kernel took 82 VGPRs for 80 and lost a wave of occupancy.
+  static constexpr bool kGenStatesFirst = !TP::MAT;
+  // The traced shadow lanes' mask is derived on the scalar unit from the trace guard's and the shade
+  // guard's ballots (spt_kernel.hip, 5): between generate and shade a lane is idle, kStPath or
+  // kStShadow, so the mask is the one and-not the other instead of a third compare. Only where both
+  // ballots exist at the region's convergent top level and the state does not change between them:
+  // the literal early-resolve kernels with wave-uniform event counters. There the light compare on the
+  // trace's final id is taken once as well, for the shading's NEE candidates and the resolve's light
+  // hits. The others keep their own compares (the sphere NEE kernel paid an SGPR spill and a VGPR).
+  static constexpr bool kStateMasks = kEarlyNee && !kLaneEvents;
+  // The camera / cosine select of the generated direction as bit selects on the mask ls - 1 (the
+  // generate block of spt_kernel.hip): kernels without SPEC/REFR, whose generating lanes are kStCam
+  // or kStCos only, and with the axis-aligned camera, whose wave-uniform z the compare form copies
+  // into a VGPR in every iteration (elsewhere the two forms are the same number of instructions).
+  static constexpr bool kCamMask = kGenStatesFirst && CF::CAMAX == 1;
   // For the host. The UPBOX / UPLIGHT kernels are CONSTGEO (kEarlyNee) and take their box clauses
   // from KParams (early_geo_proven inside early_nee_proven's place): clauses, not literals.
   static constexpr EarlyKind early = kEarlyNee ? (TP::UPBOX ? kEarlyClauses : kEarlyLiteral)

@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Per-basic-block instruction mix of one kernel in a hipcc -S listing (static cost map).
 
-  python tools/isa_blocks.py build/spt_kernel.s render_kernelINS_4TopoILi6 [--bb] [--min N]
+  python tools/isa_blocks.py build/spt_kernel.s KEY [KEY2 ...] [--bb] [--min N]
+
+The kernel is the one whose mangled name holds every KEY (an extern "C" kernel: whose name starts with
+it), e.g. the Topo arguments and the Cfg arguments as two substrings. A key that fits several kernels is
+an error: the candidates are listed and nothing is counted. const_nee, not a pixel-list kernel:
+  TopoILi6ELi5ELi6ELb0ELi8ELb1ELin1ELin1ELin1ELb0ELb0ELin1ELb0ELb0E CfgILi1ELi0ELi1ELi1ELi1ELi1ELi1ELi1EEELb0E
 
 --bb splits at LLVM's '; %bb.N' comments too (fall-through blocks), --min hides blocks with fewer
 VALU. `slots` weights each VALU by its issue cost on gfx950 (tools/valu_rates.hip,
@@ -61,12 +66,30 @@ def classify(op):
     return None
 
 
+def find_kernel(lines, keys):
+    """The line of the one kernel label that every key fits; SystemExit if none or several do."""
+    if isinstance(keys, str):
+        keys = [keys]
+    found = []
+    for i, l in enumerate(lines):
+        if not re.match(r"^[A-Za-z_][\w$.]*:", l):
+            continue
+        name = l.split(":", 1)[0]
+        # mangled kernels by substrings of the name, extern "C" ones by the start of it ("k_philox") or,
+        # with a colon at the end, by the whole of it ("k_empty:")
+        if (name.startswith("_Z") and all(k in name for k in keys)) or \
+                (len(keys) == 1 and (name + ":").startswith(keys[0])):
+            found.append((i, name))
+    if len(found) != 1:
+        what = "no kernel" if not found else f"{len(found)} kernels"
+        raise SystemExit(f"isa_blocks: {what} for {' + '.join(keys)}" +
+                         "".join(f"\n  {name}" for _, name in found))
+    return found[0]
+
+
 def blocks_of(path, key, bb=False):
     lines = open(path).read().splitlines()
-    # mangled kernels by a substring of the name, extern "C" ones by the whole name ("k_philox:")
-    start = next(i for i, l in enumerate(lines)
-                 if (l.startswith("_Z") and key in l and ":" in l and not l.startswith("\t"))
-                 or l.startswith(key))
+    start, _ = find_kernel(lines, key)
     blocks, cur = [], None
     for n, l in enumerate(lines[start:]):
         if n == 0 and not l.startswith("_Z"):
@@ -100,12 +123,15 @@ def blocks_of(path, key, bb=False):
 
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    path, key = args[0], args[1]
+    path, key = args[0], args[1:]
     bb = "--bb" in sys.argv
     mn = int(sys.argv[sys.argv.index("--min") + 1]) if "--min" in sys.argv else 0
+    if "--min" in sys.argv:
+        key = [k for k in key if k != sys.argv[sys.argv.index("--min") + 1]]
     blocks = blocks_of(path, key, bb)
     tot = {k: sum(b[k] for b in blocks) for k in ("valu", "slots", "salu", "smem", "lds", "vmem", "far_sel")}
     print("total", tot, "blocks", len(blocks))
+    print("kernel", find_kernel(open(path).read().splitlines(), key)[1])
     for b in blocks:
         if b["valu"] < mn:
             continue
