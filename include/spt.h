@@ -35,12 +35,17 @@ extern "C" {
                              the spt_film_adaptive_* calls; SPT_HAS_FILM_POOL, spt_film_noise_pool_map,
                              spt_film_adaptive_select_pooled and their *_host statements;
                              SPT_HAS_GUIDE, the spt_guide_* calls; SPT_HAS_DENOISE, the
-                             spt_denoise_* and spt_denoiser_* calls and spt_film_denoise */
+                             spt_denoise_* and spt_denoiser_* calls and spt_film_denoise;
+                             SPT_HAS_GUIDE_CHAIN, spt_guide_create_ex (spt_guide_info's last field,
+                             always 0 until then, now reads the guide's flags) */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
 #define SPT_HAS_FILM_POOL 1 /* the error pooled over a pixel's neighbourhood: map and selection (below) */
 #define SPT_HAS_GUIDE 1 /* guide planes: first-hit albedo, normal, depth and coverage (below) */
+#define SPT_HAS_GUIDE_CHAIN 1 /* guides that follow the specular chain: spt_guide_create_ex (below) */
+#define SPT_GUIDE_THROUGH_SPECULAR 1u /* spt_guide_create_ex flag: records of the first DIFF surface */
+#define SPT_GUIDE_MAX_CHAIN 8 /* segments of a chain at most, the camera ray included */
 #define SPT_HAS_DENOISE 1 /* the edge-stopping a-trous filter over a film and its guides (below) */
 
 typedef enum spt_status {
@@ -511,7 +516,8 @@ spt_status spt_film_adaptive_select_pooled_host(const uint64_t* sums, const uint
  * pixel order, a shard's guide holds its compact rows (spt_shard_rows), as a film does.
  * Depth is the ray parameter along the contract's direction: the distance where directions are unit,
  * and within the free-scale contract's 1.8e-3 of it in rect-only DIFF scenes. Albedo is the first
- * hit's own colour: a mirror or a glass ball reads as its .999.
+ * hit's own colour: in a first-hit guide a mirror or a glass ball reads as its .999; a guide created
+ * with SPT_GUIDE_THROUGH_SPECULAR (below) reads what is seen in or through it.
  * The resolve, n = samples_done, r = (float)((double)spp_total / n) (device kernel and host statement
  * run the same IEEE operations):
  *   albedo_k = min(((float)S_k * 2^-31) [* r when n < spp_total], 1)     spt_film_resolve's rule
@@ -519,18 +525,53 @@ spt_status spt_film_adaptive_select_pooled_host(const uint64_t* sums, const uint
  *                                                             below 1 at an edge is information
  *   depth    = hits ? (float)((double)S_6 / ((double)hits * 65536.0)) : 0    the mean over the hits
  *   coverage = (float)((double)hits / (double)n)
- *   n == 0: zeros everywhere. */
+ *   n == 0: zeros everywhere.
+ *
+ * THE SPECULAR CHAIN (SPT_HAS_GUIDE_CHAIN). A guide created by spt_guide_create_ex with
+ * SPT_GUIDE_THROUGH_SPECULAR lets the guide ray continue through perfectly specular surfaces and
+ * records the first DIFF surface it reaches. The mode belongs to the guide: every pass adds its kind of
+ * record, so one guide never mixes the two. Segment 0 is the ray above (same counter, jitter, camera
+ * chain, normaliser and nearest hit). A chain carries a throughput A = (1, 1, 1), a length D = 0.0f
+ * and a segment count. At the nearest hit of a segment (o, d) on primitive H at parameter t, with the
+ * hit point x and the geometric normal gn formed as the render forms them -- x = o + d * tr (a
+ * multiply, then an add), tr = t for a sphere and, for a rectangle with plane k on axis a, t after one
+ * correction step, fmaf(fmaf(-t, d_a, k - o_a), rcp_nr(d_a), t); gn a rectangle's +axis, a sphere's
+ * (x - centre) * (1 / r); nl = gn oriented against d as above:
+ *   H is DIFF, or this is segment SPT_GUIDE_MAX_CHAIN - 1 (the eighth): the chain ends and one record
+ *     is added: slots 0-2 fix(A_k * c_k), slots 3-5 from nl (the rule above with this segment's d),
+ *     slot 6 (uint64)(fminf(D + t, 2^20) * 65536.0f), slot 7 1. An exhausted chain so records its last
+ *     specular hit as if it were diffuse.
+ *   H is SPEC: A_k = A_k * c_k (fp32, in chain order: the first product is exact), D = D + t, and the
+ *     next segment starts at x along the render's reflection d - gn * (2 * dot(gn, d)), the products
+ *     and the subtraction rounded separately, renormalised (rsq_nr) where the scene's directions are
+ *     unit (contract v8) and left as it is in the free-scale contract: bit for bit the ray the render's
+ *     path takes.
+ *   H is REFR: A and D as for SPEC (no Fresnel factor: a guide is a feature, not radiance). With
+ *     into = dot(gn, nl) > 0, nnt = into ? 1/1.5 : 1.5, ddn = dot(d, nl),
+ *     cos2t = 1 - nnt * nnt * (1 - ddn * ddn): when cos2t < 0 (total internal reflection) the next
+ *     segment takes the reflection, else the render's refraction direction
+ *     normalize(d * nnt - gn * ((into ? 1 : -1) * (ddn * nnt + sqrtf(cos2t)))). The branch is decided,
+ *     never drawn: the guide stays noise-free.
+ *   A miss on any segment adds nothing, as a first-segment miss does.
+ * Depth is then the summed ray parameters along the chain (the optical path length where directions
+ * are unit), and the normal is the world-space normal of the surface seen, not the mirror's. Each
+ * sample still adds at most 2^36 to slot 6, so spp <= 2^24 bounds it as before. Record layout, resolve,
+ * download, the host resolve, windows, shards and spt_film_denoise do not know the mode: a chain guide
+ * is a guide. In a scene without SPEC or REFR primitives the two modes hold the same bits. */
 typedef struct spt_guide spt_guide;
 typedef struct spt_guide_info {
   int32_t width, rows, spp_total; /* rows = the shard's row count */
   int64_t samples_done;           /* samples per pixel added so far, 0 .. spp_total */
   int32_t lanes_per_pixel;        /* lanes of a wave that shared a pixel in the last launch (a power of
                                      two, 1..64: the launch's sizing, never a result); 0 before any */
-  int32_t reserved;
+  uint32_t flags;                 /* the guide's SPT_GUIDE_* flags (0: a first-hit guide) */
 } spt_guide_info;
 int32_t spt_guide_info_size(void); /* sizeof(spt_guide_info) as the library was built */
 /* A zeroed guide on `device` for passes with p's width, height, spp (= spp_total) and shard fields. */
 spt_status spt_guide_create(int32_t device, const spt_params* p, spt_guide** out);
+/* The same with flags: 0 is spt_guide_create, SPT_GUIDE_THROUGH_SPECULAR a guide of the specular chain.
+ * Unknown bits: SPT_ERR_INVALID_ARG (before any device is looked for), *out untouched. */
+spt_status spt_guide_create_ex(int32_t device, const spt_params* p, uint32_t flags, spt_guide** out);
 spt_status spt_guide_destroy(spt_guide* guide);
 spt_status spt_guide_clear(spt_guide* guide, void* stream); /* records and samples_done back to 0 */
 spt_status spt_guide_info_get(const spt_guide* guide, spt_guide_info* out);

@@ -122,7 +122,7 @@ class spt_film_adaptive_info(ctypes.Structure):
 class spt_guide_info(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("rows", ctypes.c_int32), ("spp_total", ctypes.c_int32),
                 ("samples_done", ctypes.c_int64), ("lanes_per_pixel", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("flags", ctypes.c_uint32)]
 
 
 class spt_denoise_params(ctypes.Structure):
@@ -165,7 +165,7 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_film_adaptive_noise_summary_host", "spt_film_adaptive_select_host",
            "spt_film_noise_pool_map", "spt_film_adaptive_select_pooled",
            "spt_film_noise_pool_map_host", "spt_film_adaptive_select_pooled_host",
-           "spt_guide_info_size", "spt_guide_create", "spt_guide_destroy", "spt_guide_clear",
+           "spt_guide_info_size", "spt_guide_create", "spt_guide_create_ex", "spt_guide_destroy", "spt_guide_clear",
            "spt_guide_info_get", "spt_guide_render_async", "spt_guide_resolve", "spt_guide_download",
            "spt_guide_resolve_host",
            "spt_denoise_default_params", "spt_denoiser_create", "spt_denoiser_destroy",
@@ -175,6 +175,9 @@ DENOISE_NO_DEMODULATE = 1   # SPT_DENOISE_NO_DEMODULATE: filter rgb itself, not 
 SPT_HAS_GUIDE = 1           # include/spt.h: the spt_guide_* calls (Guide, render_guides)
 GUIDE_SLOTS = 8             # a guide record: albedo 0-2, normal 3-5, depth 6 (48.16), hits 7
 GUIDE_MAX_SPP = 1 << 24
+SPT_HAS_GUIDE_CHAIN = 1     # include/spt.h: spt_guide_create_ex (Guide(..., through_specular=True))
+GUIDE_THROUGH_SPECULAR = 1  # SPT_GUIDE_THROUGH_SPECULAR: the guide ray follows SPEC / REFR to a DIFF hit
+GUIDE_MAX_CHAIN = 8         # SPT_GUIDE_MAX_CHAIN: segments of a chain at most
 COUNT_RETIRED = 0x80000000  # bit 31 of an adaptive film's counts: the pixel takes no more batches
 COUNT_MASK = 0x7FFFFFFF     # ... and the batches it holds
 POOL_MAX_RADIUS = 16        # SPT_POOL_MAX_RADIUS: the pooled calls take a radius in [1, 16]
@@ -314,6 +317,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                          I32, U32, VP, VP, VP, P(I64)]
     lib.spt_guide_info_size.argtypes = []
     lib.spt_guide_create.argtypes = [I32, P(spt_params), P(VP)]
+    lib.spt_guide_create_ex.argtypes = [I32, P(spt_params), ctypes.c_uint32, P(VP)]
     lib.spt_guide_destroy.argtypes = [VP]
     lib.spt_guide_clear.argtypes = [VP, VP]
     lib.spt_guide_info_get.argtypes = [VP, P(spt_guide_info)]
@@ -1122,12 +1126,18 @@ def guide_resolve_host(records: np.ndarray, width: int, rows: int, spp_total: in
 class Guide:
     """spt_guide: per pixel the integer sums of the first hit's colour, oriented normal, ray parameter
     and hit count over the samples added so far, on the device. The rays are the render's own camera
-    rays, so passes over disjoint sample windows add up to one object whatever the split."""
+    rays, so passes over disjoint sample windows add up to one object whatever the split.
+    through_specular: a guide of the specular chain (spt_guide_create_ex, SPT_GUIDE_THROUGH_SPECULAR):
+    every pass follows mirrors and glass to the first DIFF surface; the default holds first hits."""
 
-    def __init__(self, params: spt_params, device: int = 0):
+    def __init__(self, params: spt_params, device: int = 0, through_specular: bool = False):
         self.lib = load_library()
         self._g = ctypes.c_void_p()
-        _check(self.lib.spt_guide_create(int(device), ctypes.byref(params), ctypes.byref(self._g)))
+        if through_specular:
+            _check(self.lib.spt_guide_create_ex(int(device), ctypes.byref(params), GUIDE_THROUGH_SPECULAR,
+                                                ctypes.byref(self._g)))
+        else:
+            _check(self.lib.spt_guide_create(int(device), ctypes.byref(params), ctypes.byref(self._g)))
         self.device = device
 
     def close(self):
@@ -1144,7 +1154,7 @@ class Guide:
     def info(self) -> dict:
         i = spt_guide_info()
         _check(self.lib.spt_guide_info_get(self._g, ctypes.byref(i)))
-        return {k: int(getattr(i, k)) for k, _ in i._fields_ if k != "reserved"}
+        return {k: int(getattr(i, k)) for k, _ in i._fields_}
 
     def clear(self, stream_ptr: int = 0):
         _check(self.lib.spt_guide_clear(self._g, ctypes.c_void_p(stream_ptr or None)))
@@ -1187,11 +1197,12 @@ class Guide:
         return out
 
 
-def render_guides(prims: Sequence[spt_prim], cam: Camera, params: spt_params) -> dict:
+def render_guides(prims: Sequence[spt_prim], cam: Camera, params: spt_params,
+                  through_specular: bool = False) -> dict:
     """The guide planes of the full window [0, params.spp): {"albedo", "normal", "depth",
-    "coverage"} as float32 arrays on the host (Guide.resolve)."""
+    "coverage"} as float32 arrays on the host (Guide.resolve). through_specular: of a chain guide."""
     import torch
-    r, g = Renderer(params.device), Guide(params, params.device)
+    r, g = Renderer(params.device), Guide(params, params.device, through_specular)
     try:
         with torch.cuda.device(params.device):
             g.render(r, prims, cam, params, 0, params.spp, torch.cuda.current_stream().cuda_stream)
@@ -1454,9 +1465,10 @@ class Denoiser:
 
 def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, batch: int | None = None,
                     guide_spp: int | None = None, denoise: spt_denoise_params | None = None,
-                    return_info=False):
+                    return_info=False, through_specular: bool = False):
     """Render all params.spp samples into a noise film (batches of `batch`, default spp / 8 as in
-    render_until), fill a guide with the sample window [0, min(spp, guide_spp or 64)), and return the
+    render_until), fill a guide (through_specular: a chain guide, see Guide) with the sample window
+    [0, min(spp, guide_spp or 64)), and return the
     film's image denoised (Denoiser.denoise_film). One device. return_info: also {"noisy": the film's
     own image, "noise": the film's noise_summary, "guides": the guide planes, "se": se_out}."""
     spp = int(params.spp)
@@ -1469,7 +1481,7 @@ def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, 
     if batch < 1 or spp % batch:
         raise SptError(1, "render_denoised: batch must divide spp (every sample is rendered)")
     n_guide = min(spp, int(guide_spp or 64))
-    guide = Guide(params, params.device)
+    guide = Guide(params, params.device, through_specular)
     dn = None
     try:
         dn = Denoiser(params.width, params.height, params.device)

@@ -3,7 +3,11 @@
 //               [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]
 //               [--device N | --devices N] [--p6 | --pfm]
 //               [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]
-//               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]] [--help]
+//               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]]
+//               [--through-specular] [--help]
+//   --through-specular: with --guides and / or --denoise, the guide follows mirrors and glass to the
+//               first diffuse surface (spt_guide_create_ex, SPT_GUIDE_THROUGH_SPECULAR); alone it is a
+//               usage error.
 //   --denoise: the output file becomes the image denoised by the edge-stopping a-trous filter
 //               (spt_film_denoise: the film's image and error map, and guide planes of the first
 //               min(SPP, 64) samples' camera rays). The render goes through a noise film: --noise T
@@ -98,6 +102,7 @@ struct NoiseOpts {
 struct DenoiseOpts {
   bool on = false;
   bool iters_given = false, sigma_given = false;  // not given: the library's default
+  bool through_specular = false;                  // the guide follows the specular chain
   int iters = 0;
   double sigma = 0.0;
 };
@@ -247,7 +252,8 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
     if (denoise.sigma_given) dp.sigma_color = (float)denoise.sigma;
     spt_guide* guide = nullptr;
     spt_denoiser* dn = nullptr;
-    check(spt_guide_create(p.device, &p, &guide));
+    check(spt_guide_create_ex(p.device, &p, denoise.through_specular ? SPT_GUIDE_THROUGH_SPECULAR : 0u,
+                              &guide));
     check(spt_denoiser_create(p.device, p.width, p.height, &dn));
     check(spt_guide_render_async(ctx, guide, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
                                  std::min(p.spp, 64), nullptr));
@@ -263,11 +269,11 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
 
 // --guides: the guide planes of the full window, resolved on the device and written as three PFMs.
 void write_guides(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
-                  const std::string& prefix) {
+                  const std::string& prefix, bool through_specular) {
   spt_context* ctx = nullptr;
   spt_guide* guide = nullptr;
   check(spt_context_create(p.device, &ctx));
-  check(spt_guide_create(p.device, &p, &guide));
+  check(spt_guide_create_ex(p.device, &p, through_specular ? SPT_GUIDE_THROUGH_SPECULAR : 0u, &guide));
   spt_guide_info info{};
   check(spt_guide_info_get(guide, &info));
   const size_t npix = (size_t)info.rows * (size_t)info.width;
@@ -300,6 +306,7 @@ const char kUsage[] =
     "            [--film PATH [--add N]]\n"
     "            [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]\n"
     "            [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]]\n"
+    "            [--through-specular]\n"
     "  --guides PREFIX  also write the first-hit guide planes PREFIX_albedo.pfm, PREFIX_normal.pfm\n"
     "                   and PREFIX_depth.pfm (linear PFM). The normal is stored signed, components\n"
     "                   in [-1, 1] (not 0.5 + 0.5 n); the depth is the mean ray parameter of the\n"
@@ -307,6 +314,8 @@ const char kUsage[] =
     "  --denoise        write the image denoised by the edge-stopping a-trous filter over the noise\n"
     "                   film's image, its error map and the guide planes (--noise/--batch as given,\n"
     "                   else 8 batches; goes with --adaptive; one device)\n"
+    "  --through-specular  with --guides and/or --denoise: the guide follows mirrors and glass to\n"
+    "                   the first diffuse surface (at most 8 segments)\n"
     "  --denoise-iters N  filter iterations, 0..6 (default 5)\n"
     "  --denoise-sigma S  the colour sigma (default 4)\n";
 
@@ -348,6 +357,7 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--pool-loo")) noise.pool_loo = true;
     else if (!std::strcmp(argv[i], "--guides") && i + 1 < argc) guides = argv[++i];
     else if (!std::strcmp(argv[i], "--denoise")) denoise.on = true;
+    else if (!std::strcmp(argv[i], "--through-specular")) denoise.through_specular = true;
     else if (!std::strcmp(argv[i], "--denoise-iters") && i + 1 < argc) { denoise.iters_given = true; denoise.iters = std::atoi(argv[++i]); }
     else if (!std::strcmp(argv[i], "--denoise-sigma") && i + 1 < argc) { denoise.sigma_given = true; denoise.sigma = std::atof(argv[++i]); }
     else if (!std::strcmp(argv[i], "--help")) { std::cout << kUsage; return 0; }
@@ -355,6 +365,10 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
     else if (npos < 4) pos[npos++] = std::atoi(argv[i]);
     else out = argv[i];
+  }
+  if (denoise.through_specular && !guides && !denoise.on) {
+    std::cerr << "--through-specular goes with --guides PREFIX or --denoise\n" << kUsage;
+    return 2;
   }
   const auto t1 = std::chrono::high_resolution_clock::now();
   spt_params p;
@@ -429,7 +443,7 @@ int main(int argc, char* argv[]) {
   }
   if (guides) {  // after the image: its bytes are those of a run without the flag
     try {
-      write_guides(guide_scene, cam, p, guides);
+      write_guides(guide_scene, cam, p, guides, denoise.through_specular);
     } catch (const std::exception& e) {
       std::cerr << "guides failed: " << e.what() << std::endl;
       return 1;

@@ -63,7 +63,7 @@ struct spt_context {
   // it has its own upload event, and leaves everything above alone (stats, last_kv, the film).
   hipEvent_t ev_guide = nullptr;
   bool guide_pending = false;     // the staging may still be read by a guide pass's upload
-  int guide_bpc[2] = {0, 0};      // resident blocks per CU of the guide kernels (generic, wide); 0: not asked yet
+  int guide_bpc[4] = {0, 0, 0, 0};  // resident blocks per CU of the guide kernels ([chain * 2 + wide]); 0: not asked yet
 };
 
 extern "C" int32_t spt_shard_rows(const spt_params* p, int32_t* rows_out, int32_t cap);
@@ -307,7 +307,7 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
 spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
                             const spt_camera* cam, const spt_params* p, int32_t s_base,
                             int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
-                            void* stream_v) {
+                            uint32_t flags, void* stream_v) {
   if (!c || !rec_dev) return fail(SPT_ERR_INVALID_ARG, "null context/guide");
   spt_status st = validate(prims, n_prims, cam, p);
   if (st != SPT_OK) return st;
@@ -327,9 +327,11 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
   int light_pos = -1;
   build_geo(prims, n_prims, c->h_geo, p->light_id, &light_pos);
   const bool wide = c->h_geo->n_sph_wide > 0;
-  if (c->guide_bpc[wide] == 0) {
-    const int bpc = guide_kernel_occupancy(wide);
-    c->guide_bpc[wide] = bpc > 0 ? bpc : 4;
+  const bool chain = (flags & SPT_GUIDE_THROUGH_SPECULAR) != 0;
+  int& guide_bpc = c->guide_bpc[(chain ? 2 : 0) + (wide ? 1 : 0)];  // of the instantiation launched
+  if (guide_bpc == 0) {
+    const int bpc = guide_kernel_occupancy(wide, chain);
+    guide_bpc = bpc > 0 ? bpc : 4;
   }
   // the fp32 camera and the launch's terms (shard, magic divisors, fixed-point scale, camera chain)
   // as a render of the scene's run-time kernel would set them; the unit and queue sizes are unused
@@ -337,10 +339,10 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
   LaunchPlan plan;
   spt_params q = *p;
   q.chunk = s_count;  // one unit per pixel: never "too many work units"
-  st = plan_launch(c->n_cu, c->guide_bpc[wide], wide ? KV_WIDE : KV_GENERIC, &q, s_count,
+  st = plan_launch(c->n_cu, guide_bpc, wide ? KV_WIDE : KV_GENERIC, &q, s_count,
                    rows * p->width, &K, &plan);
   if (st != SPT_OK) return st;
-  int k = force_k > 0 ? force_k : guide_lanes_per_pixel(c->n_cu, c->guide_bpc[wide], K.n_local_pix, s_count);
+  int k = force_k > 0 ? force_k : guide_lanes_per_pixel(c->n_cu, guide_bpc, K.n_local_pix, s_count);
   uint32_t ksh = 0;
   while ((1 << (ksh + 1)) <= k && ksh < 6) ++ksh;
   k = 1 << ksh;
@@ -365,7 +367,7 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
   SPT_HIP(hipMemcpyAsync(c->d_kp, c->h_kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
   SPT_HIP(hipEventRecord(c->ev_guide, stream));
   c->guide_pending = true;
-  launch_guide_kernel(wide, (int)grid, c->d_kp, stream);
+  launch_guide_kernel(wide, chain, (int)grid, c->d_kp, stream);
   SPT_HIP(hipGetLastError());
   if (lanes_out) *lanes_out = k;
   return SPT_OK;

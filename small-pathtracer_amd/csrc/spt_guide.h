@@ -10,11 +10,12 @@
 // spt_context.cpp: one guide launch over the sample window [s_base, s_base + s_count) into the
 // records rec_dev (int64[rows * w][8], the shard's compact rows), through the context's scene upload.
 // *lanes_out = the lanes per pixel it ran with; force_k > 0 overrides the host's choice (a
-// measurement's knob, not the ABI's). A shard without rows launches nothing.
+// measurement's knob, not the ABI's). A shard without rows launches nothing. flags: the guide's
+// (SPT_GUIDE_THROUGH_SPECULAR picks the chain instantiation of the kernel).
 spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
                             const spt_camera* cam, const spt_params* p, int32_t s_base,
                             int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
-                            void* stream);
+                            uint32_t flags, void* stream);
 int spt_context_device(const spt_context* c);
 
 namespace spt_guide_math {

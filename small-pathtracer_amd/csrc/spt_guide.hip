@@ -19,6 +19,7 @@ struct spt_guide {
   long long* rec = nullptr;  // [rows * width][8], device
   size_t npix = 0;
   int32_t lanes_per_pixel = 0;  // K of the last launch
+  uint32_t flags = 0;           // SPT_GUIDE_*: the kind of record every pass adds (set at creation)
 };
 
 int spt_shard_row_count(const spt_params* p);  // spt_host.cpp
@@ -71,8 +72,10 @@ guide_resolve_kernel(const long long* __restrict__ rec, uint32_t npix, int64_t n
 
 }  // namespace
 
-extern "C" spt_status spt_guide_create(int32_t device, const spt_params* p, spt_guide** out) {
+extern "C" spt_status spt_guide_create_ex(int32_t device, const spt_params* p, uint32_t flags,
+                                          spt_guide** out) {
   if (!p || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (flags & ~SPT_GUIDE_THROUGH_SPECULAR) return fail(SPT_ERR_INVALID_ARG, "unknown guide flags");
   if (p->width <= 0 || p->height <= 0 || p->spp <= 0)
     return fail(SPT_ERR_INVALID_ARG, "width/height/spp must be positive");
   if (p->spp > kMaxSpp) return fail(SPT_ERR_INVALID_ARG, "a guide takes at most 2^24 samples per pixel");
@@ -87,6 +90,7 @@ extern "C" spt_status spt_guide_create(int32_t device, const spt_params* p, spt_
   GUIDE_HIP(hipSetDevice(device));
   spt_guide* g = new spt_guide();
   g->device = device;
+  g->flags = flags;
   g->width = p->width;
   g->height = p->height;
   g->spp_total = p->spp;
@@ -106,6 +110,10 @@ extern "C" spt_status spt_guide_create(int32_t device, const spt_params* p, spt_
   }
   *out = g;
   return SPT_OK;
+}
+
+extern "C" spt_status spt_guide_create(int32_t device, const spt_params* p, spt_guide** out) {
+  return spt_guide_create_ex(device, p, 0u, out);
 }
 
 extern "C" spt_status spt_guide_destroy(spt_guide* g) {
@@ -135,7 +143,7 @@ extern "C" spt_status spt_guide_info_get(const spt_guide* g, spt_guide_info* out
   out->spp_total = g->spp_total;
   out->samples_done = g->samples_done;
   out->lanes_per_pixel = g->lanes_per_pixel;
-  out->reserved = 0;
+  out->flags = g->flags;
   return SPT_OK;
 }
 
@@ -159,7 +167,7 @@ static spt_status guide_render(spt_context* ctx, spt_guide* g, const spt_prim* p
   if (g->npix) {
     int32_t k = 0;
     const spt_status st = spt_guide_window(ctx, prims, n_prims, cam, p, sample_base, sample_count,
-                                           g->rec, &k, force_k, stream);
+                                           g->rec, &k, force_k, g->flags, stream);
     if (st != SPT_OK) return st;
     g->lanes_per_pixel = k;
   }

@@ -1739,7 +1739,36 @@ __device__ __forceinline__ long long shfl_xor64(long long v, int m) {
   const int hi = __shfl_xor((int)(uint32_t)((unsigned long long)v >> 32), m, 64);
   return (long long)(((unsigned long long)(uint32_t)hi << 32) | (unsigned long long)(uint32_t)lo);
 }
-template <class TP>
+// The chain guide's step at a SPEC or REFR hit (include/spt.h, SPT_HAS_GUIDE_CHAIN): the throughput
+// takes the primitive's colour, the length the segment's t, and (o, d) become the ray the render's path
+// takes from here -- render_kernel's SPEC / REFR code operation for operation (oracle c_path), with the
+// refraction wherever there is one (no Fresnel draw) and the reflection on total internal reflection.
+// Only the CHAIN instantiations of guide_kernel call it; the render kernels keep their own copy.
+__device__ __forceinline__ void guide_chain_step(const DevPrim& H, bool unit, f3 x, f3 gn, f3 nl, float t,
+                                                 f3& A, float& D, f3& o, f3& d) {
+  A = mk(A.x * H.cx, A.y * H.cy, A.z * H.cz);
+  D = D + t;
+  const float k2 = 2.0f * dot3(gn, d);
+  f3 nd = mk(d.x - gn.x * k2, d.y - gn.y * k2, d.z - gn.z * k2);  // reflRay
+  if (unit) nd = normalize3(nd);
+  if (H.refl == SPT_REFR) {
+    const bool into = dot3(gn, nl) > 0.0f;
+    const float nnt = into ? 1.0f / 1.5f : 1.5f / 1.0f;
+    const float ddn = dot3(d, nl);
+    const float cos2t = 1.0f - nnt * nnt * (1.0f - ddn * ddn);
+    if (!(cos2t < 0.0f)) {  // else total internal reflection: the reflection above
+      const float kk = (into ? 1.0f : -1.0f) * (ddn * nnt + sqrtf(cos2t));
+      nd = normalize3(mk(d.x * nnt - gn.x * kk, d.y * nnt - gn.y * kk, d.z * nnt - gn.z * kk));
+    }
+  }
+  o = x;
+  d = nd;
+}
+
+// CHAIN: the guide ray goes on through SPEC and REFR primitives (spt_guide_create_ex with
+// SPT_GUIDE_THROUGH_SPECULAR) and the record is the first DIFF hit's, at most SPT_GUIDE_MAX_CHAIN
+// segments; the lanes of a group then differ in their trace counts, the reduction does not change.
+template <class TP, bool CHAIN>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SPT_NUM_SGPR)))
 guide_kernel(const KParams* __restrict__ Pg) {
   static_assert(!TP::CONSTGEO && TP::MAT && TP::SPH, "the guide kernel runs the run-time topologies");
@@ -1786,6 +1815,57 @@ guide_kernel(const KParams* __restrict__ Pg) {
       const f3 v = mk(fmaf(Fv, C->cam_cv[0], fmaf(Fu, C->cam_cu[0], px)),
                       fmaf(Fv, C->cam_cv[1], fmaf(Fu, C->cam_cu[1], py)),
                       fmaf(Fv, C->cam_cv[2], fmaf(Fu, C->cam_cu[2], pz)));
+      if constexpr (CHAIN) {
+        f3 oc = o, dc = normalize_dir(v, unit);
+        f3 A = mk(1.0f, 1.0f, 1.0f);
+        float D = 0.0f;
+        for (int seg = 0; seg < SPT_GUIDE_MAX_CHAIN; ++seg) {
+          const SPT_CONST SceneGeo* Gs = cptr(cptr(Pg)->geo);  // re-issued per trace, as G is per sample
+          int id = 0, hpos;
+          float ia_hit = 0.0f;
+          f3 inv;
+          if (!intersect_scene<TP>(Gs, rects_of<TP>(Gs), tests_of<TP>(Gs, s_test), Gs->sph, s_pos2idx, oc, dc,
+                                   id, ia_hit, hpos, inv))
+            break;  // a miss on any segment adds nothing
+          const DevPrim& H = s_prims[id];
+          const float t = hit_t<TP>(H, hpos, oc, dc, ia_hit, Gs);  // the winner's exact t
+          // the hit point and the normals as render_kernel forms them: a rectangle's t corrected
+          // (hit_plane_t) for x, a sphere's gn from x
+          float tr = t;
+          if (H.kind == SPT_RECT_XY) tr = hit_plane_t(H.w1 - oc.z, dc.z, ia_hit, t);
+          else if (H.kind == SPT_RECT_XZ) tr = hit_plane_t(H.w1 - oc.y, dc.y, ia_hit, t);
+          else if (H.kind == SPT_RECT_YZ) tr = hit_plane_t(H.w1 - oc.x, dc.x, ia_hit, t);
+          const f3 x = mk(oc.x + dc.x * tr, oc.y + dc.y * tr, oc.z + dc.z * tr);
+          f3 nl, gn;
+          if (H.kind == SPT_RECT_XY) {
+            nl = dc.z < 0.0f ? mk(0, 0, 1) : mk(0, 0, -1);
+            gn = mk(0, 0, 1);
+          } else if (H.kind == SPT_RECT_XZ) {
+            nl = dc.y < 0.0f ? mk(0, 1, 0) : mk(0, -1, 0);
+            gn = mk(0, 1, 0);
+          } else if (H.kind == SPT_RECT_YZ) {
+            nl = dc.x < 0.0f ? mk(1, 0, 0) : mk(-1, 0, 0);
+            gn = mk(1, 0, 0);
+          } else {
+            gn = mk((x.x - H.w1) * H.w5, (x.y - H.w2) * H.w5, (x.z - H.w3) * H.w5);
+            nl = dot3(gn, dc) < 0.0f ? gn : mk(-gn.x, -gn.y, -gn.z);
+          }
+          if (H.refl == SPT_DIFF || seg == SPT_GUIDE_MAX_CHAIN - 1) {
+            a0 += (long long)fix31(A.x * H.cx, scale);
+            a1 += (long long)fix31(A.y * H.cy, scale);
+            a2 += (long long)fix31(A.z * H.cz, scale);
+            const long long m0 = (long long)fix31(fabsf(nl.x), scale), m1 = (long long)fix31(fabsf(nl.y), scale);
+            const long long m2 = (long long)fix31(fabsf(nl.z), scale);
+            n0 += nl.x < 0.0f ? -m0 : m0;
+            n1 += nl.y < 0.0f ? -m1 : m1;
+            n2 += nl.z < 0.0f ? -m2 : m2;
+            dsum += (long long)(unsigned long long)(fminf(D + t, 0x1p20f) * 65536.0f);
+            hits += 1;
+            break;
+          }
+          guide_chain_step(H, unit, x, gn, nl, t, A, D, oc, dc);
+        }
+      } else {
       const f3 d = normalize_dir(v, unit);
       int id = 0, hpos;
       float ia_hit = 0.0f;
@@ -1818,6 +1898,7 @@ guide_kernel(const KParams* __restrict__ Pg) {
         dsum += (long long)(unsigned long long)(fminf(t, 0x1p20f) * 65536.0f);
         hits += 1;
       }
+      }
     }
   }
   // the group's sums: every lane of the wave takes part (a dead group's lanes hold zeros)
@@ -1844,16 +1925,21 @@ guide_kernel(const KParams* __restrict__ Pg) {
   }
 }
 
-int guide_kernel_occupancy(bool wide) {
+using GuideFn = void (*)(const KParams*);
+static GuideFn guide_fn(bool wide, bool chain) {
+  if (chain) return wide ? guide_kernel<TopoGenericWide, true> : guide_kernel<TopoGeneric, true>;
+  return wide ? guide_kernel<TopoGenericWide, false> : guide_kernel<TopoGeneric, false>;
+}
+
+int guide_kernel_occupancy(bool wide, bool chain) {
   int bpc = 0;
-  const auto fn = wide ? guide_kernel<TopoGenericWide> : guide_kernel<TopoGeneric>;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kBlock, 0) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, guide_fn(wide, chain), kBlock, 0) != hipSuccess)
+    return 0;
   return bpc;
 }
 
-void launch_guide_kernel(bool wide, int grid, const KParams* kp_dev, void* stream) {
-  hipLaunchKernelGGL(wide ? guide_kernel<TopoGenericWide> : guide_kernel<TopoGeneric>, dim3(grid),
-                     dim3(kBlock), 0, (hipStream_t)stream, kp_dev);
+void launch_guide_kernel(bool wide, bool chain, int grid, const KParams* kp_dev, void* stream) {
+  hipLaunchKernelGGL(guide_fn(wide, chain), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, kp_dev);
 }
 
 }  // namespace spt

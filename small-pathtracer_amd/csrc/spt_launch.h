@@ -48,9 +48,10 @@ void launch_finalize_slots(const unsigned long long* accum, const unsigned long 
                            float* rgb, uint32_t npix, uint32_t n_chunks, uint32_t scr_k,
                            uint32_t scr_q, const unsigned long long* stats, void* stream);
 // The guide kernel (SPT_HAS_GUIDE): guide_kernel<TopoGenericWide> for a scene with wide spheres, else
-// guide_kernel<TopoGeneric>. grid * kBlock lanes >= n_local_pix << guide_kshift.
-int guide_kernel_occupancy(bool wide);  // resident blocks per CU; <= 0: query failed
-void launch_guide_kernel(bool wide, int grid, const KParams* kp_dev, void* stream);
+// guide_kernel<TopoGeneric>. grid * kBlock lanes >= n_local_pix << guide_kshift. chain: the
+// instantiation that follows the specular chain (SPT_HAS_GUIDE_CHAIN), which has its own occupancy.
+int guide_kernel_occupancy(bool wide, bool chain);  // resident blocks per CU; <= 0: query failed
+void launch_guide_kernel(bool wide, bool chain, int grid, const KParams* kp_dev, void* stream);
 
 // ---- spt_dispatch.cpp: lanes per pixel of a guide launch (a power of two, 1..64): the smallest K
 // with n_local_pix * K >= the device's resident lanes (n_cu * bpc * kBlock), at most the window's

@@ -1,0 +1,474 @@
+"""The guide's specular chain on the GPU (include/spt.h SPT_HAS_GUIDE_CHAIN; guide_kernel<TP, true> in
+spt_kernel.hip): the downloaded int64 records, exact, against tests/guide_chain_truth.py (the header's
+rule restated from the oracle's pieces) and against the render kernels themselves; a first-hit guide
+against tests/guide_truth.py as before; the denoise path and the wrappers with a chain guide.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import guide_chain_truth as gct
+import guide_truth as gt
+import ray_truth as rt
+from test_gpu_guide import _read_pfm
+
+pytestmark = pytest.mark.gpu
+SEED = 5
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "small-pathtracer_amd", "smallpt_amd")
+BOXES = ("mirror_glass", "classic")  # no light rectangle: nee_prob = 0, as their renders have
+
+
+def _aspect(w, h):
+    return float(np.float32(w) / np.float32(h))
+
+
+def _params(spt, name, w, h, spp, **kw):
+    if name in BOXES:
+        kw.setdefault("nee_prob", 0.0)
+    return spt.default_params(width=w, height=h, spp=spp, seed=SEED, **kw)
+
+
+def _guide(spt, prims, cam, p, chain=True, windows=None, renderer=None):
+    """-> (records, info) of a fresh guide filled with `windows` (default: the full one)."""
+    r = renderer or spt.Renderer(p.device)
+    g = spt.Guide(p, p.device, through_specular=chain)
+    try:
+        for base, count in windows or [(0, p.spp)]:
+            g.render(r, prims, cam, p, base, count)
+        return g.to_numpy(), g.info()
+    finally:
+        g.close()
+        if renderer is None:
+            r.close()
+
+
+def _same(got, want, label):
+    diff = np.argwhere(got != want)
+    assert diff.size == 0, f"{label}: {len(diff)} slots differ, first {diff[:4].tolist()}: " \
+                           f"{[(int(got[tuple(i)]), int(want[tuple(i)])) for i in diff[:4]]}"
+
+
+# ---- 1. the truth, per scene class -----------------------------------------------------------------
+# (label, scene, camera, w, h, spp, the wide instantiation?, the longest chain). Which instantiation a
+# guide pass launches is the scene's: the wide one iff the scene has a wide sphere, which is when a
+# render of it launches "wide" (spt_select_kernel: the same host predicate).
+TRUTH_CASES = [("specular", "specular", {}, 48, 32, 4, False, None),
+               ("mirror_glass", "mirror_glass", {}, 32, 24, 4, True, None),
+               ("mirror_glass_tilted", "mirror_glass", rt.TILTED, 32, 24, 4, True, None),
+               ("classic", "classic", {}, 32, 24, 4, True, 1),
+               ("head", "head", {}, 64, 48, 8, False, 1),
+               ("hall", "hall", gct.HALL_CAM, 32, 24, 4, False, gct.MAX_CHAIN)]
+_truths = {}
+
+
+def _truth(spt, oracle, name, camkw, w, h, spp):
+    key = (name, tuple(sorted(camkw.items())), w, h, spp)
+    if key not in _truths:
+        prims = gct.scene(spt, name)
+        cam = spt.Camera(aspect=_aspect(w, h), **camkw)
+        _truths[key] = gct.chain_truth(oracle, prims, cam._c, _params(spt, name, w, h, spp),
+                                       return_segments=True)
+    return _truths[key]
+
+
+@pytest.mark.parametrize("label,name,camkw,w,h,spp,wide,longest", TRUTH_CASES, ids=[c[0] for c in TRUTH_CASES])
+def test_chain_records_equal_the_truth(spt, oracle, label, name, camkw, w, h, spp, wide, longest):
+    prims = gct.scene(spt, name)
+    cam = spt.Camera(aspect=_aspect(w, h), **camkw)
+    p = _params(spt, name, w, h, spp)
+    assert (spt.select_kernel(prims, cam, p)["name"] == "wide") == wide
+    rec, info = _guide(spt, prims, cam, p)
+    assert info["samples_done"] == spp and info["flags"] == spt.GUIDE_THROUGH_SPECULAR
+    want, segs = _truth(spt, oracle, name, camkw, w, h, spp)
+    assert want[..., 7].sum() > 0
+    if longest is not None:
+        assert segs.max() == longest
+    else:
+        assert segs.max() >= 2
+    _same(rec, want, label)
+    if any(q.refl != gct.DIFF for q in prims):  # ... and it is not the first-hit guide
+        assert not np.array_equal(rec, _guide(spt, prims, cam, p, chain=False)[0])
+
+
+def test_both_instantiations_are_covered():
+    assert {c[6] for c in TRUTH_CASES} == {False, True}
+    assert any(c[1] == "hall" for c in TRUTH_CASES)  # free-scale directions, chains into the cap
+
+
+# ---- 2. against the render kernels, independently of the truth helper -------------------------------
+# One specular primitive: a chain has at most 2 segments, the cap cannot matter. In the render scene
+# every DIFF primitive emits its guide-scene colour and reflects nothing, the mirror emits nothing and
+# keeps its .999: with nee_prob = 0 and no roulette a path's radiance is A * c of its first diffuse
+# vertex, and the film's sums are slots 0-2 of the chain guide. This is the test that the reflected
+# segment is the render's own ray.
+@pytest.mark.parametrize("name,w,h,spp", [("one_mirror_ball", 48, 32, 4), ("one_mirror_wall", 48, 32, 4)])
+def test_albedo_slots_equal_a_film_of_the_emitting_scene(spt, name, w, h, spp):
+    prims = gct.scene(spt, name)
+    assert sum(q.refl != gct.DIFF for q in prims) == 1
+    assert gt.unit_dirs(prims) == (name == "one_mirror_ball")
+    cam = spt.Camera(aspect=_aspect(w, h))
+    p = _params(spt, name, w, h, spp, nee_prob=0.0, rr_depth=64)
+    r, film = spt.Renderer(0), spt.Film(p, 0)
+    try:
+        film.render(r, gct.albedo_render_scene(spt, prims), cam, p, 0, spp)
+        st = r.stats()
+        assert st["misses"] == 0 and st["samples"] == w * h * spp
+        assert st["vertices"] > st["samples"]  # some paths went through the mirror
+        sums = film.to_numpy()
+        rec, _ = _guide(spt, prims, cam, p, renderer=r)
+        first, _ = _guide(spt, prims, cam, p, chain=False, renderer=r)
+    finally:
+        film.close()
+        r.close()
+    _same(rec[..., 0:3].astype(np.uint64), sums, name)
+    assert (rec[..., 7] == spp).all()
+    assert not np.array_equal(first[..., 0:3], rec[..., 0:3])
+
+
+# ---- 3. windows, lane groups, shards ---------------------------------------------------------------
+# K = 64 at 8x4 @ 96 (the cap), 8 at its window of 5 samples, 1 or 2 at 256x192 @ 2 (the resident
+# lanes of the device), as tests/test_gpu_guide.py's LANE_CASES.
+LANE_CASES = [("8x4_spp96", 8, 4, 96, (0, 96)), ("8x4_window5", 8, 4, 96, (0, 5)), ("256x192_spp2", 256, 192, 2, (0, 2))]
+_lanes = {}
+
+
+@pytest.mark.parametrize("label,w,h,spp,window", LANE_CASES, ids=[c[0] for c in LANE_CASES])
+def test_lane_groups(spt, oracle, label, w, h, spp, window):
+    prims = gct.scene(spt, "mirror_glass")
+    cam = spt.Camera(aspect=_aspect(w, h))
+    p = _params(spt, "mirror_glass", w, h, spp)
+    rec, info = _guide(spt, prims, cam, p, windows=[window])
+    _lanes[label] = info["lanes_per_pixel"]
+    if w * h <= 64:
+        _same(rec, gct.chain_truth(oracle, prims, cam._c, p, *window), label)
+    else:  # (the truth of 98304 rays is slow in numpy) the same records whatever the lanes per pixel
+        parts, _ = _guide(spt, prims, cam, p, windows=[(1, 1), (0, 1)])  # K = 1 twice
+        _same(rec, parts, label)
+        rows = [0, 130, 140, 191]  # two of them cross the balls
+        want, segs = gct.chain_truth(oracle, prims, cam._c, p, *window, rows=rows, return_segments=True)
+        assert segs.max() >= 3
+        _same(rec[rows], want, label + " rows")
+
+
+def test_lane_groups_covered_every_width():
+    assert len(_lanes) == len(LANE_CASES), "runs after test_lane_groups"
+    ks = set(_lanes.values())
+    assert _lanes["8x4_spp96"] == 64, _lanes
+    assert ks & {1, 2} and ks & {4, 8, 16, 32} and 64 in ks, _lanes
+
+
+@pytest.mark.parametrize("w,h,spp", [(8, 4, 96), (64, 48, 8)])
+def test_windows_in_any_order_and_two_shards(spt, oracle, w, h, spp):
+    prims = gct.scene(spt, "mirror_glass")
+    cam = spt.Camera(aspect=_aspect(w, h))
+    p = _params(spt, "mirror_glass", w, h, spp, tile_rows=2)
+    one, _ = _guide(spt, prims, cam, p)
+    a = spp // 3
+    ab, ia = _guide(spt, prims, cam, p, windows=[(0, a), (a, spp - a)])
+    ba, ib = _guide(spt, prims, cam, p, windows=[(a, spp - a), (0, a)])
+    assert ia["samples_done"] == ib["samples_done"] == spp
+    _same(ab, one, "windows in order")
+    _same(ba, one, "windows reversed")
+    _same(one, _truth(spt, oracle, "mirror_glass", {}, w, h, spp)[0], "the truth")
+    seen = []
+    for k in range(2):
+        q = _params(spt, "mirror_glass", w, h, spp, tile_rows=2, shard_index=k, shard_count=2)
+        rows = spt.shard_rows(q)
+        rec, info = _guide(spt, prims, cam, q)
+        assert info["rows"] == len(rows) > 0
+        _same(rec, one[rows], f"shard {k}")
+        seen += list(rows)
+    assert sorted(seen) == list(range(h))
+
+
+# ---- 4. a first-hit guide is untouched --------------------------------------------------------------
+def test_create_and_create_ex_with_no_flags_are_the_first_hit_guide(spt, oracle):
+    prims = gct.scene(spt, "mirror_glass")
+    w, h, spp = 32, 24, 4
+    cam = spt.Camera(aspect=_aspect(w, h))
+    p = _params(spt, "mirror_glass", w, h, spp)
+    lib = spt.load_library()
+    want = gt.guide_truth(oracle, prims, cam._c, p)
+    r = spt.Renderer(0)
+    plain = spt.Guide(p, 0)
+    try:
+        ex = spt.Guide.__new__(spt.Guide)  # a Guide over spt_guide_create_ex(..., 0, ...)
+        ex.lib, ex.device, ex._g = lib, 0, ctypes.c_void_p()
+        assert lib.spt_guide_create_ex(0, ctypes.byref(p), 0, ctypes.byref(ex._g)) == 0
+        try:
+            for g in (plain, ex):
+                g.render(r, prims, cam, p, 0, spp)
+                assert g.info()["flags"] == 0
+                _same(g.to_numpy(), want, "first hit")
+        finally:
+            ex.close()
+    finally:
+        plain.close()
+        r.close()
+
+
+def _frame(spt, r, prims, cam, p):
+    import torch
+    buf = torch.empty(p.height * p.width * 3, dtype=torch.float32, device="cuda:0")
+    r.render_async(prims, cam, p, buf.data_ptr())
+    st = r.stats()
+    torch.cuda.synchronize(0)
+    return buf.cpu().numpy(), {k: st[k] for k in spt.STAT_KEYS + ["shadow_proven"]}, r.kernel()
+
+
+def test_a_chain_pass_between_frames_and_alternating_guides(spt, oracle):
+    a = gct.scene(spt, "head")
+    b = gct.scene(spt, "mirror_glass")
+    cam = spt.Camera(aspect=_aspect(32, 24))
+    pa = spt.default_params(width=32, height=24, spp=8, seed=SEED)
+    pb = _params(spt, "mirror_glass", 32, 24, 4)
+    want_chain = _truth(spt, oracle, "mirror_glass", {}, 32, 24, 4)[0]
+    want_first = gt.guide_truth(oracle, b, cam._c, pb)
+    r = spt.Renderer(0)
+    chain, first = spt.Guide(pb, 0, through_specular=True), spt.Guide(pb, 0)
+    try:
+        img0, st0, k0 = _frame(spt, r, a, cam, pa)
+        chain.render(r, b, cam, pb, 0, 1)
+        assert r.kernel() == k0 and {k: r.stats()[k] for k in st0} == st0
+        img1, st1, k1 = _frame(spt, r, a, cam, pa)
+        assert k1 == k0 and st1 == st0 and np.array_equal(img0, img1)
+        # the two kinds of guide filled alternately, window by window, on one context and stream
+        first.render(r, b, cam, pb, 0, 1)
+        for s in (1, 2, 3):
+            chain.render(r, b, cam, pb, s, 1)
+            first.render(r, b, cam, pb, s, 1)
+        _same(chain.to_numpy(), want_chain, "the chain guide")
+        _same(first.to_numpy(), want_first, "the first-hit guide")
+        assert (chain.info()["flags"], first.info()["flags"]) == (1, 0)
+    finally:
+        chain.close()
+        first.close()
+        r.close()
+
+
+# ---- 5. rejections ---------------------------------------------------------------------------------
+def test_rejected_calls_leave_out_and_the_guide_untouched(spt):
+    lib = spt.load_library()
+    p = spt.default_params(width=32, height=24, spp=8, seed=SEED)
+    for flags in (2, 3, 0x80000000):
+        out = ctypes.c_void_p(0x1234)
+        assert lib.spt_guide_create_ex(0, ctypes.byref(p), flags, ctypes.byref(out)) == 1
+        assert out.value == 0x1234
+    assert lib.spt_guide_create_ex(0, ctypes.byref(p), 1, None) == 1
+    assert lib.spt_guide_create_ex(0, None, 1, ctypes.byref(ctypes.c_void_p())) == 1
+    big = spt.default_params(width=4, height=4, spp=(1 << 24) + 1, seed=SEED)
+    with pytest.raises(spt.SptError):
+        spt.Guide(big, 0, through_specular=True)
+    # a chain guide refuses what a guide refuses, and stays as it was
+    prims = gct.scene(spt, "mirror_glass")
+    cam = spt.Camera(aspect=_aspect(32, 24))
+    p = _params(spt, "mirror_glass", 32, 24, 8)
+    r, g = spt.Renderer(0), spt.Guide(p, 0, through_specular=True)
+    try:
+        g.render(r, prims, cam, p, 0, 5)
+        before, info = g.to_numpy(), g.info()
+        for q, base, count in [(_params(spt, "mirror_glass", 31, 24, 8), 5, 1), (p, 7, 2), (p, 0, 4), (p, 5, 0)]:
+            with pytest.raises(spt.SptError) as e:
+                g.render(r, prims, cam, q, base, count)
+            assert e.value.status == 1 and g.info() == info and np.array_equal(g.to_numpy(), before)
+    finally:
+        g.close()
+        r.close()
+
+
+# ---- 6. the denoise path with a chain guide --------------------------------------------------------
+W, H, SPP, BATCH, GUIDE_SPP = 64, 48, 64, 8, 16
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _session(spt, seed, chain):
+    """-> (renderer, film, guide): mirror_glass 64x48, 64 spp in batches of 8, a guide of 16 samples."""
+    prims = gct.scene(spt, "mirror_glass")
+    p = spt.default_params(width=W, height=H, spp=SPP, seed=seed, nee_prob=0.0)
+    cam = spt.Camera(aspect=_aspect(W, H))
+    r, film, guide = spt.Renderer(0), spt.Film(p, 0), spt.Guide(p, 0, through_specular=chain)
+    film.enable_noise(BATCH)
+    for k in range(SPP // BATCH):
+        film.render(r, prims, cam, p, k * BATCH, BATCH)
+        r.stats()
+    guide.render(r, prims, cam, p, 0, GUIDE_SPP)
+    return r, film, guide
+
+
+def test_film_denoise_with_a_chain_guide_equals_the_separate_calls_and_the_host(spt):
+    r, film, guide = _session(spt, 5, True)
+    dn = spt.Denoiser(W, H, 0)
+    try:
+        fused, fused_se = dn.denoise_film(film, guide, return_se=True)
+        g = guide.resolve()
+        planes = [film.resolve(), film.noise_map(), g["albedo"], g["normal"], g["depth"]]
+        apart, apart_se = dn.denoise(*planes, return_se=True)
+        fi, ni, gi = film.info(), film.noise_info(), guide.info()
+        sums, m2 = film.to_numpy(), film.noise_to_numpy()
+        hg = spt.guide_resolve_host(guide.to_numpy(), gi["width"], gi["rows"], gi["spp_total"], gi["samples_done"])
+        host = [spt.film_resolve_host(sums, fi["width"], fi["rows"], fi["spp_total"], fi["samples_done"]),
+                spt.film_noise_map_host(sums, m2, fi["width"], fi["rows"], fi["spp_total"], fi["samples_done"],
+                                        ni["batch"], ni["batches_done"]), hg["albedo"], hg["normal"], hg["depth"]]
+        want, want_se = spt.denoise_host(*host, return_se=True)
+    finally:
+        dn.close()
+        guide.close()
+        film.close()
+        r.close()
+    assert gi["flags"] == 1
+    for a, b in ((fused, apart), (fused_se, apart_se), (fused, want), (fused_se, want_se)):
+        assert np.array_equal(bits(a), bits(b))
+    for a, b in zip(planes, host):
+        assert np.array_equal(bits(a), bits(b))
+
+
+# ---- 7. quality ------------------------------------------------------------------------------------
+QUALITY_SEEDS = (1, 2, 3, 4)
+# rmse(denoised) / rmse(noisy) over the pixels whose first hit is a SPEC or REFR primitive, chain
+# guides, against the 8192-spp truth; measured on an MI355X with the default parameters
+# (profiles/r24_guide_chain_denoise.json, "test_quality"); every value is bit-deterministic.
+MEASURED_SPEC_RATIO = {1: 0.627819, 2: 0.681918, 3: 0.683924, 4: 0.678310}
+_quality = {}
+
+
+def _quality_truth(spt):
+    if "img" not in _quality:
+        prims = gct.scene(spt, "mirror_glass")
+        cam = spt.Camera(aspect=_aspect(W, H))
+        p = spt.default_params(width=W, height=H, spp=8192, seed=77, nee_prob=0.0)
+        _quality["img"] = spt.render(prims, cam, p)
+        # the mask from a first-hit guide and the scene: with the specular primitives white and the
+        # others black (the same geometry, so the same hits) the albedo is the share of the samples
+        # whose first hit is specular; at least half of them
+        marker = [spt.spt_prim.from_buffer_copy(q) for q in prims]
+        for q in marker:
+            for k in range(3):
+                q.c[k] = 0.0 if q.refl == gct.DIFF else 1.0
+        q = spt.default_params(width=W, height=H, spp=64, seed=77, nee_prob=0.0)
+        _quality["mask"] = spt.render_guides(marker, cam, q)["albedo"][..., 0] >= 0.5
+    return _quality["img"], _quality["mask"]
+
+
+def _rmse(a, b):
+    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
+
+
+@pytest.mark.parametrize("seed", QUALITY_SEEDS)
+def test_denoised_with_chain_guides_is_closer_to_the_truth(spt, seed):
+    """mirror_glass at 64x48, 64 spp in batches of 8, a guide of 16 samples; the truth is the library's
+    own 8192-spp render with another seed. Hard conditions: the denoised RMSE is below the noisy one
+    and the image mean moves by at most 2 %. Pinned: over the pixels whose first hit is specular the
+    ratio with chain guides is at most the value measured on the GPU x 1.25 (the margin is for later
+    deliberate changes of the defaults). Whether chain guides beat first-hit guides there is printed,
+    not asserted. Measured, seeds 1..4, the 255 pixels of the mask: ratios with chain guides 0.627819,
+    0.681918, 0.683924, 0.678310, with first-hit guides 0.922947, 0.917509, 0.931047, 0.927889 (noisy
+    RMSE in the mask 0.1495, 0.1494, 0.1606, 0.1354). Whole frame: noisy 0.1475, 0.1451, 0.1458, 0.1479,
+    denoised with chain guides 0.0656, 0.0644, 0.0644, 0.0660, with first-hit guides 0.0713, 0.0683,
+    0.0703, 0.0700; the mean moved by 0.82, 0.81, 0.80 and 0.79 % (first-hit: 0.87, 0.92, 0.96, 0.75 %).
+    Both hard conditions hold with either kind of guide."""
+    truth, mask = _quality_truth(spt)
+    assert 0.02 < mask.mean() < 0.5
+    out = {}
+    for chain in (True, False):
+        r, film, guide = _session(spt, seed, chain)
+        dn = spt.Denoiser(W, H, 0)
+        try:
+            out[chain] = (film.resolve(), dn.denoise_film(film, guide))
+        finally:
+            dn.close()
+            guide.close()
+            film.close()
+            r.close()
+    noisy, den = out[True]
+    _, den_first = out[False]
+    e_noisy, e_den, e_first = _rmse(noisy, truth), _rmse(den, truth), _rmse(den_first, truth)
+    m_noisy, m_den, m_first = _rmse(noisy[mask], truth[mask]), _rmse(den[mask], truth[mask]), \
+        _rmse(den_first[mask], truth[mask])
+    shift = abs(float(den.mean(dtype=np.float64)) / float(noisy.mean(dtype=np.float64)) - 1.0)
+    shift_first = abs(float(den_first.mean(dtype=np.float64)) / float(noisy.mean(dtype=np.float64)) - 1.0)
+    print(f"seed {seed}: frame rmse noisy {e_noisy:.6f} chain {e_den:.6f} first-hit {e_first:.6f}; "
+          f"specular mask ({int(mask.sum())} px) noisy {m_noisy:.6f} chain {m_den:.6f} ratio "
+          f"{m_den / m_noisy:.6f} first-hit {m_first:.6f} ratio {m_first / m_noisy:.6f}; mean shift chain "
+          f"{shift:.6f} first-hit {shift_first:.6f}")
+    assert e_den < e_noisy
+    assert shift <= 0.02
+    assert m_den / m_noisy <= MEASURED_SPEC_RATIO[seed] * 1.25
+
+
+# ---- 8. the wrappers and the drop-in program -------------------------------------------------------
+def test_wrappers_and_the_dropin_program_equal_the_explicit_calls(spt, tmp_path):
+    prims = gct.scene(spt, "mirror_glass")
+    w, h, spp, seed = 32, 24, 16, 5
+    cam = spt.Camera(aspect=_aspect(w, h))
+    p = spt.default_params(width=w, height=h, spp=spp, seed=seed, nee_prob=0.0)
+    want = {}
+    for chain in (False, True):
+        r, g = spt.Renderer(0), spt.Guide(p, 0, through_specular=chain)
+        try:
+            g.render(r, prims, cam, p, 0, spp)
+            want[chain] = g.resolve()
+        finally:
+            g.close()
+            r.close()
+        got = spt.render_guides(prims, cam, p, through_specular=chain) if chain else spt.render_guides(prims, cam, p)
+        for k in spt.GUIDE_PLANES:
+            assert np.array_equal(bits(got[k]), bits(want[chain][k])), (chain, k)
+    assert not np.array_equal(want[True]["albedo"], want[False]["albedo"])
+    # render_denoised: the explicit calls with either kind of guide
+    den = {}
+    for chain in (False, True):
+        r, film, g = spt.Renderer(0), spt.Film(p, 0), spt.Guide(p, 0, through_specular=chain)
+        dn = spt.Denoiser(w, h, 0)
+        try:
+            film.enable_noise(2)
+            for k in range(spp // 2):
+                film.render(r, prims, cam, p, k * 2, 2)
+                r.stats()
+            g.render(r, prims, cam, p, 0, spp)
+            den[chain] = dn.denoise_film(film, g)
+        finally:
+            dn.close()
+            g.close()
+            film.close()
+            r.close()
+    assert np.array_equal(bits(spt.render_denoised(prims, cam, p)), bits(den[False]))
+    assert np.array_equal(bits(spt.render_denoised(prims, cam, p, through_specular=True)), bits(den[True]))
+    assert not np.array_equal(den[True], den[False])
+    # the drop-in program
+    base = [EXE, str(w), str(h), str(spp), str(seed)]
+    files = {}
+    for chain in (False, True):
+        img, prefix = tmp_path / f"i{int(chain)}.ppm", str(tmp_path / f"g{int(chain)}")
+        run = subprocess.run(base + [str(img), "--mirror-glass", "--guides", prefix] +
+                             (["--through-specular"] if chain else []), capture_output=True, text=True, timeout=120)
+        assert run.returncode == 0, run.stdout + run.stderr
+        files[chain] = img.read_bytes()
+        for k in ("albedo", "normal"):
+            assert np.array_equal(bits(_read_pfm(prefix + f"_{k}.pfm")), bits(want[chain][k])), (chain, k)
+        depth = _read_pfm(prefix + "_depth.pfm")
+        assert np.array_equal(bits(depth[..., 0]), bits(want[chain]["depth"])), chain
+    assert files[True] == files[False]  # the image does not know the guide's kind
+    for chain in (False, True):
+        out = tmp_path / f"d{int(chain)}.pfm"
+        run = subprocess.run(base + [str(out), "--mirror-glass", "--pfm", "--denoise"] +
+                             (["--through-specular"] if chain else []), capture_output=True, text=True, timeout=120)
+        assert run.returncode == 0, run.stdout + run.stderr
+        raw = out.read_bytes()
+        data = np.frombuffer(raw[len(raw) - w * h * 12:], dtype="<f4").reshape(h, w, 3)[::-1]
+        assert np.array_equal(bits(data), bits(den[chain])), chain
+
+
+def test_dropin_through_specular_alone_is_a_usage_error(spt, tmp_path):
+    """(No GPU work: the program refuses before it renders.)"""
+    run = subprocess.run([EXE, "16", "12", "4", "1", str(tmp_path / "x.ppm"), "--through-specular"],
+                         capture_output=True, text=True, timeout=60)
+    assert run.returncode != 0 and "--through-specular" in run.stderr
+    assert not (tmp_path / "x.ppm").exists()
+    assert "--through-specular" in subprocess.run([EXE, "--help"], capture_output=True, text=True, timeout=60).stdout

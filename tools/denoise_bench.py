@@ -15,6 +15,15 @@ forms of one step alternating round by round (the plain-load form against the LD
 build has one).
 Quality: the HEAD scene at 256x192, 16 seeds at 64, 256 and 1024 spp in 8 batches with a guide of 64
 samples, against the library's own 65536-spp render merged from 16 seeds of 4096.
+
+--chain (python tools/denoise_bench.py --chain [OUT.json], default build/guide_chain_denoise.json):
+instead of the above, the quality by region on the scenes with specular primitives (mirror_glass,
+cornell_specular), same protocol, first-hit guides against guides of the specular chain
+(SPT_GUIDE_THROUGH_SPECULAR): the RMSE of the clamped image over the whole frame, over the pixels whose
+first hit is a SPEC or REFR primitive (at least half of the 64 samples of a first-hit guide of the
+scene with the specular primitives white and the rest black), over the band within 2 pixels of that
+set, and over the rest; the image-mean shift and se_out^2 / true err^2. And the configuration that
+tests/test_gpu_guide_chain.py pins.
 """
 import importlib
 import json
@@ -220,7 +229,131 @@ def quality(spt, w=256, h=192, seeds=16, spps=(64, 256, 1024)):
     return res
 
 
+def specular_masks(spt, prims, cam, w, h, seed=1000, **kw):
+    """-> {"specular", "band", "rest"}: boolean (h, w) masks from a first-hit guide of the scene with
+    its specular primitives white and the others black (the same geometry, so the same hits)."""
+    marker = [spt.spt_prim.from_buffer_copy(q) for q in prims]
+    for q in marker:
+        for k in range(3):
+            q.c[k] = 0.0 if q.refl == spt.DIFF else 1.0
+    p = spt.default_params(width=w, height=h, spp=64, seed=seed, **kw)
+    spec = spt.render_guides(marker, cam, p)["albedo"][..., 0] >= 0.5
+    near = np.zeros_like(spec)
+    pad = np.pad(spec, 2)
+    for dy in range(5):
+        for dx in range(5):
+            near |= pad[dy:dy + h, dx:dx + w]
+    band = near & ~spec
+    return {"specular": spec, "band": band, "rest": ~near}
+
+
+def _film_and_guides(spt, prims, cam, p, batch, guide_spp):
+    """-> (noisy, {chain: (denoised, se_out)}) of one film denoised with either kind of guide."""
+    r, film, dn = spt.Renderer(0), spt.Film(p, 0), spt.Denoiser(p.width, p.height, 0)
+    guides = {c: spt.Guide(p, 0, through_specular=c) for c in (False, True)}
+    try:
+        film.enable_noise(batch)
+        for k in range(p.spp // batch):
+            film.render(r, prims, cam, p, k * batch, batch)
+            r.stats()
+        out = {}
+        for c, g in guides.items():
+            g.render(r, prims, cam, p, 0, min(p.spp, guide_spp))
+            out[c] = dn.denoise_film(film, g, return_se=True)
+        return film.resolve(), out
+    finally:
+        for o in (dn, film, r, *guides.values()):
+            o.close()
+
+
+CHAIN_SCENES = {"mirror_glass": ("smallpt_mirror_glass_scene", dict(nee_prob=0.0)),
+                "cornell_specular": ("cornell_specular_scene", {})}
+
+
+def chain_quality(spt, name, w=256, h=192, seeds=16, spps=(64, 256, 1024)):
+    prims = getattr(spt, CHAIN_SCENES[name][0])()
+    kw = CHAIN_SCENES[name][1]
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = np.zeros((h, w, 3), np.float64)
+    for s in range(16):
+        truth += spt.render(prims, cam, spt.default_params(width=w, height=h, spp=4096, seed=1000 + s, **kw))
+    truth = (truth / 16).astype(np.float32)
+    masks = specular_masks(spt, prims, cam, w, h, **kw)
+    masks["frame"] = np.ones((h, w), bool)
+    res = {"scene": name, "width": w, "height": h, "seeds": seeds, "truth": "16 seeds x 4096 spp",
+           "guide_spp": 64, "pixels": {k: int(m.sum()) for k, m in masks.items()}, "by_spp": {}}
+    for spp in spps:
+        rows = {k: {"noisy": [], "first_hit": [], "chain": []} for k in masks}
+        extra = {g: {"mean_change": [], "se2_over_err2": []} for g in ("first_hit", "chain")}
+        for seed in range(1, seeds + 1):
+            p = spt.default_params(width=w, height=h, spp=spp, seed=seed, **kw)
+            noisy, out = _film_and_guides(spt, prims, cam, p, spp // 8, 64)
+            for k, m in masks.items():
+                rows[k]["noisy"].append(rmse(noisy[m], truth[m]))
+                rows[k]["first_hit"].append(rmse(out[False][0][m], truth[m]))
+                rows[k]["chain"].append(rmse(out[True][0][m], truth[m]))
+            for g, c in (("first_hit", False), ("chain", True)):
+                den, se = out[c]
+                extra[g]["mean_change"].append(float(den.mean(dtype=np.float64) / noisy.mean(dtype=np.float64) - 1.0))
+                extra[g]["se2_over_err2"].append(float(np.mean(se.astype(np.float64) ** 2) /
+                                                       np.mean((den.astype(np.float64) - truth) ** 2)))
+        one = {"regions": {}}
+        for k in masks:
+            n, f, c = (float(np.mean(rows[k][x])) for x in ("noisy", "first_hit", "chain"))
+            one["regions"][k] = {"rmse_noisy": n, "rmse_first_hit": f, "rmse_chain": c,
+                                 "ratio_first_hit": f / n, "ratio_chain": c / n, "chain_over_first_hit": c / f,
+                                 "seeds_where_chain_is_better": int(sum(a < b for a, b in zip(rows[k]["chain"],
+                                                                                              rows[k]["first_hit"])))}
+        for g in extra:
+            one[g] = {"mean_change": float(np.mean(extra[g]["mean_change"])),
+                      "mean_se_out2_over_true_err2": float(np.mean(extra[g]["se2_over_err2"]))}
+        res["by_spp"][str(spp)] = one
+    return res
+
+
+def chain_test_quality(spt):
+    """The configuration tests/test_gpu_guide_chain.py pins: mirror_glass 64x48, 64 spp in batches of
+    8, guides of 16 samples, seeds 1..4, the truth 8192 spp with seed 77; the default parameters."""
+    w, h = 64, 48
+    prims = spt.smallpt_mirror_glass_scene()
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = spt.render(prims, cam, spt.default_params(width=w, height=h, spp=8192, seed=77, nee_prob=0.0))
+    m = specular_masks(spt, prims, cam, w, h, seed=77, nee_prob=0.0)["specular"]
+    seeds = {}
+    for seed in (1, 2, 3, 4):
+        p = spt.default_params(width=w, height=h, spp=64, seed=seed, nee_prob=0.0)
+        noisy, out = _film_and_guides(spt, prims, cam, p, 8, 16)
+        row = {"rmse_noisy": rmse(noisy, truth), "mask_rmse_noisy": rmse(noisy[m], truth[m])}
+        for g, c in (("first_hit", False), ("chain", True)):
+            den = out[c][0]
+            row[g] = {"rmse": rmse(den, truth), "mask_rmse": rmse(den[m], truth[m]),
+                      "mask_ratio": rmse(den[m], truth[m]) / rmse(noisy[m], truth[m]),
+                      "mean_shift": abs(float(den.mean(dtype=np.float64) / noisy.mean(dtype=np.float64)) - 1.0)}
+        seeds[str(seed)] = row
+    return {"what": "tests/test_gpu_guide_chain.py::test_denoised_with_chain_guides_is_closer_to_the_truth",
+            "mask_pixels": int(m.sum()), "seeds": seeds}
+
+
+def main_chain(out):
+    import torch
+    spt = importlib.import_module("small-pathtracer_amd")
+    spt.load_library()
+    assert torch.cuda.is_available(), "denoise_bench needs the GPU"
+    rec = {"kernel_sources_sha16": spt.build_sources_sha16(), "device": torch.cuda.get_device_name(0),
+           "utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime())}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    rec["test_quality"] = chain_test_quality(spt)
+    json.dump(rec, open(out, "w"), indent=1)
+    rec["quality"] = {}
+    for name in CHAIN_SCENES:
+        rec["quality"][name] = chain_quality(spt, name)
+        json.dump(rec, open(out, "w"), indent=1)  # what is measured survives a failure further on
+        print(name, json.dumps({s: v["regions"] for s, v in rec["quality"][name]["by_spp"].items()}), flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--chain":
+        return main_chain(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "guide_chain_denoise.json"))
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "r19_denoise.json")
     import torch
     spt = importlib.import_module("small-pathtracer_amd")

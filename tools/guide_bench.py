@@ -11,7 +11,16 @@ events on the stream, a warm-up first and the median of --reps:
 
 A short pass is timed as --inner passes between the two events (each a clear and a launch).
 
+--chain (SPT_HAS_GUIDE_CHAIN): instead of the above, a chain guide pass (SPT_GUIDE_THROUGH_SPECULAR)
+beside a first-hit pass, alternating in one process, at 1024x768 on the two specular scenes
+(mirror_glass and cornell_specular @ 64 spp) and at C3's shape (HEAD has no specular primitive: the
+chain pass does the same traces), 20 runs after 5 warm-ups, medians with min-max, and the ratio. With
+--parent-tree DIR (a built checkout of the parent commit) the first-hit pass of this tree and of the
+parent's library are timed in alternating child processes, --rounds of them each, to show that the
+first-hit pass did not move: the parent is the yardstick, never this build against itself.
+
 usage: python tools/guide_bench.py [--reps N --inner M --out FILE.json]
+       python tools/guide_bench.py --chain [--parent-tree DIR --rounds R] [--out FILE.json]
 """
 import argparse
 import ctypes
@@ -120,15 +129,130 @@ def _sweep(reps, inner):
     print("SWEEP " + json.dumps(out))
 
 
+CHAIN_SHAPES = [("mirror_glass", 1024, 768, 64, dict(nee_prob=0.0)), ("cornell_specular", 1024, 768, 64, {}),
+                ("c3_head", 1024, 768, 512, {})]
+CHAIN_RUNS, CHAIN_WARM = 20, 5
+
+
+def _scene_of(spt, name):
+    return {"mirror_glass": spt.smallpt_mirror_glass_scene, "cornell_specular": spt.cornell_specular_scene,
+            "c3_head": spt.cornell_scene}[name]()
+
+
+def _stat(ms):
+    return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
+
+
+def _pass_ms(torch, g, r, prims, cam, p, stream):
+    g.clear(stream)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    g.render(r, prims, cam, p, 0, p.spp, stream)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def _chain_pairs(spt, torch):
+    """A chain pass and a first-hit pass of the same arguments, alternating in this process."""
+    out = {}
+    for name, w, h, spp, kw in CHAIN_SHAPES:
+        prims = _scene_of(spt, name)
+        p = spt.default_params(width=w, height=h, spp=spp, seed=1, device=0, **kw)
+        cam = spt.Camera(aspect=w / h)
+        r = spt.Renderer(0)
+        first, chain = spt.Guide(p, 0), spt.Guide(p, 0, through_specular=True)
+        stream = torch.cuda.current_stream().cuda_stream
+        ms = {"first_hit": [], "chain": []}
+        for i in range(CHAIN_WARM + CHAIN_RUNS):
+            for key, g in (("first_hit", first), ("chain", chain)):
+                t = _pass_ms(torch, g, r, prims, cam, p, stream)
+                if i >= CHAIN_WARM:
+                    ms[key].append(t)
+        hits = {k: int(g.to_numpy()[..., 7].sum()) for k, g in (("first_hit", first), ("chain", chain))}
+        out[name] = {"width": w, "height": h, "spp": spp, "first_hit_ms": _stat(ms["first_hit"]),
+                     "chain_ms": _stat(ms["chain"]), "lanes_per_pixel": first.info()["lanes_per_pixel"],
+                     "chain_over_first_hit": round(statistics.median(ms["chain"]) /
+                                                   statistics.median(ms["first_hit"]), 4),
+                     "hits": hits}
+        first.close()
+        chain.close()
+        r.close()
+    return out
+
+
+def _first_hit_child(tree):
+    """One child's work: the first-hit pass of the package under `tree` at every shape."""
+    sys.path.insert(0, tree)
+    import torch
+    spt = importlib.import_module("small-pathtracer_amd")
+    assert os.path.abspath(spt.LIB_PATH).startswith(os.path.abspath(tree)), spt.LIB_PATH
+    out = {"kernel_sources_sha16": spt.build_sources_sha16()}
+    for name, w, h, spp, kw in CHAIN_SHAPES:
+        prims = _scene_of(spt, name)
+        p = spt.default_params(width=w, height=h, spp=spp, seed=1, device=0, **kw)
+        cam = spt.Camera(aspect=w / h)
+        r, g = spt.Renderer(0), spt.Guide(p, 0)
+        stream = torch.cuda.current_stream().cuda_stream
+        ms = [_pass_ms(torch, g, r, prims, cam, p, stream) for _ in range(CHAIN_WARM + CHAIN_RUNS)][CHAIN_WARM:]
+        out[name] = ms
+        g.close()
+        r.close()
+    print("FIRSTHIT " + json.dumps(out))
+
+
+def _against_parent(parent_tree, rounds):
+    """This tree's first-hit pass and the parent's, in alternating child processes."""
+    runs = {"here": [], "parent": []}
+    for _ in range(rounds):
+        for key, tree in (("here", ROOT), ("parent", os.path.abspath(parent_tree))):
+            env = {k: v for k, v in os.environ.items() if k != "SPT_LIB"}
+            c = subprocess.run([sys.executable, os.path.abspath(__file__), "--first-hit-child", tree],
+                               env=env, capture_output=True, text=True, timeout=300)
+            line = [ln for ln in c.stdout.splitlines() if ln.startswith("FIRSTHIT ")]
+            if c.returncode != 0 or not line:
+                raise SystemExit(f"the {key} child failed:\n" + c.stdout[-2000:] + c.stderr[-2000:])
+            runs[key].append(json.loads(line[0][9:]))
+    out = {"rounds": rounds, "sha16": {k: v[0]["kernel_sources_sha16"] for k, v in runs.items()}}
+    for name, *_ in CHAIN_SHAPES:
+        here = [statistics.median(x[name]) for x in runs["here"]]
+        par = [statistics.median(x[name]) for x in runs["parent"]]
+        out[name] = {"here_ms": _stat(here), "parent_ms": _stat(par), "per_round_here": [round(v, 4) for v in here],
+                     "per_round_parent": [round(v, 4) for v in par],
+                     "here_over_parent": round(statistics.median(here) / statistics.median(par), 4)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--sweep-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--chain", action="store_true", help="chain guide passes beside first-hit passes")
+    ap.add_argument("--parent-tree", default="", help="with --chain: a built checkout of the parent commit")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--first-hit-child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.sweep_child:
         return _sweep(args.reps, args.inner)
+    if args.first_hit_child:
+        return _first_hit_child(args.first_hit_child)
+    if args.chain:
+        res = {"config": {"runs": CHAIN_RUNS, "warm_ups": CHAIN_WARM}}
+        # the children first: this process has not opened the GPU yet
+        res["first_hit_against_parent"] = (_against_parent(args.parent_tree, args.rounds) if args.parent_tree
+                                           else "not measured: no --parent-tree")
+        import torch
+        spt = importlib.import_module("small-pathtracer_amd")
+        res["kernel_sources_sha16"] = spt.build_sources_sha16()
+        res["chain_beside_first_hit"] = _chain_pairs(spt, torch)
+        print(json.dumps(res))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
     res = {"config": {"reps": args.reps, "inner": args.inner}}
     # the K sweep first, in its own process with the bench library (this one has not opened the GPU yet)
     if os.path.exists(BENCH_LIB):
