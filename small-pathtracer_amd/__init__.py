@@ -360,8 +360,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
 # The sources the render kernel is compiled from: their hash identifies a kernel build, so a PMC
 # profile committed under profiles/ can say which kernel it measured (bench.py omits hardware-counter
 # figures whose profile was taken on other sources).
-KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_variants.h", "csrc/spt_kparams.h", "csrc/spt_launch.h",
-                  "csrc/spt_dispatch.cpp", "csrc/spt_context.cpp",
+KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_trace.h", "csrc/spt_variants.h", "csrc/spt_kparams.h",
+                  "csrc/spt_launch.h", "csrc/spt_dispatch.cpp", "csrc/spt_context.cpp",
                   "csrc/spt_device.h", "csrc/spt_cornell.h", "csrc/spt_diag.h", "csrc/Makefile", "../include/spt.h", "../include/spt_flops.h", "csrc/spt_film.hip",
                   "csrc/spt_film.h", "csrc/spt_film_math.h", "csrc/spt_film_host.cpp",
                   "csrc/spt_guide.hip", "csrc/spt_guide_host.cpp", "csrc/spt_guide.h",

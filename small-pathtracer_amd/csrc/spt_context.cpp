@@ -1,7 +1,7 @@
 // spt_context.cpp — the render path's HIP runtime calls: contexts (create / reserve / destroy), one
 // launch over a sample window (spt_render_window), the statistics, and the one-shot drop-in
 // (spt_render). What to launch and how it is sized is decided in spt_dispatch.cpp; the kernels and
-// their launchers are spt_kernel.hip (spt_launch.h).
+// their launchers are spt_kernel.hip (the render) and spt_guide.hip (the guide), through spt_launch.h.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>

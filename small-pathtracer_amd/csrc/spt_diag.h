@@ -10,7 +10,7 @@
 //   -DSPT_DIAG=4  SPT_PROBE_VALU: SPT_PROBE_N extra VALU per wave-iteration (the same for vector work)
 // Tuning constants with an A/B history (SPT_STEAL_MIN, SPT_GRAB, SPT_SMALL_ITERS, SPT_SMALL_UNITS,
 // SPT_UNITS_PER_LANE, SPT_NUM_SGPR) are plain numbers with their measured defaults in
-// spt_kparams.h (SPT_NUM_SGPR: spt_kernel.hip).
+// spt_kparams.h (SPT_NUM_SGPR: spt_trace.h).
 #pragma once
 #ifndef SPT_PROBE_N
 #define SPT_PROBE_N 24

@@ -1,14 +1,245 @@
-// spt_guide.hip — the guide planes (include/spt.h, SPT_HAS_GUIDE): the object that holds a guide's
-// integer records on the device, the resolve kernel and the spt_guide_* calls. The kernel that fills
-// the records is guide_kernel (spt_kernel.hip), launched through the context (spt_context.cpp,
-// spt_guide_window); the resolve's arithmetic is spt_guide.h's, shared with the CPU statement
-// (spt_guide_host.cpp).
+// spt_guide.hip — the guide planes (include/spt.h, SPT_HAS_GUIDE), device and host: guide_kernel, which
+// fills a guide's integer records with the render's own trace (spt_trace.h), and its two launchers
+// (spt_launch.h; the context launches it, spt_context.cpp spt_guide_window); then the object that holds
+// the records on the device, the resolve kernel and the spt_guide_* calls. The resolve's arithmetic is
+// spt_guide.h's, shared with the CPU statement (spt_guide_host.cpp).
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "../../include/spt.h"
 #include "spt_guide.h"
+#include "spt_launch.h"
+#include "spt_trace.h"
+
+namespace spt {
+
+// ---- The guide kernel: the render's own first ray of every sample of the window, stopped at its
+// first vertex. Per hit sample the pixel's record int64[8] takes the hit primitive's colour in the
+// render's 1.31 fixed point (fix31), the oriented normal as sgn * fix31(|n|), the ray parameter in
+// 48.16 and a hit count; a miss adds nothing.
+// Every (pixel, sample) costs the same -- one Philox call, one trace -- so there is no queue and no
+// stealing: K = 2^guide_kshift lanes of one wave share local pixel lp = global lane >> kshift, lane l
+// of the group takes samples s_base + l, + K, ..., the eight partial sums are reduced over the group
+// with an xor butterfly of cross-lane moves (no LDS memory), and the group's first lane does the
+// read-add-write of the record. Within a launch a pixel belongs to one group and launches on one guide
+// are ordered by the caller's stream, so no atomics. The integers make the sums independent of K,
+// the window split and the shard.
+// The camera ray is the general form of contract v5 with P_c per pixel (render_kernel's CAMAX 2
+// arithmetic: the same bits as the inline general form, oracle c_path).
+//
+// The three functions below restate blocks of render_kernel (spt_kernel.hip) operation for operation,
+// and those blocks cite them back. They are not one function with the render's: every attempt to share
+// one moved render_kernel's listings (the sphere variants by up to 17 lines, the generic and wide ones
+// by 15 to 17, the wide one sitting at its 80-VGPR limit), and a pull request that leaves the render
+// kernels' machine code alone cannot afford that. tools/isa_same.py is the check that it stayed so.
+__device__ __forceinline__ long long shfl_xor64(long long v, int m) {
+  const int lo = __shfl_xor((int)(uint32_t)(unsigned long long)v, m, 64);
+  const int hi = __shfl_xor((int)(uint32_t)((unsigned long long)v >> 32), m, 64);
+  return (long long)(((unsigned long long)(uint32_t)hi << 32) | (unsigned long long)(uint32_t)lo);
+}
+
+// The vertex frame of a hit on H at the trace's t along (o, d): the hit point x, the geometric normal
+// gn and the normal nl oriented against the ray. render_kernel's generic shading branch ("plane
+// distance as the reference derives it" and "Hitable::normal, oriented against the ray"): a
+// rectangle's t corrected (hit_plane_t) for x, a sphere's gn as (x - p) * (1/r).
+// POINT: the caller goes on from x (the chain). Without it only a sphere's normal reads x, and x is
+// formed there alone, from the sphere's own t: the same bits, and a rectangle's hit point is not formed
+// at all (formed for every kind, the first-hit pass took 3 to 4 % longer than the two-branch kernel's:
+// profiles/r25_guide_bench.json).
+struct GuideVertex { f3 x, gn, nl; };
+template <bool POINT>
+__device__ __forceinline__ GuideVertex guide_vertex(const DevPrim& H, f3 o, f3 d, float ia, float t) {
+  GuideVertex V;
+  V.x = mk(0, 0, 0);
+  if constexpr (POINT) {
+    float tr = t;
+    if (H.kind == SPT_RECT_XY) tr = hit_plane_t(H.w1 - o.z, d.z, ia, t);
+    else if (H.kind == SPT_RECT_XZ) tr = hit_plane_t(H.w1 - o.y, d.y, ia, t);
+    else if (H.kind == SPT_RECT_YZ) tr = hit_plane_t(H.w1 - o.x, d.x, ia, t);
+    V.x = mk(o.x + d.x * tr, o.y + d.y * tr, o.z + d.z * tr);
+  }
+  if (H.kind == SPT_RECT_XY) {
+    V.nl = d.z < 0.0f ? mk(0, 0, 1) : mk(0, 0, -1);
+    V.gn = mk(0, 0, 1);
+  } else if (H.kind == SPT_RECT_XZ) {
+    V.nl = d.y < 0.0f ? mk(0, 1, 0) : mk(0, -1, 0);
+    V.gn = mk(0, 1, 0);
+  } else if (H.kind == SPT_RECT_YZ) {
+    V.nl = d.x < 0.0f ? mk(1, 0, 0) : mk(-1, 0, 0);
+    V.gn = mk(1, 0, 0);
+  } else {
+    if constexpr (!POINT) V.x = mk(o.x + d.x * t, o.y + d.y * t, o.z + d.z * t);
+    V.gn = mk((V.x.x - H.w1) * H.w5, (V.x.y - H.w2) * H.w5, (V.x.z - H.w3) * H.w5);
+    V.nl = dot3(V.gn, d) < 0.0f ? V.gn : mk(-V.gn.x, -V.gn.y, -V.gn.z);
+  }
+  return V;
+}
+
+// One lane's partial sums of its pixel's record, and the eight adds of one hit sample (include/spt.h,
+// the record's layout): colour c and |nl| through the render's fix31 with the launch's scale, as
+// render_kernel's path end accumulates a sample's radiance; the depth in 48.16, capped at 2^20.
+struct GuideSums { long long a0 = 0, a1 = 0, a2 = 0, n0 = 0, n1 = 0, n2 = 0, dsum = 0, hits = 0; };
+__device__ __forceinline__ void guide_record_add(GuideSums& S, f3 c, f3 nl, float depth, float scale) {
+  S.a0 += (long long)fix31(c.x, scale);
+  S.a1 += (long long)fix31(c.y, scale);
+  S.a2 += (long long)fix31(c.z, scale);
+  const long long m0 = (long long)fix31(fabsf(nl.x), scale), m1 = (long long)fix31(fabsf(nl.y), scale);
+  const long long m2 = (long long)fix31(fabsf(nl.z), scale);
+  S.n0 += nl.x < 0.0f ? -m0 : m0;
+  S.n1 += nl.y < 0.0f ? -m1 : m1;
+  S.n2 += nl.z < 0.0f ? -m2 : m2;
+  S.dsum += (long long)(unsigned long long)(fminf(depth, 0x1p20f) * 65536.0f);
+  S.hits += 1;
+}
+
+// The chain guide's step at a SPEC or REFR hit (include/spt.h, SPT_HAS_GUIDE_CHAIN): the throughput
+// takes the primitive's colour, the length the segment's t, and (o, d) become the ray the render's path
+// takes from here -- render_kernel's block "SPEC :481-482 and REFR :484-495" (oracle c_path), with the
+// refraction wherever there is one (no Fresnel draw) and the reflection on total internal reflection.
+__device__ __forceinline__ void guide_chain_step(const DevPrim& H, bool unit, f3 x, f3 gn, f3 nl, float t,
+                                                 f3& A, float& D, f3& o, f3& d) {
+  A = mk(A.x * H.cx, A.y * H.cy, A.z * H.cz);
+  D = D + t;
+  const float k2 = 2.0f * dot3(gn, d);
+  f3 nd = mk(d.x - gn.x * k2, d.y - gn.y * k2, d.z - gn.z * k2);  // reflRay
+  if (unit) nd = normalize3(nd);
+  if (H.refl == SPT_REFR) {
+    const bool into = dot3(gn, nl) > 0.0f;
+    const float nnt = into ? 1.0f / 1.5f : 1.5f / 1.0f;
+    const float ddn = dot3(d, nl);
+    const float cos2t = 1.0f - nnt * nnt * (1.0f - ddn * ddn);
+    if (!(cos2t < 0.0f)) {  // else total internal reflection: the reflection above
+      const float kk = (into ? 1.0f : -1.0f) * (ddn * nnt + sqrtf(cos2t));
+      nd = normalize3(mk(d.x * nnt - gn.x * kk, d.y * nnt - gn.y * kk, d.z * nnt - gn.z * kk));
+    }
+  }
+  o = x;
+  d = nd;
+}
+
+// One body for both kinds of record. A sample's ray is followed for at most kSegs segments and its
+// record taken at the first DIFF hit or at the last segment, whatever is hit there; a miss on any
+// segment adds nothing. CHAIN (spt_guide_create_ex with SPT_GUIDE_THROUGH_SPECULAR): kSegs is
+// SPT_GUIDE_MAX_CHAIN, the ray goes on through SPEC and REFR primitives, and the lanes of a group
+// differ in their trace counts (the reduction does not change). Without it kSegs is 1: the first-hit
+// record is the chain record of one segment, colour 1 * c (exact) and depth t.
+template <class TP, bool CHAIN>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SPT_NUM_SGPR)))
+guide_kernel(const KParams* __restrict__ Pg) {
+  static_assert(!TP::CONSTGEO && TP::MAT && TP::SPH, "the guide kernel runs the run-time topologies");
+  constexpr int kSegs = CHAIN ? SPT_GUIDE_MAX_CHAIN : 1;
+  __shared__ DevPrim s_prims[kMaxPrims];
+  __shared__ int s_pos2idx[kMaxPrims];  // grouped position -> primitive index
+  __shared__ GeoTest s_test[TP::WIDE ? 1 : kMaxPrims];
+  {  // the block's staging: render_kernel's for the run-time topologies, pasted (see above)
+    const SPT_CONST KParams* P = cptr(Pg);
+    const SPT_CONST SceneGeo* G = cptr(P->geo);
+    const int nrect = G->n_xy + G->n_xz + G->n_yz;
+    for (int i = threadIdx.x; i < P->n_prims; i += kBlock) {
+      s_prims[i] = P->prims[i];
+      s_pos2idx[i] = i < nrect ? G->rect[i].idx : G->sph[i - nrect].idx;
+      if (!TP::WIDE && i < G->n_txy + G->n_txz + G->n_tyz + 3 * G->has_room + 3 * G->n_box) {
+        const SPT_CONST GeoTest& q = G->test[i];
+        s_test[i] = GeoTest{q.k0, q.k1, q.ma, q.ha, q.mb, q.hb, q.pos0, q.pos1};
+      }
+    }
+  }
+  __syncthreads();
+
+  const SPT_CONST KParams* P = cptr(Pg);
+  const uint32_t ksh = P->guide_kshift, K = 1u << ksh;
+  const uint32_t gl = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  const uint32_t lp = gl >> ksh, l = gl & (K - 1u);
+  const bool live = lp < (uint32_t)P->n_local_pix;  // (a group is live or not as a whole)
+  GuideSums S;
+  if (live) {
+    PxKey pk;
+    float fx, fy;
+    pixel_terms<false>(P, lp, pk, fx, fy);
+    const f3 cam = mk(P->cam[0], P->cam[1], P->cam[2]);
+    const float px = fmaf(P->cam_au[0], fx, fmaf(P->cam_av[0], fy, P->cam_l[0]));
+    const float py = fmaf(P->cam_au[1], fx, fmaf(P->cam_av[1], fy, P->cam_l[1]));
+    const float pz = fmaf(P->cam_au[2], fx, fmaf(P->cam_av[2], fy, P->cam_l[2]));
+    const bool unit = unit_dirs_of<TP>(Pg);
+    const float scale = P->fix_scale;
+    const uint32_t s_lim = P->s_lim;
+    for (uint32_t s = P->s_base + l; s < s_lim; s += K) {
+      const SPT_CONST KParams* C = cptr(Pg);  // re-issued scalar loads, not long-lived SGPRs
+      const u4 r = philox_px(pk, s, 1u);
+      const float Fu = jitter_f(r.x, r.y), Fv = jitter_f(r.z, r.w);
+      const f3 v = mk(fmaf(Fv, C->cam_cv[0], fmaf(Fu, C->cam_cu[0], px)),
+                      fmaf(Fv, C->cam_cv[1], fmaf(Fu, C->cam_cu[1], py)),
+                      fmaf(Fv, C->cam_cv[2], fmaf(Fu, C->cam_cu[2], pz)));
+      f3 o = cam, d = normalize_dir(v, unit);
+      f3 A = mk(1.0f, 1.0f, 1.0f);  // the chain's throughput and length so far
+      float D = 0.0f;
+      for (int seg = 0; seg < kSegs; ++seg) {
+        // re-issued per trace, as C is per sample; the first-hit pass's one trace reads it through C,
+        // with the sample's camera loads (one wait fewer per sample: the two-branch kernel's form)
+        const SPT_CONST SceneGeo* G = cptr((CHAIN ? cptr(Pg) : C)->geo);
+        int id = 0, hpos;
+        float ia_hit = 0.0f;
+        f3 inv;
+        if (!intersect_scene<TP>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph, s_pos2idx, o, d, id,
+                                 ia_hit, hpos, inv))
+          break;
+        const DevPrim& H = s_prims[id];
+        const float t = hit_t<TP>(H, hpos, o, d, ia_hit, G);  // the winner's exact t
+        const GuideVertex V = guide_vertex<CHAIN>(H, o, d, ia_hit, t);
+        if (H.refl == SPT_DIFF || seg == kSegs - 1) {
+          guide_record_add(S, mk(A.x * H.cx, A.y * H.cy, A.z * H.cz), V.nl, CHAIN ? D + t : t, scale);
+          break;
+        }
+        guide_chain_step(H, unit, V.x, V.gn, V.nl, t, A, D, o, d);
+      }
+    }
+  }
+  // the group's sums: every lane of the wave takes part (a dead group's lanes hold zeros)
+  for (uint32_t m = 1; m < K; m <<= 1) {
+    S.a0 += shfl_xor64(S.a0, (int)m);
+    S.a1 += shfl_xor64(S.a1, (int)m);
+    S.a2 += shfl_xor64(S.a2, (int)m);
+    S.n0 += shfl_xor64(S.n0, (int)m);
+    S.n1 += shfl_xor64(S.n1, (int)m);
+    S.n2 += shfl_xor64(S.n2, (int)m);
+    S.dsum += shfl_xor64(S.dsum, (int)m);
+    S.hits += shfl_xor64(S.hits, (int)m);
+  }
+  if (live && l == 0) {
+    long long* rec = cptr(Pg)->guide_rec + 8ull * lp;
+    rec[0] += S.a0;
+    rec[1] += S.a1;
+    rec[2] += S.a2;
+    rec[3] += S.n0;
+    rec[4] += S.n1;
+    rec[5] += S.n2;
+    rec[6] += S.dsum;
+    rec[7] += S.hits;
+  }
+}
+
+// ---- The launchers (spt_launch.h)
+using GuideFn = void (*)(const KParams*);
+static GuideFn guide_fn(bool wide, bool chain) {
+  if (chain) return wide ? guide_kernel<TopoGenericWide, true> : guide_kernel<TopoGeneric, true>;
+  return wide ? guide_kernel<TopoGenericWide, false> : guide_kernel<TopoGeneric, false>;
+}
+
+int guide_kernel_occupancy(bool wide, bool chain) {
+  int bpc = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, guide_fn(wide, chain), kBlock, 0) != hipSuccess)
+    return 0;
+  return bpc;
+}
+
+void launch_guide_kernel(bool wide, bool chain, int grid, const KParams* kp_dev, void* stream) {
+  hipLaunchKernelGGL(guide_fn(wide, chain), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, kp_dev);
+}
+
+}  // namespace spt
+
+// ---- The guide object, the resolve and the spt_guide_* calls
 
 struct spt_guide {
   int device = 0;
@@ -27,7 +258,7 @@ void spt_set_last_error(const std::string& msg);
 
 namespace {
 
-constexpr int kBlock = 256;
+using spt::kBlock;  // (one block size in this file: the render path's, spt_kparams.h)
 constexpr int32_t kMaxSpp = 1 << 24;  // slot 6 adds < 2^36 per sample: 2^24 samples stay below 2^63
 
 spt_status fail(spt_status s, const std::string& msg) {

@@ -1,5 +1,5 @@
-// spt_kparams.h — what the render kernel (spt_kernel.hip) and its host side (spt_dispatch.cpp,
-// spt_context.cpp) share: the uploaded scene and parameter structs, the launch constants and the
+// spt_kparams.h — what the kernels that trace (spt_kernel.hip, spt_guide.hip; spt_trace.h) and their
+// host side (spt_dispatch.cpp, spt_context.cpp) share: the uploaded scene and parameter structs, the launch constants and the
 // tuning macros with their A/B history. Plain C++. The statistics words depend on the diagnostic
 // build (spt_diag.h), so -DSPT_DIAG builds agree between host and device.
 #pragma once

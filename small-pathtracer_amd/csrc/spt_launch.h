@@ -1,9 +1,10 @@
 // spt_launch.h — the seams of the render path (internal; the public statement is include/spt.h):
 //   spt_dispatch.cpp  pure host code, no HIP: validation, scene grouping, the kernel choice, the
 //                     launch sizing, the last-error text
-//   spt_kernel.hip    the kernels, and the three launchers below: hipLaunchKernelGGL on a template
-//                     instantiation is the one thing a plain C++ file cannot do
-//   spt_context.cpp   contexts, uploads, launches and statistics (HIP runtime calls)
+//   spt_kernel.hip    the render kernels, and their three launchers below: hipLaunchKernelGGL on a
+//                     template instantiation is the one thing a plain C++ file cannot do
+//   spt_guide.hip     the guide kernel and its two launchers (both kernels trace through spt_trace.h)
+//   spt_context.cpp  contexts, uploads, launches and statistics (HIP runtime calls)
 #pragma once
 #include <stdint.h>
 
@@ -47,6 +48,8 @@ void launch_render_kernel(int kv, int grid, const KParams* kp_dev, void* stream,
 void launch_finalize_slots(const unsigned long long* accum, const unsigned long long* slots,
                            float* rgb, uint32_t npix, uint32_t n_chunks, uint32_t scr_k,
                            uint32_t scr_q, const unsigned long long* stats, void* stream);
+
+// ---- spt_guide.hip (stream and errors as above)
 // The guide kernel (SPT_HAS_GUIDE): guide_kernel<TopoGenericWide> for a scene with wide spheres, else
 // guide_kernel<TopoGeneric>. grid * kBlock lanes >= n_local_pix << guide_kshift. chain: the
 // instantiation that follows the specular chain (SPT_HAS_GUIDE_CHAIN), which has its own occupancy.

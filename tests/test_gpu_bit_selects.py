@@ -1,5 +1,5 @@
 """The render loop's selects as bit operations on lane masks (spt_device.h: mask_lt, bsel, xor3;
-spt_kernel.hip: axis_masks, box_keys): the hit's plane axis picks o_a, d_a, 1/d_a, the normal and the
+spt_kernel.hip: axis_masks; spt_trace.h: box_keys): the hit's plane axis picks o_a, d_a, 1/d_a, the normal and the
 NEE weight's |dl_a| through two masks made from the grouped position, a slab's exit is the xor of its
 two keys and their min, and the azimuth's swap is a mask of one Philox bit.
 

@@ -1,4 +1,4 @@
-"""The guide planes on the GPU (include/spt.h SPT_HAS_GUIDE; guide_kernel in spt_kernel.hip): every
+"""The guide planes on the GPU (include/spt.h SPT_HAS_GUIDE; guide_kernel in spt_guide.hip): every
 comparison is on the downloaded int64 records, exact, against tests/guide_truth.py (the contract
 restated from the oracle's pieces) or against the render kernels themselves.
 """
@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import guide_chain_truth as gct
 import guide_truth as gt
 import ray_truth as rt
 from test_gpu_rays import ray_camera
@@ -23,7 +24,9 @@ def _aspect(w, h):
 
 
 def _scene(spt, name):
-    return spt.cornell_specular_scene() if name == "specular" else rt.scene(spt, name)
+    if name in ("specular", "mirror_glass", "hall"):
+        return gct.scene(spt, name)
+    return rt.scene(spt, name)
 
 
 def _params(spt, w, h, spp, **kw):
@@ -53,7 +56,10 @@ def _same(got, want, label):
 # ---- 1. the truth, per scene class -----------------------------------------------------------------
 TRUTH_CASES = [("head_ref", "head", {}, 64, 48, 8), ("head_tilted", "head", rt.TILTED, 64, 48, 8),
                ("spheres32", "spheres32", {}, 64, 48, 8), ("specular", "specular", {}, 48, 32, 4),
-               ("classic", "classic", {}, 32, 24, 4)]
+               ("classic", "classic", {}, 32, 24, 4),
+               # first hits mostly specular: a first-hit pass must stop there, not step on as a chain does
+               # (mirror_glass: the wide instantiation; hall: mirror rectangles, free-scale directions)
+               ("mirror_glass", "mirror_glass", {}, 32, 24, 4), ("hall", "hall", gct.HALL_CAM, 32, 24, 4)]
 
 
 @pytest.mark.parametrize("label,name,camkw,w,h,spp", TRUTH_CASES, ids=[c[0] for c in TRUTH_CASES])
@@ -61,8 +67,10 @@ def test_records_equal_the_truth(spt, oracle, label, name, camkw, w, h, spp):
     prims = _scene(spt, name)
     cam = spt.Camera(aspect=_aspect(w, h), **camkw)
     # (a Camera is its four raw vectors: the tilted one has no zero component among them)
-    # (the classic box has no light rectangle: its params carry nee_prob = 0, as its renders do)
-    p = _params(spt, w, h, spp, **(dict(nee_prob=0.0) if name == "classic" else {}))
+    # (the classic boxes have no light rectangle: their params carry nee_prob = 0, as their renders do)
+    p = _params(spt, w, h, spp, **(dict(nee_prob=0.0) if name in ("classic", "mirror_glass") else {}))
+    if name in ("classic", "mirror_glass"):
+        assert spt.select_kernel(prims, cam, p)["name"] == "wide"  # the guide's instantiation follows it
     rec, info = _guide(spt, prims, cam, p)
     assert info["samples_done"] == spp and info["width"] == w and info["rows"] == h
     want = gt.guide_truth(oracle, prims, cam._c, p)

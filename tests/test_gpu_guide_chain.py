@@ -1,5 +1,5 @@
 """The guide's specular chain on the GPU (include/spt.h SPT_HAS_GUIDE_CHAIN; guide_kernel<TP, true> in
-spt_kernel.hip): the downloaded int64 records, exact, against tests/guide_chain_truth.py (the header's
+spt_guide.hip): the downloaded int64 records, exact, against tests/guide_chain_truth.py (the header's
 rule restated from the oracle's pieces) and against the render kernels themselves; a first-hit guide
 against tests/guide_truth.py as before; the denoise path and the wrappers with a chain guide.
 """

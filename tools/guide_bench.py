@@ -15,9 +15,11 @@ A short pass is timed as --inner passes between the two events (each a clear and
 beside a first-hit pass, alternating in one process, at 1024x768 on the two specular scenes
 (mirror_glass and cornell_specular @ 64 spp) and at C3's shape (HEAD has no specular primitive: the
 chain pass does the same traces), 20 runs after 5 warm-ups, medians with min-max, and the ratio. With
---parent-tree DIR (a built checkout of the parent commit) the first-hit pass of this tree and of the
-parent's library are timed in alternating child processes, --rounds of them each, to show that the
-first-hit pass did not move: the parent is the yardstick, never this build against itself.
+--parent-tree DIR (a built checkout of the parent commit) the first-hit pass and the chain pass of this
+tree and of the parent's library are timed in alternating child processes, --rounds of them each, to
+show that neither moved: the parent is the yardstick, never this build against itself. A pass counts as
+unchanged when the median of this tree's rounds exceeds the parent's by no more than the parent's own
+min-max spread over its rounds.
 
 usage: python tools/guide_bench.py [--reps N --inner M --out FILE.json]
        python tools/guide_bench.py --chain [--parent-tree DIR --rounds R] [--out FILE.json]
@@ -181,8 +183,8 @@ def _chain_pairs(spt, torch):
     return out
 
 
-def _first_hit_child(tree):
-    """One child's work: the first-hit pass of the package under `tree` at every shape."""
+def _passes_child(tree):
+    """One child's work: the first-hit and the chain pass of the package under `tree` at every shape."""
     sys.path.insert(0, tree)
     import torch
     spt = importlib.import_module("small-pathtracer_amd")
@@ -192,34 +194,42 @@ def _first_hit_child(tree):
         prims = _scene_of(spt, name)
         p = spt.default_params(width=w, height=h, spp=spp, seed=1, device=0, **kw)
         cam = spt.Camera(aspect=w / h)
-        r, g = spt.Renderer(0), spt.Guide(p, 0)
         stream = torch.cuda.current_stream().cuda_stream
-        ms = [_pass_ms(torch, g, r, prims, cam, p, stream) for _ in range(CHAIN_WARM + CHAIN_RUNS)][CHAIN_WARM:]
-        out[name] = ms
-        g.close()
-        r.close()
-    print("FIRSTHIT " + json.dumps(out))
+        out[name] = {}
+        for key, chain in (("first_hit", False), ("chain", True)):
+            r, g = spt.Renderer(0), spt.Guide(p, 0, through_specular=chain)
+            out[name][key] = [_pass_ms(torch, g, r, prims, cam, p, stream)
+                              for _ in range(CHAIN_WARM + CHAIN_RUNS)][CHAIN_WARM:]
+            g.close()
+            r.close()
+    print("PASSES " + json.dumps(out))
 
 
 def _against_parent(parent_tree, rounds):
-    """This tree's first-hit pass and the parent's, in alternating child processes."""
+    """This tree's first-hit and chain passes and the parent's, in alternating child processes."""
     runs = {"here": [], "parent": []}
     for _ in range(rounds):
         for key, tree in (("here", ROOT), ("parent", os.path.abspath(parent_tree))):
             env = {k: v for k, v in os.environ.items() if k != "SPT_LIB"}
-            c = subprocess.run([sys.executable, os.path.abspath(__file__), "--first-hit-child", tree],
+            c = subprocess.run([sys.executable, os.path.abspath(__file__), "--passes-child", tree],
                                env=env, capture_output=True, text=True, timeout=300)
-            line = [ln for ln in c.stdout.splitlines() if ln.startswith("FIRSTHIT ")]
+            line = [ln for ln in c.stdout.splitlines() if ln.startswith("PASSES ")]
             if c.returncode != 0 or not line:
                 raise SystemExit(f"the {key} child failed:\n" + c.stdout[-2000:] + c.stderr[-2000:])
-            runs[key].append(json.loads(line[0][9:]))
+            runs[key].append(json.loads(line[0][7:]))
     out = {"rounds": rounds, "sha16": {k: v[0]["kernel_sources_sha16"] for k, v in runs.items()}}
     for name, *_ in CHAIN_SHAPES:
-        here = [statistics.median(x[name]) for x in runs["here"]]
-        par = [statistics.median(x[name]) for x in runs["parent"]]
-        out[name] = {"here_ms": _stat(here), "parent_ms": _stat(par), "per_round_here": [round(v, 4) for v in here],
-                     "per_round_parent": [round(v, 4) for v in par],
-                     "here_over_parent": round(statistics.median(here) / statistics.median(par), 4)}
+        out[name] = {}
+        for kind in ("first_hit", "chain"):
+            here = [statistics.median(x[name][kind]) for x in runs["here"]]
+            par = [statistics.median(x[name][kind]) for x in runs["parent"]]
+            over, spread = statistics.median(here) - statistics.median(par), max(par) - min(par)
+            out[name][kind] = {"here_ms": _stat(here), "parent_ms": _stat(par),
+                               "per_round_here": [round(v, 4) for v in here],
+                               "per_round_parent": [round(v, 4) for v in par],
+                               "here_over_parent": round(statistics.median(here) / statistics.median(par), 4),
+                               "here_minus_parent_ms": round(over, 4), "parent_spread_ms": round(spread, 4),
+                               "unchanged": over <= spread}
     return out
 
 
@@ -232,17 +242,17 @@ def main():
     ap.add_argument("--chain", action="store_true", help="chain guide passes beside first-hit passes")
     ap.add_argument("--parent-tree", default="", help="with --chain: a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--first-hit-child", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--passes-child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.sweep_child:
         return _sweep(args.reps, args.inner)
-    if args.first_hit_child:
-        return _first_hit_child(args.first_hit_child)
+    if args.passes_child:
+        return _passes_child(args.passes_child)
     if args.chain:
         res = {"config": {"runs": CHAIN_RUNS, "warm_ups": CHAIN_WARM}}
         # the children first: this process has not opened the GPU yet
-        res["first_hit_against_parent"] = (_against_parent(args.parent_tree, args.rounds) if args.parent_tree
-                                           else "not measured: no --parent-tree")
+        res["against_parent"] = (_against_parent(args.parent_tree, args.rounds) if args.parent_tree
+                                 else "not measured: no --parent-tree")
         import torch
         spt = importlib.import_module("small-pathtracer_amd")
         res["kernel_sources_sha16"] = spt.build_sources_sha16()

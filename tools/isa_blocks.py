@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-basic-block instruction mix of one kernel in a hipcc -S listing (static cost map).
 
-  python tools/isa_blocks.py build/spt_kernel.s KEY [KEY2 ...] [--bb] [--min N]
+  python tools/isa_blocks.py build/spt_kernel.s|build/spt_guide.s KEY [KEY2 ...] [--bb] [--min N]
 
 The kernel is the one whose mangled name holds every KEY (an extern "C" kernel: whose name starts with
 it), e.g. the Topo arguments and the Cfg arguments as two substrings. A key that fits several kernels is
