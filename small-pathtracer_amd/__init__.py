@@ -365,7 +365,8 @@ KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_trace.h", "csrc/spt_variants.
                   "csrc/spt_device.h", "csrc/spt_cornell.h", "csrc/spt_diag.h", "csrc/Makefile", "../include/spt.h", "../include/spt_flops.h", "csrc/spt_film.hip",
                   "csrc/spt_film.h", "csrc/spt_film_math.h", "csrc/spt_film_host.cpp",
                   "csrc/spt_guide.hip", "csrc/spt_guide_host.cpp", "csrc/spt_guide.h",
-                  "csrc/spt_denoise.hip", "csrc/spt_denoise_host.cpp", "csrc/spt_denoise.h")
+                  "csrc/spt_denoise.hip", "csrc/spt_denoise_host.cpp", "csrc/spt_denoise.h",
+                  "csrc/spt_status.h", "csrc/spt_window_shape.h")
 
 
 def kernel_sources_sha16() -> str:

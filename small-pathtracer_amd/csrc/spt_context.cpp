@@ -19,14 +19,6 @@
 
 using namespace spt;
 
-#define SPT_HIP(call)                                                                    \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                 \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                    \
-  } while (0)
-
 struct spt_context {
   int device = 0;
   int n_cu = 0, blocks_per_cu = 0;      // generic kernel
@@ -66,8 +58,25 @@ struct spt_context {
   int guide_bpc[4] = {0, 0, 0, 0};  // resident blocks per CU of the guide kernels ([chain * 2 + wide]); 0: not asked yet
 };
 
-extern "C" int32_t spt_shard_rows(const spt_params* p, int32_t* rows_out, int32_t cap);
-int spt_shard_row_count(const spt_params* p);  // spt_host.cpp
+// ---- spt_status.h's two helpers that call HIP
+spt_status spt::open_device(int32_t device, bool say_why) {
+  int count = 0;
+  const hipError_t ce = hipGetDeviceCount(&count);
+  if (ce != hipSuccess || count == 0)
+    return fail(SPT_ERR_NO_DEVICE,
+                say_why ? std::string("no HIP device (") + hipGetErrorString(ce) + ")" : "no HIP device");
+  if (device < 0 || device >= count) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
+  SPT_HIP(hipSetDevice(device));
+  return SPT_OK;
+}
+
+spt_status spt::copy_and_wait(int device, void* dst, const void* src, size_t bytes, int kind,
+                              void* stream) {
+  SPT_HIP(hipSetDevice(device));
+  SPT_HIP(hipMemcpyAsync(dst, src, bytes, (hipMemcpyKind)kind, (hipStream_t)stream));
+  SPT_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return SPT_OK;
+}
 
 // Variant of the calling thread's last spt_render() launch (the one-shot call owns its context).
 static thread_local int g_dropin_kv = -1;
@@ -79,11 +88,7 @@ extern "C" const char* spt_context_kernel(spt_context* c) {
 
 extern "C" spt_status spt_context_create(int32_t device, spt_context** out) {
   if (!out) return fail(SPT_ERR_INVALID_ARG, "null out");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail(SPT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= count) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
-  SPT_HIP(hipSetDevice(device));
+  SPT_TRY(open_device(device));
   hipDeviceProp_t prop;
   SPT_HIP(hipGetDeviceProperties(&prop, device));
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
@@ -166,6 +171,49 @@ static void set_last_film(spt_context* c, spt_film* film, int32_t count) {
   c->last_film_count = count;
 }
 
+// ---- The scene staging both windows go through. A window call runs in three steps: every host-side
+// rejection (validate, the window check, stage_scene, select_variant, the list check, plan_launch);
+// then the allocations; then the stream operations. A call that returns an error from the first step
+// has queued nothing and allocated nothing.
+
+// Wait until nobody reads the pinned staging, then state the scene in it and in *K: the primitives and
+// their grouping, the fields of KParams that do not depend on the launch's sizes.
+static spt_status stage_scene(spt_context* c, const spt_prim* prims, int32_t n_prims, const spt_params* p,
+                              int32_t s_base, int32_t s_count, KParams* K, int* light_pos) {
+  if (c->pending) SPT_HIP(hipEventSynchronize(c->ev0));  // staging still read by a prior upload
+  if (c->guide_pending) SPT_HIP(hipEventSynchronize(c->ev_guide));  // ... or by a guide pass's
+  c->guide_pending = false;
+  to_dev(prims, n_prims, c->h_prims);
+  build_geo(prims, n_prims, c->h_geo, p->light_id, light_pos);
+  K->prims = c->prims;
+  K->geo = c->geo;
+  K->n_prims = n_prims;
+  K->width = p->width; K->height = p->height; K->spp = p->spp;
+  K->s_base = (uint32_t)s_base; K->s_count = (uint32_t)s_count; K->s_lim = (uint32_t)(s_base + s_count);
+  K->seed = p->seed;
+  // Ray-direction contract (oracle c_unit_dirs): unit directions iff a sphere or a REFR primitive
+  K->unit_dirs = 0;
+  for (int i = 0; i < n_prims; ++i)
+    if (prims[i].kind == SPT_SPHERE || prims[i].refl == SPT_REFR) K->unit_dirs = 1;
+  return SPT_OK;
+}
+
+// The staged scene, then (behind whatever the caller enqueues in between) the kernel parameters and
+// the event that says the staging has been read. The caller sets pending / guide_pending.
+static spt_status upload_scene(spt_context* c, int32_t n_prims, hipStream_t stream) {
+  SPT_HIP(hipMemcpyAsync(c->prims, c->h_prims, sizeof(DevPrim) * n_prims, hipMemcpyHostToDevice,
+                         stream));
+  SPT_HIP(hipMemcpyAsync(c->geo, c->h_geo, sizeof(SceneGeo), hipMemcpyHostToDevice, stream));
+  return SPT_OK;
+}
+
+static spt_status upload_params(spt_context* c, const KParams& K, hipEvent_t event, hipStream_t stream) {
+  *c->h_kp = K;
+  SPT_HIP(hipMemcpyAsync(c->d_kp, c->h_kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
+  SPT_HIP(hipEventRecord(event, stream));
+  return SPT_OK;
+}
+
 // One launch over the sample window [s_base, s_base + s_count) of the p->spp-sample image. With
 // film == nullptr the window's sums become the clamped floats of rgb_dev (finalize_slots_kernel:
 // the one-shot render, window [0, spp)); with a film they are added to it (spt_film.hip) and
@@ -179,35 +227,17 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   if (!c || (!rgb_dev && !film)) return fail(SPT_ERR_INVALID_ARG, "null context/output");
   if (list_dev && (!film || n_list == 0))
     return fail(SPT_ERR_INVALID_ARG, "a pixel list needs a film and at least one pixel");
-  spt_status st = validate(prims, n_prims, cam, p);
-  if (st != SPT_OK) return st;
+  SPT_TRY(validate(prims, n_prims, cam, p));
   if (s_base < 0 || s_count < 1 || (int64_t)s_base + s_count > p->spp)
     return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
   if (film && film->device != c->device)
     return fail(SPT_ERR_INVALID_ARG, "the film and the context are on different devices");
-  st = spt_context_reserve(c, n_prims, p);
-  if (st != SPT_OK) return st;
   SPT_HIP(hipSetDevice(c->device));
   hipStream_t stream = (hipStream_t)stream_v;
 
   KParams K{};
-  if (c->pending) SPT_HIP(hipEventSynchronize(c->ev0));  // staging still read by a prior upload
-  if (c->guide_pending) {  // ... or by a guide pass's
-    SPT_HIP(hipEventSynchronize(c->ev_guide));
-    c->guide_pending = false;
-  }
-  to_dev(prims, n_prims, c->h_prims);
   int light_pos = -1;
-  build_geo(prims, n_prims, c->h_geo, p->light_id, &light_pos);
-  SPT_HIP(hipMemcpyAsync(c->prims, c->h_prims, sizeof(DevPrim) * n_prims, hipMemcpyHostToDevice,
-                         stream));
-  SPT_HIP(hipMemcpyAsync(c->geo, c->h_geo, sizeof(SceneGeo), hipMemcpyHostToDevice, stream));
-  K.prims = c->prims;
-  K.geo = c->geo;
-  K.n_prims = n_prims;
-  K.width = p->width; K.height = p->height; K.spp = p->spp;
-  K.s_base = (uint32_t)s_base; K.s_count = (uint32_t)s_count; K.s_lim = (uint32_t)(s_base + s_count);
-  K.seed = p->seed;
+  SPT_TRY(stage_scene(c, prims, n_prims, p, s_base, s_count, &K, &light_pos));
   K.nee_prob = p->nee_prob; K.rr_depth = p->rr_depth; K.max_depth = p->max_depth;
   K.light_id = p->light_id;
   K.lx0 = p->light_x0; K.ldx = p->light_dx; K.lz0 = p->light_z0; K.ldz = p->light_dz;
@@ -237,9 +267,10 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   if (list_dev && (uint64_t)n_list > (uint64_t)rows * (uint64_t)p->width)
     return fail(SPT_ERR_INVALID_ARG, "the pixel list is longer than the shard");
   K.pix_list = list_dev;
-  st = plan_launch(c->n_cu, c->bpc[kv], kv, p, s_count, list_dev ? (int)n_list : rows * p->width, &K,
-                   &plan);
-  if (st != SPT_OK) return st;
+  SPT_TRY(plan_launch(c->n_cu, c->bpc[kv], kv, p, s_count, list_dev ? (int)n_list : rows * p->width, &K,
+                      &plan));
+  // nothing below rejects the call: the allocations, then the stream
+  SPT_TRY(spt_context_reserve(c, n_prims, p));
   const size_t n_units = K.n_units;
   K.accum = c->accum;
   if (3ull * n_units > c->slots_cap) {  // one owner store per unit (24 B): C3 208 MB, C4/C5 ~400 MB
@@ -255,10 +286,6 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   K.light_kind = light_pos >= 0 ? prims[p->light_id].kind : 0;
   K.light_pos = light_pos;
   K.scatter_uniform = (p->flags & SPT_FLAG_UNIFORM_SCATTER) ? 1 : 0;
-  // Ray-direction contract (oracle c_unit_dirs): unit directions iff a sphere or a REFR primitive
-  K.unit_dirs = 0;
-  for (int i = 0; i < n_prims; ++i)
-    if (prims[i].kind == SPT_SPHERE || prims[i].refl == SPT_REFR) K.unit_dirs = 1;
   K.nee_c = (float)((double)p->light_area / 3.14159265358979323846);
   c->n_prims = n_prims;
   c->samples = (uint64_t)K.n_local_pix * (uint64_t)s_count;
@@ -266,6 +293,7 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   for (int i = 0; i < n_prims; ++i)
     c->scene_flop += prims[i].kind == SPT_SPHERE ? SPT_FLOP_SPHERE : SPT_FLOP_RECT;
 
+  SPT_TRY(upload_scene(c, n_prims, stream));
   SPT_HIP(hipMemsetAsync(c->accum, 0, sizeof(unsigned long long) * 3 * (size_t)K.n_local_pix,
                          stream));
   SPT_HIP(hipMemsetAsync(c->queue, 0, sizeof(uint32_t), stream));
@@ -274,17 +302,14 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
   SPT_HIP(hipMemsetAsync(c->stats + 14, 0xFF, sizeof(unsigned long long), stream));
 #endif
   c->nee_by_identity = kKernelInfo[kv].nee_by_identity;
-  *c->h_kp = K;
-  SPT_HIP(hipMemcpyAsync(c->d_kp, c->h_kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
-  SPT_HIP(hipEventRecord(c->ev0, stream));
+  SPT_TRY(upload_params(c, K, c->ev0, stream));
   launch_render_kernel(kv, plan.grid, c->d_kp, stream, list_dev != nullptr);
   SPT_HIP(hipGetLastError());
   SPT_HIP(hipEventRecord(c->ev1, stream));
   const uint32_t np = (uint32_t)K.n_local_pix;
   if (film) {  // add the window's sums to the film (and resolve it into rgb_dev, if given)
     const spt_film_launch launch{c->accum, c->slots, np, plan.n_chunks, K.scr_k, K.scr_q, c->stats};
-    st = spt_film_accumulate(film, c, launch, rgb_dev, s_count, stream);
-    if (st != SPT_OK) return st;
+    SPT_TRY(spt_film_accumulate(film, c, launch, rgb_dev, s_count, stream));
   } else {
     launch_finalize_slots(c->accum, c->slots, rgb_dev, np, plan.n_chunks, K.scr_k, K.scr_q, c->stats,
                           stream);
@@ -309,23 +334,17 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
                             int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
                             uint32_t flags, void* stream_v) {
   if (!c || !rec_dev) return fail(SPT_ERR_INVALID_ARG, "null context/guide");
-  spt_status st = validate(prims, n_prims, cam, p);
-  if (st != SPT_OK) return st;
+  SPT_TRY(validate(prims, n_prims, cam, p));
   if (s_base < 0 || s_count < 1 || (int64_t)s_base + s_count > p->spp)
     return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
   const int rows = spt_shard_row_count(p);
   if (rows == 0) return SPT_OK;
   SPT_HIP(hipSetDevice(c->device));
   hipStream_t stream = (hipStream_t)stream_v;
-  if (!c->ev_guide) SPT_HIP(hipEventCreate(&c->ev_guide));
 
   KParams K{};
-  if (c->pending) SPT_HIP(hipEventSynchronize(c->ev0));  // staging still read by a prior upload
-  if (c->guide_pending) SPT_HIP(hipEventSynchronize(c->ev_guide));
-  c->guide_pending = false;
-  to_dev(prims, n_prims, c->h_prims);
   int light_pos = -1;
-  build_geo(prims, n_prims, c->h_geo, p->light_id, &light_pos);
+  SPT_TRY(stage_scene(c, prims, n_prims, p, s_base, s_count, &K, &light_pos));
   const bool wide = c->h_geo->n_sph_wide > 0;
   const bool chain = (flags & SPT_GUIDE_THROUGH_SPECULAR) != 0;
   int& guide_bpc = c->guide_bpc[(chain ? 2 : 0) + (wide ? 1 : 0)];  // of the instantiation launched
@@ -339,9 +358,8 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
   LaunchPlan plan;
   spt_params q = *p;
   q.chunk = s_count;  // one unit per pixel: never "too many work units"
-  st = plan_launch(c->n_cu, guide_bpc, wide ? KV_WIDE : KV_GENERIC, &q, s_count,
-                   rows * p->width, &K, &plan);
-  if (st != SPT_OK) return st;
+  SPT_TRY(plan_launch(c->n_cu, guide_bpc, wide ? KV_WIDE : KV_GENERIC, &q, s_count, rows * p->width, &K,
+                      &plan));
   int k = force_k > 0 ? force_k : guide_lanes_per_pixel(c->n_cu, guide_bpc, K.n_local_pix, s_count);
   uint32_t ksh = 0;
   while ((1 << (ksh + 1)) <= k && ksh < 6) ++ksh;
@@ -349,23 +367,12 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
   const uint64_t lanes = (uint64_t)K.n_local_pix << ksh;
   const uint64_t grid = (lanes + kBlock - 1) / kBlock;
   if (grid >= 0x7FFFFFFFull) return fail(SPT_ERR_INVALID_ARG, "the guide launch is too large");
-  SPT_HIP(hipMemcpyAsync(c->prims, c->h_prims, sizeof(DevPrim) * n_prims, hipMemcpyHostToDevice,
-                         stream));
-  SPT_HIP(hipMemcpyAsync(c->geo, c->h_geo, sizeof(SceneGeo), hipMemcpyHostToDevice, stream));
-  K.prims = c->prims;
-  K.geo = c->geo;
-  K.n_prims = n_prims;
-  K.width = p->width; K.height = p->height; K.spp = p->spp;
-  K.s_base = (uint32_t)s_base; K.s_count = (uint32_t)s_count; K.s_lim = (uint32_t)(s_base + s_count);
-  K.seed = p->seed;
-  K.unit_dirs = 0;  // the ray-direction contract, as spt_render_window states it
-  for (int i = 0; i < n_prims; ++i)
-    if (prims[i].kind == SPT_SPHERE || prims[i].refl == SPT_REFR) K.unit_dirs = 1;
+  // nothing below rejects the call
+  if (!c->ev_guide) SPT_HIP(hipEventCreate(&c->ev_guide));
   K.guide_rec = rec_dev;
   K.guide_kshift = ksh;
-  *c->h_kp = K;
-  SPT_HIP(hipMemcpyAsync(c->d_kp, c->h_kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
-  SPT_HIP(hipEventRecord(c->ev_guide, stream));
+  SPT_TRY(upload_scene(c, n_prims, stream));
+  SPT_TRY(upload_params(c, K, c->ev_guide, stream));
   c->guide_pending = true;
   launch_guide_kernel(wide, chain, (int)grid, c->d_kp, stream);
   SPT_HIP(hipGetLastError());
@@ -476,8 +483,7 @@ DropIn g_dropin[kMaxDropInDevices];
 extern "C" spt_status spt_render(const spt_prim* prims, int32_t n_prims, const spt_camera* cam,
                                  const spt_params* p, float* rgb_out, spt_stats* stats) {
   if (!rgb_out) return fail(SPT_ERR_INVALID_ARG, "null rgb_out");
-  spt_status st = validate(prims, n_prims, cam, p);
-  if (st != SPT_OK) return st;
+  SPT_TRY(validate(prims, n_prims, cam, p));
   if (p->device < 0 || p->device >= kMaxDropInDevices) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
   const size_t n = 3ull * (size_t)spt_shard_row_count(p) * (size_t)p->width;
   g_dropin_kv = -1;
@@ -487,13 +493,7 @@ extern "C" spt_status spt_render(const spt_prim* prims, int32_t n_prims, const s
   }
   DropIn& D = g_dropin[p->device];
   std::lock_guard<std::mutex> lock(D.mu);
-  if (!D.ctx) {
-    st = spt_context_create(p->device, &D.ctx);
-    if (st != SPT_OK) {
-      D.ctx = nullptr;
-      return st;
-    }
-  }
+  if (!D.ctx) SPT_TRY(spt_context_create(p->device, &D.ctx));  // (leaves D.ctx null when it fails)
   SPT_HIP(hipSetDevice(p->device));
   if (n > D.out_cap) {
     if (D.out) SPT_HIP(hipFree(D.out));
@@ -502,14 +502,12 @@ extern "C" spt_status spt_render(const spt_prim* prims, int32_t n_prims, const s
     SPT_HIP(hipMalloc(&D.out, n * sizeof(float)));
     D.out_cap = n;
   }
-  st = spt_render_async(D.ctx, prims, n_prims, cam, p, D.out, nullptr);
-  if (st == SPT_OK) g_dropin_kv = D.ctx->last_kv;
-  if (st == SPT_OK) {
-    spt_stats tmp;
-    st = spt_context_stats(D.ctx, stats ? stats : &tmp);
-  }
-  if (st == SPT_OK) SPT_HIP(hipMemcpy(rgb_out, D.out, n * sizeof(float), hipMemcpyDeviceToHost));
-  return st;
+  SPT_TRY(spt_render_async(D.ctx, prims, n_prims, cam, p, D.out, nullptr));
+  g_dropin_kv = D.ctx->last_kv;
+  spt_stats tmp;
+  SPT_TRY(spt_context_stats(D.ctx, stats ? stats : &tmp));
+  SPT_HIP(hipMemcpy(rgb_out, D.out, n * sizeof(float), hipMemcpyDeviceToHost));
+  return SPT_OK;
 }
 
 extern "C" spt_status spt_shutdown(void) {

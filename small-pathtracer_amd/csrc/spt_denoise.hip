@@ -5,13 +5,13 @@
 #include <hip/hip_runtime.h>
 
 #include <initializer_list>
-#include <string>
 
-#include "../../include/spt.h"
 #include "spt_denoise.h"
 #include "spt_film.h"
+#include "spt_guide.h"
 
 using namespace spt_denoise_math;
+using spt::fail;
 
 struct spt_denoiser {
   int device = 0;
@@ -27,18 +27,6 @@ struct spt_denoiser {
 namespace {
 
 constexpr int kTileX = 64, kTileY = 4, kBlock = kTileX * kTileY;  // a wave covers 64 consecutive x
-
-spt_status fail(spt_status s, const std::string& msg) {
-  spt_set_last_error(msg);
-  return s;
-}
-#define DN_HIP(call)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (call);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                   \
-  } while (0)
 
 // The block's tile -> this lane's pixel. Blocks are a 1-D grid over the tiles, rows of tiles first.
 __device__ __forceinline__ bool pixel_of(int32_t w, int32_t h, int32_t* x, int32_t* y) {
@@ -199,8 +187,8 @@ spt_status run(spt_denoiser* dn, const float* rgb, const float* se, const float*
                float* se_out, hipStream_t stream) {
   const size_t bytes = dn->npix * 3 * sizeof(float);
   if (p->iterations == 0) {
-    DN_HIP(hipMemcpyAsync(out, rgb, bytes, hipMemcpyDeviceToDevice, stream));
-    if (se_out) DN_HIP(hipMemcpyAsync(se_out, se, bytes, hipMemcpyDeviceToDevice, stream));
+    SPT_HIP(hipMemcpyAsync(out, rgb, bytes, hipMemcpyDeviceToDevice, stream));
+    if (se_out) SPT_HIP(hipMemcpyAsync(se_out, se, bytes, hipMemcpyDeviceToDevice, stream));
     return SPT_OK;
   }
   const Args A = make_args(p);
@@ -215,7 +203,7 @@ spt_status run(spt_denoiser* dn, const float* rgb, const float* se, const float*
     launch_atrous(dn, cur, (int32_t)1 << it, last, A, last ? nullptr : dn->cv[(it + 1) & 1],
                   last ? out : nullptr, last ? se_out : nullptr, g_form, stream);
   }
-  DN_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   return SPT_OK;
 }
 
@@ -242,11 +230,7 @@ extern "C" spt_status spt_denoiser_create(int32_t device, int32_t width, int32_t
     return fail(SPT_ERR_INVALID_ARG, "denoiser: width/height must be positive and hold at most 2^31 - 1 pixels");
   if (tiles_of(width, height, kTileX, kTileY) > kMaxTiles || tiles_of(width, height, kLdsX, kLdsY) > kMaxTiles)
     return fail(SPT_ERR_INVALID_ARG, "denoiser: the image is too narrow or too flat for one launch (spt.h)");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail(SPT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= count) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
-  DN_HIP(hipSetDevice(device));
+  SPT_TRY(spt::open_device(device));
   spt_denoiser* dn = new spt_denoiser();
   dn->device = device;
   dn->width = width;
@@ -290,10 +274,8 @@ extern "C" spt_status spt_denoise_async(spt_denoiser* dn, const float* rgb_dev, 
                                         const float* albedo_dev, const float* normal_dev,
                                         const float* depth_dev, const spt_denoise_params* params,
                                         float* out_dev, float* se_out_dev, void* stream) {
-  const spt_status st =
-      check_call(dn, params, out_dev, se_out_dev, {rgb_dev, se_dev, albedo_dev, normal_dev, depth_dev});
-  if (st != SPT_OK) return st;
-  DN_HIP(hipSetDevice(dn->device));
+  SPT_TRY(check_call(dn, params, out_dev, se_out_dev, {rgb_dev, se_dev, albedo_dev, normal_dev, depth_dev}));
+  SPT_HIP(hipSetDevice(dn->device));
   return run(dn, rgb_dev, se_dev, albedo_dev, normal_dev, depth_dev, params, out_dev, se_out_dev,
              (hipStream_t)stream);
 }
@@ -302,27 +284,22 @@ extern "C" spt_status spt_film_denoise(const spt_film* film, const spt_guide* gu
                                        const spt_denoise_params* params, float* out_dev,
                                        float* se_out_dev, void* stream) {
   if (!film || !guide) return fail(SPT_ERR_INVALID_ARG, "film_denoise: null film or guide");
-  const spt_status st = check_call(dn, params, out_dev, se_out_dev, {});
-  if (st != SPT_OK) return st;
+  SPT_TRY(check_call(dn, params, out_dev, se_out_dev, {}));
   if (!film->batch) return fail(SPT_ERR_INVALID_ARG, "film_denoise: not a noise film");
   if (film->batches_done < 2)
     return fail(SPT_ERR_INVALID_ARG, "film_denoise: the error needs at least two batches");
-  spt_guide_info gi{};
-  if (spt_guide_info_get(guide, &gi) != SPT_OK) return SPT_ERR_INVALID_ARG;
-  if (gi.samples_done == 0) return fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide holds no sample");
+  if (guide->samples_done == 0) return fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide holds no sample");
   if (film->shard_count > 1)
     return fail(SPT_ERR_INVALID_ARG,
                 "film_denoise: a shard's rows are not image neighbours; gather the planes and call spt_denoise_async");
-  if (film->width != dn->width || film->rows != dn->height || gi.width != dn->width ||
-      gi.rows != dn->height)
+  if (film->width != dn->width || film->rows != dn->height || !spt::shape_equal(*film, *guide))
     return fail(SPT_ERR_INVALID_ARG, "film_denoise: the film's or the guide's size differs from the denoiser's");
   if (film->device != dn->device)
     return fail(SPT_ERR_INVALID_ARG, "film_denoise: the film and the denoiser are on different devices");
-  spt_status s = spt_film_resolve(film, dn->rgb, stream);
-  if (s == SPT_OK) s = spt_film_noise_map(film, dn->se, stream);
-  if (s == SPT_OK) s = spt_guide_resolve(guide, dn->albedo, dn->normal, dn->depth, nullptr, stream);
-  if (s != SPT_OK) return s;
-  DN_HIP(hipSetDevice(dn->device));
+  SPT_TRY(spt_film_resolve(film, dn->rgb, stream));
+  SPT_TRY(spt_film_noise_map(film, dn->se, stream));
+  SPT_TRY(spt_guide_resolve(guide, dn->albedo, dn->normal, dn->depth, nullptr, stream));
+  SPT_HIP(hipSetDevice(dn->device));
   return run(dn, dn->rgb, dn->se, dn->albedo, dn->normal, dn->depth, params, out_dev, se_out_dev,
              (hipStream_t)stream);
 }
@@ -348,7 +325,7 @@ extern "C" spt_status spt_denoise_bench_kernel(spt_denoiser* dn, int32_t which, 
   hipStream_t stream = (hipStream_t)stream_v;
   const Args A = make_args(params);
   const dim3 grid((unsigned)tiles_of(dn->width, dn->height, kTileX, kTileY)), block(kBlock);
-  DN_HIP(hipSetDevice(dn->device));
+  SPT_HIP(hipSetDevice(dn->device));
   if (which == 0)
     hipLaunchKernelGGL(denoise_pack_kernel, grid, block, 0, stream, rgb, se, albedo, normal, depth, dn->width,
                        dn->height, A, dn->cv[0], dn->nz, dn->av, dn->grad);
@@ -358,7 +335,7 @@ extern "C" spt_status spt_denoise_bench_kernel(spt_denoiser* dn, int32_t which, 
   else
     launch_atrous(dn, dn->cv[0], step, which == 3, A, which == 3 ? nullptr : dn->cv[1],
                   which == 3 ? out : nullptr, which == 3 ? se_out : nullptr, form, stream);
-  DN_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   return SPT_OK;
 }
 #endif

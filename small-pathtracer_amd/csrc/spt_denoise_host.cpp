@@ -2,13 +2,10 @@
 // the CPU statement every GPU denoise test compares the device kernels against. Plain C++, no HIP: it
 // is also built into tests/probe/spt_denoise_check under the host sanitizers.
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "../../include/spt.h"
 #include "spt_denoise.h"
-
-void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp
+#include "spt_status.h"
 
 static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params layout (the Python mirror's)");
 
@@ -37,10 +34,7 @@ struct HostPlanes {
   float v(int32_t x, int32_t y) const { return cv_[(size_t)y * w + x].w; }
 };
 
-spt_status fail(const char* msg) {
-  spt_set_last_error(std::string("spt_denoise_host: ") + msg);
-  return SPT_ERR_INVALID_ARG;
-}
+spt_status fail(const char* msg) { return spt::fail(SPT_ERR_INVALID_ARG, std::string("spt_denoise_host: ") + msg); }
 
 }  // namespace
 

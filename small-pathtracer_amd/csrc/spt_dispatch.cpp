@@ -308,8 +308,6 @@ static int leak_end_of(const spt_prim* s, int n, const SceneGeo& g) {
   return 1;
 }
 
-static int tile_rows_of(const spt_params* p) { return p->tile_rows > 0 ? p->tile_rows : 8; }
-
 // Multiply-shift reciprocal of d for 31-bit numerators: l = ceil(log2 d), m = floor(2^(31+l)/d) + 1
 // (< 2^32), n / d = (n * m) >> (31 + l) exactly for all n < 2^31 (Granlund & Montgomery 1994).
 static void magic31(uint32_t d, uint32_t* m, uint32_t* sh) {
@@ -729,8 +727,7 @@ extern "C" const char* spt_kernel_name(int32_t id) {
 extern "C" spt_status spt_select_kernel(const spt_prim* prims, int32_t n_prims, const spt_camera* cam,
                                         const spt_params* p, spt_kernel_choice* out) {
   if (!out) return fail(SPT_ERR_INVALID_ARG, "null out");
-  spt_status st = validate(prims, n_prims, cam, p);
-  if (st != SPT_OK) return st;
+  SPT_TRY(validate(prims, n_prims, cam, p));
   std::unique_ptr<SceneGeo> g(new SceneGeo);
   int light_pos = -1;
   build_geo(prims, n_prims, g.get(), p->light_id, &light_pos);

@@ -1,20 +1,11 @@
 // spt_film.h — what spt_context.cpp (the render launch) and spt_film.hip (the film) share. Internal:
 // the public statement is include/spt.h.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <string>
-
-#include "../../include/spt.h"
+#include "spt_window_shape.h"
 
 // The resumable integer film: the 1.31 fixed-point sums of the samples rendered so far, in image
 // pixel order (the row layout of rgb_dev: a shard's film holds its compact rows).
-struct spt_film {
-  int device = 0;
-  int32_t width = 0, rows = 0, spp_total = 0;
-  int64_t samples_done = 0;
-  // the params the film was created for (a pass must bring the same ones)
-  int32_t height = 0, tile_rows = 0, shard_index = 0, shard_count = 1;
+struct spt_film : spt::WindowShape {
   unsigned long long* sums = nullptr;  // [rows * width][3], device
   size_t n = 0;                        // elements (3 * rows * width)
   spt_context* last_ctx = nullptr;     // the context of the last pass (it takes a guarded pass back)
@@ -71,5 +62,3 @@ spt_status spt_film_accumulate(spt_film* film, spt_context* c, const spt_film_la
 // The pass of `c` hit the runaway guard and added nothing: samples_done goes back by s_count.
 void spt_film_rollback(spt_film* film, const spt_context* c, int32_t s_count);
 void spt_film_forget_context(spt_film* film, const spt_context* c);
-
-void spt_set_last_error(const std::string& msg);

@@ -34,7 +34,8 @@
 #include "spt_film.h"
 #include "spt_film_math.h"
 
-int spt_shard_row_count(const spt_params* p);  // spt_host.cpp
+using spt::copy_and_wait;
+using spt::fail;
 
 namespace {
 
@@ -632,20 +633,6 @@ film_pool_map_kernel(Counts cs, const double* __restrict__ u, const double* __re
   se[3 * px + 2] = pool_se(g[2], n, B);
 }
 
-spt_status fail(spt_status s, const std::string& msg) {
-  spt_set_last_error(msg);
-  return s;
-}
-#define FILM_HIP(call)                                                                  \
-  do {                                                                                  \
-    hipError_t e_ = (call);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                   \
-  } while (0)
-
-int tile_rows_of(const spt_params* p) { return p->tile_rows > 0 ? p->tile_rows : 8; }
-
 unsigned quad_blocks(size_t n) { return (unsigned)(((n + 3) / 4 + kBlock - 1) / kBlock); }
 unsigned tail_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -671,26 +658,17 @@ void free_planes(spt_film* f, unsigned layers) {
   if (layers & kPoolPlanes) drop(f->pool);
 }
 
-// Copy a plane to or from the host and wait.
-spt_status plane_copy(const spt_film* f, void* dst, const void* src, size_t bytes, hipMemcpyKind kind,
-                      void* stream) {
-  FILM_HIP(hipSetDevice(f->device));
-  FILM_HIP(hipMemcpyAsync(dst, src, bytes, kind, (hipStream_t)stream));
-  FILM_HIP(hipStreamSynchronize((hipStream_t)stream));
-  return SPT_OK;
-}
-
 // The 16-byte kernel over the `body` whole quads it may take, the one-sum kernel over [body, n).
 // quad(blocks) / tail(blocks) enqueue them.
 template <class Quad, class Tail>
 spt_status launch_quads_and_tail(size_t body, size_t n, Quad quad, Tail tail) {
   if (body) {
     quad(quad_blocks(body));
-    FILM_HIP(hipGetLastError());
+    SPT_HIP(hipGetLastError());
   }
   if (body < n) {
     tail(tail_blocks(n - body));
-    FILM_HIP(hipGetLastError());
+    SPT_HIP(hipGetLastError());
   }
   return SPT_OK;
 }
@@ -735,7 +713,7 @@ spt_status adaptive_resolve(spt_film* f, float* rgb_dev, const u64* stats, hipSt
   const PixelCount cs = pixel_counts(f, stream);
   hipLaunchKernelGGL(film_adapt_resolve_kernel, dim3(tail_blocks(f->n / 3)), dim3(kBlock), 0, stream,
                      (const u64*)f->sums, cs.cnt, cs.tab, rgb_dev, f->n / 3, stats);
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   return SPT_OK;
 }
 
@@ -743,7 +721,7 @@ template <class Counts>
 spt_status noise_map_launch(const spt_film* f, const Counts& cs, float* se_dev, hipStream_t stream) {
   hipLaunchKernelGGL(film_noise_map_kernel<Counts>, dim3(tail_blocks(f->n)), dim3(kBlock), 0, stream,
                      (const u64*)f->sums, (const ulonglong2*)f->m2, se_dev, f->n, cs);
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   return SPT_OK;
 }
 
@@ -755,11 +733,11 @@ spt_status noise_summary_launch(const spt_film* f, const Counts& cs, NoisePartia
   NoisePartial* total_dev = (NoisePartial*)(parts + 5 * (size_t)f->n_partials);
   hipLaunchKernelGGL(film_noise_partials_kernel<Counts>, dim3(f->n_partials), dim3(kBlock), 0, stream,
                      (const u64*)f->sums, (const ulonglong2*)f->m2, f->n / 3, cs, parts);
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   hipLaunchKernelGGL(film_noise_total_kernel, dim3(1), dim3(kBlock), 0, stream, (const double*)parts,
                      (uint32_t)f->n_partials, total_dev);
-  FILM_HIP(hipGetLastError());
-  FILM_HIP(hipMemcpyAsync(total, total_dev, sizeof *total, hipMemcpyDeviceToHost, stream));
+  SPT_HIP(hipGetLastError());
+  SPT_HIP(hipMemcpyAsync(total, total_dev, sizeof *total, hipMemcpyDeviceToHost, stream));
   return SPT_OK;
 }
 
@@ -769,15 +747,15 @@ spt_status rebuild_list(spt_film* f, hipStream_t stream) {
   const unsigned nblk = tail_blocks(npix);
   hipLaunchKernelGGL(film_adapt_count_kernel, dim3(nblk), dim3(kBlock), 0, stream,
                      (const uint32_t*)f->cnt, npix, f->scan);
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   hipLaunchKernelGGL(film_adapt_scan_kernel, dim3(1), dim3(kBlock), 0, stream, f->scan, (uint32_t)nblk);
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   hipLaunchKernelGGL(film_adapt_scatter_kernel, dim3(nblk), dim3(kBlock), 0, stream,
                      (const uint32_t*)f->cnt, npix, (const uint32_t*)f->scan, f->list);
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   uint32_t total = 0;
-  FILM_HIP(hipMemcpyAsync(&total, f->scan + nblk, sizeof total, hipMemcpyDeviceToHost, stream));
-  FILM_HIP(hipStreamSynchronize(stream));
+  SPT_HIP(hipMemcpyAsync(&total, f->scan + nblk, sizeof total, hipMemcpyDeviceToHost, stream));
+  SPT_HIP(hipStreamSynchronize(stream));
   f->n_active = (int64_t)total;
   return SPT_OK;
 }
@@ -815,21 +793,20 @@ spt_status pool_rows_launch(const spt_film* f, const Counts& cs, int32_t R, hipS
   hipLaunchKernelGGL(film_pool_rows_kernel<Counts>, dim3((unsigned)blocks), dim3(kBlock), 0, stream,
                      (const u64*)f->sums, (const ulonglong2*)f->m2, cs, w, tiles, (uint32_t)R, npix,
                      f->pool, f->pool + 3 * npix, (uint32_t*)(f->pool + 6 * npix));
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   return SPT_OK;
 }
 
 template <class Counts>
 spt_status pool_map_launch(const spt_film* f, const Counts& cs, int32_t R, uint32_t flags, float* se_dev,
                            hipStream_t stream) {
-  const spt_status st = pool_rows_launch(f, cs, R, stream);
-  if (st != SPT_OK) return st;
+  SPT_TRY(pool_rows_launch(f, cs, R, stream));
   const size_t npix = f->n / 3;
   hipLaunchKernelGGL(film_pool_map_kernel<Counts>, dim3(tail_blocks(npix)), dim3(kBlock), 0, stream, cs,
                      (const double*)f->pool, (const double*)(f->pool + 3 * npix),
                      (const uint32_t*)(f->pool + 6 * npix), npix, (uint32_t)f->width, (uint32_t)f->rows,
                      pool_band_rows(f), R, flags, se_dev);
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   return SPT_OK;
 }
 
@@ -846,26 +823,12 @@ void adaptive_reset(spt_film* f) {
 
 extern "C" spt_status spt_film_create(int32_t device, const spt_params* p, spt_film** out) {
   if (!p || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
-  if (p->width <= 0 || p->height <= 0 || p->spp <= 0)
-    return fail(SPT_ERR_INVALID_ARG, "width/height/spp must be positive");
-  if ((uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull)
-    return fail(SPT_ERR_INVALID_ARG, "image too large for 32-bit pixel counters");
-  if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count || p->tile_rows < 0)
-    return fail(SPT_ERR_INVALID_ARG, "bad shard_index/shard_count/tile_rows");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail(SPT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= count) return fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
-  FILM_HIP(hipSetDevice(device));
+  spt::WindowShape shape;
+  SPT_TRY(spt::shape_from_params(p, 0xFFFFFFFFull, &shape));
+  SPT_TRY(spt::open_device(device));
   spt_film* f = new spt_film();
+  static_cast<spt::WindowShape&>(*f) = shape;
   f->device = device;
-  f->width = p->width;
-  f->height = p->height;
-  f->spp_total = p->spp;
-  f->tile_rows = tile_rows_of(p);
-  f->shard_index = p->shard_index;
-  f->shard_count = p->shard_count;
-  f->rows = spt_shard_row_count(p);
   f->n = 3ull * (size_t)f->rows * (size_t)f->width;
   if (f->n) {
     const hipError_t e = plane_alloc(&f->sums, f->n * sizeof(u64), true);
@@ -900,10 +863,10 @@ extern "C" spt_status spt_film_info_get(const spt_film* f, spt_film_info* out) {
 extern "C" spt_status spt_film_clear(spt_film* f, void* stream) {
   if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
   if (f->n) {
-    FILM_HIP(hipSetDevice(f->device));
-    FILM_HIP(hipMemsetAsync(f->sums, 0, f->n * sizeof(u64), (hipStream_t)stream));
-    if (f->m2) FILM_HIP(hipMemsetAsync(f->m2, 0, f->n * sizeof(ulonglong2), (hipStream_t)stream));
-    if (f->cnt) FILM_HIP(hipMemsetAsync(f->cnt, 0, f->n / 3 * sizeof(uint32_t), (hipStream_t)stream));
+    SPT_HIP(hipSetDevice(f->device));
+    SPT_HIP(hipMemsetAsync(f->sums, 0, f->n * sizeof(u64), (hipStream_t)stream));
+    if (f->m2) SPT_HIP(hipMemsetAsync(f->m2, 0, f->n * sizeof(ulonglong2), (hipStream_t)stream));
+    if (f->cnt) SPT_HIP(hipMemsetAsync(f->cnt, 0, f->n / 3 * sizeof(uint32_t), (hipStream_t)stream));
   }
   if (f->adaptive) adaptive_reset(f);  // the list is rebuilt by the next select
   f->samples_done = 0;
@@ -937,7 +900,7 @@ spt_status spt_film_accumulate(spt_film* f, spt_context* c, const spt_film_launc
                          f->sums, rgb_dev, L.npix, L.n_chunks, L.scr_k, L.scr_q, L.stats, r, full,
                          (int)aligned16(rgb_dev), (ulonglong2*)nullptr);
   }
-  FILM_HIP(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   count_pass(f, c, L.npix, s_count);
   if (listed && rgb_dev) return adaptive_resolve(f, rgb_dev, L.stats, stream);
   return SPT_OK;
@@ -964,15 +927,7 @@ extern "C" spt_status spt_film_render_async(spt_context* ctx, spt_film* f, const
                                             const spt_params* p, int32_t sample_base,
                                             int32_t sample_count, float* rgb_dev, void* stream) {
   if (!ctx || !f || !p) return fail(SPT_ERR_INVALID_ARG, "null context/film/params");
-  if (p->width != f->width || p->height != f->height || p->spp != f->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "width/height/spp differ from the film's");
-  if (p->tile_rows < 0 || tile_rows_of(p) != f->tile_rows || p->shard_index != f->shard_index ||
-      p->shard_count != f->shard_count)
-    return fail(SPT_ERR_INVALID_ARG, "the shard fields differ from the film's");
-  if (sample_base < 0 || sample_count < 1 || (int64_t)sample_base + sample_count > f->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "sample window outside [0, spp)");
-  if (f->samples_done + sample_count > f->spp_total)
-    return fail(SPT_ERR_INVALID_ARG, "the film would hold more than spp samples");
+  SPT_TRY(spt::shape_accepts(*f, p, sample_base, sample_count, "film"));
   if (f->batch && (sample_count != f->batch || sample_base % f->batch != 0))
     return fail(SPT_ERR_INVALID_ARG, "a noise film takes whole batches: sample_count == batch, sample_base % batch == 0");
   if (f->adaptive) {
@@ -983,10 +938,8 @@ extern "C" spt_status spt_film_render_async(spt_context* ctx, spt_film* f, const
   }
   // once a pixel has retired the pass runs over the active list (spt_film_accumulate)
   const bool listed = f->adaptive && f->any_retired;
-  const spt_status st = spt_render_window(ctx, prims, n_prims, cam, p, sample_base, sample_count,
-                                          rgb_dev, f, stream, listed ? f->list : nullptr,
-                                          listed ? (uint32_t)f->n_active : 0u);
-  if (st != SPT_OK) return st;
+  SPT_TRY(spt_render_window(ctx, prims, n_prims, cam, p, sample_base, sample_count, rgb_dev, f, stream,
+                            listed ? f->list : nullptr, listed ? (uint32_t)f->n_active : 0u));
   if (f->rows == 0) count_pass(f, nullptr, 0, sample_count);  // a shard without rows: still counted
   return SPT_OK;
 }
@@ -996,7 +949,7 @@ extern "C" spt_status spt_film_resolve(const spt_film* f, float* rgb_dev, void* 
   if (f->n == 0) return SPT_OK;
   if (!rgb_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
   hipStream_t stream = (hipStream_t)stream_v;
-  FILM_HIP(hipSetDevice(f->device));
+  SPT_HIP(hipSetDevice(f->device));
   if (f->adaptive) return adaptive_resolve(counts_owner(f), rgb_dev, nullptr, stream);
   int full = 0;
   const float r = resolve_factor(f->spp_total, f->samples_done, &full);
@@ -1028,23 +981,22 @@ extern "C" spt_status spt_film_merge(spt_film* dst, const spt_film* src, void* s
     return fail(SPT_ERR_INVALID_ARG, "merge needs two plain films or two noise films of equal batch");
   if (dst->n) {
     hipStream_t stream = (hipStream_t)stream_v;
-    FILM_HIP(hipSetDevice(dst->device));
+    SPT_HIP(hipSetDevice(dst->device));
     u64* d = dst->sums;
     const u64* s = src->sums;
     const size_t n = dst->n, body = n & ~(size_t)3;
-    const spt_status st = launch_quads_and_tail(
+    SPT_TRY(launch_quads_and_tail(
         body, n,
         [&](unsigned blocks) {
           hipLaunchKernelGGL(film_merge_kernel, dim3(blocks), dim3(kBlock), 0, stream, d, s, body);
         },
         [&](unsigned blocks) {
           hipLaunchKernelGGL(film_merge_tail_kernel, dim3(blocks), dim3(kBlock), 0, stream, d, s, body, n);
-        });
-    if (st != SPT_OK) return st;
+        }));
     if (dst->batch) {
       hipLaunchKernelGGL(film_merge_m2_kernel, dim3(tail_blocks(n)), dim3(kBlock), 0, stream,
                          (ulonglong2*)dst->m2, (const ulonglong2*)src->m2, n);
-      FILM_HIP(hipGetLastError());
+      SPT_HIP(hipGetLastError());
     }
   }
   dst->batches_done += src->batches_done;
@@ -1056,7 +1008,7 @@ extern "C" spt_status spt_film_download(const spt_film* f, uint64_t* host_sums, 
   if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
   if (f->n == 0) return SPT_OK;
   if (!host_sums) return fail(SPT_ERR_INVALID_ARG, "null output");
-  return plane_copy(f, host_sums, f->sums, f->n * sizeof(u64), hipMemcpyDeviceToHost, stream);
+  return copy_and_wait(f->device, host_sums, f->sums, f->n * sizeof(u64), hipMemcpyDeviceToHost, stream);
 }
 
 extern "C" spt_status spt_film_upload(spt_film* f, const uint64_t* host_sums, int64_t samples_done,
@@ -1068,9 +1020,7 @@ extern "C" spt_status spt_film_upload(spt_film* f, const uint64_t* host_sums, in
     return fail(SPT_ERR_INVALID_ARG, "a noise film holds whole batches: samples_done % batch != 0");
   if (f->n) {
     if (!host_sums) return fail(SPT_ERR_INVALID_ARG, "null input");
-    const spt_status st =
-        plane_copy(f, f->sums, host_sums, f->n * sizeof(u64), hipMemcpyHostToDevice, stream);
-    if (st != SPT_OK) return st;
+    SPT_TRY(copy_and_wait(f->device, f->sums, host_sums, f->n * sizeof(u64), hipMemcpyHostToDevice, stream));
   }
   f->samples_done = samples_done;
   return SPT_OK;
@@ -1085,7 +1035,7 @@ extern "C" spt_status spt_film_noise_enable(spt_film* f, int32_t batch) {
   if (batch < 1 || f->spp_total % batch != 0 || f->spp_total / batch < 2)
     return fail(SPT_ERR_INVALID_ARG, "batch must divide spp into at least two batches");
   if (f->n) {
-    FILM_HIP(hipSetDevice(f->device));
+    SPT_HIP(hipSetDevice(f->device));
     const unsigned blocks = tail_blocks(f->n / 3);
     hipError_t e = plane_alloc(&f->m2, f->n * sizeof(ulonglong2), true);
     if (e == hipSuccess)  // five planes of 8-byte words, then the total
@@ -1114,7 +1064,7 @@ extern "C" spt_status spt_film_noise_download(const spt_film* f, uint64_t* host_
   if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
   if (f->n == 0) return SPT_OK;
   if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null output");
-  return plane_copy(f, host_m2, f->m2, f->n * sizeof(ulonglong2), hipMemcpyDeviceToHost, stream);
+  return copy_and_wait(f->device, host_m2, f->m2, f->n * sizeof(ulonglong2), hipMemcpyDeviceToHost, stream);
 }
 
 extern "C" spt_status spt_film_noise_upload(spt_film* f, const uint64_t* host_m2, int64_t batches_done,
@@ -1125,9 +1075,7 @@ extern "C" spt_status spt_film_noise_upload(spt_film* f, const uint64_t* host_m2
     return fail(SPT_ERR_INVALID_ARG, "batches_done outside [0, spp / batch]");
   if (f->n) {
     if (!host_m2) return fail(SPT_ERR_INVALID_ARG, "null input");
-    const spt_status st =
-        plane_copy(f, f->m2, host_m2, f->n * sizeof(ulonglong2), hipMemcpyHostToDevice, stream);
-    if (st != SPT_OK) return st;
+    SPT_TRY(copy_and_wait(f->device, f->m2, host_m2, f->n * sizeof(ulonglong2), hipMemcpyHostToDevice, stream));
   }
   f->batches_done = batches_done;
   return SPT_OK;
@@ -1140,7 +1088,7 @@ extern "C" spt_status spt_film_noise_map(const spt_film* f, float* se_dev, void*
   if (f->n == 0) return SPT_OK;
   if (!se_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
   hipStream_t stream = (hipStream_t)stream_v;
-  FILM_HIP(hipSetDevice(f->device));
+  SPT_HIP(hipSetDevice(f->device));
   if (f->adaptive) return noise_map_launch(f, pixel_counts(counts_owner(f), stream), se_dev, stream);
   return noise_map_launch(f, uniform_count(f), se_dev, stream);
 }
@@ -1152,12 +1100,11 @@ extern "C" spt_status spt_film_noise_summary(spt_film* f, spt_noise_summary* out
   hipStream_t stream = (hipStream_t)stream_v;
   NoisePartial total{};
   if (f->n) {
-    FILM_HIP(hipSetDevice(f->device));
-    const spt_status st = f->adaptive ? noise_summary_launch(f, pixel_counts(f, stream), &total, stream)
-                                      : noise_summary_launch(f, uniform_count(f), &total, stream);
-    if (st != SPT_OK) return st;
+    SPT_HIP(hipSetDevice(f->device));
+    SPT_TRY(f->adaptive ? noise_summary_launch(f, pixel_counts(f, stream), &total, stream)
+                        : noise_summary_launch(f, uniform_count(f), &total, stream));
   }
-  FILM_HIP(hipStreamSynchronize(stream));
+  SPT_HIP(hipStreamSynchronize(stream));
   noise_finish(total, f->n / 3, f->batches_done, out);
   return SPT_OK;
 }
@@ -1222,7 +1169,7 @@ extern "C" spt_status spt_film_adaptive_select(spt_film* f, double se_threshold,
     *n_active = 0;
     return SPT_OK;
   }
-  FILM_HIP(hipSetDevice(f->device));
+  SPT_HIP(hipSetDevice(f->device));
   sync_counts(f, stream);
   const size_t npix = f->n / 3;
   const int all = se_threshold < 0.0;
@@ -1231,10 +1178,9 @@ extern "C" spt_status spt_film_adaptive_select(spt_film* f, double se_threshold,
     hipLaunchKernelGGL(film_adapt_mark_kernel, dim3(tail_blocks(npix)), dim3(kBlock), 0, stream,
                        (const u64*)f->sums, (const ulonglong2*)f->m2, f->cnt,
                        (const NoiseArgs*)f->table, keep_dev, npix, thr2, all);
-    FILM_HIP(hipGetLastError());
+    SPT_HIP(hipGetLastError());
   }
-  const spt_status st = rebuild_list(f, stream);
-  if (st != SPT_OK) return st;
+  SPT_TRY(rebuild_list(f, stream));
   if ((size_t)f->n_active != npix) f->any_retired = true;
   *n_active = f->n_active;
   return SPT_OK;
@@ -1246,9 +1192,10 @@ extern "C" spt_status spt_film_adaptive_download(const spt_film* f, uint32_t* ho
   if (!f->adaptive) return fail(SPT_ERR_INVALID_ARG, "not an adaptive film");
   if (f->n == 0) return SPT_OK;
   if (!host_counts) return fail(SPT_ERR_INVALID_ARG, "null output");
-  FILM_HIP(hipSetDevice(f->device));
+  SPT_HIP(hipSetDevice(f->device));
   sync_counts(counts_owner(f), (hipStream_t)stream);
-  return plane_copy(f, host_counts, f->cnt, f->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+  return copy_and_wait(f->device, host_counts, f->cnt, f->n / 3 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                       stream);
 }
 
 extern "C" spt_status spt_film_adaptive_upload(spt_film* f, const uint32_t* host_counts,
@@ -1276,9 +1223,8 @@ extern "C" spt_status spt_film_adaptive_upload(spt_film* f, const uint32_t* host
   }
   if (front < 0) front = top;
   if (top > front) return fail(SPT_ERR_INVALID_ARG, "a retired pixel holds more batches than the front");
-  const spt_status st =
-      plane_copy(f, f->cnt, host_counts, npix * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-  if (st != SPT_OK) return st;
+  SPT_TRY(copy_and_wait(f->device, f->cnt, host_counts, npix * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             stream));
   f->batches_done = front;
   f->samples_done = front * (int64_t)f->batch;
   f->cnt_front = front;
@@ -1297,14 +1243,12 @@ extern "C" spt_status spt_film_noise_pool_map(const spt_film* f, int32_t radius,
   if (!f) return fail(SPT_ERR_INVALID_ARG, "null film");
   if (!f->batch) return fail(SPT_ERR_INVALID_ARG, "not a noise film");
   if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the error needs at least two batches");
-  spt_status st = pool_args(radius, flags);
-  if (st != SPT_OK) return st;
+  SPT_TRY(pool_args(radius, flags));
   if (f->n == 0) return SPT_OK;
   if (!se_dev) return fail(SPT_ERR_INVALID_ARG, "null output");
   hipStream_t stream = (hipStream_t)stream_v;
-  FILM_HIP(hipSetDevice(f->device));
-  st = pool_scratch(counts_owner(f));
-  if (st != SPT_OK) return st;
+  SPT_HIP(hipSetDevice(f->device));
+  SPT_TRY(pool_scratch(counts_owner(f)));
   if (f->adaptive)
     return pool_map_launch(f, pixel_counts(counts_owner(f), stream), radius, flags, se_dev, stream);
   return pool_map_launch(f, uniform_count(f), radius, flags, se_dev, stream);
@@ -1317,18 +1261,15 @@ extern "C" spt_status spt_film_adaptive_select_pooled(spt_film* f, double se_thr
   if (!f->adaptive) return fail(SPT_ERR_INVALID_ARG, "not an adaptive film");
   if (se_threshold != se_threshold) return fail(SPT_ERR_INVALID_ARG, "the threshold is NaN");
   if (f->batches_done < 2) return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
-  spt_status st = pool_args(radius, flags);
-  if (st != SPT_OK) return st;
+  SPT_TRY(pool_args(radius, flags));
   // without a threshold no error is looked at: the selection by the mask alone
   if (se_threshold < 0.0 || f->n == 0)
     return spt_film_adaptive_select(f, se_threshold, keep_dev, n_active, stream_v);
   hipStream_t stream = (hipStream_t)stream_v;
-  FILM_HIP(hipSetDevice(f->device));
-  st = pool_scratch(f);
-  if (st != SPT_OK) return st;
+  SPT_HIP(hipSetDevice(f->device));
+  SPT_TRY(pool_scratch(f));
   const PixelCount cs = pixel_counts(f, stream);
-  st = pool_rows_launch(f, cs, radius, stream);
-  if (st != SPT_OK) return st;
+  SPT_TRY(pool_rows_launch(f, cs, radius, stream));
   const size_t npix = f->n / 3;
   const double thr2 = se_threshold * se_threshold;  // once, in double
   hipLaunchKernelGGL(film_pool_mark_kernel, dim3(tail_blocks(npix)), dim3(kBlock), 0, stream,
@@ -1336,9 +1277,8 @@ extern "C" spt_status spt_film_adaptive_select_pooled(spt_film* f, double se_thr
                      (const double*)f->pool, (const double*)(f->pool + 3 * npix),
                      (const uint32_t*)(f->pool + 6 * npix), npix, (uint32_t)f->width, (uint32_t)f->rows,
                      pool_band_rows(f), radius, flags, thr2);
-  FILM_HIP(hipGetLastError());
-  st = rebuild_list(f, stream);
-  if (st != SPT_OK) return st;
+  SPT_HIP(hipGetLastError());
+  SPT_TRY(rebuild_list(f, stream));
   if ((size_t)f->n_active != npix) f->any_retired = true;
   *n_active = f->n_active;
   return SPT_OK;

@@ -6,17 +6,12 @@
 #include <vector>
 
 #include "spt_film_math.h"
+#include "spt_status.h"
 
 using namespace spt_film_math;
-
-void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp: spt_last_error() text
+using spt::fail;
 
 namespace {
-
-spt_status fail(spt_status s, const char* msg) {
-  spt_set_last_error(msg);
-  return s;
-}
 
 // Which film a statement speaks of: a plain one (no noise info), a noise film, or an adaptive film
 // (per-pixel counts; its samples_done is implied by the counts and not looked at).
@@ -98,8 +93,7 @@ bool has_pixels(const spt_film_info* info) { return info && info->rows > 0 && in
 extern "C" spt_status spt_film_resolve_host(const uint64_t* sums, const spt_film_info* info,
                                             float* rgb_out) {
   size_t n = 0;
-  const spt_status st = host_args(kPlain, info, nullptr, nullptr, &n, nullptr);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kPlain, info, nullptr, nullptr, &n, nullptr));
   if (n == 0) return SPT_OK;
   if (!sums || !rgb_out) return fail(SPT_ERR_INVALID_ARG, "null sums/output");
   UniformCount cs{};
@@ -112,8 +106,7 @@ extern "C" spt_status spt_film_noise_map_host(const uint64_t* sums, const uint64
                                               const spt_film_info* info,
                                               const spt_film_noise_info* noise, float* se_out) {
   size_t n = 0;
-  const spt_status st = host_args(kNoise, info, noise, nullptr, &n, nullptr);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kNoise, info, noise, nullptr, &n, nullptr));
   if (n == 0) return SPT_OK;
   if (!sums || !m2 || !se_out) return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
   map_loop(sums, m2, n, uniform(info, noise), se_out);
@@ -125,8 +118,7 @@ extern "C" spt_status spt_film_noise_summary_host(const uint64_t* sums, const ui
                                                   const spt_film_noise_info* noise,
                                                   spt_noise_summary* out) {
   size_t n = 0;
-  const spt_status st = host_args(kNoise, info, noise, nullptr, &n, nullptr);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kNoise, info, noise, nullptr, &n, nullptr));
   if (!out || (n && (!sums || !m2))) return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
   summary_loop(sums, m2, n, uniform(info, noise), noise->batches_done, out);
   return SPT_OK;
@@ -138,8 +130,7 @@ extern "C" spt_status spt_film_adaptive_resolve_host(const uint64_t* sums, const
   size_t n = 0;
   std::vector<NoiseArgs> tab;
   if (has_pixels(info) && (!sums || !rgb_out)) return fail(SPT_ERR_INVALID_ARG, "null sums/output");
-  const spt_status st = host_args(kAdaptive, info, noise, counts, &n, &tab);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kAdaptive, info, noise, counts, &n, &tab));
   resolve_loop(sums, n, PixelCount{counts, tab.data()}, rgb_out);
   return SPT_OK;
 }
@@ -153,8 +144,7 @@ extern "C" spt_status spt_film_adaptive_noise_map_host(const uint64_t* sums, con
   std::vector<NoiseArgs> tab;
   if (has_pixels(info) && (!sums || !m2 || !se_out))
     return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const spt_status st = host_args(kAdaptive, info, noise, counts, &n, &tab);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kAdaptive, info, noise, counts, &n, &tab));
   map_loop(sums, m2, n, PixelCount{counts, tab.data()}, se_out);
   return SPT_OK;
 }
@@ -168,8 +158,7 @@ extern "C" spt_status spt_film_adaptive_noise_summary_host(const uint64_t* sums,
   std::vector<NoiseArgs> tab;
   if (!out || (has_pixels(info) && (!sums || !m2)))
     return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const spt_status st = host_args(kAdaptive, info, noise, counts, &n, &tab);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kAdaptive, info, noise, counts, &n, &tab));
   summary_loop(sums, m2, n, PixelCount{counts, tab.data()}, noise->batches_done, out);
   return SPT_OK;
 }
@@ -188,8 +177,7 @@ extern "C" spt_status spt_film_adaptive_select_host(const uint64_t* sums, const 
     return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
   if (has_pixels(info) && (!sums || !m2 || !counts_out || !list_out))
     return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  const spt_status st = host_args(kAdaptive, info, noise, counts, &n, &tab);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kAdaptive, info, noise, counts, &n, &tab));
   const bool all = se_threshold < 0.0;
   const double thr2 = se_threshold * se_threshold;  // once, in double
   int64_t na = 0;
@@ -310,13 +298,11 @@ extern "C" spt_status spt_film_noise_pool_map_host(const uint64_t* sums, const u
                                                    float* se_out) {
   size_t n = 0;
   std::vector<NoiseArgs> tab;
-  spt_status st = pool_args(band_rows, radius, flags);
-  if (st != SPT_OK) return st;
+  SPT_TRY(pool_args(band_rows, radius, flags));
   if (has_pixels(info) && (!sums || !m2 || !se_out))
     return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  st = counts ? host_args(kAdaptive, info, noise, counts, &n, &tab)
-              : host_args(kNoise, info, noise, nullptr, &n, nullptr);
-  if (st != SPT_OK) return st;
+  SPT_TRY(counts ? host_args(kAdaptive, info, noise, counts, &n, &tab)
+                 : host_args(kNoise, info, noise, nullptr, &n, nullptr));
   if (n == 0) return SPT_OK;
   if (counts)
     return pool_map_loop(sums, m2, info, PixelCount{counts, tab.data()}, band_rows, radius, flags,
@@ -332,15 +318,13 @@ extern "C" spt_status spt_film_adaptive_select_pooled_host(
   size_t n = 0;
   std::vector<NoiseArgs> tab;
   if (!n_active) return fail(SPT_ERR_INVALID_ARG, "null n_active");
-  spt_status st = pool_args(band_rows, radius, flags);
-  if (st != SPT_OK) return st;
+  SPT_TRY(pool_args(band_rows, radius, flags));
   if (se_threshold != se_threshold) return fail(SPT_ERR_INVALID_ARG, "the threshold is NaN");
   if (noise && noise->batches_done < 2)
     return fail(SPT_ERR_INVALID_ARG, "the selection needs at least two batches");
   if (has_pixels(info) && (!sums || !m2 || !counts_out || !list_out))
     return fail(SPT_ERR_INVALID_ARG, "null sums/moments/output");
-  st = host_args(kAdaptive, info, noise, counts, &n, &tab);
-  if (st != SPT_OK) return st;
+  SPT_TRY(host_args(kAdaptive, info, noise, counts, &n, &tab));
   const bool all = se_threshold < 0.0;
   const double thr2 = se_threshold * se_threshold;  // once, in double
   PoolPlanes P;

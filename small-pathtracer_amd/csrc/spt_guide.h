@@ -2,10 +2,15 @@
 // runs under the host sanitizers) and the context's guide launch (spt_context.cpp) share. Internal:
 // the public statement is include/spt.h (SPT_HAS_GUIDE). Needs -ffp-contract=off on both sides.
 #pragma once
-#include <cstdint>
-
-#include "../../include/spt.h"
 #include "spt_film_math.h"
+#include "spt_window_shape.h"
+
+struct spt_guide : spt::WindowShape {
+  long long* rec = nullptr;  // [rows * width][8], device
+  size_t npix = 0;
+  int32_t lanes_per_pixel = 0;  // K of the last launch
+  uint32_t flags = 0;           // SPT_GUIDE_*: the kind of record every pass adds (set at creation)
+};
 
 // spt_context.cpp: one guide launch over the sample window [s_base, s_base + s_count) into the
 // records rec_dev (int64[rows * w][8], the shard's compact rows), through the context's scene upload.

@@ -1,12 +1,7 @@
 // spt_guide_host.cpp — the guide's resolve as a pure host function (include/spt.h, SPT_HAS_GUIDE):
 // the CPU statement every GPU guide test compares the device kernel against. Plain C++, no HIP: it
 // is also built into tests/probe/spt_guide_check under the host sanitizers.
-#include <string>
-
-#include "../../include/spt.h"
 #include "spt_guide.h"
-
-void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp
 
 static_assert(sizeof(spt_guide_info) == 32, "spt_guide_info layout (the Python mirror's)");
 
@@ -16,15 +11,10 @@ extern "C" spt_status spt_guide_resolve_host(const int64_t* records, const spt_g
                                              float* albedo, float* normal, float* depth,
                                              float* coverage) {
   if (!info || info->width < 0 || info->rows < 0 || info->spp_total < 1 || info->samples_done < 0 ||
-      info->samples_done > info->spp_total) {
-    spt_set_last_error("spt_guide_resolve_host: bad info");
-    return SPT_ERR_INVALID_ARG;
-  }
+      info->samples_done > info->spp_total)
+    return spt::fail(SPT_ERR_INVALID_ARG, "spt_guide_resolve_host: bad info");
   const size_t npix = (size_t)info->rows * (size_t)info->width;
-  if (npix != 0 && !records) {
-    spt_set_last_error("spt_guide_resolve_host: null records");
-    return SPT_ERR_INVALID_ARG;
-  }
+  if (npix != 0 && !records) return spt::fail(SPT_ERR_INVALID_ARG, "spt_guide_resolve_host: null records");
   int full = 0;
   const float r = spt_film_math::resolve_factor(info->spp_total, info->samples_done, &full);
   for (size_t i = 0; i < npix; ++i) {

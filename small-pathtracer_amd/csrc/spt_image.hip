@@ -20,10 +20,9 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <string>
 #include <vector>
 
-#include "../../include/spt.h"
+#include "spt_status.h"
 
 namespace spt_img {
 
@@ -418,18 +417,7 @@ struct spt_encoder {
   uint64_t* h_total = nullptr;   // pinned mirror
 };
 
-void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp: spt_last_error() text
-static spt_status img_fail(spt_status s, const std::string& m) {
-  spt_set_last_error(m);
-  return s;
-}
-#define IMG_HIP(call)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return img_fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                 \
-                      std::string(#call) + ": " + hipGetErrorString(e_));                    \
-  } while (0)
+using spt::fail;
 
 extern "C" uint64_t spt_image_bound(int32_t w, int32_t h, int32_t format) {
   if (w <= 0 || h <= 0 || format < SPT_IMAGE_P3 || format > SPT_IMAGE_PFM) return 0;
@@ -439,20 +427,15 @@ extern "C" uint64_t spt_image_bound(int32_t w, int32_t h, int32_t format) {
 }
 
 extern "C" spt_status spt_encoder_create(int32_t device, spt_encoder** out) {
-  if (!out) return img_fail(SPT_ERR_INVALID_ARG, "null out");
-  int count = 0;
-  const hipError_t ce = hipGetDeviceCount(&count);
-  if (ce != hipSuccess || count == 0)
-    return img_fail(SPT_ERR_NO_DEVICE, std::string("no HIP device (") + hipGetErrorString(ce) + ")");
-  if (device < 0 || device >= count) return img_fail(SPT_ERR_INVALID_ARG, "bad device ordinal");
-  IMG_HIP(hipSetDevice(device));
+  if (!out) return fail(SPT_ERR_INVALID_ARG, "null out");
+  SPT_TRY(spt::open_device(device, /*say_why=*/true));
   spt_encoder* e = new spt_encoder();
   e->device = device;
   hipError_t r = hipMalloc(&e->total, sizeof(uint64_t));
   if (r == hipSuccess) r = hipHostMalloc(&e->h_total, sizeof(uint64_t), hipHostMallocDefault);
   if (r != hipSuccess) {
     spt_encoder_destroy(e);
-    return img_fail(SPT_ERR_OOM, "encoder alloc");
+    return fail(SPT_ERR_OOM, "encoder alloc");
   }
   *out = e;
   return SPT_OK;
@@ -471,24 +454,24 @@ extern "C" spt_status spt_encoder_destroy(spt_encoder* e) {
 extern "C" spt_status spt_encode_image(spt_encoder* e, const float* rgb_dev, int32_t w, int32_t h,
                                        int32_t format, uint8_t* out_dev, uint64_t cap,
                                        uint64_t* len_out, void* stream_v) {
-  if (!e || !rgb_dev || !out_dev || !len_out) return img_fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (!e || !rgb_dev || !out_dev || !len_out) return fail(SPT_ERR_INVALID_ARG, "null argument");
   // 3 w h <= 2^32 - 8192: the text kernels' 32-bit value index of the last block cannot wrap
   if (w <= 0 || h <= 0 || 3ull * (uint64_t)w * (uint64_t)h > 0xFFFFFFFFull - kTxtBlockVals)
-    return img_fail(SPT_ERR_INVALID_ARG, "bad image size");
-  if (format < SPT_IMAGE_P3 || format > SPT_IMAGE_PFM) return img_fail(SPT_ERR_INVALID_ARG, "bad format");
+    return fail(SPT_ERR_INVALID_ARG, "bad image size");
+  if (format < SPT_IMAGE_P3 || format > SPT_IMAGE_PFM) return fail(SPT_ERR_INVALID_ARG, "bad format");
   const std::string hd = header(w, h, format);
   // every argument check before any work is queued: a rejected call leaves out_dev and the
   // encoder's scratch as they were
-  if (((uintptr_t)rgb_dev & 15u) != 0) return img_fail(SPT_ERR_INVALID_ARG, "framebuffer must be 16-byte aligned");
+  if (((uintptr_t)rgb_dev & 15u) != 0) return fail(SPT_ERR_INVALID_ARG, "framebuffer must be 16-byte aligned");
   if (format != SPT_IMAGE_P3 && ((uintptr_t)(out_dev + hd.size()) & 15u) != 0)
-    return img_fail(SPT_ERR_INVALID_ARG, "output raster must be 16-byte aligned");
-  IMG_HIP(hipSetDevice(e->device));
+    return fail(SPT_ERR_INVALID_ARG, "output raster must be 16-byte aligned");
+  SPT_HIP(hipSetDevice(e->device));
   hipStream_t stream = (hipStream_t)stream_v;
   const uint32_t n_pix = (uint32_t)((uint64_t)w * (uint64_t)h);
   const Thresholds& T = thresholds();
   uint64_t len;
   if (format == SPT_IMAGE_P3) {
-    if (cap >= hd.size()) IMG_HIP(hipMemcpyAsync(out_dev, hd.data(), hd.size(), hipMemcpyHostToDevice, stream));
+    if (cap >= hd.size()) SPT_HIP(hipMemcpyAsync(out_dev, hd.data(), hd.size(), hipMemcpyHostToDevice, stream));
     // two passes around the toInt bytes: p6_write (+ NaN epoch) -> p3_lengths -> p3_offsets ->
     // p3_text, all on the stream
     const uint32_t nv = n_pix * 3;
@@ -497,11 +480,11 @@ extern "C" spt_status spt_encode_image(spt_encoder* e, const float* rgb_dev, int
     const size_t dig_b = (nan_b + 4 + 15) & ~size_t(15);
     const size_t need = dig_b + (((size_t)nv + 15) & ~size_t(15));
     if (need > e->scratch_cap) {
-      if (e->scratch) IMG_HIP(hipFree(e->scratch));
+      if (e->scratch) SPT_HIP(hipFree(e->scratch));
       e->scratch = nullptr;
       e->scratch_cap = 0;
-      IMG_HIP(hipMalloc(&e->scratch, need));
-      IMG_HIP(hipMemsetAsync(e->scratch, 0, need, stream));  // the NaN word starts at epoch 0
+      SPT_HIP(hipMalloc(&e->scratch, need));
+      SPT_HIP(hipMemsetAsync(e->scratch, 0, need, stream));  // the NaN word starts at epoch 0
       e->scratch_cap = need;
       e->epoch = 0;
     }
@@ -513,26 +496,26 @@ extern "C" spt_status spt_encode_image(spt_encoder* e, const float* rgb_dev, int
     const uint32_t grid1 = std::max(1u, std::min((nv / 4 + kThreads - 1) / kThreads, 2048u));
     hipLaunchKernelGGL(p6_write, dim3(grid1), dim3(kThreads), 0, stream, (const float4*)rgb_dev, nv, T,
                        (uint32_t*)digits, nan_word, epoch);
-    IMG_HIP(hipGetLastError());
+    SPT_HIP(hipGetLastError());
     hipLaunchKernelGGL(p3_lengths, dim3(nbt), dim3(kTxtThreads), 0, stream, (const uint4*)digits, rgb_dev,
                        nv, T, (const uint32_t*)nan_word, epoch, blen);
-    IMG_HIP(hipGetLastError());
+    SPT_HIP(hipGetLastError());
     hipLaunchKernelGGL(p3_offsets, dim3(1), dim3(kScanThreads), 0, stream, (const uint32_t*)blen, nbt,
                        (uint64_t)hd.size(), offs, e->total);
-    IMG_HIP(hipGetLastError());
+    SPT_HIP(hipGetLastError());
     hipLaunchKernelGGL(p3_text, dim3(nbt), dim3(kTxtThreads), 0, stream, (const uint4*)digits, rgb_dev,
                        nv, T, (const uint32_t*)nan_word, epoch, (const uint64_t*)offs, out_dev, cap);
-    IMG_HIP(hipGetLastError());
-    IMG_HIP(hipMemcpyAsync(e->h_total, e->total, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    IMG_HIP(hipStreamSynchronize(stream));  // the text length is data-dependent
+    SPT_HIP(hipGetLastError());
+    SPT_HIP(hipMemcpyAsync(e->h_total, e->total, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SPT_HIP(hipStreamSynchronize(stream));  // the text length is data-dependent
     len = *e->h_total;
     *len_out = len;
-    if (len > cap) return img_fail(SPT_ERR_INVALID_ARG, "output buffer too small (need " + std::to_string(len) + " bytes)");
+    if (len > cap) return fail(SPT_ERR_INVALID_ARG, "output buffer too small (need " + std::to_string(len) + " bytes)");
   } else {
     len = hd.size() + (uint64_t)n_pix * (format == SPT_IMAGE_P6 ? 3 : 12);
     *len_out = len;
-    if (len > cap) return img_fail(SPT_ERR_INVALID_ARG, "output buffer too small (need " + std::to_string(len) + " bytes)");
-    IMG_HIP(hipMemcpyAsync(out_dev, hd.data(), hd.size(), hipMemcpyHostToDevice, stream));
+    if (len > cap) return fail(SPT_ERR_INVALID_ARG, "output buffer too small (need " + std::to_string(len) + " bytes)");
+    SPT_HIP(hipMemcpyAsync(out_dev, hd.data(), hd.size(), hipMemcpyHostToDevice, stream));
     const uint32_t nv = n_pix * 3;
     // grid-stride loops over ~8 blocks per CU (the block prologue stages the toInt table)
     const uint32_t grid = std::max(1u, std::min((nv / 4 + kThreads - 1) / kThreads, 2048u));
@@ -550,14 +533,14 @@ extern "C" spt_status spt_encode_image(spt_encoder* e, const float* rgb_dev, int
       hipLaunchKernelGGL(pfm_write1, dim3(grid * 4), dim3(kThreads), 0, stream, rgb_dev, (uint32_t)w * 3,
                          (uint32_t)h, m, sh, (float*)(out_dev + hd.size()));
     }
-    IMG_HIP(hipGetLastError());
+    SPT_HIP(hipGetLastError());
   }
   return SPT_OK;
 }
 
 extern "C" spt_status spt_write_image(int32_t device, const float* rgb, int32_t w, int32_t h,
                                       int32_t format, const char* path) {
-  if (!rgb || !path) return img_fail(SPT_ERR_INVALID_ARG, "null argument");
+  if (!rgb || !path) return fail(SPT_ERR_INVALID_ARG, "null argument");
   spt_encoder* e = nullptr;
   spt_status st = spt_encoder_create(device, &e);
   if (st != SPT_OK) return st;
@@ -576,16 +559,16 @@ extern "C" spt_status spt_write_image(int32_t device, const float* rgb, int32_t 
     if (r == hipSuccess) r = hipMemcpy(src, rgb, n_f * sizeof(float), hipMemcpyHostToDevice);
   }
   if (r == hipSuccess) r = hipMalloc(&dev_out, cap);
-  if (r != hipSuccess) st = img_fail(SPT_ERR_OOM, std::string("write_image: ") + hipGetErrorString(r));
+  if (r != hipSuccess) st = fail(SPT_ERR_OOM, std::string("write_image: ") + hipGetErrorString(r));
   if (st == SPT_OK) st = spt_encode_image(e, on_device ? rgb : src, w, h, format, dev_out, cap, &len, nullptr);
   if (st == SPT_OK) {
     host.resize(len);
     r = hipMemcpy(host.data(), dev_out, len, hipMemcpyDeviceToHost);
-    if (r != hipSuccess) st = img_fail(SPT_ERR_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) st = fail(SPT_ERR_HIP, hipGetErrorString(r));
   }
   if (st == SPT_OK) {
     FILE* f = std::fopen(path, "wb");
-    if (!f || std::fwrite(host.data(), 1, len, f) != len) st = img_fail(SPT_ERR_INVALID_ARG, std::string("cannot write ") + path);
+    if (!f || std::fwrite(host.data(), 1, len, f) != len) st = fail(SPT_ERR_INVALID_ARG, std::string("cannot write ") + path);
     if (f) std::fclose(f);
   }
   if (src) (void)hipFree(src);

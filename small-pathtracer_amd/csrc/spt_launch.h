@@ -8,16 +8,13 @@
 #pragma once
 #include <stdint.h>
 
-#include <string>
-
-#include "../../include/spt.h"
 #include "spt_kparams.h"
+#include "spt_status.h"
 #include "spt_variants.h"
 
 namespace spt {
 
-// ---- spt_dispatch.cpp
-spt_status fail(spt_status s, const std::string& msg);  // sets spt_last_error()'s text, returns s
+// ---- spt_dispatch.cpp (and spt_status.h's fail)
 spt_status validate(const spt_prim* prims, int32_t n, const spt_camera* cam, const spt_params* p);
 void to_dev(const spt_prim* s, int n, DevPrim* out);
 // Grouped geometry; *light_pos = position of prim `light` in rect[] / sph[] (-1 if absent).

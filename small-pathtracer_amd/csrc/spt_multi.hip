@@ -19,30 +19,17 @@
 
 #include <algorithm>
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "../../include/spt.h"
+#include "spt_status.h"
 
-void spt_set_last_error(const std::string& msg);  // spt_dispatch.cpp
-int spt_shard_row_count(const spt_params* p);     // spt_host.cpp
+using spt::fail;
 
 namespace {
 
 constexpr int kMaxRanks = 64;
 constexpr int kThreads = 256;
 
-spt_status fail(spt_status s, const std::string& msg) {
-  spt_set_last_error(msg);
-  return s;
-}
-#define SPT_HIPM(call)                                                                    \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(e_ == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP,                  \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                     \
-  } while (0)
 #define SPT_NCCL(call)                                                                    \
   do {                                                                                    \
     ncclResult_t r_ = (call);                                                             \
@@ -91,8 +78,6 @@ spt_status check_layout(const spt_params* p, int32_t nranks) {
   return SPT_OK;
 }
 
-int tile_rows_of(const spt_params* p) { return p->tile_rows > 0 ? p->tile_rows : 8; }
-
 size_t shard_floats(const spt_params* p, int k) {
   spt_params q = *p;
   q.shard_index = k;
@@ -111,8 +96,7 @@ struct spt_comm {
 extern "C" spt_status spt_deinterleave_rows(const spt_params* p, int32_t nranks,
                                             const float* const* shards_dev, float* image_dev,
                                             void* stream) {
-  spt_status st = check_layout(p, nranks);
-  if (st != SPT_OK) return st;
+  SPT_TRY(check_layout(p, nranks));
   if (!shards_dev || !image_dev) return fail(SPT_ERR_INVALID_ARG, "null buffer");
   Sources src{};
   for (int k = 0; k < nranks; ++k) {
@@ -121,7 +105,7 @@ extern "C" spt_status spt_deinterleave_rows(const spt_params* p, int32_t nranks,
   }
   hipLaunchKernelGGL(deinterleave_kernel, dim3(p->height), dim3(kThreads), 0, (hipStream_t)stream,
                      src, (int)nranks, tile_rows_of(p), (int)p->height, 3 * (int)p->width, image_dev);
-  SPT_HIPM(hipGetLastError());
+  SPT_HIP(hipGetLastError());
   return SPT_OK;
 }
 
@@ -157,8 +141,7 @@ extern "C" int32_t spt_gather_plan(const spt_params* p, int32_t nranks, int32_t 
 
 extern "C" spt_status spt_deinterleave_source(const spt_params* p, int32_t nranks, int32_t row,
                                               int32_t* rank, int32_t* compact_row) {
-  spt_status st = check_layout(p, nranks);
-  if (st != SPT_OK) return st;
+  SPT_TRY(check_layout(p, nranks));
   if (!rank || !compact_row || row < 0 || row >= p->height) return fail(SPT_ERR_INVALID_ARG, "bad row");
   int k;
   size_t j;
@@ -182,7 +165,7 @@ extern "C" spt_status spt_comm_create(const uint8_t id[SPT_COMM_ID_BYTES], int32
   if (!id || !out) return fail(SPT_ERR_INVALID_ARG, "null argument");
   if (nranks < 1 || nranks > kMaxRanks || rank < 0 || rank >= nranks)
     return fail(SPT_ERR_INVALID_ARG, "bad nranks/rank");
-  SPT_HIPM(hipSetDevice(device));
+  SPT_HIP(hipSetDevice(device));
   ncclUniqueId u;
   std::memcpy(u.internal, id, SPT_COMM_ID_BYTES);
   spt_comm* c = new spt_comm();
@@ -226,11 +209,11 @@ spt_status reserve_gbuf(spt_comm* c, size_t slot) {
   if (c->rank != 0 || c->nranks < 2) return SPT_OK;
   const size_t need = slot * (size_t)(c->nranks - 1);
   if (need <= c->gbuf_cap) return SPT_OK;
-  SPT_HIPM(hipSetDevice(c->device));
-  if (c->gbuf) SPT_HIPM(hipFree(c->gbuf));
+  SPT_HIP(hipSetDevice(c->device));
+  if (c->gbuf) SPT_HIP(hipFree(c->gbuf));
   c->gbuf = nullptr;
   c->gbuf_cap = 0;
-  SPT_HIPM(hipMalloc(&c->gbuf, need * sizeof(float)));
+  SPT_HIP(hipMalloc(&c->gbuf, need * sizeof(float)));
   c->gbuf_cap = need;
   return SPT_OK;
 }
@@ -252,8 +235,7 @@ spt_status deinterleave_on_root(spt_comm* c, const spt_params* p, const float* s
 
 extern "C" spt_status spt_comm_reserve(spt_comm* c, const spt_params* p) {
   if (!c) return fail(SPT_ERR_INVALID_ARG, "null comm");
-  spt_status st = check_layout(p, c->nranks);
-  if (st != SPT_OK) return st;
+  SPT_TRY(check_layout(p, c->nranks));
   return reserve_gbuf(c, shard_floats(p, 0));
 }
 
@@ -261,18 +243,16 @@ extern "C" spt_status spt_gather_framebuffer(spt_comm* c, const spt_params* p,
                                              const float* shard_dev, float* image_dev,
                                              void* stream) {
   if (!c) return fail(SPT_ERR_INVALID_ARG, "null comm");
-  spt_status st = check_layout(p, c->nranks);
-  if (st != SPT_OK) return st;
+  SPT_TRY(check_layout(p, c->nranks));
   if (c->rank == 0 && !image_dev) return fail(SPT_ERR_INVALID_ARG, "rank 0 needs image_dev");
   if (!shard_dev && shard_floats(p, c->rank) != 0) return fail(SPT_ERR_INVALID_ARG, "null shard");
   const size_t slot = shard_floats(p, 0);  // shard 0 owns the most rows (tiles 0, n, 2n, ...)
-  st = reserve_gbuf(c, slot);
-  if (st != SPT_OK) return st;
-  SPT_HIPM(hipSetDevice(c->device));
+  SPT_TRY(reserve_gbuf(c, slot));
+  SPT_HIP(hipSetDevice(c->device));
   const hipStream_t s = (hipStream_t)stream;
   if (c->nranks > 1) {
     SPT_NCCL(ncclGroupStart());
-    st = post_gather(c, p, shard_dev, s);
+    const spt_status st = post_gather(c, p, shard_dev, s);
     const ncclResult_t r = ncclGroupEnd();
     if (st != SPT_OK) return st;
     if (r != ncclSuccess) return fail(SPT_ERR_RCCL, std::string("ncclGroupEnd: ") + ncclGetErrorString(r));

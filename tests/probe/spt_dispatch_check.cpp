@@ -184,9 +184,22 @@ static void sizing() {
   }
 }
 
+// spt::fail (spt_status.h) returns its status and sets the text spt_last_error() returns; so does a
+// rejection that goes through it.
+static void error_path() {
+  CHECK(fail(SPT_ERR_OOM, "one text") == SPT_ERR_OOM);
+  CHECK(std::strcmp(spt_last_error(), "one text") == 0);
+  CHECK(fail(SPT_ERR_INVALID_ARG, std::string("another")) == SPT_ERR_INVALID_ARG);
+  CHECK(std::strcmp(spt_last_error(), "another") == 0);
+  spt_kernel_choice ch{};
+  CHECK(spt_select_kernel(nullptr, 0, nullptr, nullptr, &ch) == SPT_ERR_INVALID_ARG);
+  CHECK(std::strcmp(spt_last_error(), "null argument") == 0);
+}
+
 int main() {
   scenes();
   sizing();
+  error_path();
   if (g_failed) {
     std::fprintf(stderr, "spt_dispatch_check: %d checks failed\n", g_failed);
     return 1;

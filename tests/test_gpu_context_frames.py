@@ -29,6 +29,8 @@ from test_gpu_film_pool import planes_at, uniform_reference
 pytestmark = pytest.mark.gpu
 
 RETIRED, MASK = np.uint32(0x80000000), np.uint32(0x7FFFFFFF)
+# the late rejection: 4096 x 4096 pixels x 128 one-sample units = 2^31 work units (plan_launch's text)
+LATE, LATE_P = "too many work units; raise chunk", dict(width=4096, height=4096, spp=128, chunk=1)
 
 
 @pytest.fixture(scope="module")
@@ -189,6 +191,9 @@ def test_rejected_calls_in_mid_pipeline(spt, torch_dev, table):
             "light_id": lambda: r.render_async(x.prims, x.cam, with_p(light_id=len(x.prims)),
                                                spare.data_ptr(), stream),
             "null output": lambda: r.render_async(x.prims, x.cam, x.p, 0, stream),
+            # a late rejection: validate accepts it, plan_launch counts 2^24 pixels x 128 one-sample
+            # units = 2^31 and refuses on host arithmetic alone, before anything is allocated
+            LATE: lambda: r.render_async(x.prims, x.cam, with_p(**LATE_P), spare.data_ptr(), stream),
         }
         assert len(x.prims) * 8 > 64 and x.p.nee_prob > 0
         enqueue(r, a, buf_a, stream)
@@ -197,6 +202,8 @@ def test_rejected_calls_in_mid_pipeline(spt, torch_dev, table):
                 with pytest.raises(spt.SptError) as e:
                     call()
                 assert e.value.status == 1, what
+                if what == LATE:
+                    assert str(e.value).split(": ", 1)[1] == LATE, str(e.value)
                 assert r.kernel() == last.kernel, (what, r.kernel())
             if last is a:
                 enqueue(r, b, buf_b, stream)
@@ -207,6 +214,55 @@ def test_rejected_calls_in_mid_pipeline(spt, torch_dev, table):
         assert bool(torch.isnan(spare).all()), "a rejected call wrote its output"
     finally:
         closing(torch, r)
+
+
+def test_rejected_late_calls_queue_nothing(spt, oracle, torch_dev, table):
+    """One context, one stream, no synchronisation between the calls: a frame, a render that
+    plan_launch rejects, a first-hit guide pass of another scene, a guide call its guide rejects, a
+    frame of a third scene. Both frames are the oracle's, the guide holds guide_truth's records of its
+    one pass (samples_done 8: the rejected guide call counted nothing). With the guide tests that put
+    a pass between frames it guards the order of the one staging step both windows share
+    (spt_context.cpp, stage_scene): the rejected calls rewrite the pinned staging at most after
+    waiting for the upload that reads it, and the next good call restates it before its own upload."""
+    import guide_truth as gt
+
+    torch = torch_dev
+    frames, truth = table
+    a, b, x = frames["tilted"], frames["specular"], frames["spheres"]
+    assert a.shape == (24, 32, 8)
+    stream = torch.cuda.current_stream().cuda_stream
+    pg = spt.default_params(width=32, height=24, spp=8, seed=15, device=0)
+    cam_g = spt.Camera(aspect=a.aspect)
+    want = gt.guide_truth(oracle, x.prims, cam_g._c, pg)
+    late, wide = spt.spt_params.from_buffer_copy(a.p), spt.spt_params.from_buffer_copy(pg)
+    for k, v in LATE_P.items():
+        setattr(late, k, v)
+    wide.width = 33
+    r, g = spt.Renderer(0), spt.Guide(pg, 0)
+    try:
+        buf_a, buf_b, spare = nan_buffer(torch, a), nan_buffer(torch, b), nan_buffer(torch, a)
+        enqueue(r, a, buf_a, stream)
+        with pytest.raises(spt.SptError) as e:
+            r.render_async(a.prims, a.cam, late, spare.data_ptr(), stream)
+        assert e.value.status == 1 and str(e.value).split(": ", 1)[1] == LATE, str(e.value)
+        g.render(r, x.prims, cam_g, pg, 0, 8, stream)
+        with pytest.raises(spt.SptError) as e:
+            g.render(r, x.prims, cam_g, wide, 0, 8, stream)
+        assert e.value.status == 1, str(e.value)
+        assert str(e.value).split(": ", 1)[1] == "width/height/spp differ from the guide's", str(e.value)
+        assert r.kernel() == a.kernel
+        enqueue(r, b, buf_b, stream)
+        assert_stats(spt, r.stats(), truth["specular"][1], "frame B")
+        torch.cuda.synchronize()
+        assert_image(buf_a, truth["tilted"][0], "frame A")
+        assert_image(buf_b, truth["specular"][0], "frame B")
+        assert bool(torch.isnan(spare).all()), "the rejected render wrote its output"
+        got = g.to_numpy()
+        assert got.shape == want.shape and np.array_equal(got, want), \
+            f"{int((got != want).sum())} guide slots differ"
+        assert g.info()["samples_done"] == 8
+    finally:
+        closing(torch, g, r)
 
 
 def window_passes(spt, fr, windows):
