@@ -37,7 +37,8 @@ extern "C" {
                              SPT_HAS_GUIDE, the spt_guide_* calls; SPT_HAS_DENOISE, the
                              spt_denoise_* and spt_denoiser_* calls and spt_film_denoise;
                              SPT_HAS_GUIDE_CHAIN, spt_guide_create_ex (spt_guide_info's last field,
-                             always 0 until then, now reads the guide's flags) */
+                             always 0 until then, now reads the guide's flags); SPT_HAS_DENOISE_PAIR,
+                             the spt_denoise_pair_* calls and spt_film_pair_denoise */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
@@ -47,6 +48,7 @@ extern "C" {
 #define SPT_GUIDE_THROUGH_SPECULAR 1u /* spt_guide_create_ex flag: records of the first DIFF surface */
 #define SPT_GUIDE_MAX_CHAIN 8 /* segments of a chain at most, the camera ray included */
 #define SPT_HAS_DENOISE 1 /* the edge-stopping a-trous filter over a film and its guides (below) */
+#define SPT_HAS_DENOISE_PAIR 1 /* two independent halves, cross-weighted, and a measured error (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -685,6 +687,83 @@ spt_status spt_denoise_host(const float* rgb, const float* se, const float* albe
 spt_status spt_film_denoise(const spt_film* film, const spt_guide* guide, spt_denoiser* dn,
                             const spt_denoise_params* params, float* out_dev, float* se_out_dev_or_null,
                             void* stream);
+
+/* ---- two-half denoising: cross-weighted a-trous and a measured error (SPT_HAS_DENOISE_PAIR) ----
+ * The samples are split into two independent halves A and B (two noise films that took disjoint
+ * windows: their spt_film_merge is the one-shot film bit for bit). Both halves run the filter above,
+ * fused tap by tap; a half's colour weights come from the OTHER half (Rousselle et al. 2012, NFOR), so
+ * a pixel's own noise no longer steers its own weights, and half the difference of the two results
+ * measures the error of their mean. Same arithmetic rules as above: exact fp32, no contraction, every
+ * sum in the order given, device and host agree bit for bit.
+ * Inputs, for a w x h image: the halves (rgb_a, se_a) and (rgb_b, se_b), h*w*3 each; albedo, normal,
+ * depth shared; an spt_denoise_params, validated as above; pair_flags, separate from params->flags: 0 or
+ * SPT_DENOISE_PAIR_OWN_WEIGHTS, other bits rejected.
+ * Prepare: each half by the prepare above with the shared divisor a_k: (c^A, v^A), (c^B, v^B). The depth
+ *   gradient is the one above.
+ * Iteration i (step 2^i): vt^A, vt^B = the 3x3 filter above of v^A, v^B. Tap order, the skipping of taps
+ *   outside the image and the centre tap (w = h_2*h_2, both halves) are as above. Every other tap has
+ *     g     = (((h_j*h_i) * w_n) * w_z) * w_a                 (shared; w_n, w_z, w_a as above)
+ *     w_c^H = phi(((d_0*d_0 + d_1*d_1) + d_2*d_2) / (sigma_color^2 * (vt^H_p + vt^H_q) + 1e-10f)),
+ *             d = c^H_p - c^H_q, for H = A and B
+ *     w^A = g * w_c^B, w^B = g * w_c^A;   with SPT_DENOISE_PAIR_OWN_WEIGHTS w^A = g * w_c^A, w^B = g * w_c^B
+ *   (g * w_c is the product above in its association order: equal halves give the single filter's bits).
+ *   Each half keeps its own sums: W += w, C_k += w*c^H_q,k, V += (w*w)*v^H_q; c'^H_k = C_k / W,
+ *   v'^H = V / (W*W).
+ * Finish: o^H_k = fminf(c^H_k * a_k, 1);  out_k = 0.5f * (o^A_k + o^B_k);
+ *   diff_k = 0.5f * (o^A_k - o^B_k), signed (optional plane);
+ *   se_out_k = (0.5f * sqrtf(v^A + v^B)) * a_k (optional plane): the propagated estimate, for comparison.
+ *   iterations == 0: o^H = rgb^H as given (no divide-and-multiply round trip), out and diff by the same
+ *   formulas, se_out_k = 0.5f * sqrtf(se_a_k*se_a_k + se_b_k*se_b_k).
+ * Swapping the halves leaves out and se_out bit-identical and negates diff exactly.
+ * WHAT diff^2 IS. out = (o^A + o^B) / 2, so with independent halves Var(out) = Var(o^A - o^B) / 4 and
+ * diff^2 is an estimate of out's variance with ONE degree of freedom per value: useless for one pixel,
+ * meaningful as a mean over many (the summary below). With SPT_DENOISE_PAIR_OWN_WEIGHTS the two results
+ * are functions of independent samples and E[diff^2] = Var(out) exactly. With cross weights A's weights
+ * are B's data: the results correlate positively and diff^2 reads LOW (measured figures: README). In both
+ * modes diff is blind to BIAS: blur that both halves share cancels in the difference, so diff^2 is
+ * an estimate of variance, not of the squared error against the true image. */
+#define SPT_DENOISE_PAIR_OWN_WEIGHTS 1u /* pair_flags: each half weighted by its own colours */
+typedef struct spt_pair_summary {
+  double rmse[3];    /* per channel: sqrt(mean over ALL pixels of (double)diff_k * (double)diff_k) */
+  double rmse_all;   /* the same over the three channels together */
+  float diff_max;    /* the largest fabsf(diff) */
+  uint32_t reserved; /* 0 */
+} spt_pair_summary;
+/* Enqueue the pair filter of seven DEVICE planes on `stream`: out_dev and, if given, se_out_dev and
+ * diff_dev (h*w*3 each). The first pair call on a denoiser allocates the pair scratch (a hipMalloc: it
+ * may synchronise the device once), 60 bytes per pixel beside spt_denoiser_create's 124 (two more
+ * ping-pong planes of (c, v), the second vt plane, the second film's rgb and se planes) and the
+ * summary's partials, 32 bytes per 256 pixels; spt_denoiser_destroy frees it. SPT_ERR_OOM if it does not fit. Rejected with
+ * SPT_ERR_INVALID_ARG, nothing queued, every output untouched: what spt_denoise_async rejects, unknown
+ * pair_flags, an output plane equal to an input plane or to another output plane. */
+spt_status spt_denoise_pair_async(spt_denoiser* dn, const float* rgb_a_dev, const float* se_a_dev,
+                                  const float* rgb_b_dev, const float* se_b_dev, const float* albedo_dev,
+                                  const float* normal_dev, const float* depth_dev,
+                                  const spt_denoise_params* params, uint32_t pair_flags, float* out_dev,
+                                  float* se_out_dev_or_null, float* diff_dev_or_null, void* stream);
+/* The same as a pure host function: the CPU statement. */
+spt_status spt_denoise_pair_host(const float* rgb_a, const float* se_a, const float* rgb_b,
+                                 const float* se_b, const float* albedo, const float* normal,
+                                 const float* depth, int32_t width, int32_t height,
+                                 const spt_denoise_params* params, uint32_t pair_flags, float* out,
+                                 float* se_out_or_null, float* diff_or_null);
+/* The figures of a diff plane (DEVICE, the denoiser's h*w*3). Waits on `stream`. A two-stage reduction
+ * in a fixed order (per-block partials, then one block; no floating-point atomics): the same plane gives
+ * the same bits every time. The host statement sums in pixel order: the two agree to rounding. */
+spt_status spt_denoise_pair_summary(spt_denoiser* dn, const float* diff_dev, spt_pair_summary* out,
+                                    void* stream);
+spt_status spt_denoise_pair_summary_host(const float* diff, int32_t width, int32_t height,
+                                         spt_pair_summary* out);
+/* Two films and a guide in one call: both films' resolves and error maps and the guide's resolve go into
+ * the denoiser's scratch, then the pair filter, all enqueued on `stream` with no host synchronisation
+ * (but the first pair call's allocation, above); the result equals spt_denoise_pair_async on the
+ * separately resolved planes bit for bit. Adaptive films work as in spt_film_denoise. Rejected, nothing
+ * queued, every output untouched: what spt_denoise_pair_async and spt_film_denoise reject, applied to
+ * either film; film_a == film_b; films whose width, rows, spp_total or device differ. */
+spt_status spt_film_pair_denoise(const spt_film* film_a, const spt_film* film_b, const spt_guide* guide,
+                                 spt_denoiser* dn, const spt_denoise_params* params, uint32_t pair_flags,
+                                 float* out_dev, float* se_out_dev_or_null, float* diff_dev_or_null,
+                                 void* stream);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

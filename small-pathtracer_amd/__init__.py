@@ -132,6 +132,15 @@ class spt_denoise_params(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class spt_pair_summary(ctypes.Structure):
+    _fields_ = [("rmse", ctypes.c_double * 3), ("rmse_all", ctypes.c_double),
+                ("diff_max", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"rmse": [float(x) for x in self.rmse], "rmse_all": float(self.rmse_all),
+                "diff_max": float(self.diff_max)}
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -169,7 +178,11 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_guide_info_get", "spt_guide_render_async", "spt_guide_resolve", "spt_guide_download",
            "spt_guide_resolve_host",
            "spt_denoise_default_params", "spt_denoiser_create", "spt_denoiser_destroy",
-           "spt_denoise_async", "spt_denoise_host", "spt_film_denoise"]
+           "spt_denoise_async", "spt_denoise_host", "spt_film_denoise",
+           "spt_denoise_pair_async", "spt_denoise_pair_host", "spt_denoise_pair_summary",
+           "spt_denoise_pair_summary_host", "spt_film_pair_denoise"]
+SPT_HAS_DENOISE_PAIR = 1    # include/spt.h: the two-half filter (denoise_pair_host, Denoiser.denoise_pair, ...)
+DENOISE_PAIR_OWN_WEIGHTS = 1  # SPT_DENOISE_PAIR_OWN_WEIGHTS: each half weighted by its own colours
 SPT_HAS_DENOISE = 1         # include/spt.h: the a-trous filter (Denoiser, denoise_host, render_denoised)
 DENOISE_NO_DEMODULATE = 1   # SPT_DENOISE_NO_DEMODULATE: filter rgb itself, not rgb / albedo
 SPT_HAS_GUIDE = 1           # include/spt.h: the spt_guide_* calls (Guide, render_guides)
@@ -333,7 +346,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_denoise_async.argtypes = [VP, VP, VP, VP, VP, VP, P(spt_denoise_params), VP, VP, VP]
     lib.spt_denoise_host.argtypes = [VP, VP, VP, VP, VP, I32, I32, P(spt_denoise_params), VP, VP]
     lib.spt_film_denoise.argtypes = [VP, VP, VP, P(spt_denoise_params), VP, VP, VP]
-    for name in ("spt_denoiser_create", "spt_denoiser_destroy", "spt_denoise_async", "spt_denoise_host"):
+    lib.spt_denoise_pair_async.argtypes = [VP] + [VP] * 7 + [P(spt_denoise_params), ctypes.c_uint32, VP, VP,
+                                                             VP, VP]
+    lib.spt_denoise_pair_host.argtypes = [VP] * 7 + [I32, I32, P(spt_denoise_params), ctypes.c_uint32, VP,
+                                                     VP, VP]
+    lib.spt_denoise_pair_summary.argtypes = [VP, VP, P(spt_pair_summary), VP]
+    lib.spt_denoise_pair_summary_host.argtypes = [VP, I32, I32, P(spt_pair_summary)]
+    lib.spt_film_pair_denoise.argtypes = [VP, VP, VP, VP, P(spt_denoise_params), ctypes.c_uint32, VP, VP,
+                                          VP, VP]
+    for name in ("spt_denoiser_create", "spt_denoiser_destroy", "spt_denoise_async", "spt_denoise_host",
+                 "spt_denoise_pair_async", "spt_denoise_pair_host", "spt_denoise_pair_summary",
+                 "spt_denoise_pair_summary_host"):
         getattr(lib, name).restype = I32
     for name in EXPORTS:
         if name.startswith("spt_film_") or name.startswith("spt_guide_"):
@@ -1383,6 +1406,49 @@ def denoise_host(rgb, se, albedo, normal, depth, params: spt_denoise_params | No
     return (out, se_out) if return_se else out
 
 
+def _pair_planes(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth):
+    """The seven planes of a pair as contiguous float32 arrays, and (height, width) from rgb_a."""
+    planes, h, w = _denoise_planes(rgb_a, se_a, albedo, normal, depth)
+    half_b = [np.ascontiguousarray(a, dtype=np.float32) for a in (rgb_b, se_b)]
+    for a, name in zip(half_b, ("rgb_b", "se_b")):
+        if a.size != h * w * 3:
+            raise SptError(1, f"{name} does not have height * width * 3 elements")
+    return [planes[0], planes[1], half_b[0], half_b[1]] + planes[2:], h, w
+
+
+def _pair_flags(own_weights) -> int:
+    return DENOISE_PAIR_OWN_WEIGHTS if own_weights is True else int(own_weights)
+
+
+def denoise_pair_host(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth,
+                      params: spt_denoise_params | None = None, own_weights=False, return_se=True,
+                      return_diff=True):
+    """spt_denoise_pair_host(): the CPU statement of the two-half filter (no device). own_weights: a
+    bool, or the pair_flags word itself. -> (out, se_out, diff), each (h, w, 3) float32; a plane that
+    was not asked for is None (and NULL in the call)."""
+    planes, h, w = _pair_planes(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth)
+    p = params if params is not None else default_denoise_params()
+    out = np.empty((h, w, 3), np.float32)
+    se_out = np.empty((h, w, 3), np.float32) if return_se else None
+    diff = np.empty((h, w, 3), np.float32) if return_diff else None
+    _check(load_library().spt_denoise_pair_host(
+        *[a.ctypes.data for a in planes], w, h, ctypes.byref(p), _pair_flags(own_weights), out.ctypes.data,
+        se_out.ctypes.data if return_se else None, diff.ctypes.data if return_diff else None))
+    return out, se_out, diff
+
+
+def pair_summary_host(diff) -> dict:
+    """spt_denoise_pair_summary_host(): {"rmse": [r, g, b], "rmse_all", "diff_max"} of a diff plane
+    (h, w, 3)."""
+    d = np.ascontiguousarray(diff, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 3:
+        raise SptError(1, "diff is not (height, width, 3)")
+    out = spt_pair_summary()
+    _check(load_library().spt_denoise_pair_summary_host(d.ctypes.data, d.shape[1], d.shape[0],
+                                                        ctypes.byref(out)))
+    return out.as_dict()
+
+
 class Denoiser:
     """spt_denoiser: the filter's scratch for width x height images on one device. Calls on one
     denoiser go on one stream."""
@@ -1464,6 +1530,86 @@ class Denoiser:
             return self._host(out, se_out)
 
 
+    # ---- the two-half filter (spt_denoise_pair_*, spt_film_pair_denoise) ----
+    def _pair_outputs(self):
+        import torch
+        n = self.width * self.height * 3
+        return [torch.empty(n, dtype=torch.float32, device=f"cuda:{self.device}") for _ in range(3)]
+
+    def _pair_host(self, bufs):
+        import torch
+        torch.cuda.synchronize(self.device)
+        return tuple(b.cpu().numpy().reshape(self.height, self.width, 3) for b in bufs)
+
+    def denoise_pair_async(self, rgb_a_ptr: int, se_a_ptr: int, rgb_b_ptr: int, se_b_ptr: int,
+                           albedo_ptr: int, normal_ptr: int, depth_ptr: int, params: spt_denoise_params,
+                           pair_flags: int, out_ptr: int, se_out_ptr: int = 0, diff_ptr: int = 0,
+                           stream_ptr: int = 0):
+        """spt_denoise_pair_async() on device pointers."""
+        V = ctypes.c_void_p
+        ins = (rgb_a_ptr, se_a_ptr, rgb_b_ptr, se_b_ptr, albedo_ptr, normal_ptr, depth_ptr)
+        _check(self.lib.spt_denoise_pair_async(self._d, *[V(x or None) for x in ins], ctypes.byref(params),
+                                               int(pair_flags), V(out_ptr or None), V(se_out_ptr or None),
+                                               V(diff_ptr or None), V(stream_ptr or None)))
+
+    def denoise_pair(self, rgb_a, se_a, rgb_b, se_b, albedo, normal, depth,
+                     params: spt_denoise_params | None = None, own_weights=False):
+        """Host arrays in (uploaded through torch) -> (out, se_out, diff) on the host, (h, w, 3) each."""
+        import torch
+        planes, h, w = _pair_planes(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth)
+        if (h, w) != (self.height, self.width):
+            raise SptError(1, "the planes are not the denoiser's height x width")
+        p = params if params is not None else default_denoise_params()
+        with torch.cuda.device(self.device):
+            dev = [torch.from_numpy(a.reshape(-1)).to(f"cuda:{self.device}") for a in planes]
+            bufs = self._pair_outputs()
+            self.denoise_pair_async(*[t.data_ptr() for t in dev], p, _pair_flags(own_weights),
+                                    *[b.data_ptr() for b in bufs], torch.cuda.current_stream().cuda_stream)
+            return self._pair_host(bufs)
+
+    def denoise_film_pair_async(self, film_a: "Film", film_b: "Film", guide: "Guide",
+                                params: spt_denoise_params, pair_flags: int, out_ptr: int,
+                                se_out_ptr: int = 0, diff_ptr: int = 0, stream_ptr: int = 0):
+        """spt_film_pair_denoise() into device pointers."""
+        V = ctypes.c_void_p
+        _check(self.lib.spt_film_pair_denoise(film_a._f, film_b._f, guide._g, self._d, ctypes.byref(params),
+                                              int(pair_flags), V(out_ptr or None), V(se_out_ptr or None),
+                                              V(diff_ptr or None), V(stream_ptr or None)))
+
+    def denoise_film_pair(self, film_a: "Film", film_b: "Film", guide: "Guide",
+                          params: spt_denoise_params | None = None, own_weights=False, return_summary=False):
+        """Both films' images and error maps and the guide's planes resolved and pair-filtered on the
+        device in one call -> (out, se_out, diff) on the host; return_summary: also pair_summary of diff."""
+        import torch
+        p = params if params is not None else default_denoise_params()
+        with torch.cuda.device(self.device):
+            bufs = self._pair_outputs()
+            stream = torch.cuda.current_stream().cuda_stream
+            self.denoise_film_pair_async(film_a, film_b, guide, p, _pair_flags(own_weights),
+                                         *[b.data_ptr() for b in bufs], stream)
+            summary = self.pair_summary(bufs[2].data_ptr(), stream) if return_summary else None
+            res = self._pair_host(bufs)
+            return res + (summary,) if return_summary else res
+
+    def pair_summary(self, diff, stream_ptr: int = 0) -> dict:
+        """spt_denoise_pair_summary(): {"rmse": [r, g, b], "rmse_all", "diff_max"} of a diff plane: a
+        device pointer (int), or a host array (h, w, 3) that is uploaded first; waits for the stream."""
+        import torch
+        out = spt_pair_summary()
+        with torch.cuda.device(self.device):
+            keep = None
+            if not isinstance(diff, int):
+                d = np.ascontiguousarray(diff, dtype=np.float32)
+                if d.size != self.width * self.height * 3:
+                    raise SptError(1, "diff does not have height * width * 3 elements")
+                keep = torch.from_numpy(d.reshape(-1)).to(f"cuda:{self.device}")
+                diff = keep.data_ptr()
+                stream_ptr = stream_ptr or torch.cuda.current_stream().cuda_stream
+            _check(self.lib.spt_denoise_pair_summary(self._d, ctypes.c_void_p(diff or None), ctypes.byref(out),
+                                                     ctypes.c_void_p(stream_ptr or None)))
+        return out.as_dict()
+
+
 def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, batch: int | None = None,
                     guide_spp: int | None = None, denoise: spt_denoise_params | None = None,
                     return_info=False, through_specular: bool = False):
@@ -1502,6 +1648,121 @@ def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, 
         if dn is not None:
             dn.close()
         guide.close()
+
+
+def _pair_batch(who: str, params: spt_params, batch):
+    """The batch size of a pair render: spp / batch even and at least 4 (two batches per half)."""
+    spp = int(params.spp)
+    if params.shard_count > 1:
+        raise SptError(1, f"{who}: a shard's rows are not image neighbours; gather the planes")
+    if batch is None:
+        if spp % 8:
+            raise SptError(1, f"{who}: spp is no multiple of 8, give batch")
+        batch = spp // 8
+    if batch < 1 or spp % batch or (spp // batch) % 2 or spp // batch < 4:
+        raise SptError(1, f"{who}: batch must divide spp into an even number of batches, at least 4")
+    return int(batch)
+
+
+@_contextmanager
+def _pair_session(params: spt_params, batch: int, through_specular: bool):
+    """-> (renderer, film A, film B, guide, denoiser, stream) on params.device; everything is closed
+    on the way out. The films are noise films of `batch`."""
+    import torch
+    made = []
+    try:
+        r = Renderer(params.device)
+        made.append(r)
+        films = []
+        for _ in range(2):
+            f = Film(params, params.device)
+            made.append(f)
+            f.enable_noise(batch)
+            films.append(f)
+        guide = Guide(params, params.device, through_specular)
+        made.append(guide)
+        dn = Denoiser(params.width, params.height, params.device)
+        made.append(dn)
+        with torch.cuda.device(params.device):
+            yield r, films[0], films[1], guide, dn, torch.cuda.current_stream().cuda_stream
+    finally:
+        for o in reversed(made):
+            o.close()
+
+
+def render_denoised_pair(prims: Sequence[spt_prim], cam: Camera, params: spt_params,
+                         batch: int | None = None, guide_spp: int | None = None,
+                         denoise: spt_denoise_params | None = None, own_weights: bool = False,
+                         through_specular: bool = False, return_info=False):
+    """Render all params.spp samples into TWO noise films (batch k of `batch` samples, default spp / 8,
+    into film A when k is even and into film B when it is odd; spp / batch must be even and at least
+    4), fill a guide as render_denoised does, and return the two-half filter's image
+    (Denoiser.denoise_film_pair). The default is cross weights: they give the better image (README);
+    own_weights=True gives the error estimate that means what it says. One device. return_info: also
+    {"diff": half the difference of the halves' results, "se": the propagated se_out, "pair": the
+    summary of diff, "guides": the guide planes, "noisy": the resolve of A merged with B in a third
+    film, which is render()'s image bit for bit}."""
+    spp = int(params.spp)
+    batch = _pair_batch("render_denoised_pair", params, batch)
+    n_guide = min(spp, int(guide_spp or 64))
+    with _pair_session(params, batch, through_specular) as (r, fa, fb, guide, dn, stream):
+        for k in range(spp // batch):
+            (fb if k & 1 else fa).render(r, prims, cam, params, k * batch, batch, 0, stream)
+            r.stats()  # a pass that hit the runaway guard raises here
+        guide.render(r, prims, cam, params, 0, n_guide, stream)
+        out, se, diff, pair = dn.denoise_film_pair(fa, fb, guide, denoise, own_weights, return_summary=True)
+        if not return_info:
+            return out
+        merged = Film(params, params.device)
+        try:
+            merged.enable_noise(batch)
+            merged.merge(fa, stream)
+            merged.merge(fb, stream)
+            buf = _film_buffer(merged)
+            merged.resolve(buf.data_ptr(), stream)
+            noisy = _film_image(merged, buf)
+        finally:
+            merged.close()
+        return out, {"diff": diff, "se": se, "pair": pair, "guides": guide.resolve(stream_ptr=stream),
+                     "noisy": noisy}
+
+
+def render_denoised_until(prims: Sequence[spt_prim], cam: Camera, params: spt_params, target_rmse: float,
+                          batch: int | None = None, min_batches: int = 4, own_weights: bool = True,
+                          guide_spp: int | None = None, denoise: spt_denoise_params | None = None,
+                          through_specular: bool = False):
+    """Render until the DENOISED image's measured error is at most target_rmse. The guide is rendered
+    first; batches of `batch` samples go in index order alternately into film A (even k) and film B
+    (odd k), params.spp the cap. After every second batch from min_batches on (rounded up to an even
+    number, at least 4) the two-half filter runs and the summary of diff is read; the render stops once
+    max(rmse) <= target_rmse. -> (the denoised image, {"samples_done", "batches_done", "rmse"}).
+    The default is own weights, because the stopping number must mean what it says. Measured on
+    renders (HEAD and mirror_glass, 256x192, 16 seeds, 64 / 256 / 1024 spp): the
+    mean diff^2 over the variance of the result across seeds is 0.99-1.00 with own weights (the halves
+    are independent, so this is exact in expectation) and 0.81 / 0.68 / 0.55 (HEAD), 0.72 / 0.55 / 0.42
+    (mirror_glass) with cross weights, where the halves' results correlate. Over the true squared error
+    against a 65536-spp render: 0.76-0.88 with own weights (the true RMSE is 1.06-1.15x the figure this
+    call stops on), 0.26-0.46 with cross weights. Both read variance only: the filter's bias is not in
+    diff (include/spt.h)."""
+    spp = int(params.spp)
+    batch = _pair_batch("render_denoised_until", params, batch)
+    need = max(4, int(min_batches) + (int(min_batches) & 1))
+    n_guide = min(spp, int(guide_spp or 64))
+    with _pair_session(params, batch, through_specular) as (r, fa, fb, guide, dn, stream):
+        guide.render(r, prims, cam, params, 0, n_guide, stream)
+        out = rmse = None
+        done = 0
+        for k in range(spp // batch):
+            (fb if k & 1 else fa).render(r, prims, cam, params, k * batch, batch, 0, stream)
+            r.stats()  # a pass that hit the runaway guard raises here
+            done = k + 1
+            if done >= need and done % 2 == 0:
+                out, _se, _diff, pair = dn.denoise_film_pair(fa, fb, guide, denoise, own_weights,
+                                                             return_summary=True)
+                rmse = pair["rmse"]
+                if max(rmse) <= target_rmse:
+                    break
+        return out, {"samples_done": done * batch, "batches_done": done, "rmse": rmse}
 
 
 def render_multi(prims: Sequence[spt_prim], cam: Camera, params: spt_params, devices,

@@ -3,8 +3,19 @@
 //               [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]
 //               [--device N | --devices N] [--p6 | --pfm]
 //               [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]
-//               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]]
-//               [--through-specular] [--help]
+//               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]
+//               [--pair [--pair-own]]] [--through-specular] [--help]
+//   --pair (with --denoise): two-half denoising (spt_film_pair_denoise). The batches go alternately
+//               into two noise films (even batch indices into A, odd into B; SPP / B must be even and
+//               at least 4), each half is filtered with colour weights taken from the other half, and
+//               the output is the mean of the two results. Prints "PAIR : r g b after N / SPP", the RMS
+//               of half the difference of the two results per channel (spt_denoise_pair_summary).
+//               --pair-own: each half is weighted by its own colours (SPT_DENOISE_PAIR_OWN_WEIGHTS):
+//               the image of the single filter, and a PAIR figure that is an unbiased estimate of the
+//               output's variance (with cross weights it reads low, include/spt.h). With --noise T the
+//               run stops on that figure instead of the film's: after every second batch from
+//               --min-batches (default 4) on, once the largest channel's is at most T. Not with
+//               --adaptive, --film or --passes.
 //   --through-specular: with --guides and / or --denoise, the guide follows mirrors and glass to the
 //               first diffuse surface (spt_guide_create_ex, SPT_GUIDE_THROUGH_SPECULAR); alone it is a
 //               usage error.
@@ -105,6 +116,7 @@ struct DenoiseOpts {
   bool through_specular = false;                  // the guide follows the specular chain
   int iters = 0;
   double sigma = 0.0;
+  bool pair = false, pair_own = false;  // --pair [--pair-own]: two films, spt_film_pair_denoise
 };
 
 void check(spt_status s) {
@@ -267,6 +279,65 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
   return dev;
 }
 
+// --denoise --pair: the batches alternately into two noise films, the guide, the two-half filter. With
+// noise.target > 0 the filter runs after every second batch from noise.min_batches on and the run ends
+// once the largest channel's RMS half-difference is at most the target. Returns the DEVICE image.
+float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
+                   const NoiseOpts& noise, const DenoiseOpts& denoise, spt_stats* total) {
+  if (noise.batch <= 0 && p.spp % 8 != 0) throw std::runtime_error("--pair: SPP is no multiple of 8, give --batch");
+  const int batch = noise.batch > 0 ? noise.batch : p.spp / 8;
+  if (p.spp % batch != 0 || (p.spp / batch) % 2 != 0 || p.spp / batch < 4)
+    throw std::runtime_error("--pair: the batch must divide SPP into an even number of batches, at least 4");
+  spt_denoise_params dp;
+  spt_denoise_default_params(&dp);
+  if (denoise.iters_given) dp.iterations = denoise.iters;
+  if (denoise.sigma_given) dp.sigma_color = (float)denoise.sigma;
+  const uint32_t pair_flags = denoise.pair_own ? SPT_DENOISE_PAIR_OWN_WEIGHTS : 0u;
+  spt_context* ctx = nullptr;
+  spt_film* film[2] = {nullptr, nullptr};
+  spt_guide* guide = nullptr;
+  spt_denoiser* dn = nullptr;
+  check(spt_context_create(p.device, &ctx));
+  for (spt_film*& f : film) {
+    check(spt_film_create(p.device, &p, &f));
+    check(spt_film_noise_enable(f, batch));
+  }
+  check(spt_guide_create_ex(p.device, &p, denoise.through_specular ? SPT_GUIDE_THROUGH_SPECULAR : 0u, &guide));
+  check(spt_denoiser_create(p.device, p.width, p.height, &dn));
+  const size_t n = 3ull * (size_t)p.width * (size_t)p.height;
+  float* dev = nullptr;  // out, then diff
+  if (hipMalloc(&dev, std::max<size_t>(n, 1) * 2 * sizeof(float)) != hipSuccess)
+    throw std::runtime_error("device allocation failed");
+  std::memset(total, 0, sizeof *total);
+  check(spt_guide_render_async(ctx, guide, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
+                               std::min(p.spp, 64), nullptr));
+  const int batches = p.spp / batch, need = std::max(4, noise.min_batches + (noise.min_batches & 1));
+  spt_pair_summary sm{};
+  int done = 0;
+  for (int k = 0; k < batches; ++k) {
+    check(spt_film_render_async(ctx, film[k & 1], scene.data(), (int32_t)scene.size(), &cam.abi(), &p,
+                                k * batch, batch, nullptr, nullptr));
+    spt_stats st{};
+    check(spt_context_stats(ctx, &st));
+    total->samples += st.samples;
+    total->vertices += st.vertices;
+    total->kernel_ms += st.kernel_ms;
+    done = k + 1;
+    const bool look = noise.target > 0.0 && done >= need && done % 2 == 0;
+    if (!look && done < batches) continue;
+    check(spt_film_pair_denoise(film[0], film[1], guide, dn, &dp, pair_flags, dev, nullptr, dev + n, nullptr));
+    check(spt_denoise_pair_summary(dn, dev + n, &sm, nullptr));
+    if (look && std::max(sm.rmse[0], std::max(sm.rmse[1], sm.rmse[2])) <= noise.target) break;
+  }
+  std::cout << "PAIR : " << sm.rmse[0] << " " << sm.rmse[1] << " " << sm.rmse[2] << " after "
+            << (int64_t)done * batch << " / " << p.spp << std::endl;
+  check(spt_denoiser_destroy(dn));
+  check(spt_guide_destroy(guide));
+  for (spt_film* f : film) check(spt_film_destroy(f));
+  check(spt_context_destroy(ctx));
+  return dev;
+}
+
 // --guides: the guide planes of the full window, resolved on the device and written as three PFMs.
 void write_guides(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
                   const std::string& prefix, bool through_specular) {
@@ -305,8 +376,8 @@ const char kUsage[] =
     "            [--device N | --devices N] [--p6 | --pfm] [--repeat N] [--passes K]\n"
     "            [--film PATH [--add N]]\n"
     "            [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]\n"
-    "            [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]]\n"
-    "            [--through-specular]\n"
+    "            [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]\n"
+    "            [--pair [--pair-own]]] [--through-specular]\n"
     "  --guides PREFIX  also write the first-hit guide planes PREFIX_albedo.pfm, PREFIX_normal.pfm\n"
     "                   and PREFIX_depth.pfm (linear PFM). The normal is stored signed, components\n"
     "                   in [-1, 1] (not 0.5 + 0.5 n); the depth is the mean ray parameter of the\n"
@@ -317,7 +388,14 @@ const char kUsage[] =
     "  --through-specular  with --guides and/or --denoise: the guide follows mirrors and glass to\n"
     "                   the first diffuse surface (at most 8 segments)\n"
     "  --denoise-iters N  filter iterations, 0..6 (default 5)\n"
-    "  --denoise-sigma S  the colour sigma (default 4)\n";
+    "  --denoise-sigma S  the colour sigma (default 4)\n"
+    "  --pair           with --denoise: two-half denoising. The batches go alternately into two films\n"
+    "                   (SPP / batch even, at least 4), each half is filtered with colour weights\n"
+    "                   from the other half, the output is the mean of the two results; prints PAIR,\n"
+    "                   the RMS of half their difference. With --noise T the run stops on that figure.\n"
+    "                   Not with --adaptive, --film or --passes.\n"
+    "  --pair-own       with --pair: each half weighted by its own colours; the PAIR figure is then an\n"
+    "                   unbiased estimate of the output's variance (with cross weights it reads low)\n";
 
 }  // namespace
 
@@ -358,6 +436,8 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--guides") && i + 1 < argc) guides = argv[++i];
     else if (!std::strcmp(argv[i], "--denoise")) denoise.on = true;
     else if (!std::strcmp(argv[i], "--through-specular")) denoise.through_specular = true;
+    else if (!std::strcmp(argv[i], "--pair")) denoise.pair = true;
+    else if (!std::strcmp(argv[i], "--pair-own")) denoise.pair_own = true;
     else if (!std::strcmp(argv[i], "--denoise-iters") && i + 1 < argc) { denoise.iters_given = true; denoise.iters = std::atoi(argv[++i]); }
     else if (!std::strcmp(argv[i], "--denoise-sigma") && i + 1 < argc) { denoise.sigma_given = true; denoise.sigma = std::atof(argv[++i]); }
     else if (!std::strcmp(argv[i], "--help")) { std::cout << kUsage; return 0; }
@@ -395,6 +475,8 @@ int main(int argc, char* argv[]) {
     if (guides) guide_scene = scene;
     if ((denoise.iters_given || denoise.sigma_given) && !denoise.on)
       throw std::runtime_error("--denoise-iters / --denoise-sigma go with --denoise");
+    if ((denoise.pair || denoise.pair_own) && !denoise.on) throw std::runtime_error("--pair goes with --denoise");
+    if (denoise.pair_own && !denoise.pair) throw std::runtime_error("--pair-own goes with --pair");
     if (denoise.on) {
       if (devices > 1) throw std::runtime_error("--denoise goes with one device: a shard's rows are not image neighbours");
       if (denoise.iters_given && (denoise.iters < 0 || denoise.iters > 6))
@@ -414,7 +496,10 @@ int main(int argc, char* argv[]) {
         throw std::runtime_error("--pool: the radius is 1..16");
       if (noise.adaptive && film_path)
         throw std::runtime_error("--adaptive does not go with --film: the counts plane has no file format");
-      image = render_film(scene, cam, p, passes, film_path, add, noise, denoise, &st);
+      if (denoise.pair && (noise.adaptive || film_path || passes > 0))
+        throw std::runtime_error("--pair does not go with --adaptive, --film or --passes");
+      image = denoise.pair ? render_pair(scene, cam, p, noise, denoise, &st)
+                           : render_film(scene, cam, p, passes, film_path, add, noise, denoise, &st);
       repeat = 0;
     }
     for (int k = 0; k < repeat; ++k) {

@@ -1,7 +1,7 @@
 // spt_denoise.h — the edge-stopping a-trous filter's arithmetic, stated once for the kernels
 // (spt_denoise.hip) and for the CPU statement (spt_denoise_host.cpp, plain C++: it runs under the host
-// sanitizers). Internal: the public statement is include/spt.h (SPT_HAS_DENOISE). Needs
-// -ffp-contract=off on both sides. IEEE fp32 + - * /, fmaxf, fminf, fabsf and sqrtf only.
+// sanitizers). Internal: the public statement is include/spt.h (SPT_HAS_DENOISE, SPT_HAS_DENOISE_PAIR).
+// Needs -ffp-contract=off on both sides. IEEE fp32 + - * /, fmaxf, fminf, fabsf and sqrtf only.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -180,6 +180,127 @@ SPT_FILM_FN void finish(const f4& cv, const f4& av, const Args& A, float* out, f
     se_out[1] = s * a1;
     se_out[2] = s * a2;
   }
+}
+
+// ---- the two-half filter (include/spt.h, SPT_HAS_DENOISE_PAIR) ----
+// Two runs of the filter above over the halves A and B that share the guides, fused tap by tap: the
+// geometric factor g of a tap is computed once, each half has its own colour weight, and a half
+// accumulates with the other half's colour weight (cross) or with its own (own). g * w_c is acc_tap's
+// product in acc_tap's association order, so equal halves give the single filter's bits.
+
+// NULL when the pair flags are known, else what is wrong with them.
+inline const char* pair_flags_error(uint32_t pair_flags) {
+  return (pair_flags & ~SPT_DENOISE_PAIR_OWN_WEIGHTS) ? "unknown pair_flags bits" : nullptr;
+}
+
+SPT_FILM_FN void acc_add(Acc& a, float w, const f4& cvq) {
+  a.w = a.w + w;
+  a.c0 = a.c0 + w * cvq.x;
+  a.c1 = a.c1 + w * cvq.y;
+  a.c2 = a.c2 + w * cvq.z;
+  a.v = a.v + (w * w) * cvq.w;
+}
+
+// One tap that is not the centre, for both halves. av.w holds vt of half A; vtb is half B's vt.
+SPT_FILM_FN void acc_tap_pair(Acc& a, Acc& b, int i, int j, int32_t step, const f4& cap, const f4& cbp,
+                              const f4& nzp, const f4& avp, float vtbp, float gx, float gy, const f4& caq,
+                              const f4& cbq, const f4& nzq, const f4& avq, float vtbq, const Args& A,
+                              bool own) {
+  float wn = fmaxf(0.0f, dot3(nzp.x, nzp.y, nzp.z, nzq.x, nzq.y, nzq.z));
+  for (int k = 0; k < A.squarings; ++k) wn = wn * wn;
+  const float dx = (float)(i * step), dy = (float)(j * step);
+  const float wz = phi(fabsf(nzp.w - nzq.w) / ((A.sd * fabsf(gx * dx + gy * dy) + 1e-3f * nzp.w) + 1e-6f));
+  const float a0 = avp.x - avq.x, a1 = avp.y - avq.y, a2 = avp.z - avq.z;
+  const float wa = phi(dot3(a0, a1, a2, a0, a1, a2) / A.sa2);
+  const float g = (((h5(j) * h5(i)) * wn) * wz) * wa;
+  const float d0 = cap.x - caq.x, d1 = cap.y - caq.y, d2 = cap.z - caq.z;
+  const float wca = phi(dot3(d0, d1, d2, d0, d1, d2) / (A.sc2 * (avp.w + avq.w) + 1e-10f));
+  const float e0 = cbp.x - cbq.x, e1 = cbp.y - cbq.y, e2 = cbp.z - cbq.z;
+  const float wcb = phi(dot3(e0, e1, e2, e0, e1, e2) / (A.sc2 * (vtbp + vtbq) + 1e-10f));
+  acc_add(a, g * (own ? wca : wcb), caq);
+  acc_add(b, g * (own ? wcb : wca), cbq);
+}
+
+// One pixel of one iteration of both halves. Planes: any accessor with f4 ca(x, y), cb(x, y), nz(x, y),
+// av(x, y) and float vtb(x, y).
+template <class Planes>
+SPT_FILM_FN void iterate_pair(const Planes& P, int32_t x, int32_t y, int32_t w, int32_t h, int32_t step,
+                              float gx, float gy, const Args& A, bool own, f4* ra, f4* rb) {
+  const f4 cap = P.ca(x, y), cbp = P.cb(x, y), nzp = P.nz(x, y), avp = P.av(x, y);
+  const float vtbp = P.vtb(x, y);
+  Acc a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  for (int j = -2; j <= 2; ++j) {
+    const int64_t yy = (int64_t)y + (int64_t)j * step;
+    if (yy < 0 || yy >= h) continue;
+    for (int i = -2; i <= 2; ++i) {
+      const int64_t xx = (int64_t)x + (int64_t)i * step;
+      if (xx < 0 || xx >= w) continue;
+      if (i == 0 && j == 0) {
+        acc_centre(a, cap);
+        acc_centre(b, cbp);
+      } else {
+        const int32_t qx = (int32_t)xx, qy = (int32_t)yy;
+        acc_tap_pair(a, b, i, j, step, cap, cbp, nzp, avp, vtbp, gx, gy, P.ca(qx, qy), P.cb(qx, qy),
+                     P.nz(qx, qy), P.av(qx, qy), P.vtb(qx, qy), A, own);
+      }
+    }
+  }
+  *ra = acc_result(a);
+  *rb = acc_result(b);
+}
+
+// The pair's outputs from the two remodulated, clamped halves oa, ob (3 floats each).
+SPT_FILM_FN void pair_combine(const float* oa, const float* ob, float* out, float* diff) {
+  for (int k = 0; k < 3; ++k) {
+    out[k] = 0.5f * (oa[k] + ob[k]);
+    if (diff) diff[k] = 0.5f * (oa[k] - ob[k]);
+  }
+}
+
+// Finish of the pair: each half remodulated and clamped, their mean, half their difference, and the
+// propagated standard error of the mean.
+SPT_FILM_FN void finish_pair(const f4& ca, const f4& cb, const f4& av, const Args& A, float* out,
+                             float* se_out, float* diff) {
+  const float a[3] = {divisor(av.x, A), divisor(av.y, A), divisor(av.z, A)};
+  const float oa[3] = {fminf(ca.x * a[0], 1.0f), fminf(ca.y * a[1], 1.0f), fminf(ca.z * a[2], 1.0f)};
+  const float ob[3] = {fminf(cb.x * a[0], 1.0f), fminf(cb.y * a[1], 1.0f), fminf(cb.z * a[2], 1.0f)};
+  pair_combine(oa, ob, out, diff);
+  if (se_out) {
+    const float s = 0.5f * sqrtf(ca.w + cb.w);
+    se_out[0] = s * a[0];
+    se_out[1] = s * a[1];
+    se_out[2] = s * a[2];
+  }
+}
+
+// iterations == 0: the halves as given.
+SPT_FILM_FN void finish_pair_zero(const float* rgb_a, const float* se_a, const float* rgb_b,
+                                  const float* se_b, float* out, float* se_out, float* diff) {
+  pair_combine(rgb_a, rgb_b, out, diff);
+  if (se_out)
+    for (int k = 0; k < 3; ++k) se_out[k] = 0.5f * sqrtf(se_a[k] * se_a[k] + se_b[k] * se_b[k]);
+}
+
+// The summary of a diff plane: the sums of (double)diff_k^2 and the largest |diff|.
+struct PairPartial {
+  double s[3];
+  float diff_max;
+};
+
+SPT_FILM_FN void pair_partial_add(PairPartial& p, const float* diff) {
+  for (int k = 0; k < 3; ++k) {
+    const double d = (double)diff[k];
+    p.s[k] += d * d;
+    p.diff_max = fmaxf(p.diff_max, fabsf(diff[k]));
+  }
+}
+
+inline void pair_summary_finish(const PairPartial& t, size_t npix, spt_pair_summary* out) {
+  const double n = (double)npix;
+  for (int k = 0; k < 3; ++k) out->rmse[k] = std::sqrt(t.s[k] / n);
+  out->rmse_all = std::sqrt(((t.s[0] + t.s[1]) + t.s[2]) / (3.0 * n));
+  out->diff_max = t.diff_max;
+  out->reserved = 0;
 }
 
 }  // namespace spt_denoise_math

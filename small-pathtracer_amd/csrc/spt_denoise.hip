@@ -1,7 +1,9 @@
 // spt_denoise.hip — the edge-stopping a-trous filter on the device (include/spt.h, SPT_HAS_DENOISE):
 // the denoiser object that owns the scratch, the pack, variance and a-trous kernels and the
-// spt_denoise_* / spt_film_denoise calls. The arithmetic is spt_denoise.h's, shared with the CPU
-// statement (spt_denoise_host.cpp): the kernels only decide which lane takes which pixel.
+// spt_denoise_* / spt_film_denoise calls, and the two-half filter (SPT_HAS_DENOISE_PAIR): its pack,
+// variance, a-trous and summary kernels, its scratch, and the spt_denoise_pair_* / spt_film_pair_denoise
+// calls. The arithmetic is spt_denoise.h's, shared with the CPU statement (spt_denoise_host.cpp): the
+// kernels only decide which lane takes which pixel.
 #include <hip/hip_runtime.h>
 
 #include <initializer_list>
@@ -22,6 +24,13 @@ struct spt_denoiser {
   float2* grad = nullptr;
   // the film path's planes (spt_film_denoise): rgb, se, albedo, normal (3 floats each), depth (1)
   float *rgb = nullptr, *se = nullptr, *albedo = nullptr, *normal = nullptr, *depth = nullptr;
+  // the pair scratch (SPT_HAS_DENOISE_PAIR), allocated by the first pair call: half B's ping-pong
+  // planes and vt, the second film's rgb and se, the summary's partials and total
+  void* pair_base = nullptr;
+  f4* cb[2] = {nullptr, nullptr};
+  float *vtb = nullptr, *rgb_b = nullptr, *se_b = nullptr;
+  double* parts = nullptr;
+  uint32_t n_parts = 0;
 };
 
 namespace {
@@ -145,6 +154,201 @@ denoise_atrous_lds_kernel(const f4* __restrict__ cv, const f4* __restrict__ nz, 
     cv_out[i] = r;
 }
 
+// ---- the two-half filter (SPT_HAS_DENOISE_PAIR): iterate_pair() on the 64 x 4 tiling ----
+
+struct DevPairPlanes {
+  const f4 *ca_, *cb_, *nz_, *av_;
+  const float* vtb_;
+  int32_t w;
+  __device__ __forceinline__ f4 ca(int32_t x, int32_t y) const { return ca_[(size_t)y * w + x]; }
+  __device__ __forceinline__ f4 cb(int32_t x, int32_t y) const { return cb_[(size_t)y * w + x]; }
+  __device__ __forceinline__ f4 nz(int32_t x, int32_t y) const { return nz_[(size_t)y * w + x]; }
+  __device__ __forceinline__ f4 av(int32_t x, int32_t y) const { return av_[(size_t)y * w + x]; }
+  __device__ __forceinline__ float vtb(int32_t x, int32_t y) const { return vtb_[(size_t)y * w + x]; }
+};
+
+// Pack of the pair: seven planes in; both halves' (c, v), the packed guides and the gradient out.
+__global__ void __launch_bounds__(kBlock)
+denoise_pair_pack_kernel(const float* __restrict__ rgb_a, const float* __restrict__ se_a,
+                         const float* __restrict__ rgb_b, const float* __restrict__ se_b,
+                         const float* __restrict__ albedo, const float* __restrict__ normal,
+                         const float* __restrict__ depth, int32_t w, int32_t h, Args A, f4* __restrict__ ca,
+                         f4* __restrict__ cb, f4* __restrict__ nz, f4* __restrict__ av,
+                         float2* __restrict__ grad) {
+  int32_t x, y;
+  if (!pixel_of(w, h, &x, &y)) return;
+  const size_t i = (size_t)y * w + x;
+  const float a[3] = {albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2]};
+  const float c0[3] = {rgb_a[3 * i], rgb_a[3 * i + 1], rgb_a[3 * i + 2]};
+  const float e0[3] = {se_a[3 * i], se_a[3 * i + 1], se_a[3 * i + 2]};
+  const float c1[3] = {rgb_b[3 * i], rgb_b[3 * i + 1], rgb_b[3 * i + 2]};
+  const float e1[3] = {se_b[3 * i], se_b[3 * i + 1], se_b[3 * i + 2]};
+  const float z = depth[i];
+  ca[i] = prepare(c0, e0, a, A);
+  cb[i] = prepare(c1, e1, a, A);
+  nz[i] = f4{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], z};
+  av[i] = f4{a[0], a[1], a[2], 0.0f};
+  const float zl = x > 0 ? depth[i - 1] : 0.0f, zr = x < w - 1 ? depth[i + 1] : 0.0f;
+  const float zu = y > 0 ? depth[i - w] : 0.0f, zd = y < h - 1 ? depth[i + w] : 0.0f;
+  grad[i] = make_float2(gradient(x, w, zl, z, zr), gradient(y, h, zu, z, zd));
+}
+
+// vt of both halves' current v: half A's into av.w, half B's into its own plane.
+__global__ void __launch_bounds__(kBlock)
+denoise_pair_variance_kernel(const f4* __restrict__ ca, const f4* __restrict__ cb, f4* __restrict__ av,
+                             float* __restrict__ vtb, int32_t w, int32_t h) {
+  int32_t x, y;
+  if (!pixel_of(w, h, &x, &y)) return;
+  const DevPlanes PA{ca, nullptr, nullptr, w}, PB{cb, nullptr, nullptr, w};
+  av[(size_t)y * w + x].w = variance_filter(PA, x, y, w, h);
+  vtb[(size_t)y * w + x] = variance_filter(PB, x, y, w, h);
+}
+
+// One iteration of both halves: a pixel per lane, five loads per tap (four of 16 bytes, vt^B's 4), the
+// bounds test per tap. LAST: the pair's finish instead of the other ping-pong planes.
+template <bool LAST>
+__global__ void __launch_bounds__(kBlock)
+denoise_atrous_pair_kernel(const f4* __restrict__ ca, const f4* __restrict__ cb, const f4* __restrict__ nz,
+                           const f4* __restrict__ av, const float* __restrict__ vtb,
+                           const float2* __restrict__ grad, int32_t w, int32_t h, int32_t step, Args A,
+                           int32_t own, f4* __restrict__ ca_out, f4* __restrict__ cb_out,
+                           float* __restrict__ out, float* __restrict__ se_out, float* __restrict__ diff) {
+  int32_t x, y;
+  if (!pixel_of(w, h, &x, &y)) return;
+  const size_t i = (size_t)y * w + x;
+  const DevPairPlanes P{ca, cb, nz, av, vtb, w};
+  const float2 g = grad[i];
+  f4 ra, rb;
+  iterate_pair(P, x, y, w, h, step, g.x, g.y, A, own != 0, &ra, &rb);
+  if constexpr (LAST) {
+    finish_pair(ra, rb, av[i], A, out + 3 * i, se_out ? se_out + 3 * i : nullptr, diff ? diff + 3 * i : nullptr);
+  } else {
+    ca_out[i] = ra;
+    cb_out[i] = rb;
+  }
+}
+
+// The LDS-tiled form of one pair iteration, for steps 1 and 2 (as denoise_atrous_lds_kernel): the 32 x 8
+// tile plus halo of the four packed planes and vt^B staged in LDS (29 KB at step 1, 43.5 KB at step 2),
+// then the same iterate_pair() on the staged copy. Same operations in the same order: same bits.
+template <int STEP>
+struct LdsPairPlanes {
+  static constexpr int kW = kLdsX + 4 * STEP;
+  const f4 *ca_, *cb_, *nz_, *av_;
+  const float* vtb_;
+  int32_t x0, y0;  // the image position of the staged region's first element
+  __device__ __forceinline__ f4 ca(int32_t x, int32_t y) const { return ca_[(y - y0) * kW + (x - x0)]; }
+  __device__ __forceinline__ f4 cb(int32_t x, int32_t y) const { return cb_[(y - y0) * kW + (x - x0)]; }
+  __device__ __forceinline__ f4 nz(int32_t x, int32_t y) const { return nz_[(y - y0) * kW + (x - x0)]; }
+  __device__ __forceinline__ f4 av(int32_t x, int32_t y) const { return av_[(y - y0) * kW + (x - x0)]; }
+  __device__ __forceinline__ float vtb(int32_t x, int32_t y) const { return vtb_[(y - y0) * kW + (x - x0)]; }
+};
+
+template <int STEP, bool LAST>
+__global__ void __launch_bounds__(kBlock)
+denoise_atrous_pair_lds_kernel(const f4* __restrict__ ca, const f4* __restrict__ cb, const f4* __restrict__ nz,
+                               const f4* __restrict__ av, const float* __restrict__ vtb,
+                               const float2* __restrict__ grad, int32_t w, int32_t h, Args A, int32_t own,
+                               f4* __restrict__ ca_out, f4* __restrict__ cb_out, float* __restrict__ out,
+                               float* __restrict__ se_out, float* __restrict__ diff) {
+  constexpr int kHalo = 2 * STEP, kW = kLdsX + 2 * kHalo, kH = kLdsY + 2 * kHalo, kN = kW * kH;
+  __shared__ f4 s_ca[kN], s_cb[kN], s_nz[kN], s_av[kN];
+  __shared__ float s_vtb[kN];
+  const uint32_t tiles_x = ((uint32_t)w + kLdsX - 1) / kLdsX;
+  const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int32_t x0 = (int32_t)(tx * kLdsX) - kHalo, y0 = (int32_t)(ty * kLdsY) - kHalo;
+  for (int e = (int)threadIdx.x; e < kN; e += kBlock) {
+    const int ly = e / kW, lx = e - ly * kW;
+    const int32_t gx = x0 + lx, gy = y0 + ly;
+    if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+      const size_t g = (size_t)gy * w + gx;
+      s_ca[e] = ca[g];
+      s_cb[e] = cb[g];
+      s_nz[e] = nz[g];
+      s_av[e] = av[g];
+      s_vtb[e] = vtb[g];
+    }
+  }
+  __syncthreads();
+  const int32_t x = (int32_t)(tx * kLdsX + (threadIdx.x & (kLdsX - 1)));
+  const int32_t y = (int32_t)(ty * kLdsY + threadIdx.x / kLdsX);
+  if (x >= w || y >= h) return;
+  const size_t i = (size_t)y * w + x;
+  const LdsPairPlanes<STEP> P{s_ca, s_cb, s_nz, s_av, s_vtb, x0, y0};
+  const float2 g = grad[i];
+  f4 ra, rb;
+  iterate_pair(P, x, y, w, h, STEP, g.x, g.y, A, own != 0, &ra, &rb);
+  if constexpr (LAST) {
+    finish_pair(ra, rb, s_av[(y - y0) * kW + (x - x0)], A, out + 3 * i, se_out ? se_out + 3 * i : nullptr,
+                diff ? diff + 3 * i : nullptr);
+  } else {
+    ca_out[i] = ra;
+    cb_out[i] = rb;
+  }
+}
+
+// iterations == 0: the halves as given, one pixel per thread.
+__global__ void __launch_bounds__(kBlock)
+denoise_pair_zero_kernel(const float* __restrict__ rgb_a, const float* __restrict__ se_a,
+                         const float* __restrict__ rgb_b, const float* __restrict__ se_b, size_t npix,
+                         float* __restrict__ out, float* __restrict__ se_out, float* __restrict__ diff) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  finish_pair_zero(rgb_a + 3 * i, se_a + 3 * i, rgb_b + 3 * i, se_b + 3 * i, out + 3 * i,
+                   se_out ? se_out + 3 * i : nullptr, diff ? diff + 3 * i : nullptr);
+}
+
+// The summary of a diff plane, in the film noise summary's shape. p[0] = the block's 256 partials
+// combined pairwise, in an order fixed by the thread index alone.
+__device__ __forceinline__ void pair_block_reduce(PairPartial* p) {
+  for (uint32_t w = kBlock / 2; w > 0; w >>= 1) {
+    __syncthreads();
+    if (threadIdx.x < w) {
+      PairPartial& a = p[threadIdx.x];
+      const PairPartial& b = p[threadIdx.x + w];
+      a.s[0] += b.s[0];
+      a.s[1] += b.s[1];
+      a.s[2] += b.s[2];
+      a.diff_max = fmaxf(a.diff_max, b.diff_max);
+    }
+  }
+  __syncthreads();
+}
+
+// Stage 1: one pixel per thread, one partial per block, as four planes of nb = gridDim.x doubles.
+__global__ void __launch_bounds__(kBlock)
+denoise_pair_partials_kernel(const float* __restrict__ diff, size_t npix, double* __restrict__ out) {
+  __shared__ PairPartial s_p[kBlock];
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  PairPartial v{};
+  if (px < npix) pair_partial_add(v, diff + 3 * px);
+  s_p[threadIdx.x] = v;
+  pair_block_reduce(s_p);
+  if (threadIdx.x == 0) {
+    const size_t nb = gridDim.x;
+    out[blockIdx.x] = s_p[0].s[0];
+    out[nb + blockIdx.x] = s_p[0].s[1];
+    out[2 * nb + blockIdx.x] = s_p[0].s[2];
+    out[3 * nb + blockIdx.x] = (double)s_p[0].diff_max;
+  }
+}
+
+// Stage 2, one block: thread t adds the partials t, t + 256, ... in that order; *total = the image's.
+__global__ void __launch_bounds__(kBlock)
+denoise_pair_total_kernel(const double* __restrict__ parts, uint32_t n, PairPartial* __restrict__ total) {
+  __shared__ PairPartial s_p[kBlock];
+  PairPartial v{};
+  for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
+    v.s[0] += parts[i];
+    v.s[1] += parts[(size_t)n + i];
+    v.s[2] += parts[2 * (size_t)n + i];
+    v.diff_max = fmaxf(v.diff_max, (float)parts[3 * (size_t)n + i]);
+  }
+  s_p[threadIdx.x] = v;
+  pair_block_reduce(s_p);
+  if (threadIdx.x == 0) *total = s_p[0];
+}
+
 size_t tiles_of(int32_t w, int32_t h, int tile_x, int tile_y) {
   return (((size_t)w + tile_x - 1) / tile_x) * (((size_t)h + tile_y - 1) / tile_y);
 }
@@ -221,6 +425,123 @@ spt_status check_call(const spt_denoiser* dn, const spt_denoise_params* p, const
   return SPT_OK;
 }
 
+// The pair scratch, allocated once per denoiser at its first pair call (spt.h: 60 bytes per pixel and
+// the summary's partials).
+spt_status pair_scratch(spt_denoiser* dn) {
+  if (dn->pair_base) return SPT_OK;
+  const size_t n = dn->npix, n4 = (n + 3) & ~(size_t)3;
+  const size_t blocks = (n + kBlock - 1) / kBlock;
+  const size_t bytes = n * 2 * sizeof(f4) + (3 * n4 + 3 * n4 + n4) * sizeof(float) +
+                       4 * blocks * sizeof(double) + sizeof(PairPartial);
+  SPT_HIP(hipSetDevice(dn->device));
+  void* base = nullptr;
+  const hipError_t e = hipMalloc(&base, bytes);
+  if (e != hipSuccess) return fail(SPT_ERR_OOM, std::string("denoiser pair scratch alloc: ") + hipGetErrorString(e));
+  dn->pair_base = base;
+  dn->cb[0] = (f4*)base;
+  dn->cb[1] = dn->cb[0] + n;
+  dn->rgb_b = (float*)(dn->cb[1] + n);
+  dn->se_b = dn->rgb_b + 3 * n4;
+  dn->vtb = dn->se_b + 3 * n4;
+  dn->parts = (double*)(dn->vtb + n4);  // 16-byte aligned: every plane before it is a multiple of 16 bytes
+  dn->n_parts = (uint32_t)blocks;
+  return SPT_OK;
+}
+
+// Which form a pair iteration takes, as g_form: 0 = by step (the tiled form for steps 1 and 2), 1 = plain
+// loads always, 2 = the tiled form where it exists. Only the bench library can change it.
+int g_pair_form = 0;
+
+// One pair iteration of step `step` from (ca, cb) into (ca_out, cb_out) (or, last, into out / se_out / diff).
+void launch_atrous_pair(const spt_denoiser* dn, const f4* ca, const f4* cb, int32_t step, bool last, const Args& A,
+                        int32_t own, f4* ca_out, f4* cb_out, float* out, float* se_out, float* diff, int form,
+                        hipStream_t stream) {
+  const int32_t w = dn->width, h = dn->height;
+  const f4 *nz = dn->nz, *av = dn->av;
+  const float* vtb = dn->vtb;
+  const float2* grad = dn->grad;
+  const dim3 block(kBlock);
+  if (form != 1 && step <= 2) {
+    const dim3 grid((unsigned)tiles_of(w, h, kLdsX, kLdsY));
+#define DN_PAIR_LDS(S, L) hipLaunchKernelGGL((denoise_atrous_pair_lds_kernel<S, L>), grid, block, 0, stream, ca, cb, nz, av, vtb, grad, w, h, A, own, ca_out, cb_out, out, se_out, diff)
+    if (step == 1 && last) DN_PAIR_LDS(1, true);
+    else if (step == 1) DN_PAIR_LDS(1, false);
+    else if (last) DN_PAIR_LDS(2, true);
+    else DN_PAIR_LDS(2, false);
+#undef DN_PAIR_LDS
+    return;
+  }
+  const dim3 grid((unsigned)tiles_of(w, h, kTileX, kTileY));
+  if (last)
+    hipLaunchKernelGGL(denoise_atrous_pair_kernel<true>, grid, block, 0, stream, ca, cb, nz, av, vtb, grad, w, h,
+                       step, A, own, ca_out, cb_out, out, se_out, diff);
+  else
+    hipLaunchKernelGGL(denoise_atrous_pair_kernel<false>, grid, block, 0, stream, ca, cb, nz, av, vtb, grad, w, h,
+                       step, A, own, ca_out, cb_out, out, se_out, diff);
+}
+
+// The pair filter of seven device planes, already validated, the pair scratch in place.
+spt_status run_pair(spt_denoiser* dn, const float* rgb_a, const float* se_a, const float* rgb_b,
+                    const float* se_b, const float* albedo, const float* normal, const float* depth,
+                    const spt_denoise_params* p, uint32_t pair_flags, float* out, float* se_out, float* diff,
+                    hipStream_t stream) {
+  const dim3 block(kBlock);
+  if (p->iterations == 0) {
+    hipLaunchKernelGGL(denoise_pair_zero_kernel, dim3(dn->n_parts), block, 0, stream, rgb_a, se_a, rgb_b, se_b,
+                       dn->npix, out, se_out, diff);
+    SPT_HIP(hipGetLastError());
+    return SPT_OK;
+  }
+  const Args A = make_args(p);
+  const int32_t own = (pair_flags & SPT_DENOISE_PAIR_OWN_WEIGHTS) ? 1 : 0;
+  const dim3 grid((unsigned)tiles_of(dn->width, dn->height, kTileX, kTileY));
+  const int32_t w = dn->width, h = dn->height;
+  hipLaunchKernelGGL(denoise_pair_pack_kernel, grid, block, 0, stream, rgb_a, se_a, rgb_b, se_b, albedo, normal,
+                     depth, w, h, A, dn->cv[0], dn->cb[0], dn->nz, dn->av, dn->grad);
+  for (int32_t it = 0; it < p->iterations; ++it) {
+    const f4 *ca = dn->cv[it & 1], *cb = dn->cb[it & 1];
+    hipLaunchKernelGGL(denoise_pair_variance_kernel, grid, block, 0, stream, ca, cb, dn->av, dn->vtb, w, h);
+    const bool last = it == p->iterations - 1;
+    launch_atrous_pair(dn, ca, cb, (int32_t)1 << it, last, A, own, last ? nullptr : dn->cv[(it + 1) & 1],
+                       last ? nullptr : dn->cb[(it + 1) & 1], last ? out : nullptr, last ? se_out : nullptr,
+                       last ? diff : nullptr, g_pair_form, stream);
+  }
+  SPT_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+spt_status check_pair_call(const spt_denoiser* dn, const spt_denoise_params* p, uint32_t pair_flags,
+                           const float* out, const float* se_out, const float* diff,
+                           std::initializer_list<const float*> inputs) {
+  if (!dn) return fail(SPT_ERR_INVALID_ARG, "null denoiser");
+  if (const char* e = params_error(p)) return fail(SPT_ERR_INVALID_ARG, std::string("denoise_pair: ") + e);
+  if (const char* e = pair_flags_error(pair_flags)) return fail(SPT_ERR_INVALID_ARG, std::string("denoise_pair: ") + e);
+  if (!out) return fail(SPT_ERR_INVALID_ARG, "denoise_pair: null output plane");
+  if (se_out == out || diff == out || (se_out && se_out == diff))
+    return fail(SPT_ERR_INVALID_ARG, "denoise_pair: two output planes are one plane");
+  for (const float* in : inputs) {
+    if (!in) return fail(SPT_ERR_INVALID_ARG, "denoise_pair: null plane");
+    if (in == out || in == se_out || in == diff)
+      return fail(SPT_ERR_INVALID_ARG, "denoise_pair: an output plane is an input plane");
+  }
+  return SPT_OK;
+}
+
+// What spt_film_denoise asks of a film, for one film of a pair.
+spt_status check_pair_film(const spt_film* film, const spt_guide* guide, const spt_denoiser* dn) {
+  if (!film->batch) return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: not a noise film");
+  if (film->batches_done < 2)
+    return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: the error needs at least two batches in each film");
+  if (film->shard_count > 1)
+    return fail(SPT_ERR_INVALID_ARG,
+                "film_pair_denoise: a shard's rows are not image neighbours; gather the planes and call spt_denoise_pair_async");
+  if (film->width != dn->width || film->rows != dn->height || !spt::shape_equal(*film, *guide))
+    return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: a film's or the guide's size differs from the denoiser's");
+  if (film->device != dn->device)
+    return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: a film and the denoiser are on different devices");
+  return SPT_OK;
+}
+
 }  // namespace
 
 extern "C" spt_status spt_denoiser_create(int32_t device, int32_t width, int32_t height,
@@ -265,6 +586,7 @@ extern "C" spt_status spt_denoiser_destroy(spt_denoiser* dn) {
   if (dn->base) {
     (void)hipSetDevice(dn->device);
     (void)hipFree(dn->base);
+    if (dn->pair_base) (void)hipFree(dn->pair_base);
   }
   delete dn;
   return SPT_OK;
@@ -304,6 +626,63 @@ extern "C" spt_status spt_film_denoise(const spt_film* film, const spt_guide* gu
              (hipStream_t)stream);
 }
 
+extern "C" spt_status spt_denoise_pair_async(spt_denoiser* dn, const float* rgb_a_dev, const float* se_a_dev,
+                                             const float* rgb_b_dev, const float* se_b_dev,
+                                             const float* albedo_dev, const float* normal_dev,
+                                             const float* depth_dev, const spt_denoise_params* params,
+                                             uint32_t pair_flags, float* out_dev, float* se_out_dev,
+                                             float* diff_dev, void* stream) {
+  SPT_TRY(check_pair_call(dn, params, pair_flags, out_dev, se_out_dev, diff_dev,
+                          {rgb_a_dev, se_a_dev, rgb_b_dev, se_b_dev, albedo_dev, normal_dev, depth_dev}));
+  SPT_TRY(pair_scratch(dn));
+  SPT_HIP(hipSetDevice(dn->device));
+  return run_pair(dn, rgb_a_dev, se_a_dev, rgb_b_dev, se_b_dev, albedo_dev, normal_dev, depth_dev, params,
+                  pair_flags, out_dev, se_out_dev, diff_dev, (hipStream_t)stream);
+}
+
+extern "C" spt_status spt_film_pair_denoise(const spt_film* film_a, const spt_film* film_b,
+                                            const spt_guide* guide, spt_denoiser* dn,
+                                            const spt_denoise_params* params, uint32_t pair_flags,
+                                            float* out_dev, float* se_out_dev, float* diff_dev, void* stream) {
+  if (!film_a || !film_b || !guide) return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: null film or guide");
+  SPT_TRY(check_pair_call(dn, params, pair_flags, out_dev, se_out_dev, diff_dev, {}));
+  if (film_a == film_b) return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: the two halves are one film");
+  if (guide->samples_done == 0) return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: the guide holds no sample");
+  SPT_TRY(check_pair_film(film_a, guide, dn));
+  SPT_TRY(check_pair_film(film_b, guide, dn));
+  if (film_a->spp_total != film_b->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise: the films' spp_total differ");
+  SPT_TRY(pair_scratch(dn));
+  SPT_TRY(spt_film_resolve(film_a, dn->rgb, stream));
+  SPT_TRY(spt_film_noise_map(film_a, dn->se, stream));
+  SPT_TRY(spt_film_resolve(film_b, dn->rgb_b, stream));
+  SPT_TRY(spt_film_noise_map(film_b, dn->se_b, stream));
+  SPT_TRY(spt_guide_resolve(guide, dn->albedo, dn->normal, dn->depth, nullptr, stream));
+  SPT_HIP(hipSetDevice(dn->device));
+  return run_pair(dn, dn->rgb, dn->se, dn->rgb_b, dn->se_b, dn->albedo, dn->normal, dn->depth, params,
+                  pair_flags, out_dev, se_out_dev, diff_dev, (hipStream_t)stream);
+}
+
+extern "C" spt_status spt_denoise_pair_summary(spt_denoiser* dn, const float* diff_dev, spt_pair_summary* out,
+                                               void* stream_v) {
+  if (!dn || !diff_dev || !out) return fail(SPT_ERR_INVALID_ARG, "denoise_pair_summary: null argument");
+  SPT_TRY(pair_scratch(dn));
+  hipStream_t stream = (hipStream_t)stream_v;
+  SPT_HIP(hipSetDevice(dn->device));
+  PairPartial* total_dev = (PairPartial*)(dn->parts + 4 * (size_t)dn->n_parts);
+  hipLaunchKernelGGL(denoise_pair_partials_kernel, dim3(dn->n_parts), dim3(kBlock), 0, stream, diff_dev,
+                     dn->npix, dn->parts);
+  SPT_HIP(hipGetLastError());
+  hipLaunchKernelGGL(denoise_pair_total_kernel, dim3(1), dim3(kBlock), 0, stream, (const double*)dn->parts,
+                     dn->n_parts, total_dev);
+  SPT_HIP(hipGetLastError());
+  PairPartial total{};
+  SPT_HIP(hipMemcpyAsync(&total, total_dev, sizeof total, hipMemcpyDeviceToHost, stream));
+  SPT_HIP(hipStreamSynchronize(stream));
+  pair_summary_finish(total, dn->npix, out);
+  return SPT_OK;
+}
+
 #ifdef SPT_DENOISE_BENCH  // tools/denoise_bench.py's library only: never in the shipped libspt.so
 // 0 = by step, 1 = plain loads always, 2 = the tiled form where it exists.
 extern "C" spt_status spt_denoise_bench_form(int32_t form) {
@@ -335,6 +714,42 @@ extern "C" spt_status spt_denoise_bench_kernel(spt_denoiser* dn, int32_t which, 
   else
     launch_atrous(dn, dn->cv[0], step, which == 3, A, which == 3 ? nullptr : dn->cv[1],
                   which == 3 ? out : nullptr, which == 3 ? se_out : nullptr, form, stream);
+  SPT_HIP(hipGetLastError());
+  return SPT_OK;
+}
+// The same two for the pair filter. spt_denoise_pair_bench_form: g_pair_form. spt_denoise_pair_bench_kernel,
+// which: 0 the pair pack of the seven planes, 1 the pair variance pass over (cv[0], cb[0]), 2 a pair a-trous
+// pass into (cv[1], cb[1]), 3 the pair a-trous pass with the finish fused in, into out / se_out / diff.
+extern "C" spt_status spt_denoise_pair_bench_form(int32_t form) {
+  if (form < 0 || form > 2) return fail(SPT_ERR_INVALID_ARG, "form: 0, 1 or 2");
+  g_pair_form = form;
+  return SPT_OK;
+}
+extern "C" spt_status spt_denoise_pair_bench_kernel(spt_denoiser* dn, int32_t which, int32_t step, int32_t form,
+                                                    const float* rgb_a, const float* se_a, const float* rgb_b,
+                                                    const float* se_b, const float* albedo, const float* normal,
+                                                    const float* depth, const spt_denoise_params* params,
+                                                    uint32_t pair_flags, float* out, float* se_out, float* diff,
+                                                    void* stream_v) {
+  if (!dn || params_error(params) || pair_flags_error(pair_flags) || which < 0 || which > 3 || step < 1 ||
+      step > 32 || (step & (step - 1)) || form < 1 || form > 2 || (form == 2 && step > 2))
+    return fail(SPT_ERR_INVALID_ARG, "pair_bench_kernel: bad argument");
+  SPT_TRY(pair_scratch(dn));
+  hipStream_t stream = (hipStream_t)stream_v;
+  const Args A = make_args(params);
+  const int32_t own = (pair_flags & SPT_DENOISE_PAIR_OWN_WEIGHTS) ? 1 : 0;
+  const dim3 grid((unsigned)tiles_of(dn->width, dn->height, kTileX, kTileY)), block(kBlock);
+  SPT_HIP(hipSetDevice(dn->device));
+  if (which == 0)
+    hipLaunchKernelGGL(denoise_pair_pack_kernel, grid, block, 0, stream, rgb_a, se_a, rgb_b, se_b, albedo, normal,
+                       depth, dn->width, dn->height, A, dn->cv[0], dn->cb[0], dn->nz, dn->av, dn->grad);
+  else if (which == 1)
+    hipLaunchKernelGGL(denoise_pair_variance_kernel, grid, block, 0, stream, (const f4*)dn->cv[0],
+                       (const f4*)dn->cb[0], dn->av, dn->vtb, dn->width, dn->height);
+  else
+    launch_atrous_pair(dn, dn->cv[0], dn->cb[0], step, which == 3, A, own, which == 3 ? nullptr : dn->cv[1],
+                       which == 3 ? nullptr : dn->cb[1], which == 3 ? out : nullptr, which == 3 ? se_out : nullptr,
+                       which == 3 ? diff : nullptr, form, stream);
   SPT_HIP(hipGetLastError());
   return SPT_OK;
 }

@@ -1,7 +1,9 @@
 // spt_denoise_host.cpp — the a-trous filter as a pure host function (include/spt.h, SPT_HAS_DENOISE):
-// the CPU statement every GPU denoise test compares the device kernels against. Plain C++, no HIP: it
-// is also built into tests/probe/spt_denoise_check under the host sanitizers.
+// the CPU statement every GPU denoise test compares the device kernels against, and below it the
+// two-half filter and its summary (SPT_HAS_DENOISE_PAIR). Plain C++, no HIP: it is also built into
+// tests/probe/spt_denoise_check and spt_denoise_pair_check under the host sanitizers.
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "spt_denoise.h"
@@ -83,5 +85,101 @@ extern "C" spt_status spt_denoise_host(const float* rgb, const float* se, const 
     nxt = t;
   }
   for (size_t i = 0; i < npix; ++i) finish(cur[i], av[i], A, out + 3 * i, se_out ? se_out + 3 * i : nullptr);
+  return SPT_OK;
+}
+
+// ---- the two-half filter (SPT_HAS_DENOISE_PAIR) ----
+static_assert(sizeof(spt_pair_summary) == 40, "spt_pair_summary layout (the Python mirror's)");
+
+namespace {
+
+struct HostPairPlanes {
+  const f4 *ca_, *cb_, *nz_, *av_;
+  const float* vtb_;
+  int32_t w;
+  f4 ca(int32_t x, int32_t y) const { return ca_[(size_t)y * w + x]; }
+  f4 cb(int32_t x, int32_t y) const { return cb_[(size_t)y * w + x]; }
+  f4 nz(int32_t x, int32_t y) const { return nz_[(size_t)y * w + x]; }
+  f4 av(int32_t x, int32_t y) const { return av_[(size_t)y * w + x]; }
+  float vtb(int32_t x, int32_t y) const { return vtb_[(size_t)y * w + x]; }
+};
+
+spt_status fail_pair(const char* msg) {
+  return spt::fail(SPT_ERR_INVALID_ARG, std::string("spt_denoise_pair_host: ") + msg);
+}
+
+}  // namespace
+
+extern "C" spt_status spt_denoise_pair_host(const float* rgb_a, const float* se_a, const float* rgb_b,
+                                            const float* se_b, const float* albedo, const float* normal,
+                                            const float* depth, int32_t width, int32_t height,
+                                            const spt_denoise_params* params, uint32_t pair_flags,
+                                            float* out, float* se_out, float* diff) {
+  if (!rgb_a || !se_a || !rgb_b || !se_b || !albedo || !normal || !depth || !out) return fail_pair("null plane");
+  if (const char* e = params_error(params)) return fail_pair(e);
+  if (const char* e = pair_flags_error(pair_flags)) return fail_pair(e);
+  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
+    return fail_pair("width/height must be positive and hold at most 2^31 - 1 pixels");
+  for (const float* o : {(const float*)out, (const float*)se_out, (const float*)diff}) {
+    if (!o) continue;
+    for (const float* in : {rgb_a, se_a, rgb_b, se_b, albedo, normal, depth})
+      if (o == in) return fail_pair("an output plane is an input plane");
+  }
+  if (se_out == out || diff == out || (se_out && se_out == diff))
+    return fail_pair("two output planes are one plane");
+  const size_t npix = (size_t)width * (size_t)height;
+  const auto at = [](float* p, size_t i) { return p ? p + 3 * i : nullptr; };
+  if (params->iterations == 0) {
+    for (size_t i = 0; i < npix; ++i)
+      finish_pair_zero(rgb_a + 3 * i, se_a + 3 * i, rgb_b + 3 * i, se_b + 3 * i, out + 3 * i, at(se_out, i),
+                       at(diff, i));
+    return SPT_OK;
+  }
+  const Args A = make_args(params);
+  const bool own = (pair_flags & SPT_DENOISE_PAIR_OWN_WEIGHTS) != 0;
+  std::vector<f4> ca0(npix), ca1(npix), cb0(npix), cb1(npix), nz(npix), av(npix);
+  std::vector<float> vtb(npix), gx(npix), gy(npix);
+  for (int32_t y = 0; y < height; ++y)
+    for (int32_t x = 0; x < width; ++x) {
+      const size_t i = (size_t)y * width + x;
+      ca0[i] = prepare(rgb_a + 3 * i, se_a + 3 * i, albedo + 3 * i, A);
+      cb0[i] = prepare(rgb_b + 3 * i, se_b + 3 * i, albedo + 3 * i, A);
+      nz[i] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]};
+      av[i] = {albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f};
+      gx[i] = gradient(x, width, x > 0 ? depth[i - 1] : 0.0f, depth[i], x < width - 1 ? depth[i + 1] : 0.0f);
+      gy[i] = gradient(y, height, y > 0 ? depth[i - width] : 0.0f, depth[i],
+                       y < height - 1 ? depth[i + width] : 0.0f);
+    }
+  f4 *cura = ca0.data(), *nxta = ca1.data(), *curb = cb0.data(), *nxtb = cb1.data();
+  for (int32_t it = 0; it < params->iterations; ++it) {
+    const HostPlanes PA{cura, nullptr, nullptr, width}, PB{curb, nullptr, nullptr, width};
+    for (int32_t y = 0; y < height; ++y)
+      for (int32_t x = 0; x < width; ++x) {
+        av[(size_t)y * width + x].w = variance_filter(PA, x, y, width, height);
+        vtb[(size_t)y * width + x] = variance_filter(PB, x, y, width, height);
+      }
+    const HostPairPlanes P{cura, curb, nz.data(), av.data(), vtb.data(), width};
+    for (int32_t y = 0; y < height; ++y)
+      for (int32_t x = 0; x < width; ++x) {
+        const size_t i = (size_t)y * width + x;
+        iterate_pair(P, x, y, width, height, (int32_t)1 << it, gx[i], gy[i], A, own, &nxta[i], &nxtb[i]);
+      }
+    std::swap(cura, nxta);
+    std::swap(curb, nxtb);
+  }
+  for (size_t i = 0; i < npix; ++i) finish_pair(cura[i], curb[i], av[i], A, out + 3 * i, at(se_out, i), at(diff, i));
+  return SPT_OK;
+}
+
+extern "C" spt_status spt_denoise_pair_summary_host(const float* diff, int32_t width, int32_t height,
+                                                    spt_pair_summary* out) {
+  if (!diff || !out) return spt::fail(SPT_ERR_INVALID_ARG, "spt_denoise_pair_summary_host: null argument");
+  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
+    return spt::fail(SPT_ERR_INVALID_ARG,
+                     "spt_denoise_pair_summary_host: width/height must be positive and hold at most 2^31 - 1 pixels");
+  const size_t npix = (size_t)width * (size_t)height;
+  PairPartial t{};
+  for (size_t i = 0; i < npix; ++i) pair_partial_add(t, diff + 3 * i);
+  pair_summary_finish(t, npix, out);
   return SPT_OK;
 }

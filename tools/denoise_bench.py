@@ -24,6 +24,19 @@ first hit is a SPEC or REFR primitive (at least half of the 64 samples of a firs
 scene with the specular primitives white and the rest black), over the band within 2 pixels of that
 set, and over the rest; the image-mean shift and se_out^2 / true err^2. And the configuration that
 tests/test_gpu_guide_chain.py pins.
+
+--pair (python tools/denoise_bench.py --pair [OUT.json], default build/r27_denoise_pair.json): the
+two-half filter (SPT_HAS_DENOISE_PAIR). Time: at both shapes, 20 timed rounds after 5 warm-up rounds,
+every round measuring by device events one spt_denoise_async, two of them, and one
+spt_denoise_pair_async (cross and own weights), the order rotating round by round; with the bench
+library also the pair call with plain loads against the pair call with the LDS-tiled form at steps 1
+and 2, and the single pair kernels (pack, variance, a-trous at every step, both forms where the tiled
+one exists) in kernel_times' shape. Quality and calibration: HEAD and mirror_glass (by region, first-hit
+guides) at 256x192, 16 seeds, 8 batches (four per half), a guide of 64 samples, truth 16 x 4096 spp, at
+64 / 256 / 1024 spp: the RMSE of the single filter, of pair-cross and of pair-own over the film's, the
+image-mean shift, and for both modes mean diff^2 and mean se_out^2 over the variance of `out` across
+the seeds and over the mean squared error against the truth. And the configuration that
+tests/test_gpu_denoise_pair.py pins.
 """
 import importlib
 import json
@@ -351,9 +364,262 @@ def main_chain(out):
         print(name, json.dumps({s: v["regions"] for s, v in rec["quality"][name]["by_spp"].items()}), flush=True)
 
 
+# ---- the two-half filter (--pair) -------------------------------------------------------------------
+def _pair_planes(w, h):
+    import denoise_pair_truth as dpt
+    tile, _clean = dpt.synthetic_halves(256, 192)
+    reps = (-(-h // 192), -(-w // 256))
+    return [np.ascontiguousarray(np.tile(a, reps + ((1,) if a.ndim == 3 else ()))[:h, :w]) for a in tile]
+
+
+def _stat(ms):
+    return {"median_ms": float(np.median(ms)), "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms))}
+
+
+def time_pair(spt, torch, w, h, runs=20, warmup=5):
+    """One single call, two single calls and one pair call per round, the order rotating."""
+    import ctypes
+    lib = spt.load_library()
+    planes = _pair_planes(w, h)
+    dev = [torch.from_numpy(a.reshape(-1)).cuda() for a in planes]
+    ra, sa, rb, sb, al, no, de = [t.data_ptr() for t in dev]
+    outs = [torch.empty(w * h * 3, dtype=torch.float32, device="cuda") for _ in range(3)]
+    o = [t.data_ptr() for t in outs]
+    dn = spt.Denoiser(w, h, 0)
+    p = spt.default_denoise_params()
+    stream = torch.cuda.current_stream().cuda_stream
+    has_form = hasattr(lib, "spt_denoise_pair_bench_form")
+    if has_form:
+        lib.spt_denoise_pair_bench_form.argtypes = [ctypes.c_int32]
+        lib.spt_denoise_pair_bench_form.restype = ctypes.c_int32
+
+    def single(n):
+        def run():
+            dn.denoise_async(ra, sa, al, no, de, p, o[0], o[1], stream)
+            if n == 2:
+                dn.denoise_async(rb, sb, al, no, de, p, o[2], o[1], stream)
+        return run
+
+    def pair(flags, form=None):
+        def run():
+            if form is not None:
+                assert lib.spt_denoise_pair_bench_form(form) == 0
+            dn.denoise_pair_async(ra, sa, rb, sb, al, no, de, p, flags, o[0], o[1], o[2], stream)
+            if form is not None:
+                lib.spt_denoise_pair_bench_form(0)
+        return run
+
+    what = [("single", single(1)), ("two_singles", single(2)), ("pair_cross", pair(0)),
+            ("pair_own", pair(spt.DENOISE_PAIR_OWN_WEIGHTS))]
+    if has_form:
+        what += [("pair_cross_plain_loads", pair(0, 1)), ("pair_cross_tiled_steps_1_2", pair(0, 2))]
+    ms = {k: [] for k, _ in what}
+    try:
+        for r in range(warmup + runs):
+            for j in range(len(what)):
+                name, run = what[(j + r) % len(what)]
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                run()
+                b.record()
+                torch.cuda.synchronize()
+                if r >= warmup:
+                    ms[name].append(a.elapsed_time(b))
+    finally:
+        dn.close()
+    res = {k: _stat(v) for k, v in ms.items()}
+    res["pair_over_single"] = res["pair_cross"]["median_ms"] / res["single"]["median_ms"]
+    res["pair_over_two_singles"] = res["pair_cross"]["median_ms"] / res["two_singles"]["median_ms"]
+    # per round: the pair call against the two single calls of the same round
+    per = np.array(ms["pair_cross"]) / np.array(ms["two_singles"])
+    res["pair_over_two_singles_per_round_min_max"] = [float(per.min()), float(per.max())]
+    if has_form:
+        per = np.array(ms["pair_cross_tiled_steps_1_2"]) / np.array(ms["pair_cross_plain_loads"])
+        res["tiled_over_plain"] = {"median": float(np.median(per)), "min": float(per.min()), "max": float(per.max())}
+    return res
+
+
+def pair_kernel_times(spt, torch, w, h, launches=50, rounds=7):
+    """Per-launch milliseconds of every pair kernel alone (the bench library's entry point)."""
+    import ctypes
+    lib = spt.load_library()
+    if not hasattr(lib, "spt_denoise_pair_bench_kernel"):
+        return {"skipped": "the loaded library has no bench entry points (make denoise_bench)"}
+    V, I32 = ctypes.c_void_p, ctypes.c_int32
+    lib.spt_denoise_pair_bench_kernel.argtypes = [V, I32, I32, I32] + [V] * 7 + [
+        ctypes.POINTER(spt.spt_denoise_params), ctypes.c_uint32, V, V, V, V]
+    lib.spt_denoise_pair_bench_kernel.restype = I32
+    dev = [torch.from_numpy(a.reshape(-1)).cuda() for a in _pair_planes(w, h)]
+    outs = [torch.empty(w * h * 3, dtype=torch.float32, device="cuda") for _ in range(3)]
+    p = spt.default_denoise_params()
+    dn = spt.Denoiser(w, h, 0)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def launch(which, step, form):
+        return lib.spt_denoise_pair_bench_kernel(dn._d, which, step, form, *[V(t.data_ptr()) for t in dev],
+                                                 ctypes.byref(p), 0, *[V(t.data_ptr()) for t in outs], V(stream))
+
+    def once(which, step, form):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(launches):
+            launch(which, step, form)
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / launches
+
+    res = {"launches_per_round": launches, "rounds": rounds}
+    try:
+        assert launch(0, 1, 1) == 0 and launch(1, 1, 1) == 0  # the scratch holds a packed pair from here on
+        has_tiled = launch(2, 1, 2) == 0
+        torch.cuda.synchronize()
+        res["tiled_form_in_this_build"] = bool(has_tiled)
+        for name, which in (("pair_pack", 0), ("pair_variance", 1)):
+            once(which, 1, 1)
+            res[name] = _stat([once(which, 1, 1) for _ in range(rounds)])
+        for step in (1, 2, 4, 8, 16, 32):
+            forms = [("plain", 1)] + ([("tiled", 2)] if has_tiled and step <= 2 else [])
+            for name, which in (("pair_atrous", 2), ("pair_atrous_finish", 3)):
+                ms = {f: [] for f, _ in forms}
+                for f, form in forms:
+                    once(which, step, form)
+                for _ in range(rounds):
+                    for f, form in forms:
+                        ms[f].append(once(which, step, form))
+                for f, _ in forms:
+                    res[f"{name}_step{step}_{f}"] = _stat(ms[f])
+    finally:
+        dn.close()
+    return res
+
+
+def pair_test_quality(spt):
+    """The configuration tests/test_gpu_denoise_pair.py pins: HEAD 64x48, 64 spp in batches of 8 (even
+    batches in A, odd in B), a guide of 16 samples, seeds 1..4, the truth 8192 spp with seed 77."""
+    w, h = 64, 48
+    prims = spt.cornell_scene()
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = spt.render(prims, cam, spt.default_params(width=w, height=h, spp=8192, seed=77))
+    res = {"cross": {}, "own": {}}
+    for seed in (1, 2, 3, 4):
+        p = spt.default_params(width=w, height=h, spp=64, seed=seed)
+        for mode, own in (("cross", False), ("own", True)):
+            den, info = spt.render_denoised_pair(prims, cam, p, batch=8, guide_spp=16, own_weights=own,
+                                                 return_info=True)
+            noisy = info["noisy"]
+            res[mode][str(seed)] = {
+                "rmse_noisy": rmse(noisy, truth), "rmse_pair": rmse(den, truth),
+                "ratio": rmse(den, truth) / rmse(noisy, truth),
+                "mean_shift": abs(float(den.mean(dtype=np.float64) / noisy.mean(dtype=np.float64)) - 1.0),
+                "diff_rmse": info["pair"]["rmse"]}
+    return {"what": "tests/test_gpu_denoise_pair.py::test_pair_result_is_closer_to_the_truth", "modes": res}
+
+
+PAIR_SCENES = {"HEAD": ("cornell_scene", {}), "mirror_glass": ("smallpt_mirror_glass_scene", dict(nee_prob=0.0))}
+
+
+def pair_quality(spt, name, w=256, h=192, seeds=16, spps=(64, 256, 1024)):
+    prims = getattr(spt, PAIR_SCENES[name][0])()
+    kw = PAIR_SCENES[name][1]
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = np.zeros((h, w, 3), np.float64)
+    for s in range(16):
+        truth += spt.render(prims, cam, spt.default_params(width=w, height=h, spp=4096, seed=1000 + s, **kw))
+    truth = (truth / 16).astype(np.float32)
+    masks = {"frame": np.ones((h, w), bool)}
+    if name != "HEAD":
+        masks.update(specular_masks(spt, prims, cam, w, h, **kw))
+    res = {"scene": name, "width": w, "height": h, "seeds": seeds, "truth": "16 seeds x 4096 spp", "guide_spp": 64,
+           "batches": 8, "pixels": {k: int(m.sum()) for k, m in masks.items()}, "by_spp": {}}
+    modes = ("single", "cross", "own")
+    for spp in spps:
+        batch = spp // 8
+        outs = {m: [] for m in modes}
+        est = {m: {"diff2": [], "se2": []} for m in modes}
+        noisy_all = []
+        for seed in range(1, seeds + 1):
+            p = spt.default_params(width=w, height=h, spp=spp, seed=seed, **kw)
+            r, fa, fb, film, guide, dn = (spt.Renderer(0), spt.Film(p, 0), spt.Film(p, 0), spt.Film(p, 0),
+                                          spt.Guide(p, 0), spt.Denoiser(w, h, 0))
+            try:
+                for f in (fa, fb, film):
+                    f.enable_noise(batch)
+                for k in range(8):
+                    (fb if k & 1 else fa).render(r, prims, cam, p, k * batch, batch)
+                    r.stats()
+                film.merge(fa)
+                film.merge(fb)
+                guide.render(r, prims, cam, p, 0, min(spp, 64))
+                noisy_all.append(film.resolve())
+                den, se = dn.denoise_film(film, guide, return_se=True)
+                outs["single"].append(den)
+                est["single"]["se2"].append(se.astype(np.float64) ** 2)
+                for m, own in (("cross", False), ("own", True)):
+                    out, se, diff = dn.denoise_film_pair(fa, fb, guide, own_weights=own)
+                    outs[m].append(out)
+                    est[m]["se2"].append(se.astype(np.float64) ** 2)
+                    est[m]["diff2"].append(diff.astype(np.float64) ** 2)
+            finally:
+                for o in (dn, guide, film, fa, fb, r):
+                    o.close()
+        one = {"regions": {}, "calibration": {}}
+        for k, mk in masks.items():
+            n = float(np.mean([rmse(x[mk], truth[mk]) for x in noisy_all]))
+            row = {"rmse_noisy": n}
+            for m in modes:
+                d = float(np.mean([rmse(x[mk], truth[mk]) for x in outs[m]]))
+                row[f"rmse_{m}"] = d
+                row[f"ratio_{m}"] = d / n
+            row["cross_over_single"] = row["rmse_cross"] / row["rmse_single"]
+            row["own_over_single"] = row["rmse_own"] / row["rmse_single"]
+            row["seeds_where_cross_beats_single"] = int(sum(
+                rmse(a[mk], truth[mk]) < rmse(b[mk], truth[mk]) for a, b in zip(outs["cross"], outs["single"])))
+            one["regions"][k] = row
+        for m in modes:
+            stack = np.stack([x.astype(np.float64) for x in outs[m]])
+            var = float(stack.var(axis=0, ddof=1).mean())
+            mse = float(np.mean((stack - truth.astype(np.float64)) ** 2))
+            noisy_mean = float(np.mean([x.mean(dtype=np.float64) for x in noisy_all]))
+            cal = {"variance_of_out_across_seeds": var, "mse_against_truth": mse,
+                   "mean_change": float(stack.mean() / noisy_mean - 1.0),
+                   "se_out2_over_variance": float(np.mean(est[m]["se2"]) / var),
+                   "se_out2_over_mse": float(np.mean(est[m]["se2"]) / mse)}
+            if est[m]["diff2"]:
+                cal["diff2_over_variance"] = float(np.mean(est[m]["diff2"]) / var)
+                cal["diff2_over_mse"] = float(np.mean(est[m]["diff2"]) / mse)
+            one["calibration"][m] = cal
+        res["by_spp"][str(spp)] = one
+    return res
+
+
+def main_pair(out):
+    import torch
+    spt = importlib.import_module("small-pathtracer_amd")
+    spt.load_library()
+    assert torch.cuda.is_available(), "denoise_bench needs the GPU"
+    rec = {"kernel_sources_sha16": spt.build_sources_sha16(), "device": torch.cuda.get_device_name(0),
+           "utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()), "time": {}, "kernels": {}}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    for w, h in ((1024, 768), (4096, 4096)):
+        rec["time"][f"{w}x{h}"] = time_pair(spt, torch, w, h)
+        rec["kernels"][f"{w}x{h}"] = pair_kernel_times(spt, torch, w, h)
+        json.dump(rec, open(out, "w"), indent=1)
+        print(f"{w}x{h}", json.dumps(rec["time"][f"{w}x{h}"]), flush=True)
+    rec["test_quality"] = pair_test_quality(spt)
+    json.dump(rec, open(out, "w"), indent=1)
+    rec["quality"] = {}
+    for name in PAIR_SCENES:
+        rec["quality"][name] = pair_quality(spt, name)
+        json.dump(rec, open(out, "w"), indent=1)  # what is measured survives a failure further on
+        print(name, json.dumps({s: (v["regions"]["frame"], v["calibration"])
+                                for s, v in rec["quality"][name]["by_spp"].items()}), flush=True)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--chain":
         return main_chain(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "guide_chain_denoise.json"))
+    if len(sys.argv) > 1 and sys.argv[1] == "--pair":
+        return main_pair(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "r27_denoise_pair.json"))
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "r19_denoise.json")
     import torch
     spt = importlib.import_module("small-pathtracer_amd")
