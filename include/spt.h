@@ -38,7 +38,9 @@ extern "C" {
                              spt_denoise_* and spt_denoiser_* calls and spt_film_denoise;
                              SPT_HAS_GUIDE_CHAIN, spt_guide_create_ex (spt_guide_info's last field,
                              always 0 until then, now reads the guide's flags); SPT_HAS_DENOISE_PAIR,
-                             the spt_denoise_pair_* calls and spt_film_pair_denoise */
+                             the spt_denoise_pair_* calls and spt_film_pair_denoise;
+                             SPT_HAS_DENOISE_BANK, the spt_denoise_bank_* calls and
+                             spt_film_pair_denoise_bank */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
@@ -49,6 +51,7 @@ extern "C" {
 #define SPT_GUIDE_MAX_CHAIN 8 /* segments of a chain at most, the camera ray included */
 #define SPT_HAS_DENOISE 1 /* the edge-stopping a-trous filter over a film and its guides (below) */
 #define SPT_HAS_DENOISE_PAIR 1 /* two independent halves, cross-weighted, and a measured error (below) */
+#define SPT_HAS_DENOISE_BANK 1 /* a few pair filters, the one of least cross-validated error per pixel (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -764,6 +767,100 @@ spt_status spt_film_pair_denoise(const spt_film* film_a, const spt_film* film_b,
                                  spt_denoiser* dn, const spt_denoise_params* params, uint32_t pair_flags,
                                  float* out_dev, float* se_out_dev_or_null, float* diff_dev_or_null,
                                  void* stream);
+
+/* ---- the filter bank: a cross-validated per-pixel error picks the filter (SPT_HAS_DENOISE_BANK) ----
+ * The pair filter run at 1..4 parameter sets (the candidates); per pixel and candidate an estimate of the
+ * WHOLE squared error of the candidate's out, bias included, from the other half's noisy pixel
+ * (Rousselle et al. 2012; Bitterli et al. 2016); the estimates smoothed along the guides; per pixel the
+ * candidate of least estimate; the candidates blended by the smoothed choice. Same arithmetic rules as
+ * above: exact fp32, no contraction, every sum in the order given, device and host agree bit for bit.
+ * Inputs: the pair filter's seven planes; cands[0..n_cands-1], n_cands in 1..4, each validated as an
+ * spt_denoise_params above; the bank parameters, an spt_bank_params as below.
+ * 1. Candidates. For each k: o^A_k, o^B_k = the pair filter's finish values o^A, o^B under cands[k] and
+ *    bank->pair_flags (iterations == 0: rgb_a, rgb_b as given); out_k = 0.5f * (o^A_k + o^B_k) and
+ *    diff_k = 0.5f * (o^A_k - o^B_k), the pair filter's out and diff bit for bit.
+ * 2. The cross-validated error of candidate k at a pixel. Per channel c:
+ *      rA = o^A_k,c - rgb_b,c;   rB = o^B_k,c - rgb_a,c
+ *      e_c = 0.5f * ((rA*rA - se_b,c*se_b,c) + (rB*rB - se_a,c*se_a,c))
+ *      m_c = e_c - diff_k,c*diff_k,c
+ *    and m_k = ((m_0 + m_1) + m_2) * (1.0f/3.0f). Signed.
+ *    Why: with own weights o^A is a function of A's samples and the noise-free guides, so it is
+ *    independent of rgb_b and E[rA^2] = MSE(o^A) + Var(rgb_b); se_b^2 is the film's estimate of
+ *    Var(rgb_b). So E[e] = bias^2 + Var(o^A), while out's error is bias^2 + Var(o^A)/2 and E[diff^2] =
+ *    Var(o^A)/2: E[m] = MSE(out). One value of m is as noisy as one value of diff^2 and may be negative.
+ * 3. Smoothing along the guides: error_iterations passes, pass j = 0.. with step 2^j, every pixel reading
+ *    the previous pass. The 25 taps in the filter's order, a tap outside the image skipped. A tap's weight
+ *    is the pair statement's geometric factor alone, g = (((h_j*h_i) * w_n) * w_z) * w_a with sigma_depth,
+ *    sigma_albedo and normal_squarings of cands[0] and the depth gradient above; the centre tap has
+ *    g = h_2*h_2 by rule. With W and M_k starting at 0.0f each tap does W += g, M_k += g * m_k(q); then
+ *    m_k(p) := M_k / W. No colour enters: the weights are independent of the samples, so a smoothed
+ *    estimate is as unbiased as a raw one.
+ * 4. Choice: k*(p) = the smallest k whose (smoothed) m_k(p) is least: k* = 0, then for k = 1.. in order
+ *    k* = k where m_k(p) < m_k*(p).
+ * 5. Blend: one more 5x5 pass at step 1 with the same g: W += g, S_k += g * (k*(q) == k ? 1.0f : 0.0f);
+ *    s_k = S_k / W. Then out_c = fminf(sum over k of s_k * out_k,c, 1) and mse = sum over k of
+ *    s_k * m_k(p) (the smoothed values at p), both sums from 0.0f with k ascending; choice = k*(p).
+ *    With one candidate s_0 = W / W = 1.0f: out is the pair filter's out bit for bit (but a -0, which
+ *    only an input below zero can give, becomes +0) and mse is m_0.
+ * Swapping the halves leaves out, mse and choice bit-identical.
+ * WHAT mse IS NOT. (a) With cross weights (pair_flags 0) o^A depends on B's samples, so rA^2 misses the
+ * covariance and e reads LOW; allowed, measured (README), not the default. (b) The least of several noisy
+ * estimates reads low by selection, as the adaptive film's pooled error did: with more than one candidate
+ * the mean of mse is a slightly optimistic figure (measured: README). (c) rgb is clamped at 1: at the
+ * light the estimate reads the clamped values. (d) se is itself an estimate from a few batches. Inputs
+ * that are not finite give unspecified values, never a fault (choice stays below n_cands). */
+#define SPT_BANK_MAX_CANDIDATES 4
+typedef struct spt_bank_params {
+  int32_t error_iterations; /* 0..3 smoothing passes of the error estimates. Default 2 */
+  uint32_t pair_flags;      /* the pair filter's; default SPT_DENOISE_PAIR_OWN_WEIGHTS */
+  uint32_t reserved[2];     /* 0 */
+} spt_bank_params;
+void spt_denoise_bank_default_params(spt_bank_params* b);
+typedef struct spt_bank_summary {
+  double mse_mean;  /* the mean over ALL pixels of (double)mse */
+  double rmse_est;  /* sqrt(max(0, mse_mean)) */
+  double share[4];  /* the fraction of pixels whose choice is k (a value above 3 counts for none) */
+  float mse_min, mse_max;
+} spt_bank_summary;
+/* Enqueue the bank of seven DEVICE planes on `stream`: out_dev (h*w*3 floats) and, if given, mse_dev (h*w
+ * floats, signed) and choice_dev (h*w bytes). Every candidate is a whole pair run (nothing is shared
+ * between candidates). The first bank call on a denoiser allocates the pair scratch (above) and the bank
+ * scratch (a hipMalloc: it may synchronise the device once), 104 bytes per pixel (the two halves' results,
+ * four out_k planes, two ping-pong planes of four error estimates) and the summary's partials, 56 bytes per
+ * 256 pixels; spt_denoiser_destroy frees it. SPT_ERR_OOM if it does not fit. Rejected with
+ * SPT_ERR_INVALID_ARG before anything is queued, every output untouched: a null denoiser, input plane,
+ * cands, bank or out_dev; n_cands outside 1..4; a candidate that spt_denoise_async rejects;
+ * error_iterations outside 0..3; unknown pair_flags; a nonzero reserved word; an output plane equal to an
+ * input plane or to another output plane. */
+spt_status spt_denoise_bank_async(spt_denoiser* dn, const float* rgb_a_dev, const float* se_a_dev,
+                                  const float* rgb_b_dev, const float* se_b_dev, const float* albedo_dev,
+                                  const float* normal_dev, const float* depth_dev,
+                                  const spt_denoise_params* cands, int32_t n_cands,
+                                  const spt_bank_params* bank, float* out_dev, float* mse_dev_or_null,
+                                  uint8_t* choice_dev_or_null, void* stream);
+/* The same as a pure host function: the CPU statement. Also rejects a width or height that is not
+ * positive or more than 2^31 - 1 pixels. */
+spt_status spt_denoise_bank_host(const float* rgb_a, const float* se_a, const float* rgb_b,
+                                 const float* se_b, const float* albedo, const float* normal,
+                                 const float* depth, int32_t width, int32_t height,
+                                 const spt_denoise_params* cands, int32_t n_cands,
+                                 const spt_bank_params* bank, float* out, float* mse_or_null,
+                                 uint8_t* choice_or_null);
+/* The figures of an mse plane and a choice plane (DEVICE, the denoiser's h*w each). Waits on `stream`.
+ * The pair summary's two-stage reduction in a fixed order (no floating-point atomics): the same planes
+ * give the same bits every time. The host statement sums in pixel order: the two agree to rounding. */
+spt_status spt_denoise_bank_summary(spt_denoiser* dn, const float* mse_dev, const uint8_t* choice_dev,
+                                    spt_bank_summary* out, void* stream);
+spt_status spt_denoise_bank_summary_host(const float* mse, const uint8_t* choice, int32_t width,
+                                         int32_t height, spt_bank_summary* out);
+/* Two films and a guide in one call, as spt_film_pair_denoise: the result equals spt_denoise_bank_async on
+ * the separately resolved planes bit for bit. Rejected, nothing queued, every output untouched: what
+ * spt_denoise_bank_async and spt_film_pair_denoise reject (sharded films included). */
+spt_status spt_film_pair_denoise_bank(const spt_film* film_a, const spt_film* film_b,
+                                      const spt_guide* guide, spt_denoiser* dn,
+                                      const spt_denoise_params* cands, int32_t n_cands,
+                                      const spt_bank_params* bank, float* out_dev, float* mse_dev_or_null,
+                                      uint8_t* choice_dev_or_null, void* stream);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

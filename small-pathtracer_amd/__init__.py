@@ -141,6 +141,21 @@ class spt_pair_summary(ctypes.Structure):
                 "diff_max": float(self.diff_max)}
 
 
+class spt_bank_params(ctypes.Structure):
+    _fields_ = [("error_iterations", ctypes.c_int32), ("pair_flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+class spt_bank_summary(ctypes.Structure):
+    _fields_ = [("mse_mean", ctypes.c_double), ("rmse_est", ctypes.c_double), ("share", ctypes.c_double * 4),
+                ("mse_min", ctypes.c_float), ("mse_max", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {"mse_mean": float(self.mse_mean), "rmse_est": float(self.rmse_est),
+                "share": [float(x) for x in self.share], "mse_min": float(self.mse_min),
+                "mse_max": float(self.mse_max)}
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -180,7 +195,11 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_denoise_default_params", "spt_denoiser_create", "spt_denoiser_destroy",
            "spt_denoise_async", "spt_denoise_host", "spt_film_denoise",
            "spt_denoise_pair_async", "spt_denoise_pair_host", "spt_denoise_pair_summary",
-           "spt_denoise_pair_summary_host", "spt_film_pair_denoise"]
+           "spt_denoise_pair_summary_host", "spt_film_pair_denoise",
+           "spt_denoise_bank_default_params", "spt_denoise_bank_async", "spt_denoise_bank_host",
+           "spt_denoise_bank_summary", "spt_denoise_bank_summary_host", "spt_film_pair_denoise_bank"]
+SPT_HAS_DENOISE_BANK = 1    # include/spt.h: the filter bank (denoise_bank_host, Denoiser.denoise_bank, ...)
+BANK_MAX_CANDIDATES = 4     # SPT_BANK_MAX_CANDIDATES
 SPT_HAS_DENOISE_PAIR = 1    # include/spt.h: the two-half filter (denoise_pair_host, Denoiser.denoise_pair, ...)
 DENOISE_PAIR_OWN_WEIGHTS = 1  # SPT_DENOISE_PAIR_OWN_WEIGHTS: each half weighted by its own colours
 SPT_HAS_DENOISE = 1         # include/spt.h: the a-trous filter (Denoiser, denoise_host, render_denoised)
@@ -354,9 +373,20 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_denoise_pair_summary_host.argtypes = [VP, I32, I32, P(spt_pair_summary)]
     lib.spt_film_pair_denoise.argtypes = [VP, VP, VP, VP, P(spt_denoise_params), ctypes.c_uint32, VP, VP,
                                           VP, VP]
+    lib.spt_denoise_bank_default_params.argtypes = [P(spt_bank_params)]
+    lib.spt_denoise_bank_default_params.restype = None
+    lib.spt_denoise_bank_async.argtypes = [VP] + [VP] * 7 + [P(spt_denoise_params), I32, P(spt_bank_params), VP,
+                                                             VP, VP, VP]
+    lib.spt_denoise_bank_host.argtypes = [VP] * 7 + [I32, I32, P(spt_denoise_params), I32, P(spt_bank_params),
+                                                     VP, VP, VP]
+    lib.spt_denoise_bank_summary.argtypes = [VP, VP, VP, P(spt_bank_summary), VP]
+    lib.spt_denoise_bank_summary_host.argtypes = [VP, VP, I32, I32, P(spt_bank_summary)]
+    lib.spt_film_pair_denoise_bank.argtypes = [VP, VP, VP, VP, P(spt_denoise_params), I32, P(spt_bank_params),
+                                               VP, VP, VP, VP]
     for name in ("spt_denoiser_create", "spt_denoiser_destroy", "spt_denoise_async", "spt_denoise_host",
                  "spt_denoise_pair_async", "spt_denoise_pair_host", "spt_denoise_pair_summary",
-                 "spt_denoise_pair_summary_host"):
+                 "spt_denoise_pair_summary_host", "spt_denoise_bank_async", "spt_denoise_bank_host",
+                 "spt_denoise_bank_summary", "spt_denoise_bank_summary_host"):
         getattr(lib, name).restype = I32
     for name in EXPORTS:
         if name.startswith("spt_film_") or name.startswith("spt_guide_"):
@@ -1449,6 +1479,74 @@ def pair_summary_host(diff) -> dict:
     return out.as_dict()
 
 
+def default_bank_params(**kw) -> spt_bank_params:
+    """spt_denoise_bank_default_params() with the given fields replaced."""
+    b = spt_bank_params()
+    load_library().spt_denoise_bank_default_params(ctypes.byref(b))
+    for k, v in kw.items():
+        if k not in ("error_iterations", "pair_flags"):
+            raise TypeError(f"spt_bank_params has no settable field {k!r}")
+        setattr(b, k, v)
+    return b
+
+
+def _bank_args(cands, bank, own_weights, error_iterations):
+    """-> (the candidates as a ctypes array, their count, the spt_bank_params). cands: a sequence of
+    spt_denoise_params. bank: an spt_bank_params, or None for the defaults with own_weights and
+    error_iterations (None: the default) put in."""
+    cands = list(cands)
+    arr = (spt_denoise_params * max(len(cands), 1))()
+    for k, c in enumerate(cands):
+        ctypes.memmove(ctypes.byref(arr, k * ctypes.sizeof(spt_denoise_params)), ctypes.byref(c),
+                       ctypes.sizeof(spt_denoise_params))
+    if bank is None:
+        bank = default_bank_params(pair_flags=_pair_flags(own_weights))
+        if error_iterations is not None:
+            bank.error_iterations = int(error_iterations)
+    return arr, len(cands), bank
+
+
+def bank_candidates(sigma_colors=(2.0, 4.0, 8.0), denoise: spt_denoise_params | None = None) -> list:
+    """One copy of `denoise` (default: the defaults) per sigma_color: the bank's candidates."""
+    cands = []
+    for sc in sigma_colors:
+        c = spt_denoise_params()
+        ctypes.memmove(ctypes.byref(c), ctypes.byref(denoise if denoise is not None else default_denoise_params()),
+                       ctypes.sizeof(c))
+        c.sigma_color = float(sc)
+        cands.append(c)
+    return cands
+
+
+def denoise_bank_host(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth, cands, bank: spt_bank_params | None = None,
+                      own_weights=True, error_iterations=None, return_mse=True, return_choice=True):
+    """spt_denoise_bank_host(): the CPU statement of the filter bank (no device). cands: 1..4
+    spt_denoise_params (bank_candidates()). -> (out (h, w, 3) float32, mse (h, w) float32, choice (h, w)
+    uint8); a plane that was not asked for is None (and NULL in the call)."""
+    planes, h, w = _pair_planes(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth)
+    arr, n, b = _bank_args(cands, bank, own_weights, error_iterations)
+    out = np.empty((h, w, 3), np.float32)
+    mse = np.empty((h, w), np.float32) if return_mse else None
+    choice = np.empty((h, w), np.uint8) if return_choice else None
+    _check(load_library().spt_denoise_bank_host(
+        *[a.ctypes.data for a in planes], w, h, arr, n, ctypes.byref(b), out.ctypes.data,
+        mse.ctypes.data if return_mse else None, choice.ctypes.data if return_choice else None))
+    return out, mse, choice
+
+
+def bank_summary_host(mse, choice) -> dict:
+    """spt_denoise_bank_summary_host(): {"mse_mean", "rmse_est", "share": [4], "mse_min", "mse_max"} of an
+    mse plane (h, w) float32 and a choice plane (h, w) uint8."""
+    m = np.ascontiguousarray(mse, dtype=np.float32)
+    c = np.ascontiguousarray(choice, dtype=np.uint8)
+    if m.ndim != 2 or c.shape != m.shape:
+        raise SptError(1, "mse and choice are not two (height, width) planes of one shape")
+    out = spt_bank_summary()
+    _check(load_library().spt_denoise_bank_summary_host(m.ctypes.data, c.ctypes.data, m.shape[1], m.shape[0],
+                                                        ctypes.byref(out)))
+    return out.as_dict()
+
+
 class Denoiser:
     """spt_denoiser: the filter's scratch for width x height images on one device. Calls on one
     denoiser go on one stream."""
@@ -1610,6 +1708,92 @@ class Denoiser:
         return out.as_dict()
 
 
+    # ---- the filter bank (spt_denoise_bank_*, spt_film_pair_denoise_bank) ----
+    def _bank_outputs(self):
+        import torch
+        n, dev = self.width * self.height, f"cuda:{self.device}"
+        return (torch.empty(n * 3, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+                torch.empty(n, dtype=torch.uint8, device=dev))
+
+    def _bank_host(self, bufs):
+        import torch
+        torch.cuda.synchronize(self.device)
+        h, w = self.height, self.width
+        return (bufs[0].cpu().numpy().reshape(h, w, 3), bufs[1].cpu().numpy().reshape(h, w),
+                bufs[2].cpu().numpy().reshape(h, w))
+
+    def denoise_bank_async(self, rgb_a_ptr: int, se_a_ptr: int, rgb_b_ptr: int, se_b_ptr: int, albedo_ptr: int,
+                           normal_ptr: int, depth_ptr: int, cands, n_cands: int, bank: spt_bank_params,
+                           out_ptr: int, mse_ptr: int = 0, choice_ptr: int = 0, stream_ptr: int = 0):
+        """spt_denoise_bank_async() on device pointers; cands: a ctypes array of spt_denoise_params."""
+        V = ctypes.c_void_p
+        ins = (rgb_a_ptr, se_a_ptr, rgb_b_ptr, se_b_ptr, albedo_ptr, normal_ptr, depth_ptr)
+        _check(self.lib.spt_denoise_bank_async(self._d, *[V(x or None) for x in ins], cands, int(n_cands),
+                                               ctypes.byref(bank), V(out_ptr or None), V(mse_ptr or None),
+                                               V(choice_ptr or None), V(stream_ptr or None)))
+
+    def denoise_bank(self, rgb_a, se_a, rgb_b, se_b, albedo, normal, depth, cands,
+                     bank: spt_bank_params | None = None, own_weights=True, error_iterations=None):
+        """Host arrays in (uploaded through torch) -> (out (h, w, 3), mse (h, w), choice (h, w) uint8) on
+        the host."""
+        import torch
+        planes, h, w = _pair_planes(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth)
+        if (h, w) != (self.height, self.width):
+            raise SptError(1, "the planes are not the denoiser's height x width")
+        arr, n, b = _bank_args(cands, bank, own_weights, error_iterations)
+        with torch.cuda.device(self.device):
+            dev = [torch.from_numpy(a.reshape(-1)).to(f"cuda:{self.device}") for a in planes]
+            bufs = self._bank_outputs()
+            self.denoise_bank_async(*[t.data_ptr() for t in dev], arr, n, b, *[x.data_ptr() for x in bufs],
+                                    torch.cuda.current_stream().cuda_stream)
+            return self._bank_host(bufs)
+
+    def denoise_film_bank_async(self, film_a: "Film", film_b: "Film", guide: "Guide", cands, n_cands: int,
+                                bank: spt_bank_params, out_ptr: int, mse_ptr: int = 0, choice_ptr: int = 0,
+                                stream_ptr: int = 0):
+        """spt_film_pair_denoise_bank() into device pointers."""
+        V = ctypes.c_void_p
+        _check(self.lib.spt_film_pair_denoise_bank(film_a._f, film_b._f, guide._g, self._d, cands, int(n_cands),
+                                                   ctypes.byref(bank), V(out_ptr or None), V(mse_ptr or None),
+                                                   V(choice_ptr or None), V(stream_ptr or None)))
+
+    def denoise_film_bank(self, film_a: "Film", film_b: "Film", guide: "Guide", cands,
+                          bank: spt_bank_params | None = None, own_weights=True, error_iterations=None,
+                          return_summary=False):
+        """Both films and the guide resolved and run through the filter bank on the device in one call ->
+        (out, mse, choice) on the host; return_summary: also bank_summary of mse and choice."""
+        import torch
+        arr, n, b = _bank_args(cands, bank, own_weights, error_iterations)
+        with torch.cuda.device(self.device):
+            bufs = self._bank_outputs()
+            stream = torch.cuda.current_stream().cuda_stream
+            self.denoise_film_bank_async(film_a, film_b, guide, arr, n, b, *[x.data_ptr() for x in bufs], stream)
+            summary = self.bank_summary(bufs[1].data_ptr(), bufs[2].data_ptr(), stream) if return_summary else None
+            res = self._bank_host(bufs)
+            return res + (summary,) if return_summary else res
+
+    def bank_summary(self, mse, choice, stream_ptr: int = 0) -> dict:
+        """spt_denoise_bank_summary(): {"mse_mean", "rmse_est", "share", "mse_min", "mse_max"} of an mse and
+        a choice plane: two device pointers (int), or two host arrays (h, w) that are uploaded first; waits
+        for the stream."""
+        import torch
+        out = spt_bank_summary()
+        with torch.cuda.device(self.device):
+            keep = None
+            if not isinstance(mse, int):
+                m = np.ascontiguousarray(mse, dtype=np.float32)
+                c = np.ascontiguousarray(choice, dtype=np.uint8)
+                if m.size != self.width * self.height or c.size != m.size:
+                    raise SptError(1, "mse or choice does not have height * width elements")
+                keep = [torch.from_numpy(a.reshape(-1)).to(f"cuda:{self.device}") for a in (m, c)]
+                mse, choice = keep[0].data_ptr(), keep[1].data_ptr()
+                stream_ptr = stream_ptr or torch.cuda.current_stream().cuda_stream
+            _check(self.lib.spt_denoise_bank_summary(self._d, ctypes.c_void_p(mse or None),
+                                                     ctypes.c_void_p(choice or None), ctypes.byref(out),
+                                                     ctypes.c_void_p(stream_ptr or None)))
+        return out.as_dict()
+
+
 def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, batch: int | None = None,
                     guide_spp: int | None = None, denoise: spt_denoise_params | None = None,
                     return_info=False, through_specular: bool = False):
@@ -1727,10 +1911,47 @@ def render_denoised_pair(prims: Sequence[spt_prim], cam: Camera, params: spt_par
                      "noisy": noisy}
 
 
+def render_denoised_bank(prims: Sequence[spt_prim], cam: Camera, params: spt_params,
+                         sigma_colors=(2.0, 4.0, 8.0), batch: int | None = None, guide_spp: int | None = None,
+                         denoise: spt_denoise_params | None = None, own_weights: bool = True,
+                         error_iterations: int | None = 3, through_specular: bool = False,
+                         return_info=False):
+    """render_denoised_pair's render (two noise films, a guide) through the filter bank
+    (Denoiser.denoise_film_bank): one candidate per sigma_color (1..4 of them), the other filter
+    parameters `denoise`'s (default: the defaults), per pixel the candidate of least cross-validated
+    error, blended. One device. The defaults come from measurements (HEAD and mirror_glass, 256x192, 16
+    seeds, 64 / 256 / 1024 spp): own weights, because with cross weights the estimate that picks
+    the filter is not merely low but negative on renders (-1.0 to -1.4 times the true squared error), and
+    three smoothing passes (error_iterations=None: the library's two), because the choice among noisy
+    estimates is the weak point: RMSE over the film's 0.257 / 0.273 / 0.329 on HEAD with three passes,
+    0.300 / 0.311 / 0.358 with two, beside 0.246 / 0.276 / 0.343 for sigma_color 8 alone and 0.239 / 0.258 /
+    0.318 for render_denoised_pair's cross weights, which remain the better image where no error plane is
+    wanted. The bank wins where the candidates fail in different places (the balls' silhouette band on
+    mirror_glass: 0.583 / 0.599 / 0.620 against 0.585-0.765 for its candidates alone).
+    return_info: also {"mse": the blended estimate of the squared
+    error, "choice": the candidate each pixel chose, "bank": the summary of the two, "guides": the guide
+    planes}."""
+    spp = int(params.spp)
+    batch = _pair_batch("render_denoised_bank", params, batch)
+    n_guide = min(spp, int(guide_spp or 64))
+    cands = bank_candidates(sigma_colors, denoise)
+    with _pair_session(params, batch, through_specular) as (r, fa, fb, guide, dn, stream):
+        for k in range(spp // batch):
+            (fb if k & 1 else fa).render(r, prims, cam, params, k * batch, batch, 0, stream)
+            r.stats()  # a pass that hit the runaway guard raises here
+        guide.render(r, prims, cam, params, 0, n_guide, stream)
+        out, mse, choice, summary = dn.denoise_film_bank(fa, fb, guide, cands, None, own_weights,
+                                                         error_iterations, return_summary=True)
+        if not return_info:
+            return out
+        return out, {"mse": mse, "choice": choice, "bank": summary, "guides": guide.resolve(stream_ptr=stream)}
+
+
 def render_denoised_until(prims: Sequence[spt_prim], cam: Camera, params: spt_params, target_rmse: float,
                           batch: int | None = None, min_batches: int = 4, own_weights: bool = True,
                           guide_spp: int | None = None, denoise: spt_denoise_params | None = None,
-                          through_specular: bool = False):
+                          through_specular: bool = False, estimate: str = "diff",
+                          sigma_colors=(2.0, 4.0, 8.0)):
     """Render until the DENOISED image's measured error is at most target_rmse. The guide is rendered
     first; batches of `batch` samples go in index order alternately into film A (even k) and film B
     (odd k), params.spp the cap. After every second batch from min_batches on (rounded up to an even
@@ -1743,7 +1964,18 @@ def render_denoised_until(prims: Sequence[spt_prim], cam: Camera, params: spt_pa
     (mirror_glass) with cross weights, where the halves' results correlate. Over the true squared error
     against a 65536-spp render: 0.76-0.88 with own weights (the true RMSE is 1.06-1.15x the figure this
     call stops on), 0.26-0.46 with cross weights. Both read variance only: the filter's bias is not in
-    diff (include/spt.h)."""
+    diff (include/spt.h).
+    estimate="bank" (opt-in): the filter bank runs instead (one candidate per sigma_colors, three
+    smoothing passes, as render_denoised_bank) and the render stops once the bank summary's rmse_est,
+    which sees bias, is at most target_rmse; "rmse" in the result is then that one figure and "bank" the
+    whole summary. NOT recommended with several candidates: the least of several noisy estimates reads low
+    by selection, and on the renders above mean mse over the true squared error is 0.37-0.69 (0.14-0.49
+    with two passes), worse than diff's 0.76-0.88. With ONE sigma_color there is no selection and the
+    figure does see bias: 0.74 / 0.85 / 0.86 at sigma_color 4 (diff: 0.80 / 0.85 / 0.76) and 0.52 / 0.69 /
+    0.78 at 8 (diff: 0.50 / 0.49 / 0.39) on HEAD at 64 / 256 / 1024 spp; at 64 spp, four batches per half,
+    it still reads low."""
+    if estimate not in ("diff", "bank"):
+        raise SptError(1, "render_denoised_until: estimate is 'diff' or 'bank'")
     spp = int(params.spp)
     batch = _pair_batch("render_denoised_until", params, batch)
     need = max(4, int(min_batches) + (int(min_batches) & 1))
@@ -1756,7 +1988,14 @@ def render_denoised_until(prims: Sequence[spt_prim], cam: Camera, params: spt_pa
             (fb if k & 1 else fa).render(r, prims, cam, params, k * batch, batch, 0, stream)
             r.stats()  # a pass that hit the runaway guard raises here
             done = k + 1
-            if done >= need and done % 2 == 0:
+            if done >= need and done % 2 == 0 and estimate == "bank":
+                out, _mse, _choice, bank = dn.denoise_film_bank(fa, fb, guide,
+                                                                bank_candidates(sigma_colors, denoise), None,
+                                                                own_weights, 3, return_summary=True)
+                rmse = bank["rmse_est"]
+                if rmse <= target_rmse:
+                    return out, {"samples_done": done * batch, "batches_done": done, "rmse": rmse, "bank": bank}
+            elif done >= need and done % 2 == 0:
                 out, _se, _diff, pair = dn.denoise_film_pair(fa, fb, guide, denoise, own_weights,
                                                              return_summary=True)
                 rmse = pair["rmse"]

@@ -4,7 +4,16 @@
 //               [--device N | --devices N] [--p6 | --pfm]
 //               [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]
 //               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]
-//               [--pair [--pair-own]]] [--through-specular] [--help]
+//               [--pair [--pair-own] [--bank S,S,.. [--bank-map PREFIX]]]] [--through-specular] [--help]
+//   --bank S,S,.. (with --denoise --pair): the filter bank (spt_film_pair_denoise_bank): one candidate per
+//               colour sigma in the list (1 to 4 of them), each half weighted by its own colours, three
+//               smoothing passes of the error estimates, per pixel the candidate of least cross-validated
+//               error, blended. Prints "BANK : rmse_est
+//               share.. after N / SPP": the bank summary's estimate of the output's RMSE, bias included,
+//               and the fraction of pixels that chose each candidate. With --noise T the run stops on
+//               rmse_est. --bank-map PREFIX also writes PREFIX_mse.pfm (the blended estimate of the squared
+//               error, signed, replicated to three channels) and PREFIX_choice.pgm (binary P5, the chosen
+//               candidate's index times 85). Not with --denoise-sigma.
 //   --pair (with --denoise): two-half denoising (spt_film_pair_denoise). The batches go alternately
 //               into two noise films (even batch indices into A, odd into B; SPP / B must be even and
 //               at least 4), each half is filtered with colour weights taken from the other half, and
@@ -72,6 +81,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -117,6 +127,8 @@ struct DenoiseOpts {
   int iters = 0;
   double sigma = 0.0;
   bool pair = false, pair_own = false;  // --pair [--pair-own]: two films, spt_film_pair_denoise
+  std::vector<float> bank;              // --bank S,S,..: the candidates' colour sigmas (spt_film_pair_denoise_bank)
+  const char* bank_map = nullptr;       // --bank-map PREFIX
 };
 
 void check(spt_status s) {
@@ -279,6 +291,26 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
   return dev;
 }
 
+// --bank-map: the mse plane and, behind it, the choice plane of the last bank call, from the device.
+void write_bank_map(const std::string& prefix, const float* mse_dev, const spt_params& p) {
+  const size_t npix = (size_t)p.width * (size_t)p.height;
+  std::vector<float> mse(npix), mse3(3 * npix);
+  std::vector<uint8_t> choice(npix);
+  if (hipMemcpy(mse.data(), mse_dev, npix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(choice.data(), mse_dev + npix, npix, hipMemcpyDeviceToHost) != hipSuccess)
+    throw std::runtime_error("bank map download failed");
+  for (size_t i = 0; i < npix; ++i) mse3[3 * i] = mse3[3 * i + 1] = mse3[3 * i + 2] = mse[i];
+  const std::string mse_path = prefix + "_mse.pfm", choice_path = prefix + "_choice.pgm";
+  if (write_ppm(mse_path.c_str(), p.width, p.height, mse3.data(), p.device, SPT_IMAGE_PFM))
+    throw std::runtime_error("cannot write " + mse_path + ": " + spt_last_error());
+  for (uint8_t& c : choice) c = (uint8_t)(c * 85);
+  FILE* f = std::fopen(choice_path.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot write " + choice_path);
+  std::fprintf(f, "P5\n%d %d\n255\n", p.width, p.height);
+  const bool ok = std::fwrite(choice.data(), 1, npix, f) == npix;
+  if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + choice_path);
+}
+
 // --denoise --pair: the batches alternately into two noise films, the guide, the two-half filter. With
 // noise.target > 0 the filter runs after every second batch from noise.min_batches on and the run ends
 // once the largest channel's RMS half-difference is at most the target. Returns the DEVICE image.
@@ -293,6 +325,13 @@ float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const 
   if (denoise.iters_given) dp.iterations = denoise.iters;
   if (denoise.sigma_given) dp.sigma_color = (float)denoise.sigma;
   const uint32_t pair_flags = denoise.pair_own ? SPT_DENOISE_PAIR_OWN_WEIGHTS : 0u;
+  const bool bank_on = !denoise.bank.empty();
+  std::vector<spt_denoise_params> cands(denoise.bank.size(), dp);
+  for (size_t k = 0; k < cands.size(); ++k) cands[k].sigma_color = denoise.bank[k];
+  spt_bank_params bp;
+  spt_denoise_bank_default_params(&bp);  // own weights
+  bp.error_iterations = 3;  // render_denoised_bank's choice: the widest smoothing picks best
+  spt_bank_summary bs{};
   spt_context* ctx = nullptr;
   spt_film* film[2] = {nullptr, nullptr};
   spt_guide* guide = nullptr;
@@ -305,7 +344,7 @@ float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const 
   check(spt_guide_create_ex(p.device, &p, denoise.through_specular ? SPT_GUIDE_THROUGH_SPECULAR : 0u, &guide));
   check(spt_denoiser_create(p.device, p.width, p.height, &dn));
   const size_t n = 3ull * (size_t)p.width * (size_t)p.height;
-  float* dev = nullptr;  // out, then diff
+  float* dev = nullptr;  // out, then diff (the bank: mse, then choice)
   if (hipMalloc(&dev, std::max<size_t>(n, 1) * 2 * sizeof(float)) != hipSuccess)
     throw std::runtime_error("device allocation failed");
   std::memset(total, 0, sizeof *total);
@@ -325,12 +364,28 @@ float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const 
     done = k + 1;
     const bool look = noise.target > 0.0 && done >= need && done % 2 == 0;
     if (!look && done < batches) continue;
+    if (bank_on) {
+      float* mse = dev + n;
+      uint8_t* choice = (uint8_t*)(mse + n / 3);
+      check(spt_film_pair_denoise_bank(film[0], film[1], guide, dn, cands.data(), (int32_t)cands.size(), &bp, dev,
+                                       mse, choice, nullptr));
+      check(spt_denoise_bank_summary(dn, mse, choice, &bs, nullptr));
+      if (look && bs.rmse_est <= noise.target) break;
+      continue;
+    }
     check(spt_film_pair_denoise(film[0], film[1], guide, dn, &dp, pair_flags, dev, nullptr, dev + n, nullptr));
     check(spt_denoise_pair_summary(dn, dev + n, &sm, nullptr));
     if (look && std::max(sm.rmse[0], std::max(sm.rmse[1], sm.rmse[2])) <= noise.target) break;
   }
-  std::cout << "PAIR : " << sm.rmse[0] << " " << sm.rmse[1] << " " << sm.rmse[2] << " after "
-            << (int64_t)done * batch << " / " << p.spp << std::endl;
+  if (bank_on) {
+    std::cout << "BANK : " << bs.rmse_est;
+    for (size_t k = 0; k < cands.size(); ++k) std::cout << " " << bs.share[k];
+    std::cout << " after " << (int64_t)done * batch << " / " << p.spp << std::endl;
+    if (denoise.bank_map) write_bank_map(denoise.bank_map, dev + n, p);
+  } else {
+    std::cout << "PAIR : " << sm.rmse[0] << " " << sm.rmse[1] << " " << sm.rmse[2] << " after "
+              << (int64_t)done * batch << " / " << p.spp << std::endl;
+  }
   check(spt_denoiser_destroy(dn));
   check(spt_guide_destroy(guide));
   for (spt_film* f : film) check(spt_film_destroy(f));
@@ -377,7 +432,7 @@ const char kUsage[] =
     "            [--film PATH [--add N]]\n"
     "            [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]\n"
     "            [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]\n"
-    "            [--pair [--pair-own]]] [--through-specular]\n"
+    "            [--pair [--pair-own] [--bank S,S,.. [--bank-map PREFIX]]]] [--through-specular]\n"
     "  --guides PREFIX  also write the first-hit guide planes PREFIX_albedo.pfm, PREFIX_normal.pfm\n"
     "                   and PREFIX_depth.pfm (linear PFM). The normal is stored signed, components\n"
     "                   in [-1, 1] (not 0.5 + 0.5 n); the depth is the mean ray parameter of the\n"
@@ -395,7 +450,12 @@ const char kUsage[] =
     "                   the RMS of half their difference. With --noise T the run stops on that figure.\n"
     "                   Not with --adaptive, --film or --passes.\n"
     "  --pair-own       with --pair: each half weighted by its own colours; the PAIR figure is then an\n"
-    "                   unbiased estimate of the output's variance (with cross weights it reads low)\n";
+    "                   unbiased estimate of the output's variance (with cross weights it reads low)\n"
+    "  --bank S,S,..    with --pair: the filter bank, one candidate per colour sigma (1 to 4), own weights;\n"
+    "                   per pixel the candidate of least cross-validated error, blended; prints BANK, the\n"
+    "                   estimated RMSE (bias included) and each candidate's share of the pixels. With\n"
+    "                   --noise T the run stops on that estimate. Not with --denoise-sigma.\n"
+    "  --bank-map PREFIX  with --bank: also write PREFIX_mse.pfm and PREFIX_choice.pgm\n";
 
 }  // namespace
 
@@ -438,6 +498,15 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--through-specular")) denoise.through_specular = true;
     else if (!std::strcmp(argv[i], "--pair")) denoise.pair = true;
     else if (!std::strcmp(argv[i], "--pair-own")) denoise.pair_own = true;
+    else if (!std::strcmp(argv[i], "--bank") && i + 1 < argc) {
+      char* s = argv[++i];
+      for (char* end = s; *s; s = *end == ',' ? end + 1 : end) {
+        denoise.bank.push_back(std::strtof(s, &end));
+        if (end == s || (*end && *end != ',')) { denoise.bank.assign(1, -1.0f); break; }
+      }
+      if (denoise.bank.empty()) denoise.bank.assign(1, -1.0f);
+    }
+    else if (!std::strcmp(argv[i], "--bank-map") && i + 1 < argc) denoise.bank_map = argv[++i];
     else if (!std::strcmp(argv[i], "--denoise-iters") && i + 1 < argc) { denoise.iters_given = true; denoise.iters = std::atoi(argv[++i]); }
     else if (!std::strcmp(argv[i], "--denoise-sigma") && i + 1 < argc) { denoise.sigma_given = true; denoise.sigma = std::atof(argv[++i]); }
     else if (!std::strcmp(argv[i], "--help")) { std::cout << kUsage; return 0; }
@@ -477,6 +546,14 @@ int main(int argc, char* argv[]) {
       throw std::runtime_error("--denoise-iters / --denoise-sigma go with --denoise");
     if ((denoise.pair || denoise.pair_own) && !denoise.on) throw std::runtime_error("--pair goes with --denoise");
     if (denoise.pair_own && !denoise.pair) throw std::runtime_error("--pair-own goes with --pair");
+    if (!denoise.bank.empty() && !denoise.pair) throw std::runtime_error("--bank goes with --denoise --pair");
+    if (denoise.bank_map && denoise.bank.empty()) throw std::runtime_error("--bank-map goes with --bank");
+    if (!denoise.bank.empty()) {
+      if (denoise.sigma_given) throw std::runtime_error("--bank gives the colour sigmas: not with --denoise-sigma");
+      if (denoise.bank.size() > SPT_BANK_MAX_CANDIDATES) throw std::runtime_error("--bank: 1 to 4 colour sigmas");
+      for (float v : denoise.bank)
+        if (!(v > 0.0f && std::isfinite(v))) throw std::runtime_error("--bank: a comma-separated list of positive, finite numbers");
+    }
     if (denoise.on) {
       if (devices > 1) throw std::runtime_error("--denoise goes with one device: a shard's rows are not image neighbours");
       if (denoise.iters_given && (denoise.iters < 0 || denoise.iters > 6))

@@ -303,4 +303,171 @@ inline void pair_summary_finish(const PairPartial& t, size_t npix, spt_pair_summ
   out->reserved = 0;
 }
 
+// ---- the filter bank (include/spt.h, SPT_HAS_DENOISE_BANK) ----
+// The pair filter at a few parameter sets, a cross-validated error estimate per pixel and candidate,
+// smoothed with the geometric factor alone, and the candidates blended by the smoothed choice.
+
+constexpr int32_t kMaxCands = SPT_BANK_MAX_CANDIDATES, kMaxErrorIterations = 3;
+
+// NULL when the candidates and the bank parameters are in range, else what is wrong with them.
+inline const char* bank_error(const spt_denoise_params* cands, int32_t n_cands, const spt_bank_params* b) {
+  if (!cands) return "null candidates";
+  if (n_cands < 1 || n_cands > kMaxCands) return "n_cands outside 1..4";
+  for (int32_t k = 0; k < n_cands; ++k)
+    if (const char* e = params_error(cands + k)) return e;
+  if (!b) return "null bank params";
+  if (b->error_iterations < 0 || b->error_iterations > kMaxErrorIterations) return "error_iterations outside 0..3";
+  if (const char* e = pair_flags_error(b->pair_flags)) return e;
+  if (b->reserved[0] != 0 || b->reserved[1] != 0) return "reserved must be 0";
+  return nullptr;
+}
+
+// The pair's finish with the halves kept: o^A and o^B as finish_pair takes them.
+SPT_FILM_FN void finish_halves(const f4& ca, const f4& cb, const f4& av, const Args& A, float* oa, float* ob) {
+  const float a[3] = {divisor(av.x, A), divisor(av.y, A), divisor(av.z, A)};
+  oa[0] = fminf(ca.x * a[0], 1.0f);
+  oa[1] = fminf(ca.y * a[1], 1.0f);
+  oa[2] = fminf(ca.z * a[2], 1.0f);
+  ob[0] = fminf(cb.x * a[0], 1.0f);
+  ob[1] = fminf(cb.y * a[1], 1.0f);
+  ob[2] = fminf(cb.z * a[2], 1.0f);
+}
+
+// Step 2: a candidate's out (3 floats) and its cross-validated error m at one pixel.
+SPT_FILM_FN float bank_error_of(const float* oa, const float* ob, const float* rgb_a, const float* se_a,
+                                const float* rgb_b, const float* se_b, float* out) {
+  float m[3];
+  for (int c = 0; c < 3; ++c) {
+    out[c] = 0.5f * (oa[c] + ob[c]);
+    const float d = 0.5f * (oa[c] - ob[c]);
+    const float ra = oa[c] - rgb_b[c], rb = ob[c] - rgb_a[c];
+    const float e = 0.5f * ((ra * ra - se_b[c] * se_b[c]) + (rb * rb - se_a[c] * se_a[c]));
+    m[c] = e - d * d;
+  }
+  return ((m[0] + m[1]) + m[2]) * (1.0f / 3.0f);
+}
+
+// The geometric factor g of a tap that is not the centre: acc_tap_pair's, with no colour in it.
+SPT_FILM_FN float geom_weight(int i, int j, int32_t step, const f4& nzp, const f4& avp, float gx, float gy,
+                              const f4& nzq, const f4& avq, const Args& A) {
+  float wn = fmaxf(0.0f, dot3(nzp.x, nzp.y, nzp.z, nzq.x, nzq.y, nzq.z));
+  for (int k = 0; k < A.squarings; ++k) wn = wn * wn;
+  const float dx = (float)(i * step), dy = (float)(j * step);
+  const float wz = phi(fabsf(nzp.w - nzq.w) / ((A.sd * fabsf(gx * dx + gy * dy) + 1e-3f * nzp.w) + 1e-6f));
+  const float a0 = avp.x - avq.x, a1 = avp.y - avq.y, a2 = avp.z - avq.z;
+  const float wa = phi(dot3(a0, a1, a2, a0, a1, a2) / A.sa2);
+  return (((h5(j) * h5(i)) * wn) * wz) * wa;
+}
+
+// Step 4: the smallest k < n whose estimate is least.
+SPT_FILM_FN int bank_choice(const f4& m, int32_t n) {
+  int k = 0;
+  float best = m.x;
+  if (n > 1 && m.y < best) {
+    k = 1;
+    best = m.y;
+  }
+  if (n > 2 && m.z < best) {
+    k = 2;
+    best = m.z;
+  }
+  if (n > 3 && m.w < best) k = 3;
+  return k;
+}
+
+// Steps 3 and 5 at one pixel. Planes: any accessor with f4 m(x, y), nz(x, y), av(x, y); m holds the four
+// candidates' estimates (those of no candidate are 0 and stay 0). BLEND false: one smoothing pass, the
+// smoothed estimates. BLEND true (step 1): the shares s_k of the n candidates among the neighbours' choices.
+template <bool BLEND, class Planes>
+SPT_FILM_FN f4 bank_pass(const Planes& P, int32_t x, int32_t y, int32_t w, int32_t h, int32_t step, float gx,
+                         float gy, const Args& A, int32_t n) {
+  const f4 nzp = P.nz(x, y), avp = P.av(x, y);
+  float W = 0.0f;
+  f4 M = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int j = -2; j <= 2; ++j) {
+    const int64_t yy = (int64_t)y + (int64_t)j * step;
+    if (yy < 0 || yy >= h) continue;
+    for (int i = -2; i <= 2; ++i) {
+      const int64_t xx = (int64_t)x + (int64_t)i * step;
+      if (xx < 0 || xx >= w) continue;
+      const int32_t qx = (int32_t)xx, qy = (int32_t)yy;
+      const f4 mq = P.m(qx, qy);
+      const float g = (i == 0 && j == 0) ? 0.375f * 0.375f
+                                         : geom_weight(i, j, step, nzp, avp, gx, gy, P.nz(qx, qy), P.av(qx, qy), A);
+      W = W + g;
+      if constexpr (BLEND) {
+        const int kq = bank_choice(mq, n);
+        M.x = M.x + g * (kq == 0 ? 1.0f : 0.0f);
+        M.y = M.y + g * (kq == 1 ? 1.0f : 0.0f);
+        M.z = M.z + g * (kq == 2 ? 1.0f : 0.0f);
+        M.w = M.w + g * (kq == 3 ? 1.0f : 0.0f);
+      } else {
+        M.x = M.x + g * mq.x;
+        M.y = M.y + g * mq.y;
+        M.z = M.z + g * mq.z;
+        M.w = M.w + g * mq.w;
+      }
+    }
+  }
+  return f4{M.x / W, M.y / W, M.z / W, M.w / W};
+}
+
+// Step 5's sums at one pixel: s the shares, m the pixel's smoothed estimates, outk the n candidates' out
+// planes `stride` floats apart, i3 = 3 * the pixel's index. -> mse.
+SPT_FILM_FN float bank_blend(const f4& s, const f4& m, int32_t n, const float* outk, size_t stride, size_t i3,
+                             float* out) {
+  const float sk[4] = {s.x, s.y, s.z, s.w}, mk[4] = {m.x, m.y, m.z, m.w};
+  float o[3] = {0.0f, 0.0f, 0.0f}, mse = 0.0f;
+  for (int k = 0; k < 4; ++k) {  // fixed bounds: sk and mk stay in registers
+    if (k >= n) break;
+    const float* q = outk + (size_t)k * stride + i3;
+    o[0] = o[0] + sk[k] * q[0];
+    o[1] = o[1] + sk[k] * q[1];
+    o[2] = o[2] + sk[k] * q[2];
+    mse = mse + sk[k] * mk[k];
+  }
+  out[0] = fminf(o[0], 1.0f);
+  out[1] = fminf(o[1], 1.0f);
+  out[2] = fminf(o[2], 1.0f);
+  return mse;
+}
+
+// The summary of an mse and a choice plane.
+struct BankPartial {
+  double sum, count[4];
+  float mn, mx;
+};
+
+SPT_FILM_FN BankPartial bank_partial_zero() {
+  BankPartial p;
+  p.sum = 0.0;
+  for (int k = 0; k < 4; ++k) p.count[k] = 0.0;
+  p.mn = INFINITY;
+  p.mx = -INFINITY;
+  return p;
+}
+
+SPT_FILM_FN void bank_partial_add(BankPartial& p, float mse, uint8_t choice) {
+  p.sum += (double)mse;
+  for (int k = 0; k < 4; ++k) p.count[k] += choice == k ? 1.0 : 0.0;
+  p.mn = fminf(p.mn, mse);
+  p.mx = fmaxf(p.mx, mse);
+}
+
+SPT_FILM_FN void bank_partial_merge(BankPartial& a, const BankPartial& b) {
+  a.sum += b.sum;
+  for (int k = 0; k < 4; ++k) a.count[k] += b.count[k];
+  a.mn = fminf(a.mn, b.mn);
+  a.mx = fmaxf(a.mx, b.mx);
+}
+
+inline void bank_summary_finish(const BankPartial& t, size_t npix, spt_bank_summary* out) {
+  const double n = (double)npix;
+  out->mse_mean = t.sum / n;
+  out->rmse_est = std::sqrt(out->mse_mean > 0.0 ? out->mse_mean : 0.0);
+  for (int k = 0; k < 4; ++k) out->share[k] = t.count[k] / n;
+  out->mse_min = t.mn;
+  out->mse_max = t.mx;
+}
+
 }  // namespace spt_denoise_math

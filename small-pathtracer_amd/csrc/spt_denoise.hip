@@ -2,7 +2,9 @@
 // the denoiser object that owns the scratch, the pack, variance and a-trous kernels and the
 // spt_denoise_* / spt_film_denoise calls, and the two-half filter (SPT_HAS_DENOISE_PAIR): its pack,
 // variance, a-trous and summary kernels, its scratch, and the spt_denoise_pair_* / spt_film_pair_denoise
-// calls. The arithmetic is spt_denoise.h's, shared with the CPU statement (spt_denoise_host.cpp): the
+// calls, and the filter bank (SPT_HAS_DENOISE_BANK): the halves-storing pair finish, the error, smoothing,
+// blend and summary kernels, its scratch, and the spt_denoise_bank_* / spt_film_pair_denoise_bank calls.
+// The arithmetic is spt_denoise.h's, shared with the CPU statement (spt_denoise_host.cpp): the
 // kernels only decide which lane takes which pixel.
 #include <hip/hip_runtime.h>
 
@@ -31,6 +33,14 @@ struct spt_denoiser {
   float *vtb = nullptr, *rgb_b = nullptr, *se_b = nullptr;
   double* parts = nullptr;
   uint32_t n_parts = 0;
+  // the bank scratch (SPT_HAS_DENOISE_BANK), allocated by the first bank call: the halves' results o^A and
+  // o^B of the candidate in flight, the four out_k planes, the ping-pong planes of the four error
+  // estimates, the bank summary's partials and total
+  void* bank_base = nullptr;
+  f4* bm[2] = {nullptr, nullptr};
+  float *oa = nullptr, *ob = nullptr, *outk = nullptr;
+  size_t outk_stride = 0;  // floats between two candidates' out planes
+  double* bank_parts = nullptr;
 };
 
 namespace {
@@ -349,6 +359,138 @@ denoise_pair_total_kernel(const double* __restrict__ parts, uint32_t n, PairPart
   if (threadIdx.x == 0) *total = s_p[0];
 }
 
+// ---- the filter bank (SPT_HAS_DENOISE_BANK) ----
+
+// The last iteration of a candidate's pair run with the halves kept: denoise_atrous_pair_kernel<true>'s
+// pixel and taps, finish_halves instead of finish_pair (plain loads at every step: the tiled form would
+// give the same bits).
+__global__ void __launch_bounds__(kBlock)
+denoise_atrous_pair_halves_kernel(const f4* __restrict__ ca, const f4* __restrict__ cb, const f4* __restrict__ nz,
+                                  const f4* __restrict__ av, const float* __restrict__ vtb,
+                                  const float2* __restrict__ grad, int32_t w, int32_t h, int32_t step, Args A,
+                                  int32_t own, float* __restrict__ oa, float* __restrict__ ob) {
+  int32_t x, y;
+  if (!pixel_of(w, h, &x, &y)) return;
+  const size_t i = (size_t)y * w + x;
+  const DevPairPlanes P{ca, cb, nz, av, vtb, w};
+  const float2 g = grad[i];
+  f4 ra, rb;
+  iterate_pair(P, x, y, w, h, step, g.x, g.y, A, own != 0, &ra, &rb);
+  finish_halves(ra, rb, av[i], A, oa + 3 * i, ob + 3 * i);
+}
+
+// Candidate k's out plane and its error estimate, one pixel per thread: component k of the pixel's 16-byte
+// element of estimates (candidate 0 writes the whole element, the others' components 0).
+__global__ void __launch_bounds__(kBlock)
+denoise_bank_error_kernel(const float* __restrict__ oa, const float* __restrict__ ob,
+                          const float* __restrict__ rgb_a, const float* __restrict__ se_a,
+                          const float* __restrict__ rgb_b, const float* __restrict__ se_b, size_t npix,
+                          int32_t k, f4* __restrict__ m, float* __restrict__ out_k) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  const float a[3] = {oa[3 * i], oa[3 * i + 1], oa[3 * i + 2]}, b[3] = {ob[3 * i], ob[3 * i + 1], ob[3 * i + 2]};
+  float o[3];
+  const float e = bank_error_of(a, b, rgb_a + 3 * i, se_a + 3 * i, rgb_b + 3 * i, se_b + 3 * i, o);
+  out_k[3 * i] = o[0];
+  out_k[3 * i + 1] = o[1];
+  out_k[3 * i + 2] = o[2];
+  if (k == 0)
+    m[i] = f4{e, 0.0f, 0.0f, 0.0f};
+  else
+    ((float*)(m + i))[k] = e;
+}
+
+struct DevBankPlanes {
+  const f4 *m_, *nz_, *av_;
+  int32_t w;
+  __device__ __forceinline__ f4 m(int32_t x, int32_t y) const { return m_[(size_t)y * w + x]; }
+  __device__ __forceinline__ f4 nz(int32_t x, int32_t y) const { return nz_[(size_t)y * w + x]; }
+  __device__ __forceinline__ f4 av(int32_t x, int32_t y) const { return av_[(size_t)y * w + x]; }
+};
+
+// One smoothing pass of the estimates: a pixel per lane, three 16-byte loads per tap (the estimates,
+// (n, z), (albedo, .)), the bounds test per tap.
+__global__ void __launch_bounds__(kBlock)
+denoise_bank_smooth_kernel(const f4* __restrict__ m, const f4* __restrict__ nz, const f4* __restrict__ av,
+                           const float2* __restrict__ grad, int32_t w, int32_t h, int32_t step, Args A,
+                           int32_t n, f4* __restrict__ m_out) {
+  int32_t x, y;
+  if (!pixel_of(w, h, &x, &y)) return;
+  const size_t i = (size_t)y * w + x;
+  const DevBankPlanes P{m, nz, av, w};
+  const float2 g = grad[i];
+  m_out[i] = bank_pass<false>(P, x, y, w, h, step, g.x, g.y, A, n);
+}
+
+// Choice and blend in one pass: the argmin of every neighbour's loaded estimates on the fly, the shares,
+// the blended image, the blended estimate and the pixel's own choice.
+__global__ void __launch_bounds__(kBlock)
+denoise_bank_blend_kernel(const f4* __restrict__ m, const f4* __restrict__ nz, const f4* __restrict__ av,
+                          const float2* __restrict__ grad, int32_t w, int32_t h, Args A, int32_t n,
+                          const float* __restrict__ outk, size_t stride, float* __restrict__ out,
+                          float* __restrict__ mse, uint8_t* __restrict__ choice) {
+  int32_t x, y;
+  if (!pixel_of(w, h, &x, &y)) return;
+  const size_t i = (size_t)y * w + x;
+  const DevBankPlanes P{m, nz, av, w};
+  const float2 g = grad[i];
+  const f4 s = bank_pass<true>(P, x, y, w, h, 1, g.x, g.y, A, n);
+  const f4 mp = m[i];
+  float o[3];
+  const float e = bank_blend(s, mp, n, outk, stride, 3 * i, o);
+  out[3 * i] = o[0];
+  out[3 * i + 1] = o[1];
+  out[3 * i + 2] = o[2];
+  if (mse) mse[i] = e;
+  if (choice) choice[i] = (uint8_t)bank_choice(mp, n);
+}
+
+// The bank summary, in the pair summary's shape: p[0] = the block's 256 partials combined pairwise.
+__device__ __forceinline__ void bank_block_reduce(BankPartial* p) {
+  for (uint32_t w = kBlock / 2; w > 0; w >>= 1) {
+    __syncthreads();
+    if (threadIdx.x < w) bank_partial_merge(p[threadIdx.x], p[threadIdx.x + w]);
+  }
+  __syncthreads();
+}
+
+// Stage 1: one pixel per thread, one partial per block, as seven planes of nb = gridDim.x doubles.
+__global__ void __launch_bounds__(kBlock)
+denoise_bank_partials_kernel(const float* __restrict__ mse, const uint8_t* __restrict__ choice, size_t npix,
+                             double* __restrict__ out) {
+  __shared__ BankPartial s_p[kBlock];
+  const size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  BankPartial v = bank_partial_zero();
+  if (px < npix) bank_partial_add(v, mse[px], choice[px]);
+  s_p[threadIdx.x] = v;
+  bank_block_reduce(s_p);
+  if (threadIdx.x == 0) {
+    const size_t nb = gridDim.x;
+    out[blockIdx.x] = s_p[0].sum;
+    for (int k = 0; k < 4; ++k) out[(size_t)(1 + k) * nb + blockIdx.x] = s_p[0].count[k];
+    out[5 * nb + blockIdx.x] = (double)s_p[0].mn;
+    out[6 * nb + blockIdx.x] = (double)s_p[0].mx;
+  }
+}
+
+// Stage 2, one block: thread t merges the partials t, t + 256, ... in that order; *total = the image's.
+__global__ void __launch_bounds__(kBlock)
+denoise_bank_total_kernel(const double* __restrict__ parts, uint32_t n, BankPartial* __restrict__ total) {
+  __shared__ BankPartial s_p[kBlock];
+  BankPartial v = bank_partial_zero();
+  for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
+    BankPartial b;
+    b.sum = parts[i];
+    for (int k = 0; k < 4; ++k) b.count[k] = parts[(size_t)(1 + k) * n + i];
+    b.mn = (float)parts[5 * (size_t)n + i];
+    b.mx = (float)parts[6 * (size_t)n + i];
+    bank_partial_merge(v, b);
+  }
+  s_p[threadIdx.x] = v;
+  bank_block_reduce(s_p);
+  if (threadIdx.x == 0) *total = s_p[0];
+}
+
 size_t tiles_of(int32_t w, int32_t h, int tile_x, int tile_y) {
   return (((size_t)w + tile_x - 1) / tile_x) * (((size_t)h + tile_y - 1) / tile_y);
 }
@@ -542,6 +684,96 @@ spt_status check_pair_film(const spt_film* film, const spt_guide* guide, const s
   return SPT_OK;
 }
 
+// The bank scratch, allocated once per denoiser at its first bank call (spt.h: 104 bytes per pixel and the
+// summary's partials).
+spt_status bank_scratch(spt_denoiser* dn) {
+  if (dn->bank_base) return SPT_OK;
+  const size_t n = dn->npix, n4 = (n + 3) & ~(size_t)3;
+  const size_t blocks = (n + kBlock - 1) / kBlock;
+  const size_t bytes = n * 2 * sizeof(f4) + (2 + kMaxCands) * 3 * n4 * sizeof(float) +
+                       7 * blocks * sizeof(double) + sizeof(BankPartial);
+  SPT_HIP(hipSetDevice(dn->device));
+  void* base = nullptr;
+  const hipError_t e = hipMalloc(&base, bytes);
+  if (e != hipSuccess) return fail(SPT_ERR_OOM, std::string("denoiser bank scratch alloc: ") + hipGetErrorString(e));
+  dn->bank_base = base;
+  dn->bm[0] = (f4*)base;
+  dn->bm[1] = dn->bm[0] + n;
+  dn->oa = (float*)(dn->bm[1] + n);
+  dn->ob = dn->oa + 3 * n4;
+  dn->outk = dn->ob + 3 * n4;
+  dn->outk_stride = 3 * n4;
+  dn->bank_parts = (double*)(dn->outk + kMaxCands * 3 * n4);  // 16-byte aligned, as the pair scratch's
+  return SPT_OK;
+}
+
+// The bank of seven device planes, already validated, the pair and the bank scratch in place.
+spt_status run_bank(spt_denoiser* dn, const float* rgb_a, const float* se_a, const float* rgb_b,
+                    const float* se_b, const float* albedo, const float* normal, const float* depth,
+                    const spt_denoise_params* cands, int32_t n_cands, const spt_bank_params* bank, float* out,
+                    float* mse, uint8_t* choice, hipStream_t stream) {
+  const dim3 block(kBlock), grid((unsigned)tiles_of(dn->width, dn->height, kTileX, kTileY)), flat(dn->n_parts);
+  const int32_t w = dn->width, h = dn->height;
+  const int32_t own = (bank->pair_flags & SPT_DENOISE_PAIR_OWN_WEIGHTS) ? 1 : 0;
+  for (int32_t k = 0; k < n_cands; ++k) {
+    const spt_denoise_params* p = cands + k;
+    const float *oa = rgb_a, *ob = rgb_b;  // iterations == 0: the halves as given
+    if (p->iterations > 0) {
+      const Args A = make_args(p);
+      hipLaunchKernelGGL(denoise_pair_pack_kernel, grid, block, 0, stream, rgb_a, se_a, rgb_b, se_b, albedo,
+                         normal, depth, w, h, A, dn->cv[0], dn->cb[0], dn->nz, dn->av, dn->grad);
+      for (int32_t it = 0; it < p->iterations; ++it) {
+        const f4 *ca = dn->cv[it & 1], *cb = dn->cb[it & 1];
+        hipLaunchKernelGGL(denoise_pair_variance_kernel, grid, block, 0, stream, ca, cb, dn->av, dn->vtb, w, h);
+        if (it < p->iterations - 1)
+          launch_atrous_pair(dn, ca, cb, (int32_t)1 << it, false, A, own, dn->cv[(it + 1) & 1],
+                             dn->cb[(it + 1) & 1], nullptr, nullptr, nullptr, g_pair_form, stream);
+        else
+          hipLaunchKernelGGL(denoise_atrous_pair_halves_kernel, grid, block, 0, stream, ca, cb,
+                             (const f4*)dn->nz, (const f4*)dn->av, (const float*)dn->vtb,
+                             (const float2*)dn->grad, w, h, (int32_t)1 << it, A, own, dn->oa, dn->ob);
+      }
+      oa = dn->oa;
+      ob = dn->ob;
+    }
+    hipLaunchKernelGGL(denoise_bank_error_kernel, flat, block, 0, stream, oa, ob, rgb_a, se_a, rgb_b, se_b,
+                       dn->npix, k, dn->bm[0], dn->outk + (size_t)k * dn->outk_stride);
+  }
+  const Args A0 = make_args(cands);
+  if (cands[n_cands - 1].iterations == 0)  // no candidate's pack left the guides in the scratch
+    hipLaunchKernelGGL(denoise_pair_pack_kernel, grid, block, 0, stream, rgb_a, se_a, rgb_b, se_b, albedo, normal,
+                       depth, w, h, A0, dn->cv[0], dn->cb[0], dn->nz, dn->av, dn->grad);
+  const f4* cur = dn->bm[0];
+  for (int32_t it = 0; it < bank->error_iterations; ++it) {
+    f4* nxt = dn->bm[(it + 1) & 1];
+    hipLaunchKernelGGL(denoise_bank_smooth_kernel, grid, block, 0, stream, cur, (const f4*)dn->nz,
+                       (const f4*)dn->av, (const float2*)dn->grad, w, h, (int32_t)1 << it, A0, n_cands, nxt);
+    cur = nxt;
+  }
+  hipLaunchKernelGGL(denoise_bank_blend_kernel, grid, block, 0, stream, cur, (const f4*)dn->nz, (const f4*)dn->av,
+                     (const float2*)dn->grad, w, h, A0, n_cands, (const float*)dn->outk, dn->outk_stride, out, mse,
+                     choice);
+  SPT_HIP(hipGetLastError());
+  return SPT_OK;
+}
+
+spt_status check_bank_call(const spt_denoiser* dn, const spt_denoise_params* cands, int32_t n_cands,
+                           const spt_bank_params* bank, const float* out, const float* mse, const uint8_t* choice,
+                           std::initializer_list<const float*> inputs) {
+  if (!dn) return fail(SPT_ERR_INVALID_ARG, "null denoiser");
+  if (const char* e = bank_error(cands, n_cands, bank)) return fail(SPT_ERR_INVALID_ARG, std::string("denoise_bank: ") + e);
+  if (!out) return fail(SPT_ERR_INVALID_ARG, "denoise_bank: null output plane");
+  const void *o = out, *m = mse, *c = choice;
+  if (m == o || c == o || (m && m == c))
+    return fail(SPT_ERR_INVALID_ARG, "denoise_bank: two output planes are one plane");
+  for (const float* in : inputs) {
+    if (!in) return fail(SPT_ERR_INVALID_ARG, "denoise_bank: null plane");
+    if (in == o || in == m || in == c)
+      return fail(SPT_ERR_INVALID_ARG, "denoise_bank: an output plane is an input plane");
+  }
+  return SPT_OK;
+}
+
 }  // namespace
 
 extern "C" spt_status spt_denoiser_create(int32_t device, int32_t width, int32_t height,
@@ -587,6 +819,7 @@ extern "C" spt_status spt_denoiser_destroy(spt_denoiser* dn) {
     (void)hipSetDevice(dn->device);
     (void)hipFree(dn->base);
     if (dn->pair_base) (void)hipFree(dn->pair_base);
+    if (dn->bank_base) (void)hipFree(dn->bank_base);
   }
   delete dn;
   return SPT_OK;
@@ -683,6 +916,67 @@ extern "C" spt_status spt_denoise_pair_summary(spt_denoiser* dn, const float* di
   return SPT_OK;
 }
 
+extern "C" spt_status spt_denoise_bank_async(spt_denoiser* dn, const float* rgb_a_dev, const float* se_a_dev,
+                                             const float* rgb_b_dev, const float* se_b_dev,
+                                             const float* albedo_dev, const float* normal_dev,
+                                             const float* depth_dev, const spt_denoise_params* cands,
+                                             int32_t n_cands, const spt_bank_params* bank, float* out_dev,
+                                             float* mse_dev, uint8_t* choice_dev, void* stream) {
+  SPT_TRY(check_bank_call(dn, cands, n_cands, bank, out_dev, mse_dev, choice_dev,
+                          {rgb_a_dev, se_a_dev, rgb_b_dev, se_b_dev, albedo_dev, normal_dev, depth_dev}));
+  SPT_TRY(pair_scratch(dn));
+  SPT_TRY(bank_scratch(dn));
+  SPT_HIP(hipSetDevice(dn->device));
+  return run_bank(dn, rgb_a_dev, se_a_dev, rgb_b_dev, se_b_dev, albedo_dev, normal_dev, depth_dev, cands, n_cands,
+                  bank, out_dev, mse_dev, choice_dev, (hipStream_t)stream);
+}
+
+extern "C" spt_status spt_film_pair_denoise_bank(const spt_film* film_a, const spt_film* film_b,
+                                                 const spt_guide* guide, spt_denoiser* dn,
+                                                 const spt_denoise_params* cands, int32_t n_cands,
+                                                 const spt_bank_params* bank, float* out_dev, float* mse_dev,
+                                                 uint8_t* choice_dev, void* stream) {
+  if (!film_a || !film_b || !guide) return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise_bank: null film or guide");
+  SPT_TRY(check_bank_call(dn, cands, n_cands, bank, out_dev, mse_dev, choice_dev, {}));
+  if (film_a == film_b) return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise_bank: the two halves are one film");
+  if (guide->samples_done == 0) return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise_bank: the guide holds no sample");
+  SPT_TRY(check_pair_film(film_a, guide, dn));
+  SPT_TRY(check_pair_film(film_b, guide, dn));
+  if (film_a->spp_total != film_b->spp_total)
+    return fail(SPT_ERR_INVALID_ARG, "film_pair_denoise_bank: the films' spp_total differ");
+  SPT_TRY(pair_scratch(dn));
+  SPT_TRY(bank_scratch(dn));
+  SPT_TRY(spt_film_resolve(film_a, dn->rgb, stream));
+  SPT_TRY(spt_film_noise_map(film_a, dn->se, stream));
+  SPT_TRY(spt_film_resolve(film_b, dn->rgb_b, stream));
+  SPT_TRY(spt_film_noise_map(film_b, dn->se_b, stream));
+  SPT_TRY(spt_guide_resolve(guide, dn->albedo, dn->normal, dn->depth, nullptr, stream));
+  SPT_HIP(hipSetDevice(dn->device));
+  return run_bank(dn, dn->rgb, dn->se, dn->rgb_b, dn->se_b, dn->albedo, dn->normal, dn->depth, cands, n_cands,
+                  bank, out_dev, mse_dev, choice_dev, (hipStream_t)stream);
+}
+
+extern "C" spt_status spt_denoise_bank_summary(spt_denoiser* dn, const float* mse_dev, const uint8_t* choice_dev,
+                                               spt_bank_summary* out, void* stream_v) {
+  if (!dn || !mse_dev || !choice_dev || !out) return fail(SPT_ERR_INVALID_ARG, "denoise_bank_summary: null argument");
+  SPT_TRY(pair_scratch(dn));
+  SPT_TRY(bank_scratch(dn));
+  hipStream_t stream = (hipStream_t)stream_v;
+  SPT_HIP(hipSetDevice(dn->device));
+  BankPartial* total_dev = (BankPartial*)(dn->bank_parts + 7 * (size_t)dn->n_parts);
+  hipLaunchKernelGGL(denoise_bank_partials_kernel, dim3(dn->n_parts), dim3(kBlock), 0, stream, mse_dev, choice_dev,
+                     dn->npix, dn->bank_parts);
+  SPT_HIP(hipGetLastError());
+  hipLaunchKernelGGL(denoise_bank_total_kernel, dim3(1), dim3(kBlock), 0, stream, (const double*)dn->bank_parts,
+                     dn->n_parts, total_dev);
+  SPT_HIP(hipGetLastError());
+  BankPartial total = bank_partial_zero();
+  SPT_HIP(hipMemcpyAsync(&total, total_dev, sizeof total, hipMemcpyDeviceToHost, stream));
+  SPT_HIP(hipStreamSynchronize(stream));
+  bank_summary_finish(total, dn->npix, out);
+  return SPT_OK;
+}
+
 #ifdef SPT_DENOISE_BENCH  // tools/denoise_bench.py's library only: never in the shipped libspt.so
 // 0 = by step, 1 = plain loads always, 2 = the tiled form where it exists.
 extern "C" spt_status spt_denoise_bench_form(int32_t form) {
@@ -750,6 +1044,40 @@ extern "C" spt_status spt_denoise_pair_bench_kernel(spt_denoiser* dn, int32_t wh
     launch_atrous_pair(dn, dn->cv[0], dn->cb[0], step, which == 3, A, own, which == 3 ? nullptr : dn->cv[1],
                        which == 3 ? nullptr : dn->cb[1], which == 3 ? out : nullptr, which == 3 ? se_out : nullptr,
                        which == 3 ? diff : nullptr, form, stream);
+  SPT_HIP(hipGetLastError());
+  return SPT_OK;
+}
+// One launch of one bank kernel on the scratch a bank call has left (call spt_denoise_bank_async first).
+// which: 0 the error kernel of candidate 0 over the scratch's halves, 1 a smoothing pass of step `step`
+// from one estimate plane into the other, 2 the choice-and-blend kernel of n_cands candidates into out /
+// mse / choice, 3 the halves-storing pair pass of step `step` over (cv[0], cb[0]).
+extern "C" spt_status spt_denoise_bank_bench_kernel(spt_denoiser* dn, int32_t which, int32_t step, int32_t n_cands,
+                                                    const float* rgb_a, const float* se_a, const float* rgb_b,
+                                                    const float* se_b, const spt_denoise_params* params,
+                                                    float* out, float* mse, uint8_t* choice, void* stream_v) {
+  if (!dn || !dn->bank_base || params_error(params) || which < 0 || which > 3 || step < 1 || step > 32 ||
+      (step & (step - 1)) || n_cands < 1 || n_cands > kMaxCands || (which == 2 && !out) ||
+      (which == 0 && (!rgb_a || !se_a || !rgb_b || !se_b)))
+    return fail(SPT_ERR_INVALID_ARG, "bank_bench_kernel: bad argument, or no bank call before");
+  hipStream_t stream = (hipStream_t)stream_v;
+  const Args A = make_args(params);
+  const int32_t w = dn->width, h = dn->height;
+  const dim3 grid((unsigned)tiles_of(w, h, kTileX, kTileY)), block(kBlock);
+  SPT_HIP(hipSetDevice(dn->device));
+  if (which == 0)
+    hipLaunchKernelGGL(denoise_bank_error_kernel, dim3(dn->n_parts), block, 0, stream, (const float*)dn->oa,
+                       (const float*)dn->ob, rgb_a, se_a, rgb_b, se_b, dn->npix, 0, dn->bm[0], dn->outk);
+  else if (which == 1)
+    hipLaunchKernelGGL(denoise_bank_smooth_kernel, grid, block, 0, stream, (const f4*)dn->bm[0], (const f4*)dn->nz,
+                       (const f4*)dn->av, (const float2*)dn->grad, w, h, step, A, n_cands, dn->bm[1]);
+  else if (which == 2)
+    hipLaunchKernelGGL(denoise_bank_blend_kernel, grid, block, 0, stream, (const f4*)dn->bm[0], (const f4*)dn->nz,
+                       (const f4*)dn->av, (const float2*)dn->grad, w, h, A, n_cands, (const float*)dn->outk,
+                       dn->outk_stride, out, mse, choice);
+  else
+    hipLaunchKernelGGL(denoise_atrous_pair_halves_kernel, grid, block, 0, stream, (const f4*)dn->cv[0],
+                       (const f4*)dn->cb[0], (const f4*)dn->nz, (const f4*)dn->av, (const float*)dn->vtb,
+                       (const float2*)dn->grad, w, h, step, A, 1, dn->oa, dn->ob);
   SPT_HIP(hipGetLastError());
   return SPT_OK;
 }

@@ -37,6 +37,19 @@ guides) at 256x192, 16 seeds, 8 batches (four per half), a guide of 64 samples, 
 image-mean shift, and for both modes mean diff^2 and mean se_out^2 over the variance of `out` across
 the seeds and over the mean squared error against the truth. And the configuration that
 tests/test_gpu_denoise_pair.py pins.
+
+--bank (python tools/denoise_bench.py --bank [OUT.json], default build/r28_denoise_bank.json): the filter
+bank (SPT_HAS_DENOISE_BANK). Cost: at both shapes, 20 timed rounds after 5 warm-up rounds, every round
+measuring by device events K spt_denoise_pair_async calls and one spt_denoise_bank_async of K candidates,
+for K = 2 and 3 (sigma_color 2, 8 and 2, 4, 8), own weights, the order rotating; the bank's overhead over
+the K pair calls per round; with the bench library the single bank kernels (error, smoothing at steps 1
+and 2, blend, the halves-storing pair pass) beside a plain pair a-trous pass of the same session. Quality
+and calibration: --pair's protocol (HEAD, and mirror_glass by region; 256x192, 16 seeds, 8 batches, a
+guide of 64 samples, truth 16 x 4096 spp, at 64 / 256 / 1024 spp): the RMSE over the film's of the bank of
+sigma_color {2, 4, 8} with own and with cross weights (and of that bank with three smoothing passes, of a
+bank of {4, 8} and of one candidate alone, where no selection takes place), of each candidate alone (pair,
+own and cross), the share of the pixels per candidate by region, and mean mse and mean own-weight diff^2
+over the mean squared error against the truth.
 """
 import importlib
 import json
@@ -615,11 +628,234 @@ def main_pair(out):
                                 for s, v in rec["quality"][name]["by_spp"].items()}), flush=True)
 
 
+# ---- the filter bank (--bank) -----------------------------------------------------------------------
+BANK_SIGMAS = (2.0, 4.0, 8.0)
+# the banks of the quality protocol: name -> (sigma_colors, own weights, error_iterations or None = default).
+# Beside the bank of the issue with own and cross weights: the widest smoothing, a bank without the narrow
+# candidate, and one candidate alone (no selection: what the estimate reads before an argmin is taken).
+BANK_VARIANTS = {"bank_own": (BANK_SIGMAS, True, None), "bank_cross": (BANK_SIGMAS, False, None),
+                 "bank_own_3_passes": (BANK_SIGMAS, True, 3), "bank_own_4_8": ((4.0, 8.0), True, None),
+                 "one_own_4": ((4.0,), True, None), "one_own_8": ((8.0,), True, None)}
+
+
+def time_bank(spt, torch, w, h, runs=20, warmup=5):
+    """K pair calls and one bank call of K candidates per round, K = 2 and 3, the order rotating."""
+    planes = _pair_planes(w, h)
+    dev = [torch.from_numpy(a.reshape(-1)).cuda() for a in planes]
+    ptr = [t.data_ptr() for t in dev]
+    outs = [torch.empty(w * h * 3, dtype=torch.float32, device="cuda") for _ in range(3)]
+    o = [t.data_ptr() for t in outs]
+    mse = torch.empty(w * h, dtype=torch.float32, device="cuda")
+    choice = torch.empty(w * h, dtype=torch.uint8, device="cuda")
+    dn = spt.Denoiser(w, h, 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    own = spt.DENOISE_PAIR_OWN_WEIGHTS
+    sets = {2: (2.0, 8.0), 3: BANK_SIGMAS}
+
+    def pairs(k):
+        cands = spt.bank_candidates(sets[k])
+
+        def run():
+            for c in cands:
+                dn.denoise_pair_async(*ptr, c, own, o[0], 0, o[2], stream)
+        return run
+
+    def bank(k):
+        arr, n, b = spt._bank_args(spt.bank_candidates(sets[k]), None, True, None)
+
+        def run():
+            dn.denoise_bank_async(*ptr, arr, n, b, o[1], mse.data_ptr(), choice.data_ptr(), stream)
+        return run
+
+    what = [("pairs_2", pairs(2)), ("bank_2", bank(2)), ("pairs_3", pairs(3)), ("bank_3", bank(3))]
+    ms = {k: [] for k, _ in what}
+    try:
+        for r in range(warmup + runs):
+            for j in range(len(what)):
+                name, run = what[(j + r) % len(what)]
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                run()
+                b.record()
+                torch.cuda.synchronize()
+                if r >= warmup:
+                    ms[name].append(a.elapsed_time(b))
+    finally:
+        dn.close()
+    res = {k: _stat(v) for k, v in ms.items()}
+    for k in (2, 3):
+        over = np.array(ms[f"bank_{k}"]) - np.array(ms[f"pairs_{k}"])
+        ratio = np.array(ms[f"bank_{k}"]) / np.array(ms[f"pairs_{k}"])
+        res[f"overhead_{k}_ms_per_round"] = _stat(over)
+        res[f"bank_over_pairs_{k}_per_round"] = {"median": float(np.median(ratio)), "min": float(ratio.min()),
+                                                 "max": float(ratio.max())}
+    return res
+
+
+def bank_kernel_times(spt, torch, w, h, launches=50, rounds=7):
+    """Per-launch milliseconds of the bank kernels alone, beside a plain pair a-trous pass."""
+    import ctypes
+    lib = spt.load_library()
+    if not hasattr(lib, "spt_denoise_bank_bench_kernel"):
+        return {"skipped": "the loaded library has no bench entry points (make denoise_bench)"}
+    V, I32 = ctypes.c_void_p, ctypes.c_int32
+    P = ctypes.POINTER(spt.spt_denoise_params)
+    lib.spt_denoise_bank_bench_kernel.argtypes = [V, I32, I32, I32] + [V] * 4 + [P, V, V, V, V]
+    lib.spt_denoise_bank_bench_kernel.restype = I32
+    lib.spt_denoise_pair_bench_kernel.argtypes = [V, I32, I32, I32] + [V] * 7 + [P, ctypes.c_uint32, V, V, V, V]
+    lib.spt_denoise_pair_bench_kernel.restype = I32
+    dev = [torch.from_numpy(a.reshape(-1)).cuda() for a in _pair_planes(w, h)]
+    ptr = [t.data_ptr() for t in dev]
+    outs = [torch.empty(w * h * 3, dtype=torch.float32, device="cuda") for _ in range(3)]
+    mse = torch.empty(w * h, dtype=torch.float32, device="cuda")
+    choice = torch.empty(w * h, dtype=torch.uint8, device="cuda")
+    p = spt.default_denoise_params()
+    dn = spt.Denoiser(w, h, 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    arr, n, b = spt._bank_args(spt.bank_candidates(BANK_SIGMAS), None, True, None)
+
+    def bank_kernel(which, step):
+        return lib.spt_denoise_bank_bench_kernel(dn._d, which, step, 3, *[V(x) for x in ptr[:4]], ctypes.byref(p),
+                                                 V(outs[0].data_ptr()), V(mse.data_ptr()), V(choice.data_ptr()),
+                                                 V(stream))
+
+    def pair_kernel(which, step):
+        return lib.spt_denoise_pair_bench_kernel(dn._d, which, step, 1, *[V(x) for x in ptr], ctypes.byref(p), 1,
+                                                 *[V(t.data_ptr()) for t in outs], V(stream))
+
+    def once(launch, *a):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(launches):
+            assert launch(*a) == 0
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / launches
+
+    what = [("bank_error", bank_kernel, 0, 1), ("bank_smooth_step1", bank_kernel, 1, 1),
+            ("bank_smooth_step2", bank_kernel, 1, 2), ("bank_blend", bank_kernel, 2, 1),
+            ("pair_halves_finish_step16_plain", bank_kernel, 3, 16),
+            ("pair_atrous_step1_plain", pair_kernel, 2, 1), ("pair_atrous_step2_plain", pair_kernel, 2, 2),
+            ("pair_atrous_step4_plain", pair_kernel, 2, 4), ("pair_atrous_finish_step16_plain", pair_kernel, 3, 16)]
+    res = {"launches_per_round": launches, "rounds": rounds}
+    try:
+        dn.denoise_bank_async(*ptr, arr, n, b, outs[0].data_ptr(), mse.data_ptr(), choice.data_ptr(), stream)
+        torch.cuda.synchronize()  # the scratch holds a packed pair, the halves and the estimates from here on
+        ms = {name: [] for name, *_ in what}
+        for name, launch, which, step in what:
+            once(launch, which, step)
+        for _ in range(rounds):
+            for name, launch, which, step in what:
+                ms[name].append(once(launch, which, step))
+        res.update({k: _stat(v) for k, v in ms.items()})
+    finally:
+        dn.close()
+    return res
+
+
+def bank_quality(spt, name, w=256, h=192, seeds=16, spps=(64, 256, 1024)):
+    prims = getattr(spt, PAIR_SCENES[name][0])()
+    kw = PAIR_SCENES[name][1]
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = np.zeros((h, w, 3), np.float64)
+    for s in range(16):
+        truth += spt.render(prims, cam, spt.default_params(width=w, height=h, spp=4096, seed=1000 + s, **kw))
+    truth = (truth / 16).astype(np.float32)
+    masks = {"frame": np.ones((h, w), bool)}
+    if name != "HEAD":
+        masks.update(specular_masks(spt, prims, cam, w, h, **kw))
+    res = {"scene": name, "width": w, "height": h, "seeds": seeds, "truth": "16 seeds x 4096 spp", "guide_spp": 64,
+           "batches": 8, "sigma_colors": list(BANK_SIGMAS),
+           "banks": {k: {"sigma_colors": list(v[0]), "own_weights": v[1], "error_iterations": 2 if v[2] is None else v[2]}
+                     for k, v in BANK_VARIANTS.items()}, "pixels": {k: int(m.sum()) for k, m in masks.items()},
+           "by_spp": {}}
+    modes = list(BANK_VARIANTS) + [f"pair_{m}_{sc:g}" for m in ("own", "cross") for sc in BANK_SIGMAS]
+    for spp in spps:
+        batch = spp // 8
+        outs = {m: [] for m in modes}
+        mse_est = {m: [] for m in BANK_VARIANTS}
+        choices = {m: [] for m in BANK_VARIANTS}
+        diff2_own = {sc: [] for sc in BANK_SIGMAS}
+        noisy_all = []
+        for seed in range(1, seeds + 1):
+            p = spt.default_params(width=w, height=h, spp=spp, seed=seed, **kw)
+            r, fa, fb, film, guide, dn = (spt.Renderer(0), spt.Film(p, 0), spt.Film(p, 0), spt.Film(p, 0),
+                                          spt.Guide(p, 0), spt.Denoiser(w, h, 0))
+            try:
+                for f in (fa, fb, film):
+                    f.enable_noise(batch)
+                for k in range(8):
+                    (fb if k & 1 else fa).render(r, prims, cam, p, k * batch, batch)
+                    r.stats()
+                film.merge(fa)
+                film.merge(fb)
+                guide.render(r, prims, cam, p, 0, min(spp, 64))
+                noisy_all.append(film.resolve())
+                for v, (sigmas, own, passes) in BANK_VARIANTS.items():
+                    out, mse, choice = dn.denoise_film_bank(fa, fb, guide, spt.bank_candidates(sigmas), None, own,
+                                                            passes)
+                    outs[v].append(out)
+                    mse_est[v].append(float(mse.mean(dtype=np.float64)))
+                    choices[v].append(choice)
+                for m, own in (("own", True), ("cross", False)):
+                    for sc in BANK_SIGMAS:
+                        out, _se, diff = dn.denoise_film_pair(fa, fb, guide, spt.default_denoise_params(sigma_color=sc),
+                                                              own)
+                        outs[f"pair_{m}_{sc:g}"].append(out)
+                        if own:
+                            diff2_own[sc].append(float(np.mean(diff.astype(np.float64) ** 2)))
+            finally:
+                for o in (dn, guide, film, fa, fb, r):
+                    o.close()
+        one = {"regions": {}, "calibration": {}}
+        for k, mk in masks.items():
+            nz = float(np.mean([rmse(x[mk], truth[mk]) for x in noisy_all]))
+            row = {"rmse_noisy": nz}
+            for m in modes:
+                row[f"ratio_{m}"] = float(np.mean([rmse(x[mk], truth[mk]) for x in outs[m]])) / nz
+            for m, (sigmas, _own, _passes) in BANK_VARIANTS.items():
+                if len(sigmas) > 1:
+                    row[f"share_{m}"] = [float(np.mean([(c[mk] == j).mean() for c in choices[m]]))
+                                         for j in range(len(sigmas))]
+            one["regions"][k] = row
+        for m in BANK_VARIANTS:
+            true = float(np.mean((np.stack(outs[m]).astype(np.float64) - truth.astype(np.float64)) ** 2))
+            one["calibration"][m] = {"mean_mse_estimate": float(np.mean(mse_est[m])), "mse_against_truth": true,
+                                     "mse_over_truth": float(np.mean(mse_est[m])) / true}
+        for sc in BANK_SIGMAS:
+            true = float(np.mean((np.stack(outs[f"pair_own_{sc:g}"]).astype(np.float64) - truth.astype(np.float64)) ** 2))
+            one["calibration"][f"pair_own_{sc:g}"] = {"diff2_over_truth": float(np.mean(diff2_own[sc])) / true}
+        res["by_spp"][str(spp)] = one
+    return res
+
+
+def main_bank(out):
+    import torch
+    spt = importlib.import_module("small-pathtracer_amd")
+    spt.load_library()
+    assert torch.cuda.is_available(), "denoise_bench needs the GPU"
+    rec = {"kernel_sources_sha16": spt.build_sources_sha16(), "device": torch.cuda.get_device_name(0),
+           "utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()), "time": {}, "kernels": {}}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    for w, h in ((1024, 768), (4096, 4096)):
+        rec["time"][f"{w}x{h}"] = time_bank(spt, torch, w, h)
+        rec["kernels"][f"{w}x{h}"] = bank_kernel_times(spt, torch, w, h)
+        json.dump(rec, open(out, "w"), indent=1)
+        print(f"{w}x{h}", json.dumps(rec["time"][f"{w}x{h}"]), json.dumps(rec["kernels"][f"{w}x{h}"]), flush=True)
+    rec["quality"] = {}
+    for name in PAIR_SCENES:
+        rec["quality"][name] = bank_quality(spt, name)
+        json.dump(rec, open(out, "w"), indent=1)  # what is measured survives a failure further on
+        print(name, json.dumps(rec["quality"][name]["by_spp"]), flush=True)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--chain":
         return main_chain(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "guide_chain_denoise.json"))
     if len(sys.argv) > 1 and sys.argv[1] == "--pair":
         return main_pair(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "r27_denoise_pair.json"))
+    if len(sys.argv) > 1 and sys.argv[1] == "--bank":
+        return main_bank(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "r28_denoise_bank.json"))
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "r19_denoise.json")
     import torch
     spt = importlib.import_module("small-pathtracer_amd")
