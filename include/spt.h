@@ -40,7 +40,8 @@ extern "C" {
                              always 0 until then, now reads the guide's flags); SPT_HAS_DENOISE_PAIR,
                              the spt_denoise_pair_* calls and spt_film_pair_denoise;
                              SPT_HAS_DENOISE_BANK, the spt_denoise_bank_* calls and
-                             spt_film_pair_denoise_bank */
+                             spt_film_pair_denoise_bank; SPT_HAS_GUIDE_LIGHT, the spt_light_guide_*
+                             and spt_light_shade_* calls */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
@@ -49,6 +50,7 @@ extern "C" {
 #define SPT_HAS_GUIDE_CHAIN 1 /* guides that follow the specular chain: spt_guide_create_ex (below) */
 #define SPT_GUIDE_THROUGH_SPECULAR 1u /* spt_guide_create_ex flag: records of the first DIFF surface */
 #define SPT_GUIDE_MAX_CHAIN 8 /* segments of a chain at most, the camera ray included */
+#define SPT_HAS_GUIDE_LIGHT 1 /* light guides: per-pixel light visibility and direct irradiance (below) */
 #define SPT_HAS_DENOISE 1 /* the edge-stopping a-trous filter over a film and its guides (below) */
 #define SPT_HAS_DENOISE_PAIR 1 /* two independent halves, cross-weighted, and a measured error (below) */
 #define SPT_HAS_DENOISE_BANK 1 /* a few pair filters, the one of least cross-validated error per pixel (below) */
@@ -601,6 +603,92 @@ spt_status spt_guide_download(const spt_guide* guide, int64_t* host_records, voi
  * spp_total and samples_done. */
 spt_status spt_guide_resolve_host(const int64_t* records, const spt_guide_info* info, float* albedo,
                                   float* normal, float* depth, float* coverage);
+
+/* ---- light guides: per-pixel light visibility and direct irradiance (SPT_HAS_GUIDE_LIGHT) ----
+ * The feature the four guide planes lack: what the light does at the surface a pixel sees. A light guide
+ * is its own object, spt_light_guide: spt_guide_create_ex keeps refusing every flag but
+ * SPT_GUIDE_THROUGH_SPECULAR. It holds one record int64[4] per pixel, in image pixel order; a shard's
+ * light guide holds its compact rows, as a guide does. For pixel p, sample s in [0, spp) and the seed:
+ *   1. THE SURFACE is the guide's own ray and vertex, operation for operation: Philox counter
+ *      (p, s, 1, seed), the jitter, contract v5's camera chain and the scene's normaliser; the nearest
+ *      hit (hit, t, id), t the winner's exact t; the hit point x and the oriented normal nl formed as the
+ *      chain guide forms them (a rectangle's t after one correction step, x = o + d * tr as a multiply
+ *      then an add, a sphere's gn = (x - centre) * (1 / r)). A light guide created with
+ *      SPT_GUIDE_THROUGH_SPECULAR follows the chain rule of SPT_HAS_GUIDE_CHAIN to the vertex where the
+ *      chain guide takes its record; without it the vertex is the first hit. A miss on any segment adds
+ *      nothing.
+ *   2. ELIGIBILITY. The sample is TESTED iff the vertex's primitive is SPT_DIFF and its index is not
+ *      light_id. The render does no NEE at a SPEC or REFR vertex, so an exhausted chain and a first-hit
+ *      mirror are not tested; a vertex on the light is the emitter itself. Otherwise the sample adds
+ *      nothing.
+ *   3. THE LIGHT POINT. r = philox(p, s, 0, seed): word 2 = 0 is used by no render or guide draw (the
+ *      render's vertex words start at 1, stream 1 is 1 | 2^31). xl = fmaf(u01(r.x), light_dx, light_x0),
+ *      zl = fmaf(u01(r.y), light_dz, light_z0), yl = light_y: the render's SPT_LIGHT_UNIFORM arithmetic,
+ *      used for either light_mode. A LIGHT GUIDE ALWAYS SAMPLES THE INTENDED RECTANGLE, also where the
+ *      render's NEE samples the glibc-wrap patch of it (SPT_LIGHT_GLIBC_WRAP): it is a feature, not
+ *      radiance.
+ *   4. THE SHADOW RAY. dl = (xl - x.x, yl - x.y, zl - x.z), three fp32 subtractions; normalised (rsq_nr)
+ *      iff the scene's directions are unit and left as it is in the free-scale contract: the render's
+ *      own rule (:466). It is traced from x with the contract's nearest hit. The sample is LIT iff it
+ *      hits and the hit's index equals light_id (the reference's test :467, for a light primitive of any
+ *      kind; with light_id outside [0, n_prims) nothing is lit).
+ *   5. THE WEIGHT of a lit sample is the render's PDF_inverse * BRDF of :471-472 restated operation for
+ *      operation, t2 the winner's exact t of the shadow ray and nee_c = (float)((double)light_area / pi):
+ *        unit directions: fabsf((light_area * dl.y) * rcp_nr(t2 * t2)) * fabsf(dot(dl, nl) * (1 / pi))
+ *        free-scale:      ((fabsf(dl.y) * fabsf(dot(dl, nl))) * nee_c) * rcp_nr((t2 * t2) * (vv * vv)),
+ *                         vv = dot(dl, dl)
+ *   6. THE RECORD. slot 0 `tested` += 1 for a tested sample; slot 1 `lit` += 1 and slot 2 `weight` +=
+ *      fix(wt) for a lit one, fix the render's own 1.31 conversion (fminf(wt * inv_spp, 1) * 2^31,
+ *      truncated); slot 3 is reserved and stays 0. spp is at most 2^24, as for a guide.
+ * All slots are integers, so the sums depend on no lane mapping, window split, window order, shard or
+ * GPU, as a guide's.
+ * The resolve, n = samples_done, r = (float)((double)spp_total / n) (device kernel and host statement run
+ * the same IEEE operations):
+ *   visibility   = tested ? (float)((double)lit / (double)tested) : 0
+ *   tested_share = (float)((double)tested / (double)n)
+ *   direct       = ((float)S_2 * 2^-31) [* r when n < spp_total]      not clamped
+ *   n == 0: zeros everywhere.
+ * `direct` is the pixel's mean of V * PDF_inverse * BRDF under uniform sampling of the light rectangle:
+ * the direct irradiance factor the render's NEE multiplies the light's emission and the surface's colour
+ * by, averaged over the pixel's samples (an untested sample counts as 0). Its per-sample clamp at spp
+ * (a sample adds at most 2^31) is the film's own.
+ * spt_guide_info describes a light guide too (flags: 0 or SPT_GUIDE_THROUGH_SPECULAR). */
+typedef struct spt_light_guide spt_light_guide;
+/* A zeroed light guide on `device` for passes with p's width, height, spp (= spp_total) and shard
+ * fields. flags: 0 or SPT_GUIDE_THROUGH_SPECULAR. Unknown bits: SPT_ERR_INVALID_ARG (before any device is
+ * looked for), *out untouched. */
+spt_status spt_light_guide_create(int32_t device, const spt_params* p, uint32_t flags, spt_light_guide** out);
+spt_status spt_light_guide_destroy(spt_light_guide* lg);
+spt_status spt_light_guide_clear(spt_light_guide* lg, void* stream); /* records and samples_done back to 0 */
+spt_status spt_light_guide_info_get(const spt_light_guide* lg, spt_guide_info* out);
+/* Enqueue the light-guide pass of the window on `stream`: spt_guide_render_async's rules, rejections
+ * (nothing queued, the light guide untouched) and use of ctx's scene upload and pinned staging. It is no
+ * render: spt_context_stats and spt_context_kernel still describe the context's last render. The light
+ * is p's (light_id, light_x0, light_dx, light_z0, light_dz, light_y, light_area). A shard without rows
+ * only counts. */
+spt_status spt_light_guide_render_async(spt_context* ctx, spt_light_guide* lg, const spt_prim* prims,
+                                        int32_t n_prims, const spt_camera* cam, const spt_params* p,
+                                        int32_t sample_base, int32_t sample_count, void* stream);
+/* Light guide -> float planes (DEVICE, rows*w floats each; any of them may be NULL). */
+spt_status spt_light_guide_resolve(const spt_light_guide* lg, float* visibility_dev, float* direct_dev,
+                                   float* tested_dev, void* stream);
+/* The records to HOST memory (rows*w*4 int64, pixel order); waits for its copy on `stream`. */
+spt_status spt_light_guide_download(const spt_light_guide* lg, int64_t* host_records, void* stream);
+/* The resolve as a pure host function (no device); planes may be NULL. Uses info's width, rows,
+ * spp_total and samples_done. */
+spt_status spt_light_guide_resolve_host(const int64_t* records, const spt_guide_info* info,
+                                        float* visibility, float* direct, float* tested);
+/* The first consumer: an albedo plane (n_pixels * 3 floats) shaded by a visibility plane (n_pixels),
+ *   m = shade_floor + (1.0f - shade_floor) * visibility     a multiply, then an add, no contraction
+ *   out_k = albedo_k * m
+ * so that a shadow edge becomes an albedo edge for a filter that demodulates by and weights on albedo.
+ * shade_floor must be finite and in (0, 1] (SPT_ERR_INVALID_ARG otherwise); 1 leaves the albedo as it is.
+ * out may equal albedo. The device call runs on the calling thread's current device, where the planes
+ * live; device kernel and host statement run the same IEEE operations. */
+spt_status spt_light_shade_async(const float* albedo_dev, const float* visibility_dev, int64_t n_pixels,
+                                 float shade_floor, float* out_dev, void* stream);
+spt_status spt_light_shade_host(const float* albedo, const float* visibility, int64_t n_pixels,
+                                float shade_floor, float* out);
 
 /* ---- denoising: a variance-guided, feature-guided a-trous wavelet filter (SPT_HAS_DENOISE) ----
  * The consumer of a noise film's error map and of the guide planes, in the style of Dammertz et al.

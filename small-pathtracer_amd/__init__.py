@@ -192,6 +192,10 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_guide_info_size", "spt_guide_create", "spt_guide_create_ex", "spt_guide_destroy", "spt_guide_clear",
            "spt_guide_info_get", "spt_guide_render_async", "spt_guide_resolve", "spt_guide_download",
            "spt_guide_resolve_host",
+           "spt_light_guide_create", "spt_light_guide_destroy", "spt_light_guide_clear",
+           "spt_light_guide_info_get", "spt_light_guide_render_async", "spt_light_guide_resolve",
+           "spt_light_guide_download", "spt_light_guide_resolve_host", "spt_light_shade_async",
+           "spt_light_shade_host",
            "spt_denoise_default_params", "spt_denoiser_create", "spt_denoiser_destroy",
            "spt_denoise_async", "spt_denoise_host", "spt_film_denoise",
            "spt_denoise_pair_async", "spt_denoise_pair_host", "spt_denoise_pair_summary",
@@ -210,6 +214,8 @@ GUIDE_MAX_SPP = 1 << 24
 SPT_HAS_GUIDE_CHAIN = 1     # include/spt.h: spt_guide_create_ex (Guide(..., through_specular=True))
 GUIDE_THROUGH_SPECULAR = 1  # SPT_GUIDE_THROUGH_SPECULAR: the guide ray follows SPEC / REFR to a DIFF hit
 GUIDE_MAX_CHAIN = 8         # SPT_GUIDE_MAX_CHAIN: segments of a chain at most
+SPT_HAS_GUIDE_LIGHT = 1     # include/spt.h: the spt_light_guide_* calls (LightGuide, render_light_guides)
+LIGHT_GUIDE_SLOTS = 4       # a light guide record: tested 0, lit 1, weight 2 (1.31 sums), reserved 3
 COUNT_RETIRED = 0x80000000  # bit 31 of an adaptive film's counts: the pixel takes no more batches
 COUNT_MASK = 0x7FFFFFFF     # ... and the batches it holds
 POOL_MAX_RADIUS = 16        # SPT_POOL_MAX_RADIUS: the pooled calls take a radius in [1, 16]
@@ -358,6 +364,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_guide_resolve.argtypes = [VP, VP, VP, VP, VP, VP]
     lib.spt_guide_download.argtypes = [VP, VP, VP]
     lib.spt_guide_resolve_host.argtypes = [VP, P(spt_guide_info), VP, VP, VP, VP]
+    lib.spt_light_guide_create.argtypes = [I32, P(spt_params), ctypes.c_uint32, P(VP)]
+    lib.spt_light_guide_destroy.argtypes = [VP]
+    lib.spt_light_guide_clear.argtypes = [VP, VP]
+    lib.spt_light_guide_info_get.argtypes = [VP, P(spt_guide_info)]
+    lib.spt_light_guide_render_async.argtypes = [VP, VP, P(spt_prim), I32, P(spt_camera), P(spt_params),
+                                                 I32, I32, VP]
+    lib.spt_light_guide_resolve.argtypes = [VP, VP, VP, VP, VP]
+    lib.spt_light_guide_download.argtypes = [VP, VP, VP]
+    lib.spt_light_guide_resolve_host.argtypes = [VP, P(spt_guide_info), VP, VP, VP]
+    lib.spt_light_shade_async.argtypes = [VP, VP, I64, ctypes.c_float, VP, VP]
+    lib.spt_light_shade_host.argtypes = [VP, VP, I64, ctypes.c_float, VP]
     lib.spt_denoise_default_params.argtypes = [P(spt_denoise_params)]
     lib.spt_denoise_default_params.restype = None
     lib.spt_denoiser_create.argtypes = [I32, I32, I32, P(VP)]
@@ -389,7 +406,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                  "spt_denoise_bank_summary", "spt_denoise_bank_summary_host"):
         getattr(lib, name).restype = I32
     for name in EXPORTS:
-        if name.startswith("spt_film_") or name.startswith("spt_guide_"):
+        if name.startswith(("spt_film_", "spt_guide_", "spt_light_")):
             getattr(lib, name).restype = I32
     for name in ("spt_comm_unique_id", "spt_comm_create", "spt_comm_destroy", "spt_comm_reserve",
                  "spt_gather_framebuffer", "spt_deinterleave_rows", "spt_render_multi",
@@ -419,7 +436,8 @@ KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_trace.h", "csrc/spt_variants.
                   "csrc/spt_film.h", "csrc/spt_film_math.h", "csrc/spt_film_host.cpp",
                   "csrc/spt_guide.hip", "csrc/spt_guide_host.cpp", "csrc/spt_guide.h",
                   "csrc/spt_denoise.hip", "csrc/spt_denoise_host.cpp", "csrc/spt_denoise.h",
-                  "csrc/spt_status.h", "csrc/spt_window_shape.h")
+                  "csrc/spt_status.h", "csrc/spt_window_shape.h", "csrc/spt_guide_device.h",
+                  "csrc/spt_guide_light.hip", "csrc/spt_guide_light_host.cpp", "csrc/spt_guide_light.h")
 
 
 def kernel_sources_sha16() -> str:
@@ -1266,6 +1284,163 @@ def render_guides(prims: Sequence[spt_prim], cam: Camera, params: spt_params,
         r.close()
 
 
+# ---------------------------------------------------------------------------------------------
+# Light guides: per-pixel light visibility and direct irradiance (spt_light_guide_*, spt_light_shade_*)
+# ---------------------------------------------------------------------------------------------
+LIGHT_GUIDE_PLANES = ("visibility", "direct", "tested")
+
+
+def light_guide_resolve_host(records: np.ndarray, width: int, rows: int, spp_total: int,
+                             samples_done: int) -> dict:
+    """spt_light_guide_resolve_host(): the CPU statement of the light guide's resolve (no device).
+    records: rows * width * 4 int64. -> {"visibility", "direct", "tested": (rows, width)} float32."""
+    a = np.ascontiguousarray(records, dtype=np.int64)
+    info = spt_guide_info(int(width), int(rows), int(spp_total), int(samples_done), 0, 0)
+    rr, ww = max(info.rows, 0), max(info.width, 0)
+    if a.size != LIGHT_GUIDE_SLOTS * rr * ww:
+        raise SptError(1, "records do not have rows * width * 4 elements")
+    out = {k: np.empty((rr, ww), np.float32) for k in LIGHT_GUIDE_PLANES}
+    _check(load_library().spt_light_guide_resolve_host(a.ctypes.data, ctypes.byref(info),
+                                                       *[out[k].ctypes.data for k in LIGHT_GUIDE_PLANES]))
+    return out
+
+
+def _shade_planes(albedo, visibility):
+    a = np.ascontiguousarray(albedo, dtype=np.float32)
+    v = np.ascontiguousarray(visibility, dtype=np.float32)
+    if a.ndim < 1 or a.shape[-1] != 3 or a.size != 3 * v.size:
+        raise SptError(1, "light_shade: albedo must hold three floats per visibility value")
+    return a, v
+
+
+def light_shade_host(albedo, visibility, shade_floor: float = 0.25, out=None) -> np.ndarray:
+    """spt_light_shade_host(): albedo (.., 3) * (shade_floor + (1 - shade_floor) * visibility), the
+    CPU statement (no device). out: a float32 array to write into (albedo itself is allowed)."""
+    a, v = _shade_planes(albedo, visibility)
+    if out is None:
+        out = np.empty_like(a)
+    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size != a.size:
+        raise SptError(1, "light_shade_host: out must be a contiguous float32 array of albedo's size")
+    _check(load_library().spt_light_shade_host(a.ctypes.data, v.ctypes.data, v.size, float(shade_floor),
+                                               out.ctypes.data))
+    return out
+
+
+def light_shade(albedo, visibility, shade_floor: float = 0.25, device: int = 0, in_place: bool = False):
+    """spt_light_shade_async() on host arrays (uploaded through torch) -> the shaded albedo on the
+    host. in_place: the device call writes over its own albedo plane (out_dev == albedo_dev)."""
+    import torch
+    a, v = _shade_planes(albedo, visibility)
+    with torch.cuda.device(device):
+        da = torch.from_numpy(a.reshape(-1)).to(f"cuda:{device}")
+        dv = torch.from_numpy(v.reshape(-1)).to(f"cuda:{device}")
+        do = da if in_place else torch.empty_like(da)
+        V = ctypes.c_void_p
+        _check(load_library().spt_light_shade_async(V(da.data_ptr() or None), V(dv.data_ptr() or None), v.size,
+                                                    float(shade_floor), V(do.data_ptr() or None),
+                                                    V(torch.cuda.current_stream().cuda_stream or None)))
+        torch.cuda.synchronize(device)
+        return do.cpu().numpy().reshape(a.shape)
+
+
+class LightGuide:
+    """spt_light_guide: per pixel the integer counts of the samples whose guide vertex was tested
+    against the light and of those that were lit, and the fixed-point sum of the lit ones' NEE weight, on
+    the device. The vertex is the guide's (through_specular: the chain guide's), the shadow ray goes to a
+    uniform point of params' light rectangle; passes over disjoint sample windows add up to one object."""
+
+    def __init__(self, params: spt_params, device: int = 0, through_specular: bool = False):
+        self.lib = load_library()
+        self._g = ctypes.c_void_p()
+        _check(self.lib.spt_light_guide_create(int(device), ctypes.byref(params),
+                                               GUIDE_THROUGH_SPECULAR if through_specular else 0,
+                                               ctypes.byref(self._g)))
+        self.device = device
+
+    def close(self):
+        if self._g:
+            self.lib.spt_light_guide_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def info(self) -> dict:
+        i = spt_guide_info()
+        _check(self.lib.spt_light_guide_info_get(self._g, ctypes.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in i._fields_}
+
+    def clear(self, stream_ptr: int = 0):
+        _check(self.lib.spt_light_guide_clear(self._g, ctypes.c_void_p(stream_ptr or None)))
+
+    def render(self, renderer: "Renderer", prims, cam: Camera, params: spt_params, base: int,
+               count: int, stream_ptr: int = 0):
+        """Enqueue the light tests of samples [base, base + count) of the params.spp-sample image and
+        add them. The renderer's statistics and kernel() still describe its last render."""
+        renderer._prims = _scene_array(prims)
+        _check(self.lib.spt_light_guide_render_async(renderer._ctx, self._g, renderer._prims, len(prims),
+                                                     ctypes.byref(cam._c), ctypes.byref(params), int(base),
+                                                     int(count), ctypes.c_void_p(stream_ptr or None)))
+
+    def to_numpy(self, stream_ptr: int = 0) -> np.ndarray:
+        """The records on the host: (rows, width, 4) int64."""
+        i = self.info()
+        out = np.zeros((i["rows"], i["width"], LIGHT_GUIDE_SLOTS), dtype=np.int64)
+        _check(self.lib.spt_light_guide_download(self._g, out.ctypes.data,
+                                                 ctypes.c_void_p(stream_ptr or None)))
+        return out
+
+    def resolve(self, planes=LIGHT_GUIDE_PLANES, stream_ptr: int = 0) -> dict:
+        """The device resolve of the planes asked for -> {"visibility", "direct", "tested": (rows,
+        width)} float32 on the host."""
+        import torch
+        i = self.info()
+        n = i["rows"] * i["width"]
+        with torch.cuda.device(self.device):
+            bufs = {k: torch.empty(max(1, n), dtype=torch.float32, device=f"cuda:{self.device}")
+                    for k in LIGHT_GUIDE_PLANES if k in planes}
+            _check(self.lib.spt_light_guide_resolve(
+                self._g, *[ctypes.c_void_p(bufs[k].data_ptr() if k in bufs else None)
+                           for k in LIGHT_GUIDE_PLANES], ctypes.c_void_p(stream_ptr or None)))
+            torch.cuda.synchronize(self.device)
+        return {k: b[:n].cpu().numpy().reshape(i["rows"], i["width"]) for k, b in bufs.items()}
+
+
+def render_light_guides(prims: Sequence[spt_prim], cam: Camera, params: spt_params,
+                        through_specular: bool = False) -> dict:
+    """The light guide's planes of the full window [0, params.spp): {"visibility", "direct", "tested"}
+    as float32 arrays on the host (LightGuide.resolve). through_specular: at the chain guide's vertex."""
+    import torch
+    r, g = Renderer(params.device), LightGuide(params, params.device, through_specular)
+    try:
+        with torch.cuda.device(params.device):
+            g.render(r, prims, cam, params, 0, params.spp, torch.cuda.current_stream().cuda_stream)
+            return g.resolve(stream_ptr=torch.cuda.current_stream().cuda_stream)
+    finally:
+        g.close()
+        r.close()
+
+
+def _light_shaded_guides(r: "Renderer", guide: "Guide", prims, cam, params, n_guide: int,
+                         through_specular: bool, shade_floor: float, stream) -> dict:
+    """The guide's planes with the albedo shaded by a light guide of the same window [0, n_guide):
+    {"albedo" (shaded), "normal", "depth", "coverage", "albedo_unshaded", "visibility"} on the host."""
+    lg = LightGuide(params, params.device, through_specular)
+    try:
+        lg.render(r, prims, cam, params, 0, n_guide, stream)
+        vis = lg.resolve(("visibility",), stream)["visibility"]
+    finally:
+        lg.close()
+    planes = guide.resolve(stream_ptr=stream)
+    planes["albedo_unshaded"] = planes["albedo"]
+    planes["visibility"] = vis
+    planes["albedo"] = light_shade(planes["albedo"], vis, shade_floor, params.device, in_place=True)
+    return planes
+
+
 def _film_buffer(film: Film):
     """A device float buffer for the film's resolved image (at least one element)."""
     import torch
@@ -1796,12 +1971,19 @@ class Denoiser:
 
 def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, batch: int | None = None,
                     guide_spp: int | None = None, denoise: spt_denoise_params | None = None,
-                    return_info=False, through_specular: bool = False):
+                    return_info=False, through_specular: bool = False, light_guide: bool = False,
+                    shade_floor: float = 0.25):
     """Render all params.spp samples into a noise film (batches of `batch`, default spp / 8 as in
     render_until), fill a guide (through_specular: a chain guide, see Guide) with the sample window
     [0, min(spp, guide_spp or 64)), and return the
     film's image denoised (Denoiser.denoise_film). One device. return_info: also {"noisy": the film's
-    own image, "noise": the film's noise_summary, "guides": the guide planes, "se": se_out}."""
+    own image, "noise": the film's noise_summary, "guides": the guide planes, "se": se_out}.
+    light_guide: a light guide (LightGuide, the same window and kind as the guide) shades the albedo
+    plane, albedo * (shade_floor + (1 - shade_floor) * visibility), before the filter takes it as its
+    demodulation divisor and as the input of its albedo weight, so a shadow edge becomes an albedo
+    edge. The planes are then resolved one by one (film resolve, error map, guide resolve) and filtered
+    by Denoiser.denoise; "guides" also holds "visibility" and "albedo_unshaded". Off (the default), the
+    calls are spt_film_denoise's as ever."""
     spp = int(params.spp)
     if params.shard_count > 1:
         raise SptError(1, "render_denoised: a shard's rows are not image neighbours; gather the planes")
@@ -1821,6 +2003,17 @@ def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, 
                 film.render(r, prims, cam, params, k * batch, batch, 0, stream)
                 r.stats()  # a pass that hit the runaway guard raises here
             guide.render(r, prims, cam, params, 0, n_guide, stream)
+            if light_guide:
+                planes = _light_shaded_guides(r, guide, prims, cam, params, n_guide, through_specular,
+                                              shade_floor, stream)
+                film.resolve(buf.data_ptr(), stream)
+                noisy = _film_image(film, buf)
+                out = dn.denoise(noisy, film.noise_map(stream_ptr=stream), planes["albedo"], planes["normal"],
+                                 planes["depth"], denoise, return_se=return_info)
+                if not return_info:
+                    return out
+                return out[0], {"noisy": noisy, "noise": film.noise_summary(stream), "guides": planes,
+                                "se": out[1]}
             out = dn.denoise_film(film, guide, denoise, return_se=return_info)
             if not return_info:
                 return out
@@ -1877,7 +2070,8 @@ def _pair_session(params: spt_params, batch: int, through_specular: bool):
 def render_denoised_pair(prims: Sequence[spt_prim], cam: Camera, params: spt_params,
                          batch: int | None = None, guide_spp: int | None = None,
                          denoise: spt_denoise_params | None = None, own_weights: bool = False,
-                         through_specular: bool = False, return_info=False):
+                         through_specular: bool = False, return_info=False, light_guide: bool = False,
+                         shade_floor: float = 0.25):
     """Render all params.spp samples into TWO noise films (batch k of `batch` samples, default spp / 8,
     into film A when k is even and into film B when it is odd; spp / batch must be even and at least
     4), fill a guide as render_denoised does, and return the two-half filter's image
@@ -1885,7 +2079,9 @@ def render_denoised_pair(prims: Sequence[spt_prim], cam: Camera, params: spt_par
     own_weights=True gives the error estimate that means what it says. One device. return_info: also
     {"diff": half the difference of the halves' results, "se": the propagated se_out, "pair": the
     summary of diff, "guides": the guide planes, "noisy": the resolve of A merged with B in a third
-    film, which is render()'s image bit for bit}."""
+    film, which is render()'s image bit for bit}. light_guide, shade_floor: as render_denoised's -- the
+    halves' images and error maps and the guide's planes are resolved one by one, the albedo shaded, and
+    Denoiser.denoise_pair filters them."""
     spp = int(params.spp)
     batch = _pair_batch("render_denoised_pair", params, batch)
     n_guide = min(spp, int(guide_spp or 64))
@@ -1894,7 +2090,17 @@ def render_denoised_pair(prims: Sequence[spt_prim], cam: Camera, params: spt_par
             (fb if k & 1 else fa).render(r, prims, cam, params, k * batch, batch, 0, stream)
             r.stats()  # a pass that hit the runaway guard raises here
         guide.render(r, prims, cam, params, 0, n_guide, stream)
-        out, se, diff, pair = dn.denoise_film_pair(fa, fb, guide, denoise, own_weights, return_summary=True)
+        planes = None
+        if light_guide:
+            planes = _light_shaded_guides(r, guide, prims, cam, params, n_guide, through_specular, shade_floor,
+                                          stream)
+            out, se, diff = dn.denoise_pair(fa.resolve(stream_ptr=stream), fa.noise_map(stream_ptr=stream),
+                                            fb.resolve(stream_ptr=stream), fb.noise_map(stream_ptr=stream),
+                                            planes["albedo"], planes["normal"], planes["depth"], denoise,
+                                            own_weights)
+            pair = dn.pair_summary(diff, stream)
+        else:
+            out, se, diff, pair = dn.denoise_film_pair(fa, fb, guide, denoise, own_weights, return_summary=True)
         if not return_info:
             return out
         merged = Film(params, params.device)
@@ -1907,7 +2113,8 @@ def render_denoised_pair(prims: Sequence[spt_prim], cam: Camera, params: spt_par
             noisy = _film_image(merged, buf)
         finally:
             merged.close()
-        return out, {"diff": diff, "se": se, "pair": pair, "guides": guide.resolve(stream_ptr=stream),
+        return out, {"diff": diff, "se": se, "pair": pair,
+                     "guides": planes if planes is not None else guide.resolve(stream_ptr=stream),
                      "noisy": noisy}
 
 

@@ -5,6 +5,14 @@
 //               [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]
 //               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]
 //               [--pair [--pair-own] [--bank S,S,.. [--bank-map PREFIX]]]] [--through-specular] [--help]
+//               [--light] [--light-guide [--shade-floor F]]
+//   --light (with --guides PREFIX): also PREFIX_visibility.pfm and PREFIX_direct.pfm, the light guide's
+//               planes (spt_light_guide_*) of the same window and kind as the guide's, grey like the depth.
+//   --light-guide (with --denoise, also with --pair; not with --bank): the guide's albedo plane is shaded
+//               by the visibility of a light guide over the guide's window (spt_light_shade_async,
+//               --shade-floor F in (0, 1], default 0.25) before the filter takes it, so a shadow edge
+//               stops the filter as an albedo edge does. The planes are then resolved one by one and
+//               filtered by spt_denoise_async / spt_denoise_pair_async.
 //   --bank S,S,.. (with --denoise --pair): the filter bank (spt_film_pair_denoise_bank): one candidate per
 //               colour sigma in the list (1 to 4 of them), each half weighted by its own colours, three
 //               smoothing passes of the error estimates, per pixel the candidate of least cross-validated
@@ -127,12 +135,35 @@ struct DenoiseOpts {
   int iters = 0;
   double sigma = 0.0;
   bool pair = false, pair_own = false;  // --pair [--pair-own]: two films, spt_film_pair_denoise
+  bool light_guide = false;             // --light-guide: the albedo plane shaded by a light guide's visibility
+  float shade_floor = 0.25f;            // --shade-floor F: the shade of a fully shadowed pixel, in (0, 1]
   std::vector<float> bank;              // --bank S,S,..: the candidates' colour sigmas (spt_film_pair_denoise_bank)
   const char* bank_map = nullptr;       // --bank-map PREFIX
 };
 
 void check(spt_status s) {
   if (s != SPT_OK) throw std::runtime_error(std::string(spt_status_string(s)) + ": " + spt_last_error());
+}
+
+// --denoise --light-guide: the guide's planes resolved one by one into a new DEVICE buffer -- albedo,
+// normal (3 floats a pixel each), depth, visibility (1 each) -- with the albedo shaded by the visibility
+// of a light guide over the guide's own window and of its kind (spt_light_shade_async, in place).
+float* shaded_guides(spt_context* ctx, const spt_guide* guide, const std::vector<spt_prim>& scene,
+                     const Camera& cam, const spt_params& p, const DenoiseOpts& denoise) {
+  const size_t npix = (size_t)p.width * (size_t)p.height;
+  float* dev = nullptr;
+  if (hipMalloc(&dev, std::max<size_t>(npix, 1) * 8 * sizeof(float)) != hipSuccess)
+    throw std::runtime_error("device allocation failed");
+  spt_light_guide* lg = nullptr;
+  check(spt_light_guide_create(p.device, &p, denoise.through_specular ? SPT_GUIDE_THROUGH_SPECULAR : 0u, &lg));
+  check(spt_light_guide_render_async(ctx, lg, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
+                                     std::min(p.spp, 64), nullptr));
+  check(spt_guide_resolve(guide, dev, dev + 3 * npix, dev + 6 * npix, nullptr, nullptr));
+  check(spt_light_guide_resolve(lg, dev + 7 * npix, nullptr, nullptr, nullptr));
+  check(spt_light_shade_async(dev, dev + 7 * npix, (int64_t)npix, denoise.shade_floor, dev, nullptr));
+  if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("light guide failed on the device");
+  check(spt_light_guide_destroy(lg));
+  return dev;
 }
 
 // SPP samples through a film: `passes` near-equal windows of the samples to render -- all of them,
@@ -281,7 +312,21 @@ float* render_film(const std::vector<spt_prim>& scene, const Camera& cam, const 
     check(spt_denoiser_create(p.device, p.width, p.height, &dn));
     check(spt_guide_render_async(ctx, guide, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
                                  std::min(p.spp, 64), nullptr));
-    check(spt_film_denoise(film, guide, dn, &dp, dev, nullptr, nullptr));
+    if (denoise.light_guide) {  // the planes one by one, the albedo shaded, spt_denoise_async
+      const size_t n = 3ull * (size_t)p.width * (size_t)p.height;
+      float* planes = shaded_guides(ctx, guide, scene, cam, p, denoise);
+      float* tmp = nullptr;  // the film's image, then its error map
+      if (hipMalloc(&tmp, std::max<size_t>(n, 1) * 2 * sizeof(float)) != hipSuccess)
+        throw std::runtime_error("device allocation failed");
+      check(spt_film_resolve(film, tmp, nullptr));
+      check(spt_film_noise_map(film, tmp + n, nullptr));
+      check(spt_denoise_async(dn, tmp, tmp + n, planes, planes + n, planes + 2 * n, &dp, dev, nullptr, nullptr));
+      if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("denoise failed on the device");
+      (void)hipFree(tmp);
+      (void)hipFree(planes);
+    } else {
+      check(spt_film_denoise(film, guide, dn, &dp, dev, nullptr, nullptr));
+    }
     if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("denoise failed on the device");
     check(spt_denoiser_destroy(dn));
     check(spt_guide_destroy(guide));
@@ -350,6 +395,12 @@ float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const 
   std::memset(total, 0, sizeof *total);
   check(spt_guide_render_async(ctx, guide, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
                                std::min(p.spp, 64), nullptr));
+  float *planes = nullptr, *halves = nullptr;  // --light-guide: the shaded guide planes; rgb and se of A, of B
+  if (denoise.light_guide) {
+    planes = shaded_guides(ctx, guide, scene, cam, p, denoise);
+    if (hipMalloc(&halves, std::max<size_t>(n, 1) * 4 * sizeof(float)) != hipSuccess)
+      throw std::runtime_error("device allocation failed");
+  }
   const int batches = p.spp / batch, need = std::max(4, noise.min_batches + (noise.min_batches & 1));
   spt_pair_summary sm{};
   int done = 0;
@@ -373,7 +424,16 @@ float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const 
       if (look && bs.rmse_est <= noise.target) break;
       continue;
     }
-    check(spt_film_pair_denoise(film[0], film[1], guide, dn, &dp, pair_flags, dev, nullptr, dev + n, nullptr));
+    if (denoise.light_guide) {
+      for (int h = 0; h < 2; ++h) {
+        check(spt_film_resolve(film[h], halves + 2 * h * n, nullptr));
+        check(spt_film_noise_map(film[h], halves + (2 * h + 1) * n, nullptr));
+      }
+      check(spt_denoise_pair_async(dn, halves, halves + n, halves + 2 * n, halves + 3 * n, planes, planes + n,
+                                   planes + 2 * n, &dp, pair_flags, dev, nullptr, dev + n, nullptr));
+    } else {
+      check(spt_film_pair_denoise(film[0], film[1], guide, dn, &dp, pair_flags, dev, nullptr, dev + n, nullptr));
+    }
     check(spt_denoise_pair_summary(dn, dev + n, &sm, nullptr));
     if (look && std::max(sm.rmse[0], std::max(sm.rmse[1], sm.rmse[2])) <= noise.target) break;
   }
@@ -386,6 +446,8 @@ float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const 
     std::cout << "PAIR : " << sm.rmse[0] << " " << sm.rmse[1] << " " << sm.rmse[2] << " after "
               << (int64_t)done * batch << " / " << p.spp << std::endl;
   }
+  if (halves) (void)hipFree(halves);
+  if (planes) (void)hipFree(planes);
   check(spt_denoiser_destroy(dn));
   check(spt_guide_destroy(guide));
   for (spt_film* f : film) check(spt_film_destroy(f));
@@ -394,8 +456,9 @@ float* render_pair(const std::vector<spt_prim>& scene, const Camera& cam, const 
 }
 
 // --guides: the guide planes of the full window, resolved on the device and written as three PFMs.
+// light: also the light guide's visibility and direct planes of the same window, as two more PFMs.
 void write_guides(const std::vector<spt_prim>& scene, const Camera& cam, const spt_params& p,
-                  const std::string& prefix, bool through_specular) {
+                  const std::string& prefix, bool through_specular, bool light) {
   spt_context* ctx = nullptr;
   spt_guide* guide = nullptr;
   check(spt_context_create(p.device, &ctx));
@@ -420,6 +483,23 @@ void write_guides(const std::vector<spt_prim>& scene, const Camera& cam, const s
     if (write_ppm(path.c_str(), info.width, info.rows, pl.data, p.device, SPT_IMAGE_PFM))
       throw std::runtime_error("cannot write " + path + ": " + spt_last_error());
   }
+  if (light) {
+    spt_light_guide* lg = nullptr;
+    check(spt_light_guide_create(p.device, &p, through_specular ? SPT_GUIDE_THROUGH_SPECULAR : 0u, &lg));
+    check(spt_light_guide_render_async(ctx, lg, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0, p.spp,
+                                       nullptr));
+    check(spt_light_guide_resolve(lg, dev, dev + npix, nullptr, nullptr));
+    if (hipMemcpy(host.data(), dev, 2 * npix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("light guide download failed");
+    const char* names[2] = {"_visibility.pfm", "_direct.pfm"};
+    for (int k = 0; k < 2; ++k) {
+      for (size_t i = 0; i < npix; ++i) depth3[3 * i] = depth3[3 * i + 1] = depth3[3 * i + 2] = host[k * npix + i];
+      const std::string path = prefix + names[k];
+      if (write_ppm(path.c_str(), info.width, info.rows, depth3.data(), p.device, SPT_IMAGE_PFM))
+        throw std::runtime_error("cannot write " + path + ": " + spt_last_error());
+    }
+    check(spt_light_guide_destroy(lg));
+  }
   (void)hipFree(dev);
   check(spt_guide_destroy(guide));
   check(spt_context_destroy(ctx));
@@ -433,6 +513,12 @@ const char kUsage[] =
     "            [--noise T [--batch B] [--adaptive [--min-batches M] [--pool R [--pool-loo]]]]\n"
     "            [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]\n"
     "            [--pair [--pair-own] [--bank S,S,.. [--bank-map PREFIX]]]] [--through-specular]\n"
+    "            [--light] [--light-guide [--shade-floor F]]\n"
+    "  --light          with --guides: also PREFIX_visibility.pfm and PREFIX_direct.pfm, the light guide's\n"
+    "                   share of lit shadow rays and mean direct irradiance factor per pixel\n"
+    "  --light-guide    with --denoise (also --pair; not --bank): shade the guide's albedo by a light\n"
+    "                   guide's visibility, albedo * (F + (1 - F) * visibility), before it is filtered on\n"
+    "  --shade-floor F  with --light-guide: the shade of a fully shadowed pixel, in (0, 1] (default 0.25)\n"
     "  --guides PREFIX  also write the first-hit guide planes PREFIX_albedo.pfm, PREFIX_normal.pfm\n"
     "                   and PREFIX_depth.pfm (linear PFM). The normal is stored signed, components\n"
     "                   in [-1, 1] (not 0.5 + 0.5 n); the depth is the mean ray parameter of the\n"
@@ -468,6 +554,8 @@ int main(int argc, char* argv[]) {
   int passes = 0, add = 0;
   const char* film_path = nullptr;
   const char* guides = nullptr;
+  bool shade_floor_given = false;
+  bool light_planes = false;  // --light (with --guides): also PREFIX_visibility.pfm and PREFIX_direct.pfm
   NoiseOpts noise;
   DenoiseOpts denoise;
   float q = -1.0f;
@@ -494,6 +582,9 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--pool") && i + 1 < argc) noise.pool_radius = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--pool-loo")) noise.pool_loo = true;
     else if (!std::strcmp(argv[i], "--guides") && i + 1 < argc) guides = argv[++i];
+    else if (!std::strcmp(argv[i], "--light")) light_planes = true;
+    else if (!std::strcmp(argv[i], "--light-guide")) denoise.light_guide = true;
+    else if (!std::strcmp(argv[i], "--shade-floor") && i + 1 < argc) { shade_floor_given = true; denoise.shade_floor = std::strtof(argv[++i], nullptr); }
     else if (!std::strcmp(argv[i], "--denoise")) denoise.on = true;
     else if (!std::strcmp(argv[i], "--through-specular")) denoise.through_specular = true;
     else if (!std::strcmp(argv[i], "--pair")) denoise.pair = true;
@@ -545,6 +636,12 @@ int main(int argc, char* argv[]) {
     if ((denoise.iters_given || denoise.sigma_given) && !denoise.on)
       throw std::runtime_error("--denoise-iters / --denoise-sigma go with --denoise");
     if ((denoise.pair || denoise.pair_own) && !denoise.on) throw std::runtime_error("--pair goes with --denoise");
+    if (light_planes && !guides) throw std::runtime_error("--light goes with --guides PREFIX");
+    if (denoise.light_guide && !denoise.on) throw std::runtime_error("--light-guide goes with --denoise");
+    if (shade_floor_given && !denoise.light_guide) throw std::runtime_error("--shade-floor goes with --light-guide");
+    if (denoise.light_guide && !denoise.bank.empty()) throw std::runtime_error("--light-guide does not go with --bank");
+    if (!(denoise.shade_floor > 0.0f && denoise.shade_floor <= 1.0f))
+      throw std::runtime_error("--shade-floor: a number in (0, 1]");
     if (denoise.pair_own && !denoise.pair) throw std::runtime_error("--pair-own goes with --pair");
     if (!denoise.bank.empty() && !denoise.pair) throw std::runtime_error("--bank goes with --denoise --pair");
     if (denoise.bank_map && denoise.bank.empty()) throw std::runtime_error("--bank-map goes with --bank");
@@ -605,7 +702,7 @@ int main(int argc, char* argv[]) {
   }
   if (guides) {  // after the image: its bytes are those of a run without the flag
     try {
-      write_guides(guide_scene, cam, p, guides, denoise.through_specular);
+      write_guides(guide_scene, cam, p, guides, denoise.through_specular, light_planes);
     } catch (const std::exception& e) {
       std::cerr << "guides failed: " << e.what() << std::endl;
       return 1;

@@ -15,6 +15,7 @@
 #include "spt_diag.h"
 #include "spt_film.h"
 #include "spt_guide.h"
+#include "spt_guide_light.h"
 #include "spt_launch.h"
 
 using namespace spt;
@@ -56,6 +57,7 @@ struct spt_context {
   hipEvent_t ev_guide = nullptr;
   bool guide_pending = false;     // the staging may still be read by a guide pass's upload
   int guide_bpc[4] = {0, 0, 0, 0};  // resident blocks per CU of the guide kernels ([chain * 2 + wide]); 0: not asked yet
+  int light_bpc[4] = {0, 0, 0, 0};  // ... and of the light-guide kernels
 };
 
 // ---- spt_status.h's two helpers that call HIP
@@ -329,10 +331,12 @@ spt_status spt_render_window(spt_context* c, const spt_prim* prims, int32_t n_pr
 // guide kernel, the records of `rec_dev` (int64[rows * w][8]) updated in place. The context's render
 // state -- statistics, last kernel, last film, the events spt_context_stats reads -- is not touched.
 // force_k > 0 (a measurement's override, never the ABI's): that many lanes per pixel.
-spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
-                            const spt_camera* cam, const spt_params* p, int32_t s_base,
-                            int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
-                            uint32_t flags, void* stream_v) {
+// light: the light guide's launch (spt_guide_light.h) -- the same pass with the light-guide kernel, the
+// records int64[rows * w][4] and the light's parameters as a render sets them.
+static spt_status guide_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
+                               const spt_camera* cam, const spt_params* p, int32_t s_base,
+                               int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
+                               uint32_t flags, bool light, void* stream_v) {
   if (!c || !rec_dev) return fail(SPT_ERR_INVALID_ARG, "null context/guide");
   SPT_TRY(validate(prims, n_prims, cam, p));
   if (s_base < 0 || s_count < 1 || (int64_t)s_base + s_count > p->spp)
@@ -347,9 +351,9 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
   SPT_TRY(stage_scene(c, prims, n_prims, p, s_base, s_count, &K, &light_pos));
   const bool wide = c->h_geo->n_sph_wide > 0;
   const bool chain = (flags & SPT_GUIDE_THROUGH_SPECULAR) != 0;
-  int& guide_bpc = c->guide_bpc[(chain ? 2 : 0) + (wide ? 1 : 0)];  // of the instantiation launched
+  int& guide_bpc = (light ? c->light_bpc : c->guide_bpc)[(chain ? 2 : 0) + (wide ? 1 : 0)];  // of the instantiation launched
   if (guide_bpc == 0) {
-    const int bpc = guide_kernel_occupancy(wide, chain);
+    const int bpc = light ? light_guide_kernel_occupancy(wide, chain) : guide_kernel_occupancy(wide, chain);
     guide_bpc = bpc > 0 ? bpc : 4;
   }
   // the fp32 camera and the launch's terms (shard, magic divisors, fixed-point scale, camera chain)
@@ -369,15 +373,41 @@ spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_pri
   if (grid >= 0x7FFFFFFFull) return fail(SPT_ERR_INVALID_ARG, "the guide launch is too large");
   // nothing below rejects the call
   if (!c->ev_guide) SPT_HIP(hipEventCreate(&c->ev_guide));
-  K.guide_rec = rec_dev;
-  K.guide_kshift = ksh;
+  if (light) {
+    K.light_rec = rec_dev;
+    K.light_kshift = ksh;
+    K.light_id = p->light_id;
+    K.lx0 = p->light_x0; K.ldx = p->light_dx; K.lz0 = p->light_z0; K.ldz = p->light_dz;
+    K.ly = p->light_y; K.larea = p->light_area;
+    K.nee_c = (float)((double)p->light_area / 3.14159265358979323846);
+  } else {
+    K.guide_rec = rec_dev;
+    K.guide_kshift = ksh;
+  }
   SPT_TRY(upload_scene(c, n_prims, stream));
   SPT_TRY(upload_params(c, K, c->ev_guide, stream));
   c->guide_pending = true;
-  launch_guide_kernel(wide, chain, (int)grid, c->d_kp, stream);
+  if (light) launch_light_guide_kernel(wide, chain, (int)grid, c->d_kp, stream);
+  else launch_guide_kernel(wide, chain, (int)grid, c->d_kp, stream);
   SPT_HIP(hipGetLastError());
   if (lanes_out) *lanes_out = k;
   return SPT_OK;
+}
+
+spt_status spt_guide_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
+                            const spt_camera* cam, const spt_params* p, int32_t s_base,
+                            int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
+                            uint32_t flags, void* stream) {
+  return guide_window(c, prims, n_prims, cam, p, s_base, s_count, rec_dev, lanes_out, force_k, flags, false,
+                      stream);
+}
+
+spt_status spt_light_guide_window(spt_context* c, const spt_prim* prims, int32_t n_prims,
+                                  const spt_camera* cam, const spt_params* p, int32_t s_base,
+                                  int32_t s_count, long long* rec_dev, int32_t* lanes_out, int force_k,
+                                  uint32_t flags, void* stream) {
+  return guide_window(c, prims, n_prims, cam, p, s_base, s_count, rec_dev, lanes_out, force_k, flags, true,
+                      stream);
 }
 
 int spt_context_device(const spt_context* c) { return c ? c->device : -1; }

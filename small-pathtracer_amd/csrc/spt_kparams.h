@@ -1,4 +1,4 @@
-// spt_kparams.h — what the kernels that trace (spt_kernel.hip, spt_guide.hip; spt_trace.h) and their
+// spt_kparams.h — what the kernels that trace (spt_kernel.hip, spt_guide.hip, spt_guide_light.hip; spt_trace.h) and their
 // host side (spt_dispatch.cpp, spt_context.cpp) share: the uploaded scene and parameter structs, the launch constants and the
 // tuning macros with their A/B history. Plain C++. The statistics words depend on the diagnostic
 // build (spt_diag.h), so -DSPT_DIAG builds agree between host and device.
@@ -214,6 +214,11 @@ struct KParams {  // in device memory, read through a laundered constant-space p
   // records int64[n_local_pix][8] and log2 of the lanes that share a pixel.
   long long* guide_rec;
   uint32_t guide_kshift;
+  // A light-guide launch (light_guide_kernel; appended likewise): the records int64[n_local_pix][4] and
+  // log2 of the lanes that share a pixel. It reads the light's fields above (light_id, lx0 .. larea,
+  // nee_c) as a render does.
+  uint32_t light_kshift;
+  long long* light_rec;
 };
 
 }  // namespace spt

@@ -4,6 +4,7 @@
 //   spt_kernel.hip    the render kernels, and their three launchers below: hipLaunchKernelGGL on a
 //                     template instantiation is the one thing a plain C++ file cannot do
 //   spt_guide.hip     the guide kernel and its two launchers (both kernels trace through spt_trace.h)
+//   spt_guide_light.hip  the light-guide kernel and its two launchers (it traces through spt_trace.h too)
 //   spt_context.cpp  contexts, uploads, launches and statistics (HIP runtime calls)
 #pragma once
 #include <stdint.h>
@@ -52,6 +53,12 @@ void launch_finalize_slots(const unsigned long long* accum, const unsigned long 
 // instantiation that follows the specular chain (SPT_HAS_GUIDE_CHAIN), which has its own occupancy.
 int guide_kernel_occupancy(bool wide, bool chain);  // resident blocks per CU; <= 0: query failed
 void launch_guide_kernel(bool wide, bool chain, int grid, const KParams* kp_dev, void* stream);
+
+// ---- spt_guide_light.hip (stream and errors as above)
+// The light-guide kernel (SPT_HAS_GUIDE_LIGHT): the same four instantiations, chosen the same way.
+// grid * kBlock lanes >= n_local_pix << light_kshift.
+int light_guide_kernel_occupancy(bool wide, bool chain);  // resident blocks per CU; <= 0: query failed
+void launch_light_guide_kernel(bool wide, bool chain, int grid, const KParams* kp_dev, void* stream);
 
 // ---- spt_dispatch.cpp: lanes per pixel of a guide launch (a power of two, 1..64): the smallest K
 // with n_local_pix * K >= the device's resident lanes (n_cu * bpc * kBlock), at most the window's

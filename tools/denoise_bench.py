@@ -50,6 +50,17 @@ sigma_color {2, 4, 8} with own and with cross weights (and of that bank with thr
 bank of {4, 8} and of one candidate alone, where no selection takes place), of each candidate alone (pair,
 own and cross), the share of the pixels per candidate by region, and mean mse and mean own-weight diff^2
 over the mean squared error against the truth.
+
+--light-guide (python tools/denoise_bench.py --light-guide [OUT.json], default
+build/guide_light_denoise.json): what shading the albedo plane by a light guide's visibility
+(SPT_HAS_GUIDE_LIGHT, render_denoised(light_guide=True)) buys, by region, with --pair's protocol (HEAD and
+mirror_glass, first-hit guides; 256x192, 16 seeds, 8 batches, guide and light guide of 64 samples, truth
+16 x 4096 spp, at 64 / 256 / 1024 spp): the RMSE of the denoised image over the film's for the single
+filter and the cross-weighted pair, without the light guide and with it at shade_floor 0.1, 0.25 and
+0.5; over the whole frame, over the shadow band (the pixels with 0.05 < visibility < 0.95 in a light guide
+of 1024 samples, seed 1000, and the pixels within 2 of them) and over the fully lit and fully shadowed
+rest; the seeds in which the shaded run beats the plain one; and the image-mean shift. mirror_glass has
+no light rectangle: its light guide samples a 24 x 24 square of the light sphere's cap (prim 8).
 """
 import importlib
 import json
@@ -849,7 +860,115 @@ def main_bank(out):
         print(name, json.dumps(rec["quality"][name]["by_spp"]), flush=True)
 
 
+# ---- --light-guide: the albedo plane shaded by a light guide's visibility --------------------------------
+LIGHT_FLOORS = (0.1, 0.25, 0.5)
+
+
+def _light_scene_params(name, p):
+    if name == "mirror_glass":  # the classic box: a square of the light sphere's cap (tools/guide_bench.py)
+        p.light_id = 8
+        p.light_x0, p.light_dx, p.light_z0, p.light_dz = 38.0, 24.0, 69.6, 24.0
+        p.light_y, p.light_area = 81.6, 576.0
+    return p
+
+
+def _dilate(mask, radius):
+    out = mask.copy()
+    h, w = mask.shape
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            ys, yd = (slice(max(dy, 0), h + min(dy, 0)), slice(max(-dy, 0), h + min(-dy, 0)))
+            xs, xd = (slice(max(dx, 0), w + min(dx, 0)), slice(max(-dx, 0), w + min(-dx, 0)))
+            out[yd, xd] |= mask[ys, xs]
+    return out
+
+
+def light_quality(spt, name, w=256, h=192, seeds=16, spps=(64, 256, 1024)):
+    prims = getattr(spt, PAIR_SCENES[name][0])()
+    kw = PAIR_SCENES[name][1]
+    cam = spt.Camera(aspect=float(np.float32(w) / np.float32(h)))
+    truth = np.zeros((h, w, 3), np.float64)
+    for s in range(16):
+        truth += spt.render(prims, cam, spt.default_params(width=w, height=h, spp=4096, seed=1000 + s, **kw))
+    truth = (truth / 16).astype(np.float32)
+    ref = spt.render_light_guides(prims, cam, _light_scene_params(
+        name, spt.default_params(width=w, height=h, spp=1024, seed=1000, **kw)))
+    band = _dilate((ref["visibility"] > 0.05) & (ref["visibility"] < 0.95), 2)
+    masks = {"frame": np.ones((h, w), bool), "shadow_band": band, "rest": ~band}
+    variants = ["off"] + [f"floor_{f}" for f in LIGHT_FLOORS]
+    res = {"scene": name, "width": w, "height": h, "seeds": seeds, "truth": "16 seeds x 4096 spp", "guide_spp": 64,
+           "light_guide_spp": 64, "band": "0.05 < visibility < 0.95 at 1024 samples (seed 1000), dilated by 2",
+           "batches": 8, "pixels": {k: int(m.sum()) for k, m in masks.items()},
+           "reference_visibility_mean": float(ref["visibility"].mean()),
+           "reference_tested_mean": float(ref["tested"].mean()), "by_spp": {}}
+    for spp in spps:
+        batch = spp // 8
+        outs = {(f, v): [] for f in ("single", "cross") for v in variants}
+        noisy_all = []
+        for seed in range(1, seeds + 1):
+            p = _light_scene_params(name, spt.default_params(width=w, height=h, spp=spp, seed=seed, **kw))
+            r, fa, fb, film, guide, lg, dn = (spt.Renderer(0), spt.Film(p, 0), spt.Film(p, 0), spt.Film(p, 0),
+                                              spt.Guide(p, 0), spt.LightGuide(p, 0), spt.Denoiser(w, h, 0))
+            try:
+                for f in (fa, fb, film):
+                    f.enable_noise(batch)
+                for k in range(8):
+                    (fb if k & 1 else fa).render(r, prims, cam, p, k * batch, batch)
+                    r.stats()
+                film.merge(fa)
+                film.merge(fb)
+                guide.render(r, prims, cam, p, 0, min(spp, 64))
+                lg.render(r, prims, cam, p, 0, min(spp, 64))
+                g, vis = guide.resolve(), lg.resolve(("visibility",))["visibility"]
+                rgb, se = film.resolve(), film.noise_map()
+                halves = [fa.resolve(), fa.noise_map(), fb.resolve(), fb.noise_map()]
+                noisy_all.append(rgb)
+                outs[("single", "off")].append(dn.denoise_film(film, guide))
+                outs[("cross", "off")].append(dn.denoise_film_pair(fa, fb, guide)[0])
+                for f in LIGHT_FLOORS:
+                    shaded = spt.light_shade(g["albedo"], vis, f)
+                    outs[("single", f"floor_{f}")].append(dn.denoise(rgb, se, shaded, g["normal"], g["depth"]))
+                    outs[("cross", f"floor_{f}")].append(dn.denoise_pair(*halves, shaded, g["normal"], g["depth"])[0])
+            finally:
+                for o in (dn, lg, guide, film, fa, fb, r):
+                    o.close()
+        one = {"regions": {}, "mean_change": {}}
+        noisy_mean = float(np.mean([x.mean(dtype=np.float64) for x in noisy_all]))
+        for k, mk in masks.items():
+            n = float(np.mean([rmse(x[mk], truth[mk]) for x in noisy_all]))
+            row = {"rmse_noisy": n}
+            for f in ("single", "cross"):
+                per = {v: [rmse(x[mk], truth[mk]) for x in outs[(f, v)]] for v in variants}
+                for v in variants:
+                    row[f"ratio_{f}_{v}"] = float(np.mean(per[v])) / n
+                for v in variants[1:]:
+                    row[f"{f}_{v}_over_off"] = float(np.mean(per[v]) / np.mean(per["off"]))
+                    row[f"seeds_where_{f}_{v}_beats_off"] = int(sum(a < b for a, b in zip(per[v], per["off"])))
+            one["regions"][k] = row
+        for (f, v), xs in outs.items():
+            one["mean_change"][f"{f}_{v}"] = float(np.mean([x.mean(dtype=np.float64) for x in xs]) / noisy_mean - 1.0)
+        res["by_spp"][str(spp)] = one
+    return res
+
+
+def main_light(out):
+    import torch
+    spt = importlib.import_module("small-pathtracer_amd")
+    spt.load_library()
+    assert torch.cuda.is_available(), "denoise_bench needs the GPU"
+    rec = {"kernel_sources_sha16": spt.build_sources_sha16(), "device": torch.cuda.get_device_name(0),
+           "utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()), "shade_floors": list(LIGHT_FLOORS), "quality": {}}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    for name in PAIR_SCENES:
+        rec["quality"][name] = light_quality(spt, name)
+        json.dump(rec, open(out, "w"), indent=1)  # what is measured survives a failure further on
+        print(name, json.dumps({s: v["regions"]["shadow_band"] for s, v in rec["quality"][name]["by_spp"].items()}),
+              flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--light-guide":
+        return main_light(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "guide_light_denoise.json"))
     if len(sys.argv) > 1 and sys.argv[1] == "--chain":
         return main_chain(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "guide_chain_denoise.json"))
     if len(sys.argv) > 1 and sys.argv[1] == "--pair":

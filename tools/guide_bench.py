@@ -21,8 +21,15 @@ show that neither moved: the parent is the yardstick, never this build against i
 unchanged when the median of this tree's rounds exceeds the parent's by no more than the parent's own
 min-max spread over its rounds.
 
+--light (SPT_HAS_GUIDE_LIGHT): a light-guide pass (spt_light_guide_render_async) of either kind beside a
+first-hit guide pass and a chain guide pass of the same build, all four alternating in one process, at
+the --chain leg's shapes and with its protocol; the ratios are to the guide pass of the same kind.
+mirror_glass has no light rectangle: its light guide samples a 24 x 24 square of the light sphere's
+cap (prim 8). --parent-tree DIR times the two guide passes against the parent's library as --chain does.
+
 usage: python tools/guide_bench.py [--reps N --inner M --out FILE.json]
        python tools/guide_bench.py --chain [--parent-tree DIR --rounds R] [--out FILE.json]
+       python tools/guide_bench.py --light [--parent-tree DIR --rounds R] [--out FILE.json]
 """
 import argparse
 import ctypes
@@ -183,6 +190,49 @@ def _chain_pairs(spt, torch):
     return out
 
 
+def _light_params(name, p):
+    """The light a light guide of scene `name` samples: the parameters' rectangle, or for the classic
+    box a square of the light sphere's cap (prim 8, centred (50, 81.6) at the ceiling)."""
+    if name == "mirror_glass":
+        p.light_id = 8
+        p.light_x0, p.light_dx, p.light_z0, p.light_dz = 38.0, 24.0, 69.6, 24.0
+        p.light_y, p.light_area = 81.6, 576.0
+    return p
+
+
+def _light_passes(spt, torch):
+    """The two guide passes and the two light-guide passes of the same arguments, alternating."""
+    out = {}
+    for name, w, h, spp, kw in CHAIN_SHAPES:
+        prims = _scene_of(spt, name)
+        p = _light_params(name, spt.default_params(width=w, height=h, spp=spp, seed=1, device=0, **kw))
+        cam = spt.Camera(aspect=w / h)
+        r = spt.Renderer(0)
+        objs = (("first_hit", spt.Guide(p, 0)), ("chain", spt.Guide(p, 0, through_specular=True)),
+                ("light", spt.LightGuide(p, 0)), ("light_chain", spt.LightGuide(p, 0, through_specular=True)))
+        stream = torch.cuda.current_stream().cuda_stream
+        ms = {k: [] for k, _ in objs}
+        for i in range(CHAIN_WARM + CHAIN_RUNS):
+            for key, g in objs:
+                t = _pass_ms(torch, g, r, prims, cam, p, stream)
+                if i >= CHAIN_WARM:
+                    ms[key].append(t)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        rec = {k: g.to_numpy() for k, g in objs[2:]}
+        out[name] = {"width": w, "height": h, "spp": spp, **{k + "_ms": _stat(v) for k, v in ms.items()},
+                     "lanes_per_pixel": {k: g.info()["lanes_per_pixel"] for k, g in objs},
+                     "light_over_first_hit": round(med["light"] / med["first_hit"], 4),
+                     "light_chain_over_chain": round(med["light_chain"] / med["chain"], 4),
+                     "chain_over_first_hit": round(med["chain"] / med["first_hit"], 4),
+                     "samples": w * h * spp,
+                     "tested": {k: int(v[..., 0].sum()) for k, v in rec.items()},
+                     "lit": {k: int(v[..., 1].sum()) for k, v in rec.items()}}
+        for _, g in objs:
+            g.close()
+        r.close()
+    return out
+
+
 def _passes_child(tree):
     """One child's work: the first-hit and the chain pass of the package under `tree` at every shape."""
     sys.path.insert(0, tree)
@@ -240,7 +290,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--sweep-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--chain", action="store_true", help="chain guide passes beside first-hit passes")
-    ap.add_argument("--parent-tree", default="", help="with --chain: a built checkout of the parent commit")
+    ap.add_argument("--light", action="store_true", help="light-guide passes beside the guide passes")
+    ap.add_argument("--parent-tree", default="", help="with --chain / --light: a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--passes-child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -248,7 +299,7 @@ def main():
         return _sweep(args.reps, args.inner)
     if args.passes_child:
         return _passes_child(args.passes_child)
-    if args.chain:
+    if args.chain or args.light:
         res = {"config": {"runs": CHAIN_RUNS, "warm_ups": CHAIN_WARM}}
         # the children first: this process has not opened the GPU yet
         res["against_parent"] = (_against_parent(args.parent_tree, args.rounds) if args.parent_tree
@@ -256,7 +307,10 @@ def main():
         import torch
         spt = importlib.import_module("small-pathtracer_amd")
         res["kernel_sources_sha16"] = spt.build_sources_sha16()
-        res["chain_beside_first_hit"] = _chain_pairs(spt, torch)
+        if args.light:
+            res["light_beside_guides"] = _light_passes(spt, torch)
+        else:
+            res["chain_beside_first_hit"] = _chain_pairs(spt, torch)
         print(json.dumps(res))
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
