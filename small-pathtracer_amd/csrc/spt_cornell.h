@@ -80,6 +80,23 @@ constexpr int cornell_pos_of(int idx) {
 }
 constexpr int kCornellPosOfPrim0 = cornell_pos_of(0);  // Front (:288), XY
 static_assert(kCornellPosOfPrim0 == 0, "prim 0 is the first XY rect");
+// The position a literal kernel puts into its keys and indexes its primitive table by (its slot).
+// A position enters a key only as the low six bits, the tie-break among candidates whose t share the
+// upper 26 (the smaller wins), and the winner's slot never leaves the kernel. With axis_bits
+// (KernelTraits::kAxisBits) the slots carry the rectangle's kind in bits 4 and 5: XY keep 0..5, XZ
+// become 16 + j, YZ 32 + j. The map is strictly increasing, so every comparison of two keys, and
+// with it every winner, is the grouped numbering's; the largest slot is 37 < 63, so the "no hit" key
+// still ranks last. Bit 4 of a winning key then says XZ and bit 5 YZ.
+constexpr int kAxisBitXZ = 4, kAxisBitYZ = 5;
+constexpr int cornell_slot(int pos, bool axis_bits) {
+  return !axis_bits || pos < kCornellNXY ? pos
+         : pos < kCornellNXY + kCornellNXZ ? (1 << kAxisBitXZ) + (pos - kCornellNXY)
+                                           : (1 << kAxisBitYZ) + (pos - kCornellNXY - kCornellNXZ);
+}
+static_assert(kCornellNXY <= 16 && kCornellNXZ <= 16 && kCornellNYZ <= 16 &&
+                  cornell_slot(16, true) == 37 && cornell_slot(kCornellPosOfPrim0, true) == 0 &&
+                  cornell_slot(5, true) < cornell_slot(6, true) && cornell_slot(10, true) < cornell_slot(11, true),
+              "the slots: increasing, below 63, a kind per bit");
 
 // The contract's rect tests over the grouped list (oracle c_build_tests): inside each kind group,
 // in order, a rectangle pairs with the first later unpaired one of bit-identical bounds on a

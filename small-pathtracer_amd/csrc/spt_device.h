@@ -104,6 +104,20 @@ __device__ __forceinline__ uint32_t band_andn(uint32_t a, uint32_t m, uint32_t n
   asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x40" : "=v"(r) : "v"(a), "v"(m), "v"(n));
   return r;
 }
+//   a & ~m & ~n, ONE v_bitop3 (0x10 = S0 & ~S1 & ~S2)
+__device__ __forceinline__ uint32_t band_nor(uint32_t a, uint32_t m, uint32_t n) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x10" : "=v"(r) : "v"(a), "v"(m), "v"(n));
+  return r;
+}
+//   bit_mask<B>(v): all ones iff bit B of v is set, ONE v_bfe_i32 (the signed one-bit field at B).
+//   Opaque like mask_lt.
+template <int B>
+__device__ __forceinline__ uint32_t bit_mask(uint32_t v) {
+  uint32_t m;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(v), "n"(B));
+  return m;
+}
 //   the bits of 1.0f with the inverse of a's sign bit, 1.0 | (~a & 2^31): +1 for a negative a, -1
 //   for a positive one. ONE v_bitop3 (0xae = (~S0 & S1) | S2) with the inline constant 1.0.
 __device__ __forceinline__ uint32_t sign_against(uint32_t a) {
@@ -142,6 +156,22 @@ __device__ __forceinline__ u4 philox_px(PxKey pk, uint32_t c1, uint32_t c2) {
 // (bits 0x3F800000 | m) minus 1 -- an or and a subtract (rounds 1-4: shift, half-rate conversion,
 // multiply)
 __device__ __forceinline__ float u01(uint32_t v) { return __uint_as_float(0x3F800000u | (v >> 9)) - 1.0f; }
+// The float with exponent field E (E << 23 its bits) and a random word's top 23 bits as its
+// significand, (E << 23) | (v >> 9): the low 32 bits of the 64-bit word {E, v} shifted right by 9,
+// since the low 23 bits of E << 23 are zero -- the funnel shift v_alignbit_b32(E, v, 9), ONE
+// instruction where the shift and the or are two (KernelTraits::kFunnelFloats; E sits in an SGPR).
+// E = 0x7F: 1 + m 2^-23 (u01's float); E = 0x96: 2^23 + m (the LREF light lattice's).
+template <uint32_t E>
+__device__ __forceinline__ float funnel_float(uint32_t v) {
+  static_assert(E < 256u, "an exponent field");
+  return __uint_as_float(__builtin_amdgcn_alignbit(E, v, 9u));
+}
+// u01 with that float: the same bits
+template <bool FUNNEL>
+__device__ __forceinline__ float u01_as(uint32_t v) {
+  if constexpr (FUNNEL) return funnel_float<0x7Fu>(v) - 1.0f;
+  else return u01(v);
+}
 // 16-bit draw from the low bytes of two Philox words (RR and NEE-mix draws, camera jitter; see
 // the kernel): (lo & 0xFF) | (hi & 0xFF) << 8 as ONE v_perm_b32 (bytes {hi:lo}[4], [0], 0, 0).
 __device__ __forceinline__ uint32_t u16i(uint32_t lo, uint32_t hi) {
@@ -292,9 +322,10 @@ __device__ __forceinline__ void disk_dir(uint32_t ra, float& c_out, float& s_out
 // uniform: the reference's commented-out uniform hemisphere (:352-359), radial sqrt(r2(2-r2)) and
 // normal component 1-r2 (SPT_FLAG_UNIFORM_SCATTER; oracle c_cosine).
 // unit: the unit-direction contract (rsq_nr) or the free-scale one (rsq_nr2; oracle c_unit_dirs).
-template <bool AXIS = false>
+// FUNNEL: xi2's float as one funnel shift (funnel_float; the same bits).
+template <bool AXIS = false, bool FUNNEL = false>
 __device__ __forceinline__ f3 cosine_vec(f3 nl, uint32_t ra, uint32_t rb, bool uniform, bool unit) {
-  const float xi2 = u01(rb);
+  const float xi2 = u01_as<FUNNEL>(rb);
   float s, c;
   disk_dir(ra, c, s);  // the azimuth r1 = 2*pi*xi1 of :343
   float r2s, s1;

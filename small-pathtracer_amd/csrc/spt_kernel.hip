@@ -72,9 +72,10 @@ template <class CF> __device__ __forceinline__ int light_id_of(const SPT_CONST K
   if constexpr (CF::LREF == 1) return kRefLightId; else return P->light_id;
 }
 // The light's id in the kernel's primitive numbering: its grouped position in the HEAD kernels
-// (s_prims is loaded in position order there, intersect_scene), its prims[] index elsewhere
+// (s_prims is loaded by slot there, cornell_slot; intersect_scene), its prims[] index elsewhere
 template <class TP, class CF> __device__ __forceinline__ int light_slot_of(const SPT_CONST KParams* P) {
-  if constexpr (TP::CONSTGEO) return kCornellLightPos; else return light_id_of<CF>(P);
+  if constexpr (TP::CONSTGEO) return cornell_slot(kCornellLightPos, KernelTraits<TP, CF>::kAxisBits);
+  else return light_id_of<CF>(P);
 }
 template <class CF> __device__ __forceinline__ int rr_depth_of(const SPT_CONST KParams* P) {
   if constexpr (CF::LREF == 1) return kRefRrDepth; else return P->rr_depth;
@@ -83,12 +84,21 @@ template <class CF> __device__ __forceinline__ int rr_depth_of(const SPT_CONST K
 // two lane masks (spt_device.h, mask_lt): xy = pos is an XY rect, xyxz = an XY or an XZ one. What the
 // axis picks -- o_a, d_a, 1/d_a, the NEE weight's |dl_a| -- is then two full-rate bit selects, and the
 // normal three ands, where the compares' SGPR-pair masks fed half-rate VOP3 selects.
-struct AxisMasks { uint32_t xy, xyxz; };
+// AXB (KernelTraits::kAxisBits): pos is a slot with the kind in its bits (cornell_slot), and the masks
+// are yz = bit 5 and xz = bit 4 spread over the word, one v_bfe_i32 each where mask_lt is a subtract and
+// a shift. The picks and the normal keep their instruction counts with the masks' roles restated: x
+// under yz, else y under xz, else z. (Slot 63, a miss of the kMissEntry kernels, sets both: nothing
+// reads what that lane picks.)
+struct AxisMasks { uint32_t xy, xyxz, yz, xz; };  // (AXB: yz, xz; else xy, xyxz)
+template <bool AXB>
 __device__ __forceinline__ AxisMasks axis_masks(int pos) {
-  return AxisMasks{mask_lt<kCornellNXY>(pos), mask_lt<kCornellNXY + kCornellNXZ>(pos)};
+  if constexpr (AXB) return AxisMasks{0, 0, bit_mask<kAxisBitYZ>((uint32_t)pos), bit_mask<kAxisBitXZ>((uint32_t)pos)};
+  else return AxisMasks{mask_lt<kCornellNXY>(pos), mask_lt<kCornellNXY + kCornellNXZ>(pos), 0, 0};
 }
+template <bool AXB>
 __device__ __forceinline__ float axis_pick(AxisMasks m, float z, float y, float x) {
-  return bself(m.xy, z, bself(m.xyxz, y, x));
+  if constexpr (AXB) return bself(m.yz, x, bself(m.xz, y, z));
+  else return bself(m.xy, z, bself(m.xyxz, y, x));
 }
 
 // An event counter takes the lanes of mask m, at a convergent point of the render loop. Wave-uniform
@@ -299,14 +309,19 @@ render_kernel(const KParams* __restrict__ Pg) {
     const SPT_CONST SceneGeo* G = cptr(P->geo);
     const int nrect = G->n_xy + G->n_xz + G->n_yz;
     for (int i = threadIdx.x; i < P->n_prims; i += kBlock) {
-      // HEAD geometry (every primitive a rectangle): s_prims by grouped position (kPosIds)
-      s_prims[i] = P->prims[TP::CONSTGEO ? G->rect[i].idx : i];
+      // HEAD geometry (every primitive a rectangle): s_prims by the grouped position's slot
+      s_prims[TP::CONSTGEO ? cornell_slot(i, KernelTraits<TP, CF>::kAxisBits) : i] =
+          P->prims[TP::CONSTGEO ? G->rect[i].idx : i];
       s_pos2idx[i] = i < nrect ? G->rect[i].idx : G->sph[i - nrect].idx;
       if ((!TP::CONSTGEO || TP::UPBOX) && !TP::WIDE && i < G->n_txy + G->n_txz + G->n_tyz + 3 * G->has_room + 3 * G->n_box) {
         const SPT_CONST GeoTest& q = G->test[i];
-        s_test[i] = GeoTest{q.k0, q.k1, q.ma, q.ha, q.mb, q.hb, q.pos0, q.pos1};
+        // (the uploaded boxes of the room-literal kernels: their positions as the kernel's slots)
+        constexpr bool kSlots = TP::CONSTGEO && KernelTraits<TP, CF>::kAxisBits;
+        s_test[i] = GeoTest{q.k0, q.k1, q.ma, q.ha, q.mb, q.hb, cornell_slot(q.pos0, kSlots), cornell_slot(q.pos1, kSlots)};
       }
     }
+    // the entry a miss reads (kMissEntry): no emission, so its T * e is the +0 prim 0's was
+    if (KernelTraits<TP, CF>::kMissEntry && threadIdx.x == 63) s_prims[63] = DevPrim{};
   }
   __syncthreads();
 
@@ -604,7 +619,7 @@ render_kernel(const KParams* __restrict__ Pg) {
       [[maybe_unused]] const bool cam = ls == kStCam;
       if (ls != kStSpec) SPT_REGION(cam ? 3 : 8);
       const bool unit = unit_dirs_of<TP>(Pg);
-      f3 v = cosine_vec<!TP::SPH>(nl, r.z, r.w, TP::MAT && cptr(Pg)->scatter_uniform != 0, unit);
+      f3 v = cosine_vec<!TP::SPH, KT::kFunnelFloats>(nl, r.z, r.w, TP::MAT && cptr(Pg)->scatter_uniform != 0, unit);
       // the vertex this ray leads to: dp1 (1 for a new sample's camera ray)
       const uint32_t ctr2 = (uint32_t)dp1 | (TP::MAT ? branch << 24 : 0u);
       r = philox_px(pk, s, ctr2);
@@ -693,11 +708,12 @@ render_kernel(const KParams* __restrict__ Pg) {
       int hpos;
       f3 inv;  // 1/d per axis (rcp_nr), the trace's
       // (the early-resolve kernels trace a shadow ray only when the light accepts it: it never misses)
-      bool hit = intersect_scene<TP>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph, s_pos2idx, o, d,
+      bool hit = intersect_scene<TP, KT::kAxisBits, KT::kMissEntry>(G, rects_of<TP>(G), tests_of<TP>(G, s_test), G->sph, s_pos2idx, o, d,
                                      id, ia_hit, hpos, inv);
       // the hit's plane axis (the literal rect-only kernels), made once here for the shading too
-      [[maybe_unused]] const AxisMasks am = axis_masks(TP::CONSTGEO ? hpos : 0);
-      if constexpr (TP::CONSTGEO) ia_hit = axis_pick(am, inv.z, inv.y, inv.x);
+      constexpr bool kAxb = KT::kAxisBits;
+      [[maybe_unused]] const AxisMasks am = axis_masks<kAxb>(TP::CONSTGEO ? hpos : 0);
+      if constexpr (TP::CONSTGEO) ia_hit = axis_pick<kAxb>(am, inv.z, inv.y, inv.x);
 
       // 5) resolve a shadow ray: the light is reached iff the nearest hit is the light (:467). Then
       //    the light is the next vertex (shaded in the common block below, T = T*f*weight); else the
@@ -779,8 +795,8 @@ render_kernel(const KParams* __restrict__ Pg) {
           // the normal is the axis, oriented against the ray (:123,:166,:209).
           float oa, da, ia = ia_hit;
           if constexpr (TP::CONSTGEO) {  // the axis from the position: bit selects (axis_masks)
-            oa = axis_pick(am, o.z, o.y, o.x);
-            da = axis_pick(am, d.z, d.y, d.x);
+            oa = axis_pick<kAxb>(am, o.z, o.y, o.x);
+            da = axis_pick<kAxb>(am, d.z, d.y, d.x);
           } else {
             const bool kxy = kind == SPT_RECT_XY, kxz = kind == SPT_RECT_XZ;
             oa = kxy ? o.z : (kxz ? o.y : o.x);
@@ -806,6 +822,10 @@ render_kernel(const KParams* __restrict__ Pg) {
             // sg on the hit's axis, +0 on the other two, as the selects gave: sg & ~(xy | xz),
             // sg & (xy | xz) & ~xy, sg & xy
             const uint32_t sb = __float_as_uint(sg);
+            // (kAxisBits: sg & yz, sg & xz, sg & ~yz & ~xz)
+            if constexpr (kAxb)
+              nl = mk(__uint_as_float(sb & am.yz), __uint_as_float(sb & am.xz), __uint_as_float(band_nor(sb, am.yz, am.xz)));
+            else
             nl = mk(__uint_as_float(band_andn(sb, sb, am.xyxz)), __uint_as_float(band_andn(sb, am.xyxz, am.xy)),
                     __uint_as_float(sb & am.xy));
           } else {
@@ -953,8 +973,11 @@ render_kernel(const KParams* __restrict__ Pg) {
                 // 0x4B000000 | m is 2^23 + m, so the sum is the same real, rounded once: one or and
                 // one fma (rounds 1-4: shift, 24-bit multiply, conversion, fma)
                 static_assert(kRefLdxi == 36u && kRefLdzi == 36u, "LREF light lattice");
-                xl = fmaf(__uint_as_float(0x4B000000u | (r.x >> 9)), 0x1p-22f, lx0 - 3.0f);
-                zl = fmaf(__uint_as_float(0x4B000000u | (r.y >> 9)), 0x1p-22f, lz0 - 3.0f);
+                // (kFunnelFloats: the shift and the or as one funnel shift, funnel_float)
+                const float mx = KT::kFunnelFloats ? funnel_float<0x96u>(r.x) : __uint_as_float(0x4B000000u | (r.x >> 9));
+                const float mz = KT::kFunnelFloats ? funnel_float<0x96u>(r.y) : __uint_as_float(0x4B000000u | (r.y >> 9));
+                xl = fmaf(mx, 0x1p-22f, lx0 - 3.0f);
+                zl = fmaf(mz, 0x1p-22f, lz0 - 3.0f);
               } else {
                 xl = D->lx_lattice ? fmaf((float)(r.x >> D->lx_shift), D->lx_scale, D->lx0m1)
                                    : fmaf((float)(int32_t)(((r.x >> 8) << 7) * ldxi), 0x1p-31f, lx0);
@@ -986,7 +1009,7 @@ render_kernel(const KParams* __restrict__ Pg) {
               // arithmetic with |dl . nl| = |dl_a| on the normal's axis a (the dot's zero terms are
               // exact) and t = the light's own t, the bits the trace returns for it. The resolve
               // then needs neither the light's t nor the weight (round 4: -5 VALU per iteration).
-              const float adot = fabsf(axis_pick(am, dl.z, dl.y, dl.x));
+              const float adot = fabsf(axis_pick<kAxb>(am, dl.z, dl.y, dl.x));
               const float num = fabsf(dl.y) * adot;
               const float vv = dot3(dl, dl);
               w_nee = (num * kRefNeeC) * rcp_nr((h.tt * h.tt) * (vv * vv));

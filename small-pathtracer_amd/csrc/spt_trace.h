@@ -114,20 +114,22 @@ __device__ __forceinline__ uint32_t key_s(float t, uint32_t pos) {  // wave-unif
 template <int J> struct CornellTestPtr {
   __device__ constexpr const CTest* operator->() const { return &kCornellTests.t[J]; }
 };
-template <int J, bool PAIR>
+// (AXB: the literal kernels' slots with the kind in bits 4 and 5, cornell_slot; KernelTraits::kAxisBits)
+template <int J, bool PAIR, bool AXB>
 __device__ __forceinline__ void plane_keys(CornellTestPtr<J>, float t0, float t1, uint32_t& kp) {
-  if constexpr (PAIR) kp = umin(key_c<kCornellTests.t[J].pos0>(t0), key_c<kCornellTests.t[J].pos1>(t1));
-  else kp = key_c<kCornellTests.t[J].pos0>(t0);
+  constexpr int P0 = cornell_slot(kCornellTests.t[J].pos0, AXB), P1 = cornell_slot(kCornellTests.t[J].pos1, AXB);
+  if constexpr (PAIR) kp = umin(key_c<P0>(t0), key_c<P1>(t1));
+  else kp = key_c<P0>(t0);
 }
-template <int J, bool PAIR>  // (unused J: a runtime pointer)
+template <int J, bool PAIR, bool AXB>  // (unused J, AXB: a runtime pointer, its positions the host's)
 __device__ __forceinline__ void plane_keys(const GeoTest* g, float t0, float t1, uint32_t& kp) {
   kp = umin(key_v(t0, (uint32_t)g->pos0), key_v(t1, (uint32_t)g->pos1));
 }
-template <int J, bool PAIR>
+template <int J, bool PAIR, bool AXB>
 __device__ __forceinline__ void plane_keys(const SPT_CONST GeoTest* g, float t0, float t1, uint32_t& kp) {
   kp = umin(key_v(t0, (uint32_t)g->pos0), key_v(t1, (uint32_t)g->pos1));
 }
-template <int J, bool PAIR, class GP>
+template <int J, bool PAIR, bool AXB = false, class GP>
 __device__ __forceinline__ void rect_cand(GP g, const Ray6& r, uint32_t& tmin) {
   const float t0 = plane_t(g->k0 - r.oa, r.ia);
   float t1 = t0;
@@ -136,7 +138,7 @@ __device__ __forceinline__ void rect_cand(GP g, const Ray6& r, uint32_t& tmin) {
     t1 = plane_t(g->k1 - r.oa, r.ia);
     kb = umin(kb, __float_as_uint(t1));
   }
-  plane_keys<J, PAIR>(g, t0, t1, kp);
+  plane_keys<J, PAIR, AXB>(g, t0, t1, kp);
   const float tb = __uint_as_float(kb);  // the chosen plane's t
   // in-plane offsets from the centre, a = d_b * t + (o_b - mid_b): the origin's offset is per ray
   // and shared by every rectangle with that centre (CSE'd across the unrolled tests)
@@ -144,11 +146,11 @@ __device__ __forceinline__ void rect_cand(GP g, const Ray6& r, uint32_t& tmin) {
   const bool inb = (bool)((int)(fabsf(a) <= g->ha) & (int)(fabsf(b) <= g->hb));
   tmin = umin(tmin, inb ? kp : 0xFFFFFFFFu);
 }
-template <int J>
+template <int J, bool AXB>
 __device__ __forceinline__ void cornell_test(const Ray6* rays, uint32_t& tmin) {
   constexpr CTest T = kCornellTests.t[J];
   if constexpr (J != kCornellRoom[0] && J != kCornellRoom[1] && J != kCornellRoom[2] && !cornell_in_box(J))
-    rect_cand<J, T.pos0 != T.pos1>(CornellTestPtr<J>{}, rays[T.axis], tmin);
+    rect_cand<J, T.pos0 != T.pos1, AXB>(CornellTestPtr<J>{}, rays[T.axis], tmin);
 }
 // A box of contract v6 (oracle c_find_boxes / c_intersect): an XY pair Z (planes z), a YZ pair X
 // (planes x) and an XZ top, standing on the room's floor F (the room's XZ pair, k0). Per axis the two
@@ -175,6 +177,7 @@ __device__ __forceinline__ void box_keys(int kx0, int kx1, int kz0, int kz1, int
   tmin = umin(tmin, en <= ex ? umin((uint32_t)en, (uint32_t)ex) : 0xFFFFFFFFu);
 }
 // The room of contract v6 as the same slab (from inside: the exit face, the nearest positive wall)
+template <bool AXB>
 __device__ __forceinline__ void cornell_room(const Ray6* rays, uint32_t& tmin) {
   constexpr CTest Z = kCornellTests.t[kCornellRoom[0]], Y = kCornellTests.t[kCornellRoom[1]];
   constexpr CTest X = kCornellTests.t[kCornellRoom[2]];
@@ -185,26 +188,26 @@ __device__ __forceinline__ void cornell_room(const Ray6* rays, uint32_t& tmin) {
   // way), so the distance is the same bits.
   static_assert(__builtin_bit_cast(uint32_t, Z.k0) == 0u && __builtin_bit_cast(uint32_t, Y.k0) == 0u,
                 "HEAD room: Front z = +0, Bottom y = +0");
-  box_keys((int)key_c<X.pos0>(plane_t(X.k0 - rx.oa, rx.ia)), (int)key_c<X.pos1>(plane_t(X.k1 - rx.oa, rx.ia)),
-           (int)key_c<Z.pos0>(plane_t(-rz.oa, rz.ia)), (int)key_c<Z.pos1>(plane_t(Z.k1 - rz.oa, rz.ia)),
-           (int)key_c<Y.pos0>(plane_t(-ry.oa, ry.ia)), (int)key_c<Y.pos1>(plane_t(Y.k1 - ry.oa, ry.ia)),
+  box_keys((int)key_c<cornell_slot(X.pos0, AXB)>(plane_t(X.k0 - rx.oa, rx.ia)), (int)key_c<cornell_slot(X.pos1, AXB)>(plane_t(X.k1 - rx.oa, rx.ia)),
+           (int)key_c<cornell_slot(Z.pos0, AXB)>(plane_t(-rz.oa, rz.ia)), (int)key_c<cornell_slot(Z.pos1, AXB)>(plane_t(Z.k1 - rz.oa, rz.ia)),
+           (int)key_c<cornell_slot(Y.pos0, AXB)>(plane_t(-ry.oa, ry.ia)), (int)key_c<cornell_slot(Y.pos1, AXB)>(plane_t(Y.k1 - ry.oa, ry.ia)),
            tmin);
 }
-template <int B>
+template <int B, bool AXB>
 __device__ __forceinline__ void cornell_box(const Ray6* rays, uint32_t& tmin) {
   constexpr CTest Z = kCornellTests.t[kCornellBoxes.t[B][0]], X = kCornellTests.t[kCornellBoxes.t[B][1]];
   constexpr CTest T = kCornellTests.t[kCornellBoxes.t[B][2]], F = kCornellTests.t[kCornellRoom[1]];
   const Ray6 &rz = rays[2], &ry = rays[1], &rx = rays[0];
-  box_keys((int)key_c<X.pos0>(plane_t(X.k0 - rx.oa, rx.ia)), (int)key_c<X.pos1>(plane_t(X.k1 - rx.oa, rx.ia)),
-           (int)key_c<Z.pos0>(plane_t(Z.k0 - rz.oa, rz.ia)), (int)key_c<Z.pos1>(plane_t(Z.k1 - rz.oa, rz.ia)),
+  box_keys((int)key_c<cornell_slot(X.pos0, AXB)>(plane_t(X.k0 - rx.oa, rx.ia)), (int)key_c<cornell_slot(X.pos1, AXB)>(plane_t(X.k1 - rx.oa, rx.ia)),
+           (int)key_c<cornell_slot(Z.pos0, AXB)>(plane_t(Z.k0 - rz.oa, rz.ia)), (int)key_c<cornell_slot(Z.pos1, AXB)>(plane_t(Z.k1 - rz.oa, rz.ia)),
            // (the floor's key as cornell_room spells it: the same value, CSE'd)
-           (int)key_c<F.pos0>(plane_t(-ry.oa, ry.ia)), (int)key_c<T.pos0>(plane_t(T.k0 - ry.oa, ry.ia)),
+           (int)key_c<cornell_slot(F.pos0, AXB)>(plane_t(-ry.oa, ry.ia)), (int)key_c<cornell_slot(T.pos0, AXB)>(plane_t(T.k0 - ry.oa, ry.ia)),
            tmin);
 }
-template <int... B>
+template <bool AXB, int... B>
 __device__ __forceinline__ void cornell_boxes(std::integer_sequence<int, B...>, const Ray6* rays,
                                               uint32_t& tmin) {
-  (cornell_box<B>(rays, tmin), ...);
+  (cornell_box<B, AXB>(rays, tmin), ...);
 }
 // The same for uploaded geometry: the room (rm[0] its XY pair, rm[1] XZ, rm[2] YZ) and a box (bx[0]
 // the XY pair, bx[1] the YZ pair, bx[2] the top; fl the room's XZ pair, its k0 the floor)
@@ -228,10 +231,10 @@ __device__ __forceinline__ void geo_box(GT bx, GT fl, const Ray6& rz, const Ray6
            (int)key_v(plane_t(fl->k0 - ry.oa, ry.ia), (uint32_t)fl->pos0),
            (int)key_v(plane_t(bx[2].k0 - ry.oa, ry.ia), (uint32_t)bx[2].pos0), tmin);
 }
-template <int... J>
+template <bool AXB, int... J>
 __device__ __forceinline__ void cornell_tests(std::integer_sequence<int, J...>, const Ray6* rays,
                                               uint32_t& tmin) {
-  (cornell_test<J>(rays, tmin), ...);
+  (cornell_test<J, AXB>(rays, tmin), ...);
 }
 
 template <int N, class GT>  // the tests of one kind group, uploaded geometry (every test as a pair)
@@ -257,12 +260,12 @@ __device__ __forceinline__ RectHit rect_eval(GP g, const Ray6& r) {
 // The uploaded light of the room-literal UPLIGHT kernels (a single XZ test at the HEAD light's grouped
 // position, read from the uploaded scene through scalar loads): rect_cand's arithmetic for a single,
 // with the position literal.
-template <class GT>
+template <bool AXB, class GT>
 __device__ __forceinline__ void light_cand(const GT& g, const Ray6& r, uint32_t& tmin) {
   const float t0 = plane_t(g.k0 - r.oa, r.ia);
   const float a = fmaf(r.db, t0, r.ob - g.ma), b = fmaf(r.dc, t0, r.oc - g.mb);
   const bool inb = (bool)((int)(fabsf(a) <= g.ha) & (int)(fabsf(b) <= g.hb));
-  tmin = umin(tmin, inb ? key_c<kCornellLightPos>(t0) : 0xFFFFFFFFu);
+  tmin = umin(tmin, inb ? key_c<cornell_slot(kCornellLightPos, AXB)>(t0) : 0xFFFFFFFFu);
 }
 // The same light's own test (rect_eval on a GeoTest): t and whether the in-plane test accepts.
 template <class GT>
@@ -346,7 +349,11 @@ __device__ __forceinline__ auto tests_of(const SPT_CONST SceneGeo* G, const GeoT
 }
 // The scene's room of contract v5 in uploaded geometry: SceneGeo.room_test[] (three GeoTests kept
 // out of the per-kind test lists) and the box (host build_geo, oracle c_find_room).
-template <class TP, class GP, class GT, class SP>
+// AXB (KernelTraits::kAxisBits; literal kernels): the keys carry cornell_slot's numbering, and so do
+// the positions of the uploaded boxes' tests the kernel staged; id and pos_out are slots.
+// MISS (KernelTraits::kMissEntry; literal leak-end kernels): a miss reports the "no hit" key's own
+// low bits, slot 63, as its position and id, without the select.
+template <class TP, bool AXB = false, bool MISS = false, class GP, class GT, class SP>
 __device__ __forceinline__ bool intersect_scene(const SPT_CONST SceneGeo* G, GP rect, GT tests,
                                                 SP sphs, const int* pos2idx, f3 o, f3 d, int& id,
                                                 float& ia_hit, int& pos_out, f3& inv) {
@@ -356,19 +363,19 @@ __device__ __forceinline__ bool intersect_scene(const SPT_CONST SceneGeo* G, GP 
   if constexpr (TP::CONSTGEO) {
     const Ray6 rays[3] = {ray6<0>(o, d, ix, iy, iz), ray6<1>(o, d, ix, iy, iz),
                           ray6<2>(o, d, ix, iy, iz)};
-    cornell_room(rays, tmin);
+    cornell_room<AXB>(rays, tmin);
     if constexpr (TP::UPBOX) {
       // the uploaded HEAD-topology tests (host-checked: n_txy 0, n_txz 1, n_tyz 0): the light, the
       // room's three pairs (its XZ pair's k0 the floor), then the two boxes' three tests each. The
       // room is literal (HEAD's, host-checked), the boxes come from LDS, the light is literal or
       // (UPLIGHT) read through scalar loads from the uploaded scene
-      if constexpr (TP::UPLIGHT) light_cand(G->test[0], rays[1], tmin);
-      else cornell_tests(std::make_integer_sequence<int, kCornellTests.n>{}, rays, tmin);  // the light
+      if constexpr (TP::UPLIGHT) light_cand<AXB>(G->test[0], rays[1], tmin);
+      else cornell_tests<AXB>(std::make_integer_sequence<int, kCornellTests.n>{}, rays, tmin);  // the light
       geo_box(tests + 4, tests + 2, rays[2], rays[1], rays[0], tmin);
       geo_box(tests + 7, tests + 2, rays[2], rays[1], rays[0], tmin);
     } else {
-      cornell_tests(std::make_integer_sequence<int, kCornellTests.n>{}, rays, tmin);  // the light
-      cornell_boxes(std::make_integer_sequence<int, kCornellBoxes.n>{}, rays, tmin);
+      cornell_tests<AXB>(std::make_integer_sequence<int, kCornellTests.n>{}, rays, tmin);  // the light
+      cornell_boxes<AXB>(std::make_integer_sequence<int, kCornellBoxes.n>{}, rays, tmin);
     }
   } else {
     const int ntxy = n_of<TP>(TP::NTXY, G->n_txy), ntxz = n_of<TP>(TP::NTXZ, G->n_txz);
@@ -408,8 +415,12 @@ __device__ __forceinline__ bool intersect_scene(const SPT_CONST SceneGeo* G, GP 
   const bool hit = tmin < kKeyNone;
   int pos = (int)(tmin & 63u);  // (63 on a miss: a valid LDS index, the id is kept)
   // HEAD kernels: a miss reports the position of prim 0, whose id a missed path ray keeps (:373-374),
-  // so the shading takes the hit's plane axis from the same two position compares as ia_hit
-  if constexpr (TP::CONSTGEO) pos = hit ? pos : kCornellPosOfPrim0;
+  // so the shading takes the hit's plane axis from the same two position compares as ia_hit.
+  // MISS: a miss ends the path in the shading block that follows, and nothing the lane makes from the
+  // hit's position or primitive is read after it but the emission its L takes, T * e: the lane reads
+  // slot 63, which the kernel stages with zero emission, and adds T * 0 as it did with prim 0's
+  static_assert(!MISS || TP::CONSTGEO, "MISS: a literal kernel");
+  if constexpr (TP::CONSTGEO && !MISS) pos = hit ? pos : cornell_slot(kCornellPosOfPrim0, AXB);
   // 1/d of the hit rectangle's plane axis (the winner's t and its hit point, see the shading)
   const int nxy = TP::CONSTGEO ? kCornellNXY : n_of<TP>(TP::NXY, G->n_xy);
   const int nxz = TP::CONSTGEO ? kCornellNXZ : n_of<TP>(TP::NXZ, G->n_xz);
@@ -420,7 +431,8 @@ __device__ __forceinline__ bool intersect_scene(const SPT_CONST SceneGeo* G, GP 
   int idn;
   if constexpr (TP::CONSTGEO) idn = pos;
   else idn = keep(pos2idx[pos]);
-  id = hit ? idn : id;
+  if constexpr (MISS) id = idn;  // (no shadow ray of these kernels misses: none keeps a vertex's id)
+  else id = hit ? idn : id;
   pos_out = pos;
   return hit;
 }

@@ -154,6 +154,23 @@ struct KernelTraits {
   // or kStCos only, and with the axis-aligned camera, whose wave-uniform z the compare form copies
   // into a VGPR in every iteration (elsewhere the two forms are the same number of instructions).
   static constexpr bool kCamMask = kGenStatesFirst && CF::CAMAX == 1;
+  // Round 30, the literal kernels (TP::CONSTGEO: HEAD's and the room-literal edited-scene ones); the
+  // run-time-geometry and generic kernels keep their instructions (tools/isa_same.py).
+  // A random word's unit-interval float, (E << 23) | (r >> 9), as one funnel shift (spt_device.h,
+  // funnel_float): the cosine sample's xi2 and the LREF light lattice's two words.
+  static constexpr bool kFunnelFloats = TP::CONSTGEO;
+  // The primitive slots carry the rectangle's kind in bits 4 and 5 (spt_cornell.h, cornell_slot), so
+  // the hit's two plane-axis masks are two one-bit field extracts of the winning position where the
+  // grouped numbering needed a subtract and a shift each (spt_kernel.hip, axis_masks). The room-literal
+  // NEE kernels (upbox_nee, uplight_nee and their any-camera forms) keep the grouped numbering: with
+  // the slots each of them paid one more SGPR spill (profiles/r30_vgprs.txt).
+  static constexpr bool kAxisBits = TP::CONSTGEO && !(TP::UPBOX && CF::NEE == 1);
+  // A miss reads the table entry its key's low bits name, slot 63 staged with zero emission, instead
+  // of selecting prim 0's position behind the hit compare (spt_trace.h, intersect_scene): the literal
+  // leak-end kernels, where a miss ends the path in the same shading block, and of those the ones in
+  // which no shadow ray can miss and keep its vertex's id -- the early-resolve NEE kernels, which
+  // trace a shadow ray only when the light's own test accepts it, and the cosine-only ones.
+  static constexpr bool kMissEntry = TP::CONSTGEO && CF::LEAK == 1 && (kEarlyNee || CF::NEE == 0);
   // For the host. The UPBOX / UPLIGHT kernels are CONSTGEO (kEarlyNee) and take their box clauses
   // from KParams (early_geo_proven inside early_nee_proven's place): clauses, not literals.
   static constexpr EarlyKind early = kEarlyNee ? (TP::UPBOX ? kEarlyClauses : kEarlyLiteral)

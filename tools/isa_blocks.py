@@ -37,6 +37,8 @@ QUARTER = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_sin_", "v_cos_", "v_exp_", "v_log_"
 # read 18 cycles in the probe, where all eight waves of a SIMD do the same: a wait of the wave, not an
 # issue slot, so it stays at one slot here and is counted apart (`far_sel`).
 HALF += ("v_subrev_co_u32",)
+# Round 30 (profiles/r30_valu_rates.txt): v_alignbit_b32 is half rate (4.2 cycles), like v_bfe_i32 (4.3).
+HALF += ("v_alignbit_b32",)
 SGPR_SRC = re.compile(r"\bs(\d+|\[\d+:\d+\])")
 
 

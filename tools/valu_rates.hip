@@ -158,6 +158,21 @@ __global__ void __launch_bounds__(256) k_rate(uint32_t* out, uint32_t seed) {
       EACH(M)
 #undef M
     }
+    // round 30: the funnel shift that is a shift-or pair (a random word's unit-interval float), all
+    // sources in VGPRs and in the render loop's form (the high word an SGPR, the shift an inline
+    // constant), and the signed one-bit field extract that spreads a key bit over a word (a lane mask)
+    if constexpr (K == 55) { DO3("v_alignbit_b32") }
+    if constexpr (K == 56) {
+#define M(X) asm volatile("v_alignbit_b32 %0, %1, %0, 9" : "+v"(X) : "s"(seed));
+      EACH(M)
+#undef M
+    }
+    if constexpr (K == 57) { DO3("v_bfe_i32") }
+    if constexpr (K == 58) {
+#define M(X) asm volatile("v_bfe_i32 %0, %0, 4, 1" : "+v"(X));
+      EACH(M)
+#undef M
+    }
   }
   out[blockIdx.x * 256 + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7 ^ (uint32_t)sink;
 }
@@ -248,6 +263,7 @@ int main() {
   R32(37, "v_addc_co_u32_e64") R32(39, "v_mbcnt_lo_u32_b32") R32(40, "v_mbcnt_hi_u32_b32")
   R32(46, "v_ashrrev_i32") R32(47, "v_and_b32") R32(48, "v_bitop3_b32 sgpr") R32(54, "v_bitop3_b32 0xe4")
   R32(49, "v_sub_u32") R32(50, "v_subrev_co_u32 vcc") R32(51, "v_subrev_co_u32 sgpr")
+  R32(55, "v_alignbit_b32") R32(56, "v_alignbit_b32 s,v,9") R32(57, "v_bfe_i32") R32(58, "v_bfe_i32 v,4,1")
   // per compare + select pair, and per instruction of one compare and eight selects (9 per 8 counted)
   R32(52, "v_cmp vcc + cndmask_e32")
   report("cmp vcc, 8 cndmask_e32",
