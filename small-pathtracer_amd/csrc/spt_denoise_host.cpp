@@ -2,7 +2,8 @@
 // the CPU statement every GPU denoise test compares the device kernels against, and below it the
 // two-half filter and its summary (SPT_HAS_DENOISE_PAIR) and the filter bank (SPT_HAS_DENOISE_BANK). Plain
 // C++, no HIP: it is also built into tests/probe/spt_denoise_check, spt_denoise_pair_check and
-// spt_denoise_bank_check under the host sanitizers.
+// spt_denoise_bank_check under the host sanitizers. The three filters share one argument check
+// (check_call), one guide pack (HostGuides) and spt_denoise.h's accessor over row-major planes.
 #include <cstring>
 #include <utility>
 #include <vector>
@@ -11,6 +12,9 @@
 #include "spt_status.h"
 
 static_assert(sizeof(spt_denoise_params) == 32, "spt_denoise_params layout (the Python mirror's)");
+static_assert(sizeof(spt_pair_summary) == 40, "spt_pair_summary layout (the Python mirror's)");
+static_assert(sizeof(spt_bank_params) == 16, "spt_bank_params layout (the Python mirror's)");
+static_assert(sizeof(spt_bank_summary) == 56, "spt_bank_summary layout (the Python mirror's)");
 
 extern "C" void spt_denoise_default_params(spt_denoise_params* p) {
   if (!p) return;
@@ -24,20 +28,56 @@ extern "C" void spt_denoise_default_params(spt_denoise_params* p) {
   p->reserved = 0;
 }
 
+extern "C" void spt_denoise_bank_default_params(spt_bank_params* b) {
+  if (!b) return;
+  b->error_iterations = 2;
+  b->pair_flags = SPT_DENOISE_PAIR_OWN_WEIGHTS;
+  b->reserved[0] = b->reserved[1] = 0;
+}
+
 namespace {
 
 using namespace spt_denoise_math;
+using HostPlanes = Planes<RowMajor>;
 
-struct HostPlanes {
-  const f4 *cv_, *nz_, *av_;
-  int32_t w;
-  f4 cv(int32_t x, int32_t y) const { return cv_[(size_t)y * w + x]; }
-  f4 nz(int32_t x, int32_t y) const { return nz_[(size_t)y * w + x]; }
-  f4 av(int32_t x, int32_t y) const { return av_[(size_t)y * w + x]; }
-  float v(int32_t x, int32_t y) const { return cv_[(size_t)y * w + x].w; }
+spt_status fail(const char* who, const char* msg) {
+  return spt::fail(SPT_ERR_INVALID_ARG, std::string(who) + ": " + msg);
+}
+
+// What every entry point asks of its arguments, in the order it reports them: the planes there (outs'
+// first is the one output that must be; a summary has no output plane), the parameters (perr: what is
+// wrong with them, or NULL), the size, no output an input, the outputs distinct.
+spt_status check_call(const char* who, const char* perr, int32_t width, int32_t height, PlaneList outs,
+                      PlaneList ins) {
+  if (!outs.size() && any_null(ins)) return fail(who, "null argument");
+  if (any_null(ins) || (outs.size() && !*outs.begin())) return fail(who, "null plane");
+  if (perr) return fail(who, perr);
+  if (const char* e = size_error(width, height)) return fail(who, e);
+  if (const char* e = inputs_error(outs, ins)) return fail(who, e);
+  if (const char* e = outputs_error(outs)) return fail(who, e);
+  return SPT_OK;
+}
+
+// The packed guides and the depth gradient of a whole image.
+struct HostGuides {
+  std::vector<f4> nz, av;
+  std::vector<float> gx, gy;
+  HostGuides(const float* normal, const float* depth, const float* albedo, int32_t width, int32_t height)
+      : nz((size_t)width * height), av(nz.size()), gx(nz.size()), gy(nz.size()) {
+    for (int32_t y = 0; y < height; ++y)
+      for (int32_t x = 0; x < width; ++x) {
+        const size_t i = (size_t)y * width + x;
+        pack_guides(normal, depth, albedo + 3 * i, x, y, width, height, i, &nz[i], &av[i], &gx[i], &gy[i]);
+      }
+  }
 };
 
-spt_status fail(const char* msg) { return spt::fail(SPT_ERR_INVALID_ARG, std::string("spt_denoise_host: ") + msg); }
+// fn(x, y, i) at every pixel, rows first.
+template <class Fn>
+void for_pixels(int32_t width, int32_t height, const Fn& fn) {
+  for (int32_t y = 0; y < height; ++y)
+    for (int32_t x = 0; x < width; ++x) fn(x, y, (size_t)y * width + x);
+}
 
 }  // namespace
 
@@ -45,13 +85,8 @@ extern "C" spt_status spt_denoise_host(const float* rgb, const float* se, const 
                                        const float* normal, const float* depth, int32_t width,
                                        int32_t height, const spt_denoise_params* params, float* out,
                                        float* se_out) {
-  if (!rgb || !se || !albedo || !normal || !depth || !out) return fail("null plane");
-  if (const char* e = params_error(params)) return fail(e);
-  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
-    return fail("width/height must be positive and hold at most 2^31 - 1 pixels");
-  for (const float* in : {rgb, se, albedo, normal, depth})
-    if (out == in || (se_out && se_out == in)) return fail("an output plane is an input plane");
-  if (se_out == out) return fail("out and se_out are one plane");
+  SPT_TRY(check_call("spt_denoise_host", params_error(params), width, height, {out, se_out},
+                     {rgb, se, albedo, normal, depth}));
   const size_t npix = (size_t)width * (size_t)height;
   if (params->iterations == 0) {
     std::memcpy(out, rgb, npix * 3 * sizeof(float));
@@ -59,55 +94,25 @@ extern "C" spt_status spt_denoise_host(const float* rgb, const float* se, const 
     return SPT_OK;
   }
   const Args A = make_args(params);
-  std::vector<f4> cv0(npix), cv1(npix), nz(npix), av(npix);
-  std::vector<float> gx(npix), gy(npix);
-  for (int32_t y = 0; y < height; ++y)
-    for (int32_t x = 0; x < width; ++x) {
-      const size_t i = (size_t)y * width + x;
-      cv0[i] = prepare(rgb + 3 * i, se + 3 * i, albedo + 3 * i, A);
-      nz[i] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]};
-      av[i] = {albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f};
-      gx[i] = gradient(x, width, x > 0 ? depth[i - 1] : 0.0f, depth[i], x < width - 1 ? depth[i + 1] : 0.0f);
-      gy[i] = gradient(y, height, y > 0 ? depth[i - width] : 0.0f, depth[i],
-                       y < height - 1 ? depth[i + width] : 0.0f);
-    }
+  std::vector<f4> cv0(npix), cv1(npix);
+  HostGuides G(normal, depth, albedo, width, height);
+  for (size_t i = 0; i < npix; ++i) cv0[i] = prepare(rgb + 3 * i, se + 3 * i, albedo + 3 * i, A);
   f4 *cur = cv0.data(), *nxt = cv1.data();
   for (int32_t it = 0; it < params->iterations; ++it) {
-    const HostPlanes P{cur, nz.data(), av.data(), width};
-    for (int32_t y = 0; y < height; ++y)
-      for (int32_t x = 0; x < width; ++x) av[(size_t)y * width + x].w = variance_filter(P, x, y, width, height);
-    for (int32_t y = 0; y < height; ++y)
-      for (int32_t x = 0; x < width; ++x) {
-        const size_t i = (size_t)y * width + x;
-        nxt[i] = iterate(P, x, y, width, height, (int32_t)1 << it, gx[i], gy[i], A);
-      }
-    f4* t = cur;
-    cur = nxt;
-    nxt = t;
+    const HostPlanes P{{width}, G.nz.data(), G.av.data(), cur};
+    for_pixels(width, height,
+               [&](int32_t x, int32_t y, size_t i) { G.av[i].w = variance_filter(P, x, y, width, height); });
+    for_pixels(width, height, [&](int32_t x, int32_t y, size_t i) {
+      nxt[i] = iterate(P, x, y, width, height, (int32_t)1 << it, G.gx[i], G.gy[i], A);
+    });
+    std::swap(cur, nxt);
   }
-  for (size_t i = 0; i < npix; ++i) finish(cur[i], av[i], A, out + 3 * i, se_out ? se_out + 3 * i : nullptr);
+  for (size_t i = 0; i < npix; ++i) finish(cur[i], G.av[i], A, out + 3 * i, se_out ? se_out + 3 * i : nullptr);
   return SPT_OK;
 }
 
 // ---- the two-half filter (SPT_HAS_DENOISE_PAIR) ----
-static_assert(sizeof(spt_pair_summary) == 40, "spt_pair_summary layout (the Python mirror's)");
-
 namespace {
-
-struct HostPairPlanes {
-  const f4 *ca_, *cb_, *nz_, *av_;
-  const float* vtb_;
-  int32_t w;
-  f4 ca(int32_t x, int32_t y) const { return ca_[(size_t)y * w + x]; }
-  f4 cb(int32_t x, int32_t y) const { return cb_[(size_t)y * w + x]; }
-  f4 nz(int32_t x, int32_t y) const { return nz_[(size_t)y * w + x]; }
-  f4 av(int32_t x, int32_t y) const { return av_[(size_t)y * w + x]; }
-  float vtb(int32_t x, int32_t y) const { return vtb_[(size_t)y * w + x]; }
-};
-
-spt_status fail_pair(const char* msg) {
-  return spt::fail(SPT_ERR_INVALID_ARG, std::string("spt_denoise_pair_host: ") + msg);
-}
 
 // The pair filter of validated arguments: out / se_out / diff as spt_denoise_pair_host gives them, or (the
 // bank: out NULL) the two halves' finish values o^A and o^B, 3 floats per pixel each.
@@ -132,41 +137,32 @@ void pair_filter(const float* rgb_a, const float* se_a, const float* rgb_b, cons
   }
   const Args A = make_args(params);
   const bool own = (pair_flags & SPT_DENOISE_PAIR_OWN_WEIGHTS) != 0;
-  std::vector<f4> ca0(npix), ca1(npix), cb0(npix), cb1(npix), nz(npix), av(npix);
-  std::vector<float> vtb(npix), gx(npix), gy(npix);
-  for (int32_t y = 0; y < height; ++y)
-    for (int32_t x = 0; x < width; ++x) {
-      const size_t i = (size_t)y * width + x;
-      ca0[i] = prepare(rgb_a + 3 * i, se_a + 3 * i, albedo + 3 * i, A);
-      cb0[i] = prepare(rgb_b + 3 * i, se_b + 3 * i, albedo + 3 * i, A);
-      nz[i] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]};
-      av[i] = {albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f};
-      gx[i] = gradient(x, width, x > 0 ? depth[i - 1] : 0.0f, depth[i], x < width - 1 ? depth[i + 1] : 0.0f);
-      gy[i] = gradient(y, height, y > 0 ? depth[i - width] : 0.0f, depth[i],
-                       y < height - 1 ? depth[i + width] : 0.0f);
-    }
+  std::vector<f4> ca0(npix), ca1(npix), cb0(npix), cb1(npix);
+  std::vector<float> vtb(npix);
+  HostGuides G(normal, depth, albedo, width, height);
+  for (size_t i = 0; i < npix; ++i) {
+    ca0[i] = prepare(rgb_a + 3 * i, se_a + 3 * i, albedo + 3 * i, A);
+    cb0[i] = prepare(rgb_b + 3 * i, se_b + 3 * i, albedo + 3 * i, A);
+  }
   f4 *cura = ca0.data(), *nxta = ca1.data(), *curb = cb0.data(), *nxtb = cb1.data();
   for (int32_t it = 0; it < params->iterations; ++it) {
-    const HostPlanes PA{cura, nullptr, nullptr, width}, PB{curb, nullptr, nullptr, width};
-    for (int32_t y = 0; y < height; ++y)
-      for (int32_t x = 0; x < width; ++x) {
-        av[(size_t)y * width + x].w = variance_filter(PA, x, y, width, height);
-        vtb[(size_t)y * width + x] = variance_filter(PB, x, y, width, height);
-      }
-    const HostPairPlanes P{cura, curb, nz.data(), av.data(), vtb.data(), width};
-    for (int32_t y = 0; y < height; ++y)
-      for (int32_t x = 0; x < width; ++x) {
-        const size_t i = (size_t)y * width + x;
-        iterate_pair(P, x, y, width, height, (int32_t)1 << it, gx[i], gy[i], A, own, &nxta[i], &nxtb[i]);
-      }
+    const HostPlanes P{{width}, G.nz.data(), G.av.data(), cura, curb, vtb.data()};
+    const HostPlanes PB{{width}, nullptr, nullptr, curb};
+    for_pixels(width, height, [&](int32_t x, int32_t y, size_t i) {
+      G.av[i].w = variance_filter(P, x, y, width, height);
+      vtb[i] = variance_filter(PB, x, y, width, height);
+    });
+    for_pixels(width, height, [&](int32_t x, int32_t y, size_t i) {
+      iterate_pair(P, x, y, width, height, (int32_t)1 << it, G.gx[i], G.gy[i], A, own, &nxta[i], &nxtb[i]);
+    });
     std::swap(cura, nxta);
     std::swap(curb, nxtb);
   }
   for (size_t i = 0; i < npix; ++i) {
     if (out)
-      finish_pair(cura[i], curb[i], av[i], A, out + 3 * i, at(se_out, i), at(diff, i));
+      finish_pair(cura[i], curb[i], G.av[i], A, out + 3 * i, at(se_out, i), at(diff, i));
     else
-      finish_halves(cura[i], curb[i], av[i], A, oa + 3 * i, ob + 3 * i);
+      finish_halves(cura[i], curb[i], G.av[i], A, oa + 3 * i, ob + 3 * i);
   }
 }
 
@@ -177,18 +173,9 @@ extern "C" spt_status spt_denoise_pair_host(const float* rgb_a, const float* se_
                                             const float* depth, int32_t width, int32_t height,
                                             const spt_denoise_params* params, uint32_t pair_flags,
                                             float* out, float* se_out, float* diff) {
-  if (!rgb_a || !se_a || !rgb_b || !se_b || !albedo || !normal || !depth || !out) return fail_pair("null plane");
-  if (const char* e = params_error(params)) return fail_pair(e);
-  if (const char* e = pair_flags_error(pair_flags)) return fail_pair(e);
-  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
-    return fail_pair("width/height must be positive and hold at most 2^31 - 1 pixels");
-  for (const float* o : {(const float*)out, (const float*)se_out, (const float*)diff}) {
-    if (!o) continue;
-    for (const float* in : {rgb_a, se_a, rgb_b, se_b, albedo, normal, depth})
-      if (o == in) return fail_pair("an output plane is an input plane");
-  }
-  if (se_out == out || diff == out || (se_out && se_out == diff))
-    return fail_pair("two output planes are one plane");
+  const char* perr = params_error(params);
+  SPT_TRY(check_call("spt_denoise_pair_host", perr ? perr : pair_flags_error(pair_flags), width, height,
+                     {out, se_out, diff}, {rgb_a, se_a, rgb_b, se_b, albedo, normal, depth}));
   pair_filter(rgb_a, se_a, rgb_b, se_b, albedo, normal, depth, width, height, params, pair_flags, out, se_out,
               diff, nullptr, nullptr);
   return SPT_OK;
@@ -196,63 +183,23 @@ extern "C" spt_status spt_denoise_pair_host(const float* rgb_a, const float* se_
 
 extern "C" spt_status spt_denoise_pair_summary_host(const float* diff, int32_t width, int32_t height,
                                                     spt_pair_summary* out) {
-  if (!diff || !out) return spt::fail(SPT_ERR_INVALID_ARG, "spt_denoise_pair_summary_host: null argument");
-  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
-    return spt::fail(SPT_ERR_INVALID_ARG,
-                     "spt_denoise_pair_summary_host: width/height must be positive and hold at most 2^31 - 1 pixels");
+  SPT_TRY(check_call("spt_denoise_pair_summary_host", nullptr, width, height, {}, {diff, out}));
   const size_t npix = (size_t)width * (size_t)height;
-  PairPartial t{};
+  PairPartial t = pair_partial_zero();
   for (size_t i = 0; i < npix; ++i) pair_partial_add(t, diff + 3 * i);
   pair_summary_finish(t, npix, out);
   return SPT_OK;
 }
 
 // ---- the filter bank (SPT_HAS_DENOISE_BANK) ----
-static_assert(sizeof(spt_bank_params) == 16, "spt_bank_params layout (the Python mirror's)");
-static_assert(sizeof(spt_bank_summary) == 56, "spt_bank_summary layout (the Python mirror's)");
-
-extern "C" void spt_denoise_bank_default_params(spt_bank_params* b) {
-  if (!b) return;
-  b->error_iterations = 2;
-  b->pair_flags = SPT_DENOISE_PAIR_OWN_WEIGHTS;
-  b->reserved[0] = b->reserved[1] = 0;
-}
-
-namespace {
-
-struct HostBankPlanes {
-  const f4 *m_, *nz_, *av_;
-  int32_t w;
-  f4 m(int32_t x, int32_t y) const { return m_[(size_t)y * w + x]; }
-  f4 nz(int32_t x, int32_t y) const { return nz_[(size_t)y * w + x]; }
-  f4 av(int32_t x, int32_t y) const { return av_[(size_t)y * w + x]; }
-};
-
-spt_status fail_bank(const char* msg) {
-  return spt::fail(SPT_ERR_INVALID_ARG, std::string("spt_denoise_bank_host: ") + msg);
-}
-
-}  // namespace
-
 extern "C" spt_status spt_denoise_bank_host(const float* rgb_a, const float* se_a, const float* rgb_b,
                                             const float* se_b, const float* albedo, const float* normal,
                                             const float* depth, int32_t width, int32_t height,
                                             const spt_denoise_params* cands, int32_t n_cands,
                                             const spt_bank_params* bank, float* out, float* mse,
                                             uint8_t* choice) {
-  if (!rgb_a || !se_a || !rgb_b || !se_b || !albedo || !normal || !depth || !out) return fail_bank("null plane");
-  if (const char* e = bank_error(cands, n_cands, bank)) return fail_bank(e);
-  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
-    return fail_bank("width/height must be positive and hold at most 2^31 - 1 pixels");
-  const void* outs[3] = {out, mse, choice};
-  for (const void* o : outs) {
-    if (!o) continue;
-    for (const float* in : {rgb_a, se_a, rgb_b, se_b, albedo, normal, depth})
-      if (o == (const void*)in) return fail_bank("an output plane is an input plane");
-  }
-  if ((const void*)mse == (const void*)out || (const void*)choice == (const void*)out ||
-      (mse && (const void*)mse == (const void*)choice))
-    return fail_bank("two output planes are one plane");
+  SPT_TRY(check_call("spt_denoise_bank_host", bank_error(cands, n_cands, bank), width, height,
+                     {out, mse, choice}, {rgb_a, se_a, rgb_b, se_b, albedo, normal, depth}));
   const size_t npix = (size_t)width * (size_t)height;
   // 1, 2: every candidate's halves, its out and its error estimate
   std::vector<float> oa(3 * npix), ob(3 * npix), outk((size_t)n_cands * 3 * npix);
@@ -268,46 +215,30 @@ extern "C" spt_status spt_denoise_bank_host(const float* rgb_a, const float* se_
   }
   // 3: the smoothing passes, with the geometric factor of cands[0]
   const Args A = make_args(cands);
-  std::vector<f4> nz(npix), av(npix);
-  std::vector<float> gx(npix), gy(npix);
-  for (int32_t y = 0; y < height; ++y)
-    for (int32_t x = 0; x < width; ++x) {
-      const size_t i = (size_t)y * width + x;
-      nz[i] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]};
-      av[i] = {albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f};
-      gx[i] = gradient(x, width, x > 0 ? depth[i - 1] : 0.0f, depth[i], x < width - 1 ? depth[i + 1] : 0.0f);
-      gy[i] = gradient(y, height, y > 0 ? depth[i - width] : 0.0f, depth[i],
-                       y < height - 1 ? depth[i + width] : 0.0f);
-    }
+  const HostGuides G(normal, depth, albedo, width, height);
   f4 *cur = m0.data(), *nxt = m1.data();
+  const auto planes = [&] { return HostPlanes{{width}, G.nz.data(), G.av.data(), nullptr, nullptr, nullptr, cur}; };
   for (int32_t it = 0; it < bank->error_iterations; ++it) {
-    const HostBankPlanes P{cur, nz.data(), av.data(), width};
-    for (int32_t y = 0; y < height; ++y)
-      for (int32_t x = 0; x < width; ++x) {
-        const size_t i = (size_t)y * width + x;
-        nxt[i] = bank_pass<false>(P, x, y, width, height, (int32_t)1 << it, gx[i], gy[i], A, n_cands);
-      }
+    const HostPlanes P = planes();
+    for_pixels(width, height, [&](int32_t x, int32_t y, size_t i) {
+      nxt[i] = bank_pass<false>(P, x, y, width, height, (int32_t)1 << it, G.gx[i], G.gy[i], A, n_cands);
+    });
     std::swap(cur, nxt);
   }
   // 4, 5: the choice and the blend
-  const HostBankPlanes P{cur, nz.data(), av.data(), width};
-  for (int32_t y = 0; y < height; ++y)
-    for (int32_t x = 0; x < width; ++x) {
-      const size_t i = (size_t)y * width + x;
-      const f4 s = bank_pass<true>(P, x, y, width, height, 1, gx[i], gy[i], A, n_cands);
-      const float e = bank_blend(s, cur[i], n_cands, outk.data(), 3 * npix, 3 * i, out + 3 * i);
-      if (mse) mse[i] = e;
-      if (choice) choice[i] = (uint8_t)bank_choice(cur[i], n_cands);
-    }
+  const HostPlanes P = planes();
+  for_pixels(width, height, [&](int32_t x, int32_t y, size_t i) {
+    const f4 s = bank_pass<true>(P, x, y, width, height, 1, G.gx[i], G.gy[i], A, n_cands);
+    const float e = bank_blend(s, cur[i], n_cands, outk.data(), 3 * npix, 3 * i, out + 3 * i);
+    if (mse) mse[i] = e;
+    if (choice) choice[i] = (uint8_t)bank_choice(cur[i], n_cands);
+  });
   return SPT_OK;
 }
 
 extern "C" spt_status spt_denoise_bank_summary_host(const float* mse, const uint8_t* choice, int32_t width,
                                                     int32_t height, spt_bank_summary* out) {
-  if (!mse || !choice || !out) return spt::fail(SPT_ERR_INVALID_ARG, "spt_denoise_bank_summary_host: null argument");
-  if (width <= 0 || height <= 0 || (int64_t)width * (int64_t)height > kMaxPixels)
-    return spt::fail(SPT_ERR_INVALID_ARG,
-                     "spt_denoise_bank_summary_host: width/height must be positive and hold at most 2^31 - 1 pixels");
+  SPT_TRY(check_call("spt_denoise_bank_summary_host", nullptr, width, height, {}, {mse, choice, out}));
   const size_t npix = (size_t)width * (size_t)height;
   BankPartial t = bank_partial_zero();
   for (size_t i = 0; i < npix; ++i) bank_partial_add(t, mse[i], choice[i]);
