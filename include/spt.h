@@ -41,7 +41,8 @@ extern "C" {
                              the spt_denoise_pair_* calls and spt_film_pair_denoise;
                              SPT_HAS_DENOISE_BANK, the spt_denoise_bank_* calls and
                              spt_film_pair_denoise_bank; SPT_HAS_GUIDE_LIGHT, the spt_light_guide_*
-                             and spt_light_shade_* calls */
+                             and spt_light_shade_* calls; SPT_HAS_TEMPORAL, the spt_temporal_* calls
+                             and spt_film_temporal_accumulate */
 #define SPT_HAS_FILM 1    /* progressive rendering: sample windows into a resumable integer film */
 #define SPT_HAS_FILM_NOISE 1 /* the film's second moment: error map, RMSE estimate (below) */
 #define SPT_HAS_FILM_ADAPTIVE 1 /* per-pixel batch counts, passes over the pixels still noisy (below) */
@@ -54,6 +55,7 @@ extern "C" {
 #define SPT_HAS_DENOISE 1 /* the edge-stopping a-trous filter over a film and its guides (below) */
 #define SPT_HAS_DENOISE_PAIR 1 /* two independent halves, cross-weighted, and a measured error (below) */
 #define SPT_HAS_DENOISE_BANK 1 /* a few pair filters, the one of least cross-validated error per pixel (below) */
+#define SPT_HAS_TEMPORAL 1 /* temporal accumulation: the last frame reprojected through the guides (below) */
 
 typedef enum spt_status {
   SPT_OK = 0,
@@ -949,6 +951,138 @@ spt_status spt_film_pair_denoise_bank(const spt_film* film_a, const spt_film* fi
                                       const spt_denoise_params* cands, int32_t n_cands,
                                       const spt_bank_params* bank, float* out_dev, float* mse_dev_or_null,
                                       uint8_t* choice_dev_or_null, void* stream);
+
+/* ---- temporal accumulation: the last frame's film reprojected through the guides (SPT_HAS_TEMPORAL) ----
+ * The temporal half of SVGF in front of the a-trous filter above: the previous frame's accumulated colour
+ * and variance are reprojected into the new camera, tested against the geometry and blended with the new
+ * frame, and the filter is handed an input with a smaller se. Exact fp32 arithmetic as the filter's: IEEE
+ * + - * /, fmaxf, fminf, fabsf, sqrtf, floorf and one float -> int conversion that is reached only after
+ * float range checks; no contraction; every sum in the order given here, so the kernel and the host
+ * statement agree bit for bit.
+ * Inputs, for a w x h frame in pixel order (y = 0 the top row): rgb, se, albedo, normal (h*w*3 each) and
+ * depth (h*w), the five planes of spt_denoise_async; the frame's camera; an spt_temporal_params.
+ * State, kept between calls, per pixel: colour c[3], variance v[3], length n, world position X[3] and
+ * normal N[3] (13 floats, the planes of an spt_temporal_state), and the camera that made them. The
+ * object holds two copies, used ping-pong: a frame gathers from its predecessor's neighbours while it
+ * writes its own.
+ * Host constants, computed in double and rounded to fp32 once per value. For a camera: o = origin,
+ * E = lower_left_corner - origin, Hx = horizontal / w, Vy = vertical / h. For the previous camera
+ * (primed below): M, the inverse of the 3x3 matrix with the columns (Hx', Vy', E'), by cofactors:
+ * rows (Vy' x E') / det, (E' x Hx') / det, (Hx' x Vy') / det with det = (Hx'_0*r_0 + Hx'_1*r_1) + Hx'_2*r_2,
+ * r = Vy' x E'. A camera whose det is 0 or whose constants are not finite is rejected (SPT_ERR_INVALID_ARG)
+ * in the call that brings it. These are the pixel's MEAN ray under the contract's jitter: a sample's
+ * su = (x - 0.5 + ju) / w with ju uniform on [0, 1) has the mean x / w, and sv likewise has the mean
+ * (h - 1 - y) / h: the reference's own half-pixel quirk (tests/guide_truth.py, camera_rays, builds the
+ * same ray sample by sample: its fx and fy are x - 0.5 and h - 1 - y - 0.5 before the jitter is added).
+ * Per pixel (x, y):
+ * 1. The current estimate. a_k = fmaxf(albedo_k, albedo_floor), or 1 with SPT_TEMPORAL_NO_DEMODULATE;
+ *    c_k = rgb_k / a_k;  e_k = se_k / a_k;  var_k = e_k * e_k.
+ * 2. The world point. D_k = (E_k + Hx_k * (float)x) + Vy_k * (float)(h - 1 - y);
+ *    len = sqrtf((D_0*D_0 + D_1*D_1) + D_2*D_2);  X_k = o_k + (D_k / len) * z, z the pixel's depth. A pixel
+ *    with z == 0 (a miss) has no surface: it takes no history and its state and n_out get n = 0, which
+ *    no later tap accepts.
+ * 3. The previous pixel. q = X - o';  (A, B, C) = M q, rows in order, each (m_0*q_0 + m_1*q_1) + m_2*q_2.
+ *    History is refused unless C > 0. fx = A / C;  fy = (float)(h - 1) - B / C. History is refused unless
+ *    fx >= -1, fx < (float)w, fy >= -1 and fy < (float)h (float compares: a NaN fails them).
+ *    x0 = floorf(fx), tx = fx - x0, and y0, ty likewise.
+ * 4. The taps (x0 + i, y0 + j), j then i in {0, 1}. A tap outside the image is skipped. Its weight is
+ *    b = (i ? tx : 1 - tx) * (j ? ty : 1 - ty). A tap q is valid iff n_q > 0, and
+ *    (N_p,0*N_q,0 + N_p,1*N_q,1) + N_p,2*N_q,2 >= normal_min with N_p the current normal as given (a short
+ *    normal at an edge fails this on purpose), and fabsf((N_p,0*d_0 + N_p,1*d_1) + N_p,2*d_2) <=
+ *    plane_tol * z_p with d = X_q - X_p. With W, Ch_k, Vh_k, Nh starting at 0.0f, each valid tap in order
+ *    does W += b, Ch_k += b*c_q,k, Vh_k += b*v_q,k, Nh += b*n_q. History is refused unless W >= 0.25f;
+ *    otherwise c_h = Ch / W, v_h = Vh / W, n_h = Nh / W.
+ * 5. The same-camera rule. When the twelve doubles of the previous camera equal the current camera's
+ *    (the host decides once per call), steps 3 and 4 use the single tap (x, y) with b = 1 under the same
+ *    validity tests: progressive use with a static camera has no resampling blur at all.
+ * 6. The blend. n' = fminf(n_h + 1, n_max);  alpha = 1 / n';  beta = 1 - alpha;
+ *    c'_k = beta*c_h,k + alpha*c_k;  v'_k = (beta*beta)*v_h,k + (alpha*alpha)*var_k. With history refused,
+ *    or on the first frame: c' = c, v' = var, n' = 1 (0 at a miss).
+ * 7. The outputs. rgb_out_k = fminf(c'_k * a_k, 1);  se_out_k = sqrtf(v'_k) * a_k; the optional plane
+ *    n_out (h*w) = n'; the optional plane hist (h*w*3) = c_h,k * a_k, or rgb_k copied where history was
+ *    refused (for debugging and tests). The new state is (c', v', n', X, N_p) and the camera.
+ * What it is not. There are no motion vectors: the scene must be static between frames, and a moved
+ * primitive is either refused by the tests of step 4 or ghosts. A first-hit guide reprojects a mirror's
+ * surface, not what is seen in it, so reflections and refractions lag the camera; a chain guide's depth
+ * is an optical length, not a position, and the film path refuses it. v' treats frames as independent and
+ * the bilinear taps as one sample: an estimate, like se_out of the filter. While n' < n_max a static
+ * camera gives v' = var / n'; once n' stays at n_max the blend is an exponential average and v' falls on
+ * towards var / (2 n_max - 1). plane_tol's default 0.01 sits five times above the 1.8e-3 relative depth
+ * error that the free-scale direction contract allows. Inputs that are not finite give unspecified
+ * values, never a fault: no address is formed before the range checks of steps 3 and 4. */
+#define SPT_TEMPORAL_NO_DEMODULATE 1u /* accumulate rgb itself, not rgb / albedo; other flag bits must be 0 */
+typedef struct spt_temporal_params {
+  float n_max;        /* finite, >= 1: the history's length at most. Default 32 */
+  float normal_min;   /* -1..1. Default 0.9 */
+  float plane_tol;    /* finite, >= 0. Default 0.01 */
+  float albedo_floor; /* finite, > 0. Default 0.01 */
+  uint32_t flags;     /* SPT_TEMPORAL_NO_DEMODULATE */
+  uint32_t reserved;  /* 0 */
+} spt_temporal_params;
+void spt_temporal_default_params(spt_temporal_params* p);
+/* The 13 planes of a state, HOST pointers: c, v, X, N of h*w*3 floats, n of h*w. */
+typedef struct spt_temporal_state {
+  float *c, *v, *n, *X, *N;
+} spt_temporal_state;
+typedef struct spt_temporal_info {
+  int64_t frames;        /* accepted accumulate calls since creation or the last reset */
+  int32_t width, height;
+  int32_t has_history;   /* frames > 0: the next call reprojects */
+  int32_t reserved;
+} spt_temporal_info;
+/* An accumulator for width x height frames on `device`. It owns the two copies of the state (52 bytes
+ * per pixel each: three 16-byte words and a float) and five planes for the film path below, allocated
+ * here; no later call allocates on the device. Rejected: width or height not positive, more than
+ * 2^31 - 1 pixels, or a shape whose tiles of 64 x 4 pixels do not fit one launch (2^24 - 1 tiles). Calls
+ * on one accumulator are serialised by the caller on one stream. */
+typedef struct spt_temporal spt_temporal;
+spt_status spt_temporal_create(int32_t device, int32_t width, int32_t height, spt_temporal** out);
+spt_status spt_temporal_destroy(spt_temporal* tp);
+/* Drop the history: the next frame is a first frame. Queues nothing. */
+spt_status spt_temporal_reset(spt_temporal* tp);
+spt_status spt_temporal_info_get(const spt_temporal* tp, spt_temporal_info* out);
+/* Enqueue one frame of five DEVICE planes on `stream`: rgb_out_dev and se_out_dev (h*w*3 each) and, if
+ * given, n_out_dev (h*w) and hist_dev (h*w*3). No host synchronisation. Rejected with
+ * SPT_ERR_INVALID_ARG, nothing queued, the outputs and the state untouched: a null plane, a parameter
+ * that is not finite or out of range, unknown flag bits, a nonzero reserved word, a singular camera, an
+ * output pointer equal to an input or to another output. */
+spt_status spt_temporal_accumulate_async(spt_temporal* tp, const float* rgb_dev, const float* se_dev,
+                                         const float* albedo_dev, const float* normal_dev,
+                                         const float* depth_dev, const spt_camera* cam,
+                                         const spt_temporal_params* params, float* rgb_out_dev,
+                                         float* se_out_dev, float* n_out_dev_or_null,
+                                         float* hist_dev_or_null, void* stream);
+/* The same as a pure host function (no device), HOST pointers: the CPU statement. prev and prev_cam are
+ * the previous state and its camera, both NULL on a first frame; next receives the new state (its planes
+ * are outputs: none may be an input, a plane of prev or another output). Also rejects a width or height
+ * that is not positive or more than 2^31 - 1 pixels. */
+spt_status spt_temporal_accumulate_host(const float* rgb, const float* se, const float* albedo,
+                                        const float* normal, const float* depth, int32_t width,
+                                        int32_t height, const spt_camera* cam,
+                                        const spt_temporal_params* params,
+                                        const spt_temporal_state* prev_or_null,
+                                        const spt_camera* prev_cam_or_null, float* rgb_out, float* se_out,
+                                        float* n_out_or_null, float* hist_or_null,
+                                        const spt_temporal_state* next);
+/* The state of the last accepted frame into 13 HOST planes, and its camera if asked. Waits on `stream`.
+ * Rejected: no frame since the last reset. For tests and checkpoints. */
+spt_status spt_temporal_state_download(spt_temporal* tp, const spt_temporal_state* out,
+                                       spt_camera* cam_out_or_null, void* stream);
+/* Film and guide in one call: the film's resolve, its error map and the guide's resolve go into the
+ * accumulator's planes and the frame is accumulated from them, all enqueued on `stream` with no host
+ * synchronisation; the result equals spt_temporal_accumulate_async on the separately resolved planes bit
+ * for bit. Where albedo_out_dev, normal_out_dev (h*w*3) or depth_out_dev (h*w) is given, the guide's
+ * plane is resolved there instead, so that spt_denoise_async can follow without a second resolve. An
+ * adaptive film works unchanged. Rejected, nothing queued, outputs and state untouched: what
+ * spt_temporal_accumulate_async rejects (the three planes count as outputs); what spt_film_denoise rejects
+ * (a plain film, batches_done < 2, an empty guide, a size or device mismatch, a sharded film); a guide
+ * created with SPT_GUIDE_THROUGH_SPECULAR. The guide's device is the caller's duty, as there. */
+spt_status spt_film_temporal_accumulate(const spt_film* film, const spt_guide* guide, spt_temporal* tp,
+                                        const spt_camera* cam, const spt_temporal_params* params,
+                                        float* rgb_out_dev, float* se_out_dev, float* n_out_dev_or_null,
+                                        float* hist_dev_or_null, float* albedo_out_dev_or_null,
+                                        float* normal_out_dev_or_null, float* depth_out_dev_or_null,
+                                        void* stream);
 
 /* ---- multi-GPU: row-tile shards and ONE framebuffer gather over RCCL ----
  * The reference's only parallel construct is the OpenMP pragma over its row loop (:526-528). Here

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import atexit
 import ctypes
+import math
 import os
 from contextlib import contextmanager as _contextmanager
 from typing import Iterable, Sequence
@@ -156,6 +157,20 @@ class spt_bank_summary(ctypes.Structure):
                 "mse_max": float(self.mse_max)}
 
 
+class spt_temporal_params(ctypes.Structure):
+    _fields_ = [("n_max", ctypes.c_float), ("normal_min", ctypes.c_float), ("plane_tol", ctypes.c_float),
+                ("albedo_floor", ctypes.c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class spt_temporal_state(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("c", "v", "n", "X", "N")]
+
+
+class spt_temporal_info(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("has_history", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class spt_gather_op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("peer", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
@@ -201,7 +216,13 @@ EXPORTS = ["spt_default_params", "spt_camera_init", "spt_scene_cornell", "spt_sc
            "spt_denoise_pair_async", "spt_denoise_pair_host", "spt_denoise_pair_summary",
            "spt_denoise_pair_summary_host", "spt_film_pair_denoise",
            "spt_denoise_bank_default_params", "spt_denoise_bank_async", "spt_denoise_bank_host",
-           "spt_denoise_bank_summary", "spt_denoise_bank_summary_host", "spt_film_pair_denoise_bank"]
+           "spt_denoise_bank_summary", "spt_denoise_bank_summary_host", "spt_film_pair_denoise_bank",
+           "spt_temporal_default_params", "spt_temporal_create", "spt_temporal_destroy", "spt_temporal_reset",
+           "spt_temporal_info_get", "spt_temporal_accumulate_async", "spt_temporal_accumulate_host",
+           "spt_temporal_state_download", "spt_film_temporal_accumulate"]
+SPT_HAS_TEMPORAL = 1        # include/spt.h: temporal accumulation (TemporalAccumulator, temporal_accumulate_host)
+TEMPORAL_NO_DEMODULATE = 1  # SPT_TEMPORAL_NO_DEMODULATE: accumulate rgb itself, not rgb / albedo
+TEMPORAL_STATE_PLANES = (("c", 3), ("v", 3), ("n", 1), ("X", 3), ("N", 3))  # spt_temporal_state, in order
 SPT_HAS_DENOISE_BANK = 1    # include/spt.h: the filter bank (denoise_bank_host, Denoiser.denoise_bank, ...)
 BANK_MAX_CANDIDATES = 4     # SPT_BANK_MAX_CANDIDATES
 SPT_HAS_DENOISE_PAIR = 1    # include/spt.h: the two-half filter (denoise_pair_host, Denoiser.denoise_pair, ...)
@@ -400,6 +421,22 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.spt_denoise_bank_summary_host.argtypes = [VP, VP, I32, I32, P(spt_bank_summary)]
     lib.spt_film_pair_denoise_bank.argtypes = [VP, VP, VP, VP, P(spt_denoise_params), I32, P(spt_bank_params),
                                                VP, VP, VP, VP]
+    lib.spt_temporal_default_params.argtypes = [P(spt_temporal_params)]
+    lib.spt_temporal_default_params.restype = None
+    lib.spt_temporal_create.argtypes = [I32, I32, I32, P(VP)]
+    lib.spt_temporal_destroy.argtypes = [VP]
+    lib.spt_temporal_reset.argtypes = [VP]
+    lib.spt_temporal_info_get.argtypes = [VP, P(spt_temporal_info)]
+    lib.spt_temporal_accumulate_async.argtypes = [VP] + [VP] * 5 + [P(spt_camera), P(spt_temporal_params), VP, VP,
+                                                                    VP, VP, VP]
+    lib.spt_temporal_accumulate_host.argtypes = [VP] * 5 + [I32, I32, P(spt_camera), P(spt_temporal_params),
+                                                            P(spt_temporal_state), P(spt_camera), VP, VP, VP, VP,
+                                                            P(spt_temporal_state)]
+    lib.spt_temporal_state_download.argtypes = [VP, P(spt_temporal_state), P(spt_camera), VP]
+    lib.spt_film_temporal_accumulate.argtypes = [VP, VP, VP, P(spt_camera), P(spt_temporal_params)] + [VP] * 8
+    for name in ("spt_temporal_create", "spt_temporal_destroy", "spt_temporal_reset", "spt_temporal_info_get",
+                 "spt_temporal_accumulate_async", "spt_temporal_accumulate_host", "spt_temporal_state_download"):
+        getattr(lib, name).restype = I32
     for name in ("spt_denoiser_create", "spt_denoiser_destroy", "spt_denoise_async", "spt_denoise_host",
                  "spt_denoise_pair_async", "spt_denoise_pair_host", "spt_denoise_pair_summary",
                  "spt_denoise_pair_summary_host", "spt_denoise_bank_async", "spt_denoise_bank_host",
@@ -437,7 +474,8 @@ KERNEL_SOURCES = ("csrc/spt_kernel.hip", "csrc/spt_trace.h", "csrc/spt_variants.
                   "csrc/spt_guide.hip", "csrc/spt_guide_host.cpp", "csrc/spt_guide.h",
                   "csrc/spt_denoise.hip", "csrc/spt_denoise_host.cpp", "csrc/spt_denoise.h",
                   "csrc/spt_status.h", "csrc/spt_window_shape.h", "csrc/spt_guide_device.h",
-                  "csrc/spt_guide_light.hip", "csrc/spt_guide_light_host.cpp", "csrc/spt_guide_light.h")
+                  "csrc/spt_guide_light.hip", "csrc/spt_guide_light_host.cpp", "csrc/spt_guide_light.h",
+                  "csrc/spt_temporal.hip", "csrc/spt_temporal_host.cpp", "csrc/spt_temporal.h")
 
 
 def kernel_sources_sha16() -> str:
@@ -2025,6 +2063,255 @@ def render_denoised(prims: Sequence[spt_prim], cam: Camera, params: spt_params, 
         if dn is not None:
             dn.close()
         guide.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# Temporal accumulation (include/spt.h, SPT_HAS_TEMPORAL)
+# ---------------------------------------------------------------------------------------------
+def default_temporal_params(**kw) -> spt_temporal_params:
+    """spt_temporal_default_params() with the given fields replaced."""
+    p = spt_temporal_params()
+    load_library().spt_temporal_default_params(ctypes.byref(p))
+    for k, v in kw.items():
+        if k not in dict(spt_temporal_params._fields_):
+            raise TypeError(f"spt_temporal_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _camera_struct(cam) -> spt_camera:
+    return cam._c if isinstance(cam, Camera) else cam
+
+
+def _temporal_state(h: int, w: int):
+    """An empty state: its planes as a dict and the spt_temporal_state that points at them."""
+    planes = {k: np.empty((h, w, c) if c > 1 else (h, w), np.float32) for k, c in TEMPORAL_STATE_PLANES}
+    return planes, spt_temporal_state(*[planes[k].ctypes.data for k, _ in TEMPORAL_STATE_PLANES])
+
+
+def temporal_accumulate_host(rgb, se, albedo, normal, depth, cam, params: spt_temporal_params | None = None,
+                             prev: dict | None = None, prev_cam=None) -> dict:
+    """spt_temporal_accumulate_host(): the CPU statement of one frame (no device). Planes as (h, w, 3)
+    float32, depth (h, w); cam a Camera or an spt_camera; prev the "state" of the previous frame's result
+    and prev_cam its camera (both None on a first frame). -> {"rgb", "se", "n", "hist", "state": {"c", "v",
+    "n", "X", "N"}}."""
+    planes, h, w = _denoise_planes(rgb, se, albedo, normal, depth)
+    p = params if params is not None else default_temporal_params()
+    out = {"rgb": np.empty((h, w, 3), np.float32), "se": np.empty((h, w, 3), np.float32),
+           "n": np.empty((h, w), np.float32), "hist": np.empty((h, w, 3), np.float32)}
+    state, nxt = _temporal_state(h, w)
+    old, keep = None, []
+    if prev is not None:
+        for k, c in TEMPORAL_STATE_PLANES:
+            a = np.ascontiguousarray(prev[k], dtype=np.float32)
+            if a.size != h * w * c:
+                raise SptError(1, f"the previous state's {k} does not have height * width * {c} elements")
+            keep.append(a)
+        old = spt_temporal_state(*[a.ctypes.data for a in keep])
+    _check(load_library().spt_temporal_accumulate_host(
+        *[a.ctypes.data for a in planes], w, h, ctypes.byref(_camera_struct(cam)), ctypes.byref(p),
+        ctypes.byref(old) if old is not None else None,
+        ctypes.byref(_camera_struct(prev_cam)) if prev_cam is not None else None,
+        out["rgb"].ctypes.data, out["se"].ctypes.data, out["n"].ctypes.data, out["hist"].ctypes.data,
+        ctypes.byref(nxt)))
+    out["state"] = state
+    return out
+
+
+class TemporalAccumulator:
+    """spt_temporal: the accumulated film of width x height frames on one device, reprojected into every
+    new frame's camera. Calls on one accumulator go on one stream."""
+
+    def __init__(self, width: int, height: int, device: int = 0):
+        self.lib = load_library()
+        self._t = ctypes.c_void_p()
+        _check(self.lib.spt_temporal_create(int(device), int(width), int(height), ctypes.byref(self._t)))
+        self.width, self.height, self.device = int(width), int(height), int(device)
+
+    def close(self):
+        if self._t:
+            self.lib.spt_temporal_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def reset(self):
+        """Drop the history: the next frame is a first frame."""
+        _check(self.lib.spt_temporal_reset(self._t))
+
+    def info(self) -> dict:
+        i = spt_temporal_info()
+        _check(self.lib.spt_temporal_info_get(self._t, ctypes.byref(i)))
+        return {"frames": int(i.frames), "width": int(i.width), "height": int(i.height),
+                "has_history": bool(i.has_history)}
+
+    def state_to_numpy(self, stream_ptr: int = 0, return_camera=False):
+        """The last frame's state on the host: {"c", "v", "n", "X", "N"}; return_camera: also its spt_camera."""
+        state, st = _temporal_state(self.height, self.width)
+        cam = spt_camera()
+        _check(self.lib.spt_temporal_state_download(self._t, ctypes.byref(st), ctypes.byref(cam),
+                                                    ctypes.c_void_p(stream_ptr or None)))
+        return (state, cam) if return_camera else state
+
+    def accumulate_async(self, rgb_ptr: int, se_ptr: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int, cam,
+                         params: spt_temporal_params, rgb_out_ptr: int, se_out_ptr: int, n_out_ptr: int = 0,
+                         hist_ptr: int = 0, stream_ptr: int = 0):
+        """spt_temporal_accumulate_async() on device pointers."""
+        V = ctypes.c_void_p
+        _check(self.lib.spt_temporal_accumulate_async(
+            self._t, V(rgb_ptr or None), V(se_ptr or None), V(albedo_ptr or None), V(normal_ptr or None),
+            V(depth_ptr or None), ctypes.byref(_camera_struct(cam)), ctypes.byref(params), V(rgb_out_ptr or None),
+            V(se_out_ptr or None), V(n_out_ptr or None), V(hist_ptr or None), V(stream_ptr or None)))
+
+    def accumulate_film_async(self, film: "Film", guide: "Guide", cam, params: spt_temporal_params,
+                              rgb_out_ptr: int, se_out_ptr: int, n_out_ptr: int = 0, hist_ptr: int = 0,
+                              albedo_ptr: int = 0, normal_ptr: int = 0, depth_ptr: int = 0, stream_ptr: int = 0):
+        """spt_film_temporal_accumulate() into device pointers; albedo_ptr, normal_ptr, depth_ptr: where
+        the guide's resolved planes go when the caller wants them (for a denoise call that follows)."""
+        V = ctypes.c_void_p
+        _check(self.lib.spt_film_temporal_accumulate(
+            film._f, guide._g, self._t, ctypes.byref(_camera_struct(cam)), ctypes.byref(params),
+            V(rgb_out_ptr or None), V(se_out_ptr or None), V(n_out_ptr or None), V(hist_ptr or None),
+            V(albedo_ptr or None), V(normal_ptr or None), V(depth_ptr or None), V(stream_ptr or None)))
+
+    def _outputs(self):
+        import torch
+        n, dev = self.width * self.height, f"cuda:{self.device}"
+        return {k: torch.empty(n * c, dtype=torch.float32, device=dev)
+                for k, c in (("rgb", 3), ("se", 3), ("n", 1), ("hist", 3))}
+
+    def _host(self, bufs) -> dict:
+        import torch
+        torch.cuda.synchronize(self.device)
+        return {k: t.cpu().numpy().reshape((self.height, self.width, 3) if k != "n" else (self.height, self.width))
+                for k, t in bufs.items()}
+
+    def accumulate(self, rgb, se, albedo, normal, depth, cam, params: spt_temporal_params | None = None) -> dict:
+        """Host arrays in (uploaded through torch) -> {"rgb", "se", "n", "hist"} on the host."""
+        import torch
+        planes, h, w = _denoise_planes(rgb, se, albedo, normal, depth)
+        if (h, w) != (self.height, self.width):
+            raise SptError(1, "the planes are not the accumulator's height x width")
+        p = params if params is not None else default_temporal_params()
+        with torch.cuda.device(self.device):
+            dev = [torch.from_numpy(a.reshape(-1)).to(f"cuda:{self.device}") for a in planes]
+            o = self._outputs()
+            self.accumulate_async(*[t.data_ptr() for t in dev], cam, p, o["rgb"].data_ptr(), o["se"].data_ptr(),
+                                  o["n"].data_ptr(), o["hist"].data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return self._host(o)
+
+    def accumulate_film(self, film: "Film", guide: "Guide", cam, params: spt_temporal_params | None = None) -> dict:
+        """The film's image, its error map and the guide's planes resolved and accumulated on the device in
+        one call -> {"rgb", "se", "n", "hist"} on the host."""
+        import torch
+        p = params if params is not None else default_temporal_params()
+        with torch.cuda.device(self.device):
+            o = self._outputs()
+            self.accumulate_film_async(film, guide, cam, p, o["rgb"].data_ptr(), o["se"].data_ptr(),
+                                       o["n"].data_ptr(), o["hist"].data_ptr(),
+                                       stream_ptr=torch.cuda.current_stream().cuda_stream)
+            return self._host(o)
+
+
+def orbit_cameras(frames: int, degrees: float, lookfrom=LOOKFROM, lookat=(50, 40, 5), **camera_kw) -> list:
+    """`frames` cameras: camera k has lookfrom rotated about the vertical axis through lookat by k * degrees
+    (camera 0 is Camera(lookfrom, lookat, **camera_kw) itself)."""
+    f, a = _v3(lookfrom), _v3(lookat)
+    dx, dz = f[0] - a[0], f[2] - a[2]
+    cams = []
+    for k in range(int(frames)):
+        if k == 0:
+            cams.append(Camera(f, a, **camera_kw))
+            continue
+        t = math.radians(k * float(degrees))
+        c, s = math.cos(t), math.sin(t)
+        cams.append(Camera((a[0] + c * dx + s * dz, f[1], a[2] - s * dx + c * dz), a, **camera_kw))
+    return cams
+
+
+def render_sequence(prims: Sequence[spt_prim], cams, params: spt_params, batch: int | None = None,
+                    temporal: bool = True, denoise: bool = True, denoise_params: spt_denoise_params | None = None,
+                    temporal_params: spt_temporal_params | None = None, guide_spp: int | None = None) -> list:
+    """One frame per camera of `cams`, frame k with the seed params.seed + k: a noise film of params.spp
+    samples (batches of `batch`, default spp / 8) and a first-hit guide (the window [0, min(spp, guide_spp
+    or 64))), accumulated over the frames before it (TemporalAccumulator.accumulate_film) and then filtered
+    (Denoiser.denoise_async on the accumulated planes). -> the list of images, (h, w, 3) float32 each.
+    temporal=False: every frame on its own, render_denoised() of that camera and seed bit for bit
+    (denoise=False: the film's image). The scene must not change between the frames (spt.h)."""
+    import torch
+    spp = int(params.spp)
+    if params.shard_count > 1:
+        raise SptError(1, "render_sequence: a shard's rows are not image neighbours; gather the planes")
+    if batch is None:
+        if spp % 8:
+            raise SptError(1, "render_sequence: spp is no multiple of 8, give batch")
+        batch = spp // 8
+    if batch < 1 or spp % batch or spp // batch < 2:
+        raise SptError(1, "render_sequence: batch must divide spp into at least two batches")
+    n_guide = min(spp, int(guide_spp or 64))
+    frames = []
+
+    def frame_params(k):
+        p = spt_params.from_buffer_copy(params)
+        p.seed = (int(params.seed) + k) & 0xFFFFFFFF
+        return p
+
+    if not temporal:
+        for k, cam in enumerate(cams):
+            p = frame_params(k)
+            if denoise:
+                frames.append(render_denoised(prims, cam, p, batch, guide_spp, denoise_params))
+            else:
+                with _film_session(p, batch) as (r, film, buf, stream):
+                    for b in range(spp // batch):
+                        film.render(r, prims, cam, p, b * batch, batch, 0, stream)
+                        r.stats()
+                    film.resolve(buf.data_ptr(), stream)
+                    frames.append(_film_image(film, buf))
+        return frames
+    tp_params = temporal_params if temporal_params is not None else default_temporal_params()
+    dn_params = denoise_params if denoise_params is not None else default_denoise_params()
+    w, h, dev = int(params.width), int(params.height), f"cuda:{params.device}"
+    acc = TemporalAccumulator(w, h, params.device)
+    dn = Denoiser(w, h, params.device) if denoise else None
+    r = Renderer(params.device)
+    try:
+        with torch.cuda.device(params.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            new = lambda c: torch.empty(w * h * c, dtype=torch.float32, device=dev)  # noqa: E731
+            rgb, se, albedo, normal, depth, out = new(3), new(3), new(3), new(3), new(1), new(3)
+            for k, cam in enumerate(cams):
+                p = frame_params(k)
+                film, guide = Film(p, p.device), Guide(p, p.device)
+                try:
+                    film.enable_noise(batch)
+                    for b in range(spp // batch):
+                        film.render(r, prims, cam, p, b * batch, batch, 0, stream)
+                        r.stats()  # a pass that hit the runaway guard raises here
+                    guide.render(r, prims, cam, p, 0, n_guide, stream)
+                    acc.accumulate_film_async(film, guide, cam, tp_params, rgb.data_ptr(), se.data_ptr(),
+                                              albedo_ptr=albedo.data_ptr(), normal_ptr=normal.data_ptr(),
+                                              depth_ptr=depth.data_ptr(), stream_ptr=stream)
+                    img = rgb
+                    if denoise:
+                        dn.denoise_async(rgb.data_ptr(), se.data_ptr(), albedo.data_ptr(), normal.data_ptr(),
+                                         depth.data_ptr(), dn_params, out.data_ptr(), 0, stream)
+                        img = out
+                    torch.cuda.synchronize(params.device)
+                    frames.append(img.cpu().numpy().reshape(h, w, 3))
+                finally:
+                    guide.close()
+                    film.close()
+    finally:
+        r.close()
+        if dn is not None:
+            dn.close()
+        acc.close()
+    return frames
 
 
 def _pair_batch(who: str, params: spt_params, batch):

@@ -6,6 +6,17 @@
 //               [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]
 //               [--pair [--pair-own] [--bank S,S,.. [--bank-map PREFIX]]]] [--through-specular] [--help]
 //               [--light] [--light-guide [--shade-floor F]]
+//               [--frames N --orbit DEG [--temporal [--temporal-nmax M]]]
+//   --frames N --orbit DEG: N frames, frame k from LOOKFROM rotated about the vertical axis through the
+//               look-at point by k * DEG degrees, with the seed SEED + k, each through a noise film
+//               (every sample, 8 batches or --batch B). The frame index goes before OUT's extension:
+//               image.ppm -> image.0000.ppm ... With --denoise each frame is filtered (--denoise-iters and
+//               --denoise-sigma as given; a first-hit guide of min(SPP, 64) samples). --temporal: every
+//               frame is first accumulated over the frames before it (spt_film_temporal_accumulate:
+//               the last frame's film reprojected through the guide's depth and normal; the scene does
+//               not move), --temporal-nmax M the history's length at most (default 32). One device; not
+//               with --noise, --film, --passes, --repeat, --guides, --pair, --adaptive,
+//               --through-specular or --light-guide.
 //   --light (with --guides PREFIX): also PREFIX_visibility.pfm and PREFIX_direct.pfm, the light guide's
 //               planes (spt_light_guide_*) of the same window and kind as the guide's, grey like the depth.
 //   --light-guide (with --denoise, also with --pair; not with --bank): the guide's albedo plane is shaded
@@ -505,6 +516,106 @@ void write_guides(const std::vector<spt_prim>& scene, const Camera& cam, const s
   check(spt_context_destroy(ctx));
 }
 
+// --frames N --orbit DEG: frame k's camera, LOOKFROM rotated about the vertical axis through the look-at
+// point by k * DEG degrees.
+Camera orbit_camera(int k, double degrees, float aspect) {
+  const Vec at(50, 40, 5);
+  if (k == 0) return Camera(LOOKFROM, at, Vec(0, 1, 0), 65, aspect);
+  const double t = (k * degrees) * (M_PI / 180.0), c = std::cos(t), s = std::sin(t);
+  const double dx = LOOKFROM.x - at.x, dz = LOOKFROM.z - at.z;
+  const double cx = c * dx, sz = s * dz, sx = s * dx, cz = c * dz;
+  return Camera(Vec((at.x + cx) + sz, LOOKFROM.y, (at.z - sx) + cz), at, Vec(0, 1, 0), 65, aspect);
+}
+
+struct OrbitOpts {
+  int frames = 0;
+  double degrees = 0.0;
+  bool orbit_given = false, temporal = false, nmax_given = false;
+  float nmax = 32.0f;
+};
+
+// The frames of an orbit, one file each: a noise film per frame (every sample, in batches), accumulated
+// over its predecessors with --temporal, filtered with --denoise.
+void render_orbit(const std::vector<spt_prim>& scene, spt_params p, const OrbitOpts& orbit, int batch,
+                  const DenoiseOpts& denoise, const char* out, int format, spt_stats* total) {
+  if (batch <= 0 && p.spp % 8 != 0) throw std::runtime_error("--frames: SPP is no multiple of 8, give --batch");
+  if (batch <= 0) batch = p.spp / 8;
+  if (p.spp % batch != 0 || p.spp / batch < 2)
+    throw std::runtime_error("--frames: the batch must divide SPP into at least two batches");
+  const size_t npix = (size_t)p.width * (size_t)p.height;
+  const uint32_t seed0 = p.seed;
+  spt_context* ctx = nullptr;
+  spt_temporal* tp = nullptr;
+  spt_denoiser* dn = nullptr;
+  check(spt_context_create(p.device, &ctx));
+  if (orbit.temporal) check(spt_temporal_create(p.device, p.width, p.height, &tp));
+  if (denoise.on) check(spt_denoiser_create(p.device, p.width, p.height, &dn));
+  spt_denoise_params dp;
+  spt_denoise_default_params(&dp);
+  if (denoise.iters_given) dp.iterations = denoise.iters;
+  if (denoise.sigma_given) dp.sigma_color = (float)denoise.sigma;
+  spt_temporal_params tpp;
+  spt_temporal_default_params(&tpp);
+  if (orbit.nmax_given) tpp.n_max = orbit.nmax;
+  float* dev = nullptr;  // rgb, se, albedo, normal (3 floats a pixel each), depth (1), the filtered image (3)
+  if (hipMalloc(&dev, std::max<size_t>(npix, 1) * 16 * sizeof(float)) != hipSuccess)
+    throw std::runtime_error("device allocation failed");
+  float *rgb = dev, *se = dev + 3 * npix, *albedo = dev + 6 * npix, *normal = dev + 9 * npix;
+  float *depth = dev + 12 * npix, *filtered = dev + 13 * npix;
+  std::string name(out);
+  const size_t dot = name.find_last_of('.'), slash = name.find_last_of('/');
+  const size_t cut = dot != std::string::npos && (slash == std::string::npos || dot > slash) ? dot : name.size();
+  std::memset(total, 0, sizeof *total);
+  for (int k = 0; k < orbit.frames; ++k) {
+    const Camera cam = orbit_camera(k, orbit.degrees, float(p.width) / float(p.height));
+    p.seed = seed0 + (uint32_t)k;
+    spt_film* film = nullptr;
+    spt_guide* guide = nullptr;
+    check(spt_film_create(p.device, &p, &film));
+    check(spt_film_noise_enable(film, batch));
+    for (int b = 0; b < p.spp / batch; ++b) {
+      check(spt_film_render_async(ctx, film, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, b * batch, batch,
+                                  nullptr, nullptr));
+      spt_stats st{};
+      check(spt_context_stats(ctx, &st));
+      total->samples += st.samples;
+      total->vertices += st.vertices;
+      total->kernel_ms += st.kernel_ms;
+    }
+    const float* image = rgb;
+    if (orbit.temporal || denoise.on) {
+      check(spt_guide_create(p.device, &p, &guide));
+      check(spt_guide_render_async(ctx, guide, scene.data(), (int32_t)scene.size(), &cam.abi(), &p, 0,
+                                   std::min(p.spp, 64), nullptr));
+    }
+    if (orbit.temporal) {
+      check(spt_film_temporal_accumulate(film, guide, tp, &cam.abi(), &tpp, rgb, se, nullptr, nullptr, albedo,
+                                         normal, depth, nullptr));
+      if (denoise.on) {
+        check(spt_denoise_async(dn, rgb, se, albedo, normal, depth, &dp, filtered, nullptr, nullptr));
+        image = filtered;
+      }
+    } else if (denoise.on) {
+      check(spt_film_denoise(film, guide, dn, &dp, filtered, nullptr, nullptr));
+      image = filtered;
+    } else {
+      check(spt_film_resolve(film, rgb, nullptr));
+    }
+    if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("a frame failed on the device");
+    char index[16];
+    std::snprintf(index, sizeof index, ".%04d", k);
+    const std::string path = name.substr(0, cut) + index + name.substr(cut);
+    if (write_ppm(path.c_str(), p.width, p.height, image, p.device, format))
+      throw std::runtime_error("cannot write " + path + ": " + spt_last_error());
+    if (guide) check(spt_guide_destroy(guide));
+    check(spt_film_destroy(film));
+  }
+  (void)hipFree(dev);
+  if (dn) check(spt_denoiser_destroy(dn));
+  if (tp) check(spt_temporal_destroy(tp));
+  check(spt_context_destroy(ctx));
+}
+
 const char kUsage[] =
     "smallpt_amd [W H SPP [SEED [OUT.ppm]]] [--cos] [--uniform] [--reference-leaks] [--q Q]\n"
     "            [--specular | --classic | --mirror-glass | --spheres32 [--max-depth D]]\n"
@@ -514,6 +625,13 @@ const char kUsage[] =
     "            [--guides PREFIX] [--denoise [--denoise-iters N] [--denoise-sigma S]\n"
     "            [--pair [--pair-own] [--bank S,S,.. [--bank-map PREFIX]]]] [--through-specular]\n"
     "            [--light] [--light-guide [--shade-floor F]]\n"
+    "            [--frames N --orbit DEG [--temporal [--temporal-nmax M]]]\n"
+    "  --frames N --orbit DEG  N frames, the camera rotated about the vertical axis through the look-at\n"
+    "                   point by DEG per frame, seed SEED + k, the frame index before OUT's extension\n"
+    "                   (image.0000.ppm ...); goes with --denoise and --batch, one device\n"
+    "  --temporal       with --frames: accumulate every frame over the frames before it, reprojected\n"
+    "                   through the first-hit guide (the scene does not move), before it is written or filtered\n"
+    "  --temporal-nmax M  with --temporal: the history's length at most, >= 1 (default 32)\n"
     "  --light          with --guides: also PREFIX_visibility.pfm and PREFIX_direct.pfm, the light guide's\n"
     "                   share of lit shadow rays and mean direct irradiance factor per pixel\n"
     "  --light-guide    with --denoise (also --pair; not --bank): shade the guide's albedo by a light\n"
@@ -558,6 +676,7 @@ int main(int argc, char* argv[]) {
   bool light_planes = false;  // --light (with --guides): also PREFIX_visibility.pfm and PREFIX_direct.pfm
   NoiseOpts noise;
   DenoiseOpts denoise;
+  OrbitOpts orbit;
   float q = -1.0f;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--cos")) cosine = true;
@@ -600,6 +719,10 @@ int main(int argc, char* argv[]) {
     else if (!std::strcmp(argv[i], "--bank-map") && i + 1 < argc) denoise.bank_map = argv[++i];
     else if (!std::strcmp(argv[i], "--denoise-iters") && i + 1 < argc) { denoise.iters_given = true; denoise.iters = std::atoi(argv[++i]); }
     else if (!std::strcmp(argv[i], "--denoise-sigma") && i + 1 < argc) { denoise.sigma_given = true; denoise.sigma = std::atof(argv[++i]); }
+    else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) orbit.frames = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) { orbit.orbit_given = true; orbit.degrees = std::atof(argv[++i]); }
+    else if (!std::strcmp(argv[i], "--temporal")) orbit.temporal = true;
+    else if (!std::strcmp(argv[i], "--temporal-nmax") && i + 1 < argc) { orbit.nmax_given = true; orbit.nmax = std::strtof(argv[++i], nullptr); }
     else if (!std::strcmp(argv[i], "--help")) { std::cout << kUsage; return 0; }
     else if (!std::strcmp(argv[i], "--p6")) format = SPT_IMAGE_P6;
     else if (!std::strcmp(argv[i], "--pfm")) format = SPT_IMAGE_PFM;
@@ -650,6 +773,29 @@ int main(int argc, char* argv[]) {
       if (denoise.bank.size() > SPT_BANK_MAX_CANDIDATES) throw std::runtime_error("--bank: 1 to 4 colour sigmas");
       for (float v : denoise.bank)
         if (!(v > 0.0f && std::isfinite(v))) throw std::runtime_error("--bank: a comma-separated list of positive, finite numbers");
+    }
+    if ((orbit.temporal || orbit.nmax_given || orbit.orbit_given) && orbit.frames == 0)
+      throw std::runtime_error("--orbit / --temporal / --temporal-nmax go with --frames N");
+    if (orbit.nmax_given && !orbit.temporal) throw std::runtime_error("--temporal-nmax goes with --temporal");
+    if (orbit.frames != 0) {
+      if (orbit.frames < 1 || orbit.frames > 9999) throw std::runtime_error("--frames: 1..9999");
+      if (!orbit.orbit_given || !std::isfinite(orbit.degrees)) throw std::runtime_error("--frames goes with --orbit DEG");
+      if (!(orbit.nmax >= 1.0f && std::isfinite(orbit.nmax))) throw std::runtime_error("--temporal-nmax: a finite number >= 1");
+      if (devices > 0 || repeat > 1 || passes > 0 || film_path || noise.on || noise.adaptive || noise.pool_radius ||
+          noise.pool_loo || guides || denoise.pair || denoise.through_specular || denoise.light_guide)
+        throw std::runtime_error("--frames goes with one device and not with --noise, --film, --passes, --repeat, "
+                                 "--guides, --pair, --adaptive, --through-specular or --light-guide");
+      if (denoise.iters_given && (denoise.iters < 0 || denoise.iters > 6)) throw std::runtime_error("--denoise-iters: 0..6");
+      if (denoise.sigma_given && !(denoise.sigma > 0.0 && std::isfinite((float)denoise.sigma)))
+        throw std::runtime_error("--denoise-sigma: a positive, finite number");
+      render_orbit(scene, p, orbit, noise.batch, denoise, out, format, &st);
+      const auto t2 = std::chrono::high_resolution_clock::now();
+      const double samples = (double)p.width * p.height * p.spp * orbit.frames;
+      std::cout << "FRAMES : " << orbit.frames << "  KERNEL_MS : " << st.kernel_ms << "  MSAMPLES/S : "
+                << samples / (st.kernel_ms * 1e3) << std::endl;
+      std::cout << " DURATION : " << std::chrono::duration_cast<std::chrono::milliseconds>(t2 - t1).count()
+                << std::endl;
+      return 0;
     }
     if (denoise.on) {
       if (devices > 1) throw std::runtime_error("--denoise goes with one device: a shard's rows are not image neighbours");
